@@ -8,7 +8,11 @@ With N GPUs the frame is split into interleaved 16x16 tiles, one process per GPU
 and the RGBA8 tiles are gathered to rank 0 over RCCL (strong scaling: the frame
 is fixed).  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--size PX]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--size PX] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line (metric, value,
+ms_per_step, ...).  --full adds what the headline figure does not need: the work counters of a counting frame, the
+latency of a lone frame, kernel times per launch, the roofline with its live PMC child runs and the CPU baseline.
 
 `python bench.py --gpus N` starts its own N ranks (fresh child processes, started before this
 process imports torch or touches a GPU); under `python -m torch.distributed.run --nproc-per-node N`
@@ -233,6 +237,34 @@ def live_pmc(child_args, seconds=300.0, extra_env=None, frames=None):
         shutil.rmtree(out_dir, ignore_errors=True)
 
 
+DUMP_MAX_BYTES = 48 * 10 ** 6       # --dump-outputs: a larger frame is written as a fixed, seeded sample of its pixels
+DUMP_SEED = 0x5EED
+
+
+def dump_frame(out_dir, frame, W, H):
+    """--dump-outputs: the RGBA8 frame the timed path delivered in its last step (one uint32 per pixel: the row-major W x H
+    frame, or a rehearsed shard's tile-major pixels) as float32 channels 0..255 in DIR/frame_rgba.npy, [H, W, 4] (or [n, 4]
+    for a shard).  A frame above DUMP_MAX_BYTES is sampled instead: frame_rgba.npy [n, 4] holds the pixels at the buffer
+    positions frame_pixel_index.npy [n] (float64; y * W + x for a whole frame) lists, the same n pixels on every run.
+    Returns the names written."""
+    import numpy as np
+    from owlexabrick_amd import harness
+    os.makedirs(out_dir, exist_ok=True)
+    px = np.asarray(frame).view(np.uint32).reshape(-1)
+    files = {}
+    if px.size * 4 * 4 <= DUMP_MAX_BYTES:
+        rgba = harness.unpack_rgba8(px).astype(np.float32)
+        files["frame_rgba"] = rgba.reshape(H, W, 4) if px.size == W * H else rgba
+    else:
+        n = DUMP_MAX_BYTES // (4 * 4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.size, size=n, replace=False))
+        files["frame_rgba"] = harness.unpack_rgba8(px[idx]).astype(np.float32)
+        files["frame_pixel_index"] = idx.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(files)
+
+
 def useful_flops(st, grad):
     """SURVEY 8(d), informational: ~60 flop per addBasisFunctions call (+~70 with derivatives), ~40 per integrateVolume"""
     return st["brick_visits"] * (60.0 + (70.0 if grad else 0.0)) + st["samples"] * 40.0
@@ -255,10 +287,15 @@ def main():
                          "instead of the generator's own 8^3 blocks, e.g. profiles/c4_exajet_exabuilder_bricks7.npy = the bricks this "
                          "repo's exaBuilder makes of the scene's cells (tools/builder_bench.py --save-bricks7)")
     ap.add_argument("--no-grad", action="store_true", help="gradient shading off (reference default is on)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="the whole report: besides the timed steps, the work counters of a counting frame, the latency of a "
+                         "lone frame, kernel times per launch (and of basis form 0), the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame of the last timed step to DIR/*.npy (float32; see dump_frame)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"], help="with --full: the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=45.0)
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
-                    help="on: rank 0 of a 1-GPU run measures HBM bytes and VALU instructions of the march kernel live (two "
+                    help="with --full. on: rank 0 of a 1-GPU run measures HBM bytes and VALU instructions of the march kernel live (two "
                          "short child runs of this script under rocprofv3 --pmc); auto: the same when the full report is "
                          "being produced (CPU baseline not switched off) and this process is not itself being profiled; "
                          "off / failure: the committed profiles/hbm_traffic.json of the same workload")
@@ -284,6 +321,10 @@ def main():
     ap.add_argument("--spawn-check", action="store_true",
                     help="every rank prints its RANK/WORLD_SIZE/MASTER_* as one JSON line and exits (no GPU; tests)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.pmc == "on" and not args.full:
+        ap.error("--pmc on measures the roofline of the full report: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -351,7 +392,7 @@ def main():
     # the CPU baseline needs the oracle's own scene (its own region build, serial C);
     # start it now on one core so it overlaps the GPU part
     oracle_box = {}
-    want_cpu = (args.cpu_baseline == "auto" and rank == 0 and world == 1 and args.iso is None and args.spp == 1
+    want_cpu = (args.full and args.cpu_baseline == "auto" and rank == 0 and world == 1 and args.iso is None and args.spp == 1
                 and len(scene.fields) == 1 and not os.environ.get("EXA_BENCH_SHARD"))     # (a rehearsed shard is not a frame)
 
     def build_oracle():
@@ -506,9 +547,11 @@ def main():
             consumed[k].record(comm_stream)
 
     # work counters of this frame (instrumented kernel variant, frameID 0)
-    R.updateFrameID(0)
-    _, st = R.renderStats()
-    log("stats:", {k: v for k, v in st.items() if k not in ("kernel_ms", "rebuild_ms")})
+    st = None
+    if args.full:
+        R.updateFrameID(0)
+        _, st = R.renderStats()
+        log("stats:", {k: v for k, v in st.items() if k not in ("kernel_ms", "rebuild_ms")})
     # the first frames are synchronous in every mode: the launch-order feedback measures tile costs on a
     # synchronous frame and re-orders the launch
     for Rk in Rs:
@@ -546,12 +589,22 @@ def main():
     if use_dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    # the frame of the last timed step: rank 0's gathered frame, or the shard buffer that step rendered into (the frames
+    # rendered below overwrite shards[0]); written once the guard check below has passed
+    last_frame = None
+    if args.dump_outputs and rank == 0:
+        last_frame = (final if use_dist else shards[(frame_no[0] - 1) % len(shards)]).cpu().numpy()
     # after the timed region every handle renders one synchronous frame: a synchronous render reads the loop-guard flag
-    # (frames queued with async_ do not), so a guard that tripped inside the timed region fails the run here
+    # (frames queued with async_ do not), so a guard that tripped inside the timed region fails the run here.  Handle 0
+    # rendered its timed frames synchronously with one frame in flight; with several, --full renders it synchronously
+    # below (kernel time per launch), a plain run here.
     torch.cuda.synchronize()
-    for Rk in Rs[1:]:
+    for Rk in (Rs if F > 1 and not args.full else Rs[1:]):
         Rk.render(device_ptr=shards[0].data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
-    if F > 1:
+    if last_frame is not None:
+        names = dump_frame(args.dump_outputs, last_frame, W, H)
+        log(f"outputs of the last timed step: {', '.join(n + '.npy' for n in names)} in {args.dump_outputs}")
+    if F > 1 and args.full:
         # kernel time per launch (HIP events on the launch stream) on synchronous frames after the timed region: with
         # several frames in flight a launch shares the GPU with its neighbours and its own duration says little
         for _ in range(min(5, max(2, args.steps))):
@@ -562,7 +615,7 @@ def main():
     #      loop would see.  With one frame in flight the timed region above already is that; with several, measure it
     #      here with the critical tiles marched wide (wide_march = 1, the lone-frame default) ----
     latency_ms = None
-    if F > 1 and not os.environ.get("EXA_BENCH_NO_LATENCY"):      # (the PMC children below only need the timed region's frames)
+    if F > 1 and args.full and not os.environ.get("EXA_BENCH_NO_LATENCY"):      # (the PMC children below only need the timed region's frames)
         R.setOption("wide_march", 1)
         cur = torch.cuda.current_stream().cuda_stream
         for _ in range(3):                          # layout changed: cost feedback measures, re-orders, assigns wide tiles
@@ -603,7 +656,7 @@ def main():
     # the same frame with the basis sums in the reference's source order (option basis_form 0), lone synchronous frames: what
     # the default association (a numerics change within the stated tolerance) buys is then separable in the line
     kernel_ms_form0 = None
-    if basis_form == 1 and not os.environ.get("EXA_BENCH_NO_LATENCY"):
+    if basis_form == 1 and args.full and not os.environ.get("EXA_BENCH_NO_LATENCY"):
         cur = torch.cuda.current_stream().cuda_stream
         R.setOption("basis_form", 0)
         R.updateFrameID(0)
@@ -617,17 +670,17 @@ def main():
         R.render(device_ptr=shards[0].data_ptr(), stream=cur)          # shards[0] holds a frame of the default form again
 
     # aggregate per-rank work counters and kernel time
-    agg = torch.tensor([st["samples"], st["brick_visits"], st["corner_loads"], st["segments"], st["nodes_visited"],
-                        st["pixels"]], dtype=torch.float64, device=cdev)
-    kmax = torch.tensor([float(np.mean(kernel_ms))], dtype=torch.float64, device=cdev)
-    if use_dist:
-        dist.all_reduce(agg, op=dist.ReduceOp.SUM)
-        dist.all_reduce(kmax, op=dist.ReduceOp.MAX)
-    samples_total = float(agg[0].item())
+    if args.full:
+        agg = torch.tensor([st["samples"], st["brick_visits"], st["corner_loads"], st["segments"], st["nodes_visited"],
+                            st["pixels"]], dtype=torch.float64, device=cdev)
+        kmax = torch.tensor([float(np.mean(kernel_ms))], dtype=torch.float64, device=cdev)
+        if use_dist:
+            dist.all_reduce(agg, op=dist.ReduceOp.SUM)
+            dist.all_reduce(kmax, op=dist.ReduceOp.MAX)
+        samples_total = float(agg[0].item())
 
     if rank == 0:
         fps = args.steps / elapsed
-        k_ms = float(np.mean(kernel_ms))                   # this rank's launches (HIP events on the launch stream)
         cfg = scenes.CONFIGS[args.config]
         out = {
             "metric": f"frames/sec at {W}^2 DVR{'+iso' if args.iso is not None else ''}{'+AO' if args.ao else ''}"
@@ -637,7 +690,7 @@ def main():
             **({"rehearsal_of": f"rank {shard_rank} of a {shard_world}-GPU job, on one GPU; value is this rank's frame rate"} if rehearse else {}),
             "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "frames_in_flight": F,
-            "msamples_per_s": samples_total / 1e6 * fps * args.spp,
+            **({"msamples_per_s": samples_total / 1e6 * fps * args.spp} if args.full else {}),
             "config": {"workload": f"{args.config} (seed {cfg['seed']:#x} procedural AMR, scale {args.scale}"
                                    f"{', bricks from ' + os.path.basename(args.bricks_file) if args.bricks_file else ''}): "
                                    f"{scene.num_cells} cells / {scene.bricks7.shape[0]} bricks / "
@@ -656,65 +709,67 @@ def main():
                                  + (f", {'RCCL (nccl)' if backend == 'nccl' else backend} gather to rank 0"
                                     f"{', overlapped with the next frame' if pipelined else ''}" if use_dist else ""),
                        "backend": backend if use_dist else None,
-                       "samples_per_frame": samples_total, "kernel_ms_max_over_ranks": float(kmax.item())},
-            "latency_ms": latency_ms if latency_ms is not None else 1000.0 * elapsed / args.steps,
+                       **({"samples_per_frame": samples_total, "kernel_ms_max_over_ranks": float(kmax.item())} if args.full else {})},
+            **({"latency_ms": latency_ms if latency_ms is not None else 1000.0 * elapsed / args.steps} if args.full else {}),
         }
         if F > 1:
             out["ms_per_step_note"] = (f"elapsed / steps with {F} frames in flight — a throughput: the tail of one frame (its longest rays, few "
                                        "waves busy) overlaps the bulk of the next, so it can be BELOW roofline.kernel_ms, which is one lone "
                                        "synchronous launch, and below latency_ms (one frame at a time); every frame is rendered completely")
-        out["config"]["latency_ms"] = ("one frame at a time (march, gather, untile, host waits), wide march on: the figure "
-                                       "comparable with a 1-GPU line" if latency_ms is not None else "= ms_per_step (one frame in flight)")
-        # ---- roofline: the frame's launches against the resource that binds them.  No dense contraction on
-        #      this path (no MFMA) and the working set is cache-resident (HBM far from its peak), what limits the march is
-        #      vector-instruction issue: frac = measured wave64 VALU instructions / kernel time against 1024 SIMDs x one
-        #      VALU instruction per 2 cycles.  The HBM view (PMC bytes against 8 TB/s) and the useful-flop fraction stand
-        #      beside it.  SURVEY 8(d)'s byte formula counts what the LANES REQUEST (most of it served by L1/L2): it is kept
-        #      as requested_bytes and never turned into a fraction of the HBM peak. ----
-        B = algorithmic_bytes(st, st["pixels"], 0)         # per launch of this rank, frame 0
-        flops = useful_flops(st, not args.no_grad)
-        roof = {"bound": "valu_issue", "achieved": None, "peak": VALU_PEAK_GINSTR, "unit": "G wave-instr/s", "frac": None,
-                "traffic": None,
-                "kernel": ("renderFrameKdKernel" if args.accel else "renderFrameKernel")
-                          + (" + surfacePrepassKdKernel" if (args.iso is not None and args.accel) else ""),
-                "kernel_ms": k_ms,
-                **({"kernel_ms_basis_form0": kernel_ms_form0,
-                    "kernel_ms_basis_form0_note": "the same frame with option basis_form 0 (basis sums in the reference's source order, nothing "
-                                                  "fused), lone synchronous frames after the timed region: kernel_ms / this = what the default "
-                                                  "association contributes"} if kernel_ms_form0 is not None else {}),
-                "peak_note": "256 CUs x 4 SIMDs x 1 wave64 VALU instruction / 2 cycles at 2.4 GHz (MI355X_MICROARCH.md)",
-                "useful_flops_per_launch": flops,
-                "useful_flop_frac": flops / (k_ms * 1e-3) / (F32_VECTOR_PEAK_TFLOPS * 1e12),
-                "useful_flop_note": f"SURVEY 8(d) flop counts (60 per brick visit + 70 with derivatives, 40 per sample) / kernel time / "
-                                    f"{F32_VECTOR_PEAK_TFLOPS} TFLOP/s f32 vector peak (FMA = 2).  The counts are the REFERENCE's operations per call; "
-                                    + ("basis_form 1 reaches the same sums with 49 (fused) instead of 116 operations per visit, so this "
-                                       "fraction measures delivered reference work, not issued flops"
-                                       if basis_form == 1 else "basis_form 0 executes them unfused, one rounding each: 0.5 is its ceiling"),
-                "requested_bytes": B,
-                "requested_bytes_note": "SURVEY 8(d) formula: bytes the lanes request per launch (36 B per brick visit, 4 B per cell, 44 B "
-                                        "per segment, node bytes, 20 B per pixel); served mostly by L1/L2, NOT an HBM figure",
-                "requested_bytes_breakdown": {"brick_records_and_leaf_entries": 36 * st["brick_visits"],
-                                              "cell_scalars": 4 * st["corner_loads"],
-                                              "region_records": 44 * (st["segments"] + st["iso_segments"]),
-                                              "accel_nodes": st.get("node_bytes", 64) * st["nodes_visited"],
-                                              "framebuffer": 20 * st["pixels"]}}
-        out["roofline"] = roof
-        traffic_file = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        key = f"{args.config}@{args.scale}@{W}"
-        traffic = vi = None
-        stock = (world == 1 and not rehearse and args.iso is None and args.spp == 1 and not args.ao
-                 and args.camera == "default" and args.fields is None and not args.no_grad and not args.option
-                 and not args.bricks_file)   # what profiles/hbm_traffic.json was measured on
-        profiled = any(k.startswith("ROCPROF") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-        if args.pmc == "on" or (args.pmc == "auto" and args.cpu_baseline == "auto" and not profiled):
-            out["_pmc_child"] = True          # measured below, after the process group is gone
-        elif os.path.exists(traffic_file) and stock:
-            try:
-                tf = json.load(open(traffic_file))
-                traffic, vi = tf.get(key), tf.get(key + ":valu_wave_instructions")
-                roof["pmc_source"] = tf.get(key + ":note")
-            except Exception as e:  # noqa: BLE001
-                log(f"could not read {traffic_file}: {e}")
+        if args.full:
+            k_ms = float(np.mean(kernel_ms))                   # this rank's launches (HIP events on the launch stream)
+            out["config"]["latency_ms"] = ("one frame at a time (march, gather, untile, host waits), wide march on: the figure "
+                                           "comparable with a 1-GPU line" if latency_ms is not None else "= ms_per_step (one frame in flight)")
+            # ---- roofline: the frame's launches against the resource that binds them.  No dense contraction on
+            #      this path (no MFMA) and the working set is cache-resident (HBM far from its peak), what limits the march is
+            #      vector-instruction issue: frac = measured wave64 VALU instructions / kernel time against 1024 SIMDs x one
+            #      VALU instruction per 2 cycles.  The HBM view (PMC bytes against 8 TB/s) and the useful-flop fraction stand
+            #      beside it.  SURVEY 8(d)'s byte formula counts what the LANES REQUEST (most of it served by L1/L2): it is kept
+            #      as requested_bytes and never turned into a fraction of the HBM peak. ----
+            B = algorithmic_bytes(st, st["pixels"], 0)         # per launch of this rank, frame 0
+            flops = useful_flops(st, not args.no_grad)
+            roof = {"bound": "valu_issue", "achieved": None, "peak": VALU_PEAK_GINSTR, "unit": "G wave-instr/s", "frac": None,
+                    "traffic": None,
+                    "kernel": ("renderFrameKdKernel" if args.accel else "renderFrameKernel")
+                              + (" + surfacePrepassKdKernel" if (args.iso is not None and args.accel) else ""),
+                    "kernel_ms": k_ms,
+                    **({"kernel_ms_basis_form0": kernel_ms_form0,
+                        "kernel_ms_basis_form0_note": "the same frame with option basis_form 0 (basis sums in the reference's source order, nothing "
+                                                      "fused), lone synchronous frames after the timed region: kernel_ms / this = what the default "
+                                                      "association contributes"} if kernel_ms_form0 is not None else {}),
+                    "peak_note": "256 CUs x 4 SIMDs x 1 wave64 VALU instruction / 2 cycles at 2.4 GHz (MI355X_MICROARCH.md)",
+                    "useful_flops_per_launch": flops,
+                    "useful_flop_frac": flops / (k_ms * 1e-3) / (F32_VECTOR_PEAK_TFLOPS * 1e12),
+                    "useful_flop_note": f"SURVEY 8(d) flop counts (60 per brick visit + 70 with derivatives, 40 per sample) / kernel time / "
+                                        f"{F32_VECTOR_PEAK_TFLOPS} TFLOP/s f32 vector peak (FMA = 2).  The counts are the REFERENCE's operations per call; "
+                                        + ("basis_form 1 reaches the same sums with 49 (fused) instead of 116 operations per visit, so this "
+                                           "fraction measures delivered reference work, not issued flops"
+                                           if basis_form == 1 else "basis_form 0 executes them unfused, one rounding each: 0.5 is its ceiling"),
+                    "requested_bytes": B,
+                    "requested_bytes_note": "SURVEY 8(d) formula: bytes the lanes request per launch (36 B per brick visit, 4 B per cell, 44 B "
+                                            "per segment, node bytes, 20 B per pixel); served mostly by L1/L2, NOT an HBM figure",
+                    "requested_bytes_breakdown": {"brick_records_and_leaf_entries": 36 * st["brick_visits"],
+                                                  "cell_scalars": 4 * st["corner_loads"],
+                                                  "region_records": 44 * (st["segments"] + st["iso_segments"]),
+                                                  "accel_nodes": st.get("node_bytes", 64) * st["nodes_visited"],
+                                                  "framebuffer": 20 * st["pixels"]}}
+            out["roofline"] = roof
+            traffic_file = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            key = f"{args.config}@{args.scale}@{W}"
+            traffic = vi = None
+            stock = (world == 1 and not rehearse and args.iso is None and args.spp == 1 and not args.ao
+                     and args.camera == "default" and args.fields is None and not args.no_grad and not args.option
+                     and not args.bricks_file)   # what profiles/hbm_traffic.json was measured on
+            profiled = any(k.startswith("ROCPROF") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
+            if args.pmc == "on" or (args.pmc == "auto" and args.cpu_baseline == "auto" and not profiled):
+                out["_pmc_child"] = True          # measured below, after the process group is gone
+            elif os.path.exists(traffic_file) and stock:
+                try:
+                    tf = json.load(open(traffic_file))
+                    traffic, vi = tf.get(key), tf.get(key + ":valu_wave_instructions")
+                    roof["pmc_source"] = tf.get(key + ":note")
+                except Exception as e:  # noqa: BLE001
+                    log(f"could not read {traffic_file}: {e}")
         if args.dump:
             img = (final if use_dist else shards[0]).cpu().numpy().view(np.uint32).reshape(H, W)
             harness.write_png(args.dump, img)
@@ -781,77 +836,78 @@ def main():
         Rk.close()
 
     if rank == 0:
-        roof = out["roofline"]
-        if out.pop("_pmc_child", False):
-            # live counters of this very workload, after this process has left the process group and freed its scene
-            # copies: fresh children of rank 0 (program after `--` = the python executable) render what THIS rank rendered
-            # (its shard of the frame for a multi-GPU job) under rocprofv3 --pmc, counters only
-            child = ["--config", args.config, "--scale", str(args.scale), "--size", str(W), "--steps", "2", "--warmup", "1",
-                     "--tile-order", str(args.tile_order), "--accel", str(args.accel), "--cpu-baseline", "off", "--pmc", "off",
-                     "--in-flight", str(F), "--spp", str(args.spp), "--camera", args.camera]
-            child += ["--no-grad"] if args.no_grad else []
-            child += ["--basis-form", str(args.basis_form)]
-            child += ["--fields", str(args.fields)] if args.fields is not None else []
-            child += ["--bricks-file", os.path.abspath(args.bricks_file)] if args.bricks_file else []
-            child += ["--iso", str(args.iso)] if args.iso is not None else []
-            child += ["--ao"] if args.ao else []
-            for kv in args.option:
-                child += ["--option", kv]
-            extra = {"EXA_BENCH_SHARD": f"{shard_rank},{shard_world}"} if shard_world > 1 else {}
-            t = time.perf_counter()
-            # the measured line so far goes to stderr first: if a PMC child is interrupted from outside, the frame rate is not lost
-            log("result before the live PMC passes (roofline.achieved / frac / traffic pending): " + json.dumps(out))
-            vals, n = live_pmc(child, extra_env=extra, frames=2 * args.spp)      # the child times 2 steps of spp frames each
-            shard_note = " (the shard of this rank)" if shard_world > 1 else ""
-            if vals:
-                fetch = sum(d.get("FETCH_SIZE", 0.0) for d in vals.values())
-                write = sum(d.get("WRITE_SIZE", 0.0) for d in vals.values())
-                # gfx950 counts a 128-B read request as 64 B in FETCH_SIZE (MI355X_MICROARCH.md): 2 * FETCH_SIZE is the upper bound
-                traffic = (2.0 * fetch + write) * 1024.0
-                vi = sum(d.get("SQ_INSTS_VALU", 0.0) for d in vals.values())
-                roof["pmc_source"] = (f"live: rocprofv3 --pmc passes {[' '.join(c) for c in PMC_PASSES]} run by this bench.py on the same "
-                                      f"workload{shard_note} ({n} frames averaged, "
-                                      f"{time.perf_counter() - t:.0f}s); traffic = 2*FETCH_SIZE({fetch:.6g} KiB) + WRITE_SIZE({write:.6g} KiB)")
-                if len(vals) > 1:
-                    roof["per_kernel"] = {cls: {"valu_wave_instructions": d.get("SQ_INSTS_VALU"),
-                                                "hbm_bytes": (2.0 * d.get("FETCH_SIZE", 0.0) + d.get("WRITE_SIZE", 0.0)) * 1024.0}
-                                          for cls, d in vals.items()}
+        if args.full:
+            roof = out["roofline"]
+            if out.pop("_pmc_child", False):
+                # live counters of this very workload, after this process has left the process group and freed its scene
+                # copies: fresh children of rank 0 (program after `--` = the python executable) render what THIS rank rendered
+                # (its shard of the frame for a multi-GPU job) under rocprofv3 --pmc, counters only
+                child = ["--config", args.config, "--scale", str(args.scale), "--size", str(W), "--steps", "2", "--warmup", "1",
+                         "--tile-order", str(args.tile_order), "--accel", str(args.accel), "--cpu-baseline", "off", "--pmc", "off",
+                         "--in-flight", str(F), "--spp", str(args.spp), "--camera", args.camera]
+                child += ["--no-grad"] if args.no_grad else []
+                child += ["--basis-form", str(args.basis_form)]
+                child += ["--fields", str(args.fields)] if args.fields is not None else []
+                child += ["--bricks-file", os.path.abspath(args.bricks_file)] if args.bricks_file else []
+                child += ["--iso", str(args.iso)] if args.iso is not None else []
+                child += ["--ao"] if args.ao else []
+                for kv in args.option:
+                    child += ["--option", kv]
+                extra = {"EXA_BENCH_SHARD": f"{shard_rank},{shard_world}"} if shard_world > 1 else {}
+                t = time.perf_counter()
+                # the measured line so far goes to stderr first: if a PMC child is interrupted from outside, the frame rate is not lost
+                log("result before the live PMC passes (roofline.achieved / frac / traffic pending): " + json.dumps(out))
+                vals, n = live_pmc(child, extra_env=extra, frames=2 * args.spp)      # the child times 2 steps of spp frames each
+                shard_note = " (the shard of this rank)" if shard_world > 1 else ""
+                if vals:
+                    fetch = sum(d.get("FETCH_SIZE", 0.0) for d in vals.values())
+                    write = sum(d.get("WRITE_SIZE", 0.0) for d in vals.values())
+                    # gfx950 counts a 128-B read request as 64 B in FETCH_SIZE (MI355X_MICROARCH.md): 2 * FETCH_SIZE is the upper bound
+                    traffic = (2.0 * fetch + write) * 1024.0
+                    vi = sum(d.get("SQ_INSTS_VALU", 0.0) for d in vals.values())
+                    roof["pmc_source"] = (f"live: rocprofv3 --pmc passes {[' '.join(c) for c in PMC_PASSES]} run by this bench.py on the same "
+                                          f"workload{shard_note} ({n} frames averaged, "
+                                          f"{time.perf_counter() - t:.0f}s); traffic = 2*FETCH_SIZE({fetch:.6g} KiB) + WRITE_SIZE({write:.6g} KiB)")
+                    if len(vals) > 1:
+                        roof["per_kernel"] = {cls: {"valu_wave_instructions": d.get("SQ_INSTS_VALU"),
+                                                    "hbm_bytes": (2.0 * d.get("FETCH_SIZE", 0.0) + d.get("WRITE_SIZE", 0.0)) * 1024.0}
+                                              for cls, d in vals.items()}
+                else:
+                    log(f"live PMC pass not available ({n})")
+                    roof["pmc_live_error"] = str(n)
+                    if os.path.exists(traffic_file) and stock:
+                        tf = json.load(open(traffic_file))
+                        traffic, vi = tf.get(key), tf.get(key + ":valu_wave_instructions")
+                        roof["pmc_source"] = tf.get(key + ":note")
+            k_s = roof["kernel_ms"] * 1e-3
+            roof["traffic"] = traffic
+            # what the march can touch at all (device copies the frame reads): traffic / resident = how often a byte comes from HBM again
+            nf, nleaf = len(scene.fields), int(prep.scene.leafListSize)
+            res = {"cell_scalars": scene.num_cells * 4 * nf,
+                   "interleaved_copy_of_the_primary_channels": scene.num_cells * 4 * nf if 2 <= nf <= 4 else 0,
+                   "march_headers_along_the_leaf_list": nleaf * 32,
+                   "kd_nodes_and_march_copy": 2 * int(prep.scene.numKdNodes) * 16,
+                   "region_info": int(prep.scene.numRegions) * 16}
+            if st.get("walk_leaf_visits", 0) > 0:
+                # the frame took the rope walk: 64 B per leaf (regions + gaps = empty child slots of the kd-tree) and the 16-B nodes
+                # behind the links are what it reads instead of the kd-tree's march copy
+                kdn = prep.kd_nodes()
+                gaps = int((kdn["left"] == binding.KD_EMPTY).sum() + (kdn["right"] == binding.KD_EMPTY).sum()) if len(kdn) else 0
+                res["rope_leaves_and_nodes"] = (int(prep.scene.numRegions) + gaps) * 64 + int(prep.scene.numKdNodes) * 16
+            roof["hbm_resident_bytes"] = int(sum(res.values()))
+            roof["hbm_resident_breakdown"] = res
+            if traffic:
+                roof["traffic_over_resident"] = traffic / roof["hbm_resident_bytes"]
+            if traffic:
+                gbs = traffic / k_s / 1e9
+                roof["hbm_measured"] = {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS}
+                roof["requested_over_fetched"] = roof["requested_bytes"] / traffic
+            if vi:
+                roof["achieved"] = vi / k_s / 1e9
+                roof["frac"] = roof["achieved"] / VALU_PEAK_GINSTR
+                roof["valu_wave_instructions_per_launch"] = vi
             else:
-                log(f"live PMC pass not available ({n})")
-                roof["pmc_live_error"] = str(n)
-                if os.path.exists(traffic_file) and stock:
-                    tf = json.load(open(traffic_file))
-                    traffic, vi = tf.get(key), tf.get(key + ":valu_wave_instructions")
-                    roof["pmc_source"] = tf.get(key + ":note")
-        k_s = roof["kernel_ms"] * 1e-3
-        roof["traffic"] = traffic
-        # what the march can touch at all (device copies the frame reads): traffic / resident = how often a byte comes from HBM again
-        nf, nleaf = len(scene.fields), int(prep.scene.leafListSize)
-        res = {"cell_scalars": scene.num_cells * 4 * nf,
-               "interleaved_copy_of_the_primary_channels": scene.num_cells * 4 * nf if 2 <= nf <= 4 else 0,
-               "march_headers_along_the_leaf_list": nleaf * 32,
-               "kd_nodes_and_march_copy": 2 * int(prep.scene.numKdNodes) * 16,
-               "region_info": int(prep.scene.numRegions) * 16}
-        if st.get("walk_leaf_visits", 0) > 0:
-            # the frame took the rope walk: 64 B per leaf (regions + gaps = empty child slots of the kd-tree) and the 16-B nodes
-            # behind the links are what it reads instead of the kd-tree's march copy
-            kdn = prep.kd_nodes()
-            gaps = int((kdn["left"] == binding.KD_EMPTY).sum() + (kdn["right"] == binding.KD_EMPTY).sum()) if len(kdn) else 0
-            res["rope_leaves_and_nodes"] = (int(prep.scene.numRegions) + gaps) * 64 + int(prep.scene.numKdNodes) * 16
-        roof["hbm_resident_bytes"] = int(sum(res.values()))
-        roof["hbm_resident_breakdown"] = res
-        if traffic:
-            roof["traffic_over_resident"] = traffic / roof["hbm_resident_bytes"]
-        if traffic:
-            gbs = traffic / k_s / 1e9
-            roof["hbm_measured"] = {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS}
-            roof["requested_over_fetched"] = roof["requested_bytes"] / traffic
-        if vi:
-            roof["achieved"] = vi / k_s / 1e9
-            roof["frac"] = roof["achieved"] / VALU_PEAK_GINSTR
-            roof["valu_wave_instructions_per_launch"] = vi
-        else:
-            roof["note"] = "no counters for this configuration: achieved / frac are not reported rather than estimated"
+                roof["note"] = "no counters for this configuration: achieved / frac are not reported rather than estimated"
         print(json.dumps(out), flush=True)
 
 

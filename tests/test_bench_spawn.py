@@ -7,6 +7,8 @@ import subprocess
 import sys
 import time
 
+import pytest
+
 from common import ROOT
 
 BENCH = os.path.join(ROOT, "bench.py")
@@ -146,3 +148,75 @@ def test_pmc_child_that_the_profiler_refuses_is_ended_at_once(tmp_path, monkeypa
     vals, why = bench.live_pmc(["--steps", "1"], seconds=60.0, frames=1)
     assert vals is None and "refused by the profiler" in why and "error code 38" in why
     assert time.time() - t < 20.0
+
+
+def test_dump_outputs_writes_the_last_frame_as_float32_within_the_size_cap(tmp_path):
+    """bench.py --dump-outputs: a small frame whole, [H, W, 4] float32 channels; a 2048^2 frame as a seeded sample of its
+    pixels, the same pixels on every call, and under 64 MB in all"""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 2 ** 32, size=(64, 96), dtype=np.uint32)
+    assert bench.dump_frame(str(tmp_path / "s"), small.view(np.int32), 96, 64) == ["frame_rgba"]
+    a = np.load(tmp_path / "s" / "frame_rgba.npy")
+    assert a.dtype == np.float32 and a.shape == (64, 96, 4)
+    for c in range(4):
+        assert np.array_equal(a[..., c], (small >> (8 * c)) & 255)
+    big = rng.integers(0, 2 ** 32, size=(2048, 2048), dtype=np.uint32)
+    for d in ("b1", "b2"):
+        assert bench.dump_frame(str(tmp_path / d), big.view(np.int32), 2048, 2048) == ["frame_pixel_index", "frame_rgba"]
+    assert sum(f.stat().st_size for f in (tmp_path / "b1").iterdir()) <= 64 * 10 ** 6
+    idx, rgba = np.load(tmp_path / "b1" / "frame_pixel_index.npy"), np.load(tmp_path / "b1" / "frame_rgba.npy")
+    assert idx.dtype == np.float64 and rgba.dtype == np.float32 and rgba.shape == (len(idx), 4) and len(idx) > 10 ** 6
+    assert np.array_equal(idx, np.load(tmp_path / "b2" / "frame_pixel_index.npy"))
+    assert np.array_equal(rgba, np.load(tmp_path / "b2" / "frame_rgba.npy"))
+    picked = big.reshape(-1)[idx.astype(np.int64)]
+    for c in range(4):
+        assert np.array_equal(rgba[:, c], (picked >> (8 * c)) & 255)
+
+
+def test_pmc_on_without_full_is_an_error():
+    """the live PMC passes belong to the full report: `--pmc on` in a plain run says so instead of being ignored"""
+    out = subprocess.run([sys.executable, BENCH, "--pmc", "on"], env=_env(), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 2 and "--full" in out.stderr
+
+
+def _read_png(path):
+    """RGBA8 rows of a harness.write_png file (filter 0 on every row), top row first"""
+    import struct
+    import zlib
+    import numpy as np
+    png, pos, idat = open(path, "rb").read(), 8, b""
+    while pos < len(png):
+        n, typ = struct.unpack(">I4s", png[pos:pos + 8])
+        if typ == b"IHDR":
+            W, H = struct.unpack(">II", png[pos + 8:pos + 16])
+        if typ == b"IDAT":
+            idat += png[pos + 8:pos + 8 + n]
+        pos += 12 + n
+    rows = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(H, 1 + 4 * W)
+    assert (rows[:, 0] == 0).all()
+    return rows[:, 1:].reshape(H, W, 4)
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_frame_of_the_last_timed_step(tmp_path):
+    """a plain run: the headline fields, no --full figures, --steps honoured, and --dump-outputs holds the frame of the last
+    timed step.  One warm-up and one timed step with four frames in flight put that frame in shard buffer 1 (buffers 2 and 3
+    are never rendered into), the --dump PNG is the same frame rendered again after the timed region."""
+    import numpy as np
+    png = tmp_path / "f.png"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "1", "--warmup", "1", "--scale", "0.12", "--size", "512",
+                        "--dump-outputs", str(tmp_path / "out"), "--dump", str(png)], env=_env(), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 1 and line["frames_in_flight"] == 4
+    assert not any(k in line for k in ("roofline", "cpu_baseline", "latency_ms", "msamples_per_s"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame_rgba.npy"]
+    dumped = np.load(tmp_path / "out" / "frame_rgba.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (512, 512, 4)
+    assert (dumped[..., 3] > 0).any()
+    assert np.array_equal(dumped, _read_png(png)[::-1].astype(np.float32))

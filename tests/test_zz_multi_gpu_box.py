@@ -52,7 +52,7 @@ def test_bench_two_ranks_over_rccl_gives_the_one_rank_frame():
         for n in (1, 2):
             png = os.path.join(d, f"f{n}.png")
             r = subprocess.run([sys.executable, bench, "--gpus", str(n), "--steps", "3", "--warmup", "1", "--scale", "0.12", "--size", "512",
-                                "--cpu-baseline", "off", "--pmc", "off", "--dump", png], env=env, capture_output=True, text=True, timeout=900)
+                                "--full", "--cpu-baseline", "off", "--pmc", "off", "--dump", png], env=env, capture_output=True, text=True, timeout=900)
             assert r.returncode == 0, r.stderr[-2000:]
             lines[n] = (json.loads(r.stdout.strip().splitlines()[-1]), open(png, "rb").read())
         assert lines[2][0]["n_ranks_seen"] == 2 and lines[2][0]["n_gpus"] == 2 and lines[2][0]["config"]["backend"] == "nccl"

@@ -38,7 +38,7 @@ else
   for rep in 1 2; do
     for so in "$LIBS"/libexa_hip_*.so; do
       name=$(basename "$so" .so); name=${name#libexa_hip_}
-      EXA_HIP_LIB="$so" timeout -k 10 120 python3 "$ROOT/bench.py" --cpu-baseline off --pmc off --in-flight 1 --steps 20 --warmup 3 "$@" > "$OUT/$name.$rep.json" 2> "$OUT/$name.$rep.err" \
+      EXA_HIP_LIB="$so" timeout -k 10 120 python3 "$ROOT/bench.py" --full --cpu-baseline off --pmc off --in-flight 1 --steps 20 --warmup 3 "$@" > "$OUT/$name.$rep.json" 2> "$OUT/$name.$rep.err" \
         && python3 -c "import json,sys; d=json.loads(open('$OUT/$name.$rep.json').read().strip().splitlines()[-1]); print('%-12s rep $rep  %.3f ms/frame  kernel %.3f ms  %.2f fps' % ('$name', d['ms_per_step'], d['roofline']['kernel_ms'], d['value']))" | tee -a "$OUT/results.txt" \
         || { echo "$name failed" | tee -a "$OUT/results.txt"; tail -3 "$OUT/$name.$rep.err"; }
     done

@@ -4,8 +4,8 @@ set -o pipefail
 O=gpurun_out
 python -m pytest tests/test_gpu_interleave.py tests/test_gpu_parity.py tests/test_gpu_configs.py -x -q > $O/r03_e_tests.log 2>&1; tail -3 $O/r03_e_tests.log
 for sp in 1 0; do
-  EXA_HIP_VERBOSE=1 python bench.py --config c3_gear --iso 0.5 --steps 20 --cpu-baseline off --pmc off --option prepass_split=$sp > $O/r03_e_c3iso_sp$sp.json 2> $O/r03_e_c3iso_sp$sp.err; grep -h "pre-pass costs" $O/r03_e_c3iso_sp$sp.err | tail -1
-  EXA_HIP_VERBOSE=1 python bench.py --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --cpu-baseline off --pmc off --option prepass_split=$sp > $O/r03_e_c5_sp$sp.json 2> $O/r03_e_c5_sp$sp.err; grep -h "pre-pass costs" $O/r03_e_c5_sp$sp.err | tail -1
+  EXA_HIP_VERBOSE=1 python bench.py --full --config c3_gear --iso 0.5 --steps 20 --cpu-baseline off --pmc off --option prepass_split=$sp > $O/r03_e_c3iso_sp$sp.json 2> $O/r03_e_c3iso_sp$sp.err; grep -h "pre-pass costs" $O/r03_e_c3iso_sp$sp.err | tail -1
+  EXA_HIP_VERBOSE=1 python bench.py --full --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --cpu-baseline off --pmc off --option prepass_split=$sp > $O/r03_e_c5_sp$sp.json 2> $O/r03_e_c5_sp$sp.err; grep -h "pre-pass costs" $O/r03_e_c5_sp$sp.err | tail -1
 done
 python - <<'PY'
 import json,glob

@@ -8,9 +8,9 @@ python gpu_fuzz.py 0 199 --many --keep-going > ../$O/r03_f_fuzz_many.log 2>&1; t
 python gpu_fuzz.py 3300 3499 --rich --keep-going > ../$O/r03_f_fuzz_rich.log 2>&1; tail -2 ../$O/r03_f_fuzz_rich.log
 python gpu_fuzz.py 1000 1199 --keep-going > ../$O/r03_f_fuzz_plain.log 2>&1; tail -2 ../$O/r03_f_fuzz_plain.log
 cd ..
-python bench.py --config c3_gear --iso 0.5 --steps 20 --cpu-baseline off --pmc on > $O/r03_f_c3iso.json 2> $O/r03_f_c3iso.err
-python bench.py --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --cpu-baseline off --pmc on > $O/r03_f_c5.json 2> $O/r03_f_c5.err
-python bench.py --config c2_lanl --size 1024 --steps 50 --cpu-baseline off --pmc on > $O/r03_f_c2.json 2> $O/r03_f_c2.err
+python bench.py --full --config c3_gear --iso 0.5 --steps 20 --cpu-baseline off --pmc on > $O/r03_f_c3iso.json 2> $O/r03_f_c3iso.err
+python bench.py --full --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --cpu-baseline off --pmc on > $O/r03_f_c5.json 2> $O/r03_f_c5.err
+python bench.py --full --config c2_lanl --size 1024 --steps 50 --cpu-baseline off --pmc on > $O/r03_f_c2.json 2> $O/r03_f_c2.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob("gpurun_out/r03_f_c*.json")):

@@ -4,8 +4,8 @@ O=gpurun_out
 python -m pytest tests/test_gpu_interleave.py -x -q > $O/r03_h_tests.log 2>&1; tail -2 $O/r03_h_tests.log
 (cd tests && python gpu_fuzz_sched.py 300 339 --keep-going > ../$O/r03_h_fuzz_sched.log 2>&1; tail -1 ../$O/r03_h_fuzz_sched.log)
 for d in 1 0; do
-  python bench.py --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --cpu-baseline off --pmc off --option ao_defer=$d > $O/r03_h_c5_defer$d.json 2> $O/r03_h_c5_defer$d.err
-  python bench.py --config c3_gear --iso 0.5 --ao --steps 20 --cpu-baseline off --pmc off --option ao_defer=$d > $O/r03_h_c3isoao_defer$d.json 2> $O/r03_h_c3isoao_defer$d.err
+  python bench.py --full --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --cpu-baseline off --pmc off --option ao_defer=$d > $O/r03_h_c5_defer$d.json 2> $O/r03_h_c5_defer$d.err
+  python bench.py --full --config c3_gear --iso 0.5 --ao --steps 20 --cpu-baseline off --pmc off --option ao_defer=$d > $O/r03_h_c3isoao_defer$d.json 2> $O/r03_h_c3isoao_defer$d.err
 done
 python - <<'PY'
 import json,glob

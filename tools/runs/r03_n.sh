@@ -15,5 +15,5 @@ run sched gpu_fuzz_sched.py 20000 20399
 run state gpu_fuzz_state.py 20000 20199
 run tracer gpu_fuzz_tracer.py 20000 20199
 cd ..
-python bench.py > $O/r03_n_bench.json 2> $O/r03_n_bench.err; tail -c 400 $O/r03_n_bench.json; echo
+python bench.py --full > $O/r03_n_bench.json 2> $O/r03_n_bench.err; tail -c 400 $O/r03_n_bench.json; echo
 echo done

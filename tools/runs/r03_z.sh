@@ -2,10 +2,10 @@
 # round 3, final reference measurements (burst priority, 256 cost classes)
 set -o pipefail
 O=gpurun_out
-python bench.py > $O/r03_z_bench.json 2> $O/r03_z_bench.err; tail -c 300 $O/r03_z_bench.json; echo
+python bench.py --full > $O/r03_z_bench.json 2> $O/r03_z_bench.err; tail -c 300 $O/r03_z_bench.json; echo
 bash tools/config_timeline.sh $O/r03_z_tl_c4 --steps 10 --pmc off
 bash tools/pmc_run.sh $O/r03_z_pmc_c4 > $O/r03_z_pmc_c4.txt 2>&1; grep -E "^==|SQ_INSTS_VALU |lane util|WAVE_CYCLES|FETCH_SIZE .*GB|L2 hit|L1 miss" $O/r03_z_pmc_c4.txt | head -24
-b() { name=$1; shift; python bench.py --cpu-baseline off --pmc on "$@" > $O/r03_z_$name.json 2> $O/r03_z_$name.err || tail -3 $O/r03_z_$name.err; }
+b() { name=$1; shift; python bench.py --full --cpu-baseline off --pmc on "$@" > $O/r03_z_$name.json 2> $O/r03_z_$name.err || tail -3 $O/r03_z_$name.err; }
 b c2 --config c2_lanl --size 1024 --steps 50
 b c3iso --config c3_gear --iso 0.5 --steps 20
 b c3 --config c3_gear --steps 20

@@ -5,9 +5,9 @@ set -o pipefail
 O=gpurun_out
 python -m pytest tests/test_gpu_parity.py -x -q -k "per_axis" > $O/r04_a_tests.log 2>&1; tail -3 $O/r04_a_tests.log
 for rep in 1 2; do for f in 0 1; do
-  python bench.py --steps 20 --cpu-baseline off --pmc off --basis-form $f > $O/r04_a_bench_f$f.$rep.json 2> $O/r04_a_bench_f$f.$rep.err || tail -5 $O/r04_a_bench_f$f.$rep.err
+  python bench.py --full --steps 20 --cpu-baseline off --pmc off --basis-form $f > $O/r04_a_bench_f$f.$rep.json 2> $O/r04_a_bench_f$f.$rep.err || tail -5 $O/r04_a_bench_f$f.$rep.err
 done; done
-python bench.py --steps 20 --pmc off --basis-form 1 > $O/r04_a_bench_f1_cpu.json 2> $O/r04_a_bench_f1_cpu.err || tail -5 $O/r04_a_bench_f1_cpu.err
+python bench.py --full --steps 20 --pmc off --basis-form 1 > $O/r04_a_bench_f1_cpu.json 2> $O/r04_a_bench_f1_cpu.err || tail -5 $O/r04_a_bench_f1_cpu.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob("gpurun_out/r04_a_bench_f*.json")):

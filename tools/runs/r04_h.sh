@@ -2,7 +2,7 @@
 # round 4: the other configurations with the per-axis basis sums (and the source order beside it where it is quick)
 set -o pipefail
 O=gpurun_out
-b() { name=$1; shift; python bench.py --cpu-baseline off --pmc off "$@" > $O/r04_h_$name.json 2> $O/r04_h_$name.err || tail -3 $O/r04_h_$name.err; }
+b() { name=$1; shift; python bench.py --full --cpu-baseline off --pmc off "$@" > $O/r04_h_$name.json 2> $O/r04_h_$name.err || tail -3 $O/r04_h_$name.err; }
 for f in 1 0; do
 b c2_f$f --config c2_lanl --size 1024 --steps 50 --basis-form $f
 b c3iso_f$f --config c3_gear --iso 0.5 --steps 20 --basis-form $f

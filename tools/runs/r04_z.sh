@@ -2,10 +2,10 @@
 # round 4, reference measurements of the committed state
 set -o pipefail
 O=gpurun_out
-python bench.py > $O/r04_z_bench.json 2> $O/r04_z_bench.err; tail -c 400 $O/r04_z_bench.json; echo
+python bench.py --full > $O/r04_z_bench.json 2> $O/r04_z_bench.err; tail -c 400 $O/r04_z_bench.json; echo
 bash tools/config_timeline.sh $O/r04_z_tl_c4 --steps 10 --pmc off | cut -c1-200
 bash tools/pmc_run.sh $O/r04_z_pmc_c4 --pmc off > $O/r04_z_pmc_c4.txt 2>&1; grep -E "^==|SQ_INSTS_VALU |lane util|WAVE_CYCLES|FETCH_SIZE .*GB|L2 hit|L1 miss" $O/r04_z_pmc_c4.txt | head -24
-b() { name=$1; shift; python bench.py --cpu-baseline off --pmc on "$@" > $O/r04_z_$name.json 2> $O/r04_z_$name.err || tail -3 $O/r04_z_$name.err; }
+b() { name=$1; shift; python bench.py --full --cpu-baseline off --pmc on "$@" > $O/r04_z_$name.json 2> $O/r04_z_$name.err || tail -3 $O/r04_z_$name.err; }
 b c2 --config c2_lanl --size 1024 --steps 50
 b c3iso --config c3_gear --iso 0.5 --steps 20
 b c3 --config c3_gear --steps 20
@@ -24,7 +24,7 @@ for f in sorted(glob.glob("gpurun_out/r04_z_*.json")):
 PY
 EXA_BASIS_FORM=1 python tests/gpu_diag.py > $O/r04_z_diag.txt 2>&1; tail -12 $O/r04_z_diag.txt
 python tests/gpu_shard_scaling.py 1.0 4 > $O/r04_z_shard_scaling.txt 2>&1; tail -8 $O/r04_z_shard_scaling.txt
-EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,8 python bench.py --steps 20 --cpu-baseline off > $O/r04_z_rank0of8_nccl.json 2> $O/r04_z_rank0of8_nccl.err || tail -5 $O/r04_z_rank0of8_nccl.err
+EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,8 python bench.py --full --steps 20 --cpu-baseline off > $O/r04_z_rank0of8_nccl.json 2> $O/r04_z_rank0of8_nccl.err || tail -5 $O/r04_z_rank0of8_nccl.err
 python -c "
 import json; d=json.loads(open('gpurun_out/r04_z_rank0of8_nccl.json').read().strip().splitlines()[-1]); print('rank 0 of 8 rehearsal: %.3f ms/frame (F=%d), latency %.3f ms' % (d['ms_per_step'], d['frames_in_flight'], d['latency_ms']))"
 echo done

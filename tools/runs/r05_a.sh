@@ -6,7 +6,7 @@ stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"
 timeout -k 10 120 tools/micro/div_exact 4000 > $O/r05_a_div.log 2>&1; stop $?; cat $O/r05_a_div.log
 timeout -k 10 420 python tests/gpu_rope_quick.py > $O/r05_a_quick.log 2>&1; stop $?; grep -c "ok=True" $O/r05_a_quick.log; grep -E "ok=False|: False|FAILURES|Error|error" $O/r05_a_quick.log | head -20
 for w in 1 2; do
-  EXA_HIP_VERBOSE=1 timeout -k 10 300 python bench.py --steps 20 --cpu-baseline off --pmc off --in-flight 1 --option walk=$w > $O/r05_a_w$w.json 2> $O/r05_a_w$w.err; stop $?
+  EXA_HIP_VERBOSE=1 timeout -k 10 300 python bench.py --full --steps 20 --cpu-baseline off --pmc off --in-flight 1 --option walk=$w > $O/r05_a_w$w.json 2> $O/r05_a_w$w.err; stop $?
   python - <<PY
 import json
 try:

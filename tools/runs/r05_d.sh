@@ -5,7 +5,7 @@ O=gpurun_out
 stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"; exit "$rc"; fi; }
 timeout -k 10 420 python tests/gpu_rope_quick.py > $O/r05_d_quick.log 2>&1; rc=$?; stop $rc; grep -c "ok=True" $O/r05_d_quick.log; grep -E "ok=False|: False|FAILURES|Error|error" $O/r05_d_quick.log | head -20
 [ $rc -ne 0 ] && exit $rc
-b() { name=$1; shift; timeout -k 10 400 python bench.py --cpu-baseline off --pmc off --in-flight 1 "$@" > $O/r05_d_$name.json 2> $O/r05_d_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_d_$name.err; }
+b() { name=$1; shift; timeout -k 10 400 python bench.py --full --cpu-baseline off --pmc off --in-flight 1 "$@" > $O/r05_d_$name.json 2> $O/r05_d_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_d_$name.err; }
 for w in 1 2; do
   b c4_w$w --steps 20 --option walk=$w
   b c3_w$w --config c3_gear --steps 20 --option walk=$w

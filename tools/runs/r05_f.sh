@@ -7,7 +7,7 @@ stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -x -q -k "ao or iso or mesh or contour" > $O/r05_f_parity_surf.log 2>&1; rc=$?; stop $rc; tail -3 $O/r05_f_parity_surf.log
 [ $rc -ne 0 ] && exit $rc
-b() { name=$1; shift; timeout -k 10 500 python bench.py --cpu-baseline off --pmc off --in-flight 1 "$@" > $O/r05_f_$name.json 2> $O/r05_f_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_f_$name.err; }
+b() { name=$1; shift; timeout -k 10 500 python bench.py --full --cpu-baseline off --pmc off --in-flight 1 "$@" > $O/r05_f_$name.json 2> $O/r05_f_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_f_$name.err; }
 for ov in 0 1; do
   b c5_ov$ov --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 --option ao_overlap=$ov
   b c3isoao_ov$ov --config c3_gear --iso 0.5 --ao --steps 20 --option ao_overlap=$ov

@@ -6,8 +6,8 @@ stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/r05_g_gpu_suite.log 2>&1; rc=$?; stop $rc; tail -4 $O/r05_g_gpu_suite.log
 [ $rc -ne 0 ] && exit $rc
 mkdir -p $O/r05_g_csv_c3iso $O/r05_g_csv_c3
-EXA_BENCH_KEEP_PMC_CSV=$PWD/$O/r05_g_csv_c3iso timeout -k 10 600 python bench.py --config c3_gear --iso 0.5 --steps 20 --cpu-baseline off --pmc on --in-flight 1 > $O/r05_g_c3iso.json 2> $O/r05_g_c3iso.err; stop $?
-EXA_BENCH_KEEP_PMC_CSV=$PWD/$O/r05_g_csv_c3 timeout -k 10 600 python bench.py --config c3_gear --steps 20 --cpu-baseline off --pmc on --in-flight 1 > $O/r05_g_c3.json 2> $O/r05_g_c3.err; stop $?
+EXA_BENCH_KEEP_PMC_CSV=$PWD/$O/r05_g_csv_c3iso timeout -k 10 600 python bench.py --full --config c3_gear --iso 0.5 --steps 20 --cpu-baseline off --pmc on --in-flight 1 > $O/r05_g_c3iso.json 2> $O/r05_g_c3iso.err; stop $?
+EXA_BENCH_KEEP_PMC_CSV=$PWD/$O/r05_g_csv_c3 timeout -k 10 600 python bench.py --full --config c3_gear --steps 20 --cpu-baseline off --pmc on --in-flight 1 > $O/r05_g_c3.json 2> $O/r05_g_c3.err; stop $?
 python - <<'PY'
 import json
 for n in ("c3iso", "c3"):

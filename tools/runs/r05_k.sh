@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out
 stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"; exit "$rc"; fi; }
-b() { name=$1; shift; timeout -k 10 500 python bench.py --cpu-baseline off --in-flight 1 --scale 1.25 --steps 10 "$@" > $O/r05_k_$name.json 2> $O/r05_k_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_k_$name.err; }
+b() { name=$1; shift; timeout -k 10 500 python bench.py --full --cpu-baseline off --in-flight 1 --scale 1.25 --steps 10 "$@" > $O/r05_k_$name.json 2> $O/r05_k_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_k_$name.err; }
 b to4_bo0 --pmc on
 b to4_bo1 --pmc on --option brick_order=1
 b to5_bo0 --pmc on --tile-order 5

@@ -7,7 +7,7 @@ for sc in 1.0 1.25; do
 for to in 4 6; do
 for cl in 1 4 16 64 256; do
   name=s${sc}_to${to}_cl${cl}
-  EXA_COST_CLASSES=$cl timeout -k 10 400 python bench.py --cpu-baseline off --pmc off --in-flight 1 --scale $sc --steps 10 --tile-order $to > $O/r05_l_$name.json 2> $O/r05_l_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_l_$name.err
+  EXA_COST_CLASSES=$cl timeout -k 10 400 python bench.py --full --cpu-baseline off --pmc off --in-flight 1 --scale $sc --steps 10 --tile-order $to > $O/r05_l_$name.json 2> $O/r05_l_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_l_$name.err
 done; done; done
 python - <<'PY'
 import json,glob

@@ -7,7 +7,7 @@ stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"
 for to in 4 6; do
 for cl in 1 8 32 256; do
   name=to${to}_cl${cl}
-  EXA_COST_CLASSES=$cl timeout -k 10 300 python bench.py --cpu-baseline off --pmc off --steps 30 --tile-order $to > $O/r05_l2_$name.json 2> $O/r05_l2_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_l2_$name.err
+  EXA_COST_CLASSES=$cl timeout -k 10 300 python bench.py --full --cpu-baseline off --pmc off --steps 30 --tile-order $to > $O/r05_l2_$name.json 2> $O/r05_l2_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_l2_$name.err
 done; done
 python - <<'PY'
 import json,glob

@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out
 stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"; exit "$rc"; fi; }
-b() { name=$1; shift; for cl in 1 256; do EXA_COST_CLASSES=$cl timeout -k 10 400 python bench.py --cpu-baseline off --pmc off "$@" > $O/r05_l3_${name}_cl$cl.json 2> $O/r05_l3_${name}_cl$cl.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_l3_${name}_cl$cl.err; done; }
+b() { name=$1; shift; for cl in 1 256; do EXA_COST_CLASSES=$cl timeout -k 10 400 python bench.py --full --cpu-baseline off --pmc off "$@" > $O/r05_l3_${name}_cl$cl.json 2> $O/r05_l3_${name}_cl$cl.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_l3_${name}_cl$cl.err; done; }
 b c2 --config c2_lanl --size 1024 --steps 100
 b c3 --config c3_gear --steps 30
 b c3iso --config c3_gear --iso 0.5 --steps 30

@@ -4,8 +4,8 @@ set -o pipefail
 O=gpurun_out
 stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"; exit "$rc"; fi; }
 for F in 1 2 3 4 6; do
-  EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,8 timeout -k 10 400 python bench.py --steps 40 --cpu-baseline off --pmc off --in-flight $F > $O/r05_m_r0of8_F$F.json 2> $O/r05_m_r0of8_F$F.err; stop $?
-  timeout -k 10 400 python bench.py --steps 30 --cpu-baseline off --pmc off --in-flight $F > $O/r05_m_n1_F$F.json 2> $O/r05_m_n1_F$F.err; stop $?
+  EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,8 timeout -k 10 400 python bench.py --full --steps 40 --cpu-baseline off --pmc off --in-flight $F > $O/r05_m_r0of8_F$F.json 2> $O/r05_m_r0of8_F$F.err; stop $?
+  timeout -k 10 400 python bench.py --full --steps 30 --cpu-baseline off --pmc off --in-flight $F > $O/r05_m_n1_F$F.json 2> $O/r05_m_n1_F$F.err; stop $?
 done
 python - <<'PY'
 import json,glob

@@ -3,9 +3,9 @@
 set -o pipefail
 O=gpurun_out
 for w in 2 4 8; do
-  EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,$w timeout -k 10 400 python bench.py --steps 40 --cpu-baseline off --pmc off > $O/r05_p_r0of$w.json 2> $O/r05_p_r0of$w.err; rc=$?; [ $rc -ge 124 ] && exit $rc
+  EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,$w timeout -k 10 400 python bench.py --full --steps 40 --cpu-baseline off --pmc off > $O/r05_p_r0of$w.json 2> $O/r05_p_r0of$w.err; rc=$?; [ $rc -ge 124 ] && exit $rc
 done
-( time timeout -k 10 900 python bench.py > $O/r05_p_bench.json 2> $O/r05_p_bench.err ) 2> $O/r05_p_bench.time; rc=$?; [ $rc -ge 124 ] && exit $rc
+( time timeout -k 10 900 python bench.py --full > $O/r05_p_bench.json 2> $O/r05_p_bench.err ) 2> $O/r05_p_bench.time; rc=$?; [ $rc -ge 124 ] && exit $rc
 grep real $O/r05_p_bench.time
 python - <<'PY'
 import json,glob

@@ -7,7 +7,7 @@ stop() { rc=$1; if [ "$rc" -ge 124 ]; then echo "step killed (rc $rc): stopping"
 tools/ab_variants.sh run; stop $?
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/r05_u_gpu_tests.log 2>&1; rc=$?; tail -4 $O/r05_u_gpu_tests.log; stop $rc
 [ $rc -ne 0 ] && exit $rc
-b() { name=$1; shift; timeout -k 10 400 python bench.py --cpu-baseline off --pmc off "$@" > $O/r05_u_$name.json 2> $O/r05_u_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_u_$name.err; }
+b() { name=$1; shift; timeout -k 10 400 python bench.py --full --cpu-baseline off --pmc off "$@" > $O/r05_u_$name.json 2> $O/r05_u_$name.err; rc=$?; stop $rc; [ $rc -ne 0 ] && tail -3 $O/r05_u_$name.err; }
 b c4 --steps 50
 b c2 --config c2_lanl --size 1024 --steps 50
 b s125 --scale 1.25 --steps 10

@@ -7,9 +7,9 @@ O=gpurun_out; mkdir -p $O/v
 for rep in 1 2; do
   for so in build/variants/libexa_hip_surf*.so; do
     name=$(basename "$so" .so); name=${name#libexa_hip_}
-    EXA_HIP_LIB="$so" timeout -k 10 300 python bench.py --cpu-baseline off --pmc off --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 > $O/v/c5_$name.$rep.json 2> $O/v/c5_$name.$rep.err
+    EXA_HIP_LIB="$so" timeout -k 10 300 python bench.py --full --cpu-baseline off --pmc off --size 4096 --iso 0.5 --ao --spp 16 --steps 3 --warmup 1 > $O/v/c5_$name.$rep.json 2> $O/v/c5_$name.$rep.err
     rc=$?; [ $rc -ge 124 ] && { echo "killed"; exit $rc; }
-    EXA_HIP_LIB="$so" timeout -k 10 300 python bench.py --cpu-baseline off --pmc off --iso 0.5 --steps 20 > $O/v/c4iso_$name.$rep.json 2> $O/v/c4iso_$name.$rep.err
+    EXA_HIP_LIB="$so" timeout -k 10 300 python bench.py --full --cpu-baseline off --pmc off --iso 0.5 --steps 20 > $O/v/c4iso_$name.$rep.json 2> $O/v/c4iso_$name.$rep.err
     rc=$?; [ $rc -ge 124 ] && { echo "killed"; exit $rc; }
     python - "$name" "$rep" <<'PY' | tee -a gpurun_out/v/results.txt
 import json,sys

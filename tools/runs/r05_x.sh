@@ -4,7 +4,7 @@
 set -o pipefail
 O=gpurun_out
 for w in 1 2 4 8; do
-  EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,$w timeout -k 10 400 python bench.py --steps 40 --cpu-baseline off --pmc off > $O/r05_x_r0of$w.json 2> $O/r05_x_r0of$w.err; rc=$?; [ $rc -ge 124 ] && exit $rc
+  EXA_BENCH_FORCE_DIST=1 EXA_BENCH_SHARD=0,$w timeout -k 10 400 python bench.py --full --steps 40 --cpu-baseline off --pmc off > $O/r05_x_r0of$w.json 2> $O/r05_x_r0of$w.err; rc=$?; [ $rc -ge 124 ] && exit $rc
 done
 python - <<'PY'
 import json,glob
