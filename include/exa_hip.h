@@ -187,6 +187,10 @@ const char *exa_prep_last_error(void);
  * planes are in the range of the walk's short exact division. */
 int exa_prep_ropes(const ExaPrep *, uint64_t *numLeaves, uint64_t *numNodes, float *leafBoxes, int32_t *leafLinks,
                    int32_t *leafRegion, ExaKdNode *nodes, int32_t *flags);
+/* diagnostic: replaces the prep's region kd-tree by a caller's own (what a caller may hand exa_hip_create in
+ * ExaHipScene.kdNodes); exa_prep_scene and exa_prep_ropes then see that tree.  Checked as exa_hip_create checks it: axis 0..2,
+ * references in range, children after their parent. */
+int exa_prep_set_kd_tree(ExaPrep *, const ExaKdNode *nodes, uint64_t numNodes, int32_t root);
 
 /* ------------------------------------------------------------------ */
 /* device module                                                       */

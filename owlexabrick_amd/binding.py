@@ -89,7 +89,7 @@ KDNODE_DTYPE = np.dtype([("split", "<f4"), ("axis", "<i4"), ("left", "<i4"), ("r
 KD_EMPTY = -2 ** 31
 
 # every symbol include/exa_hip.h declares
-ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa_prep_scene", "exa_prep_last_error", "exa_prep_ropes",
+ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa_prep_scene", "exa_prep_last_error", "exa_prep_ropes", "exa_prep_set_kd_tree",
                "exa_hip_create", "exa_hip_create_multi", "exa_hip_destroy", "exa_hip_resize", "exa_hip_set_frame_state",
                "exa_hip_set_xf", "exa_hip_set_triangles", "exa_hip_reset_tracer", "exa_hip_set_tracer_enabled",
                "exa_hip_advance_tracer", "exa_hip_read_traces", "exa_hip_set_params", "exa_hip_set_shard", "exa_hip_output_pixels",
@@ -123,6 +123,7 @@ def lib():
         L.exa_prep_destroy.argtypes = [vp]
         L.exa_prep_ropes.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp, vp, C.POINTER(C.c_int32)]
         L.exa_prep_scene.argtypes = [vp, C.POINTER(ExaHipScene)]
+        L.exa_prep_set_kd_tree.argtypes = [vp, vp, C.c_uint64, C.c_int32]
         L.exa_prep_last_error.restype = C.c_char_p
         L.exa_hip_create.argtypes = [C.POINTER(ExaHipScene), C.c_int32, C.POINTER(vp)]
         L.exa_hip_create_multi.argtypes = [C.POINTER(ExaHipScene), C.POINTER(C.c_int32), C.c_int32, C.POINTER(vp)]
@@ -211,6 +212,14 @@ class Prep:
                                 nodes.ctypes.data, C.byref(flags)):
             raise RuntimeError(lib().exa_prep_last_error().decode())
         return dict(boxes=boxes, links=links, region=region, nodes=nodes[:nn.value], flags=int(flags.value))
+
+    def set_kd_tree(self, nodes, root):
+        """replace the region kd-tree (KDNODE_DTYPE array, root reference) by a caller's own, as a caller may hand the module its
+        own tree in ExaHipScene.kdNodes: ropes() and a Renderer made from this prep then see it"""
+        nodes = np.ascontiguousarray(nodes, dtype=KDNODE_DTYPE)
+        if lib().exa_prep_set_kd_tree(self.h, nodes.ctypes.data if len(nodes) else None, len(nodes), int(root)):
+            raise RuntimeError(lib().exa_prep_last_error().decode())
+        lib().exa_prep_scene(self.h, C.byref(self.scene))
 
     def voxel_bounds(self):
         return (np.array(self.scene.voxelBounds_lo, dtype=np.float32),

@@ -397,6 +397,26 @@ int exa_prep_ropes(const ExaPrep *P, uint64_t *numLeaves, uint64_t *numNodes, fl
   return 0;
 }
 
+int exa_prep_set_kd_tree(ExaPrep *P, const ExaKdNode *nodes, uint64_t numNodes, int32_t root)
+{
+  if (!P || (numNodes && !nodes)) return 1;
+  const uint64_t nr = P->regions.size();
+  auto refOk = [&](int32_t ref) {
+    if (ref == EXA_KD_EMPTY) return true;
+    return ref >= 0 ? uint64_t(ref) < numNodes : uint64_t(~ref) < nr;
+  };
+  bool ok = refOk(root) && root != EXA_KD_EMPTY && numNodes < 0x7fffffffull;
+  for (uint64_t i = 0; ok && i < numNodes; i++) {
+    const ExaKdNode &n = nodes[i];
+    ok = n.axis >= 0 && n.axis <= 2 && refOk(n.left) && refOk(n.right)
+         && (n.left < 0 || uint64_t(n.left) > i) && (n.right < 0 || uint64_t(n.right) > i);
+  }
+  if (!ok) { g_prepError = "exa_prep_set_kd_tree: malformed kd-tree"; return 1; }
+  P->kdNodes.assign(nodes, nodes + numNodes);
+  P->kdRoot = root;
+  return 0;
+}
+
 int exa_prep_scene(const ExaPrep *P, ExaHipScene *out)
 {
   if (!P || !out) return 1;

@@ -54,11 +54,14 @@ inline void buildRopesHost(const ExaKdNode *kd, size_t nk, int32_t root, const f
     if (n.left == EXA_KD_EMPTY) n.left = ~int32_t(nr + out.gaps++);
     if (n.right == EXA_KD_EMPTY) n.right = ~int32_t(nr + out.gaps++);
   }
+  // every plane the walk divides by: the leaves' faces (the region domains; a gap's faces are split planes or root faces), the
+  // split planes of its descent (a caller's own tree may split a gap by any plane, leaving every region's box its domain), the
+  // root box
+  auto onGrid = [](float v) { return std::isfinite(v) && std::fabs(v) <= 1073741824.f && v * 1024.f == std::nearbyint(v * 1024.f); };
   out.planesOnGrid = true;
-  for (size_t i = 0; i < 6 * nr; i++) {
-    const float v = dom[i];
-    out.planesOnGrid = out.planesOnGrid && std::isfinite(v) && std::fabs(v) <= 1073741824.f && v * 1024.f == std::nearbyint(v * 1024.f);
-  }
+  for (size_t i = 0; i < 6 * nr; i++) out.planesOnGrid = out.planesOnGrid && onGrid(dom[i]);
+  for (const ExaKdNode &n : out.nodes) out.planesOnGrid = out.planesOnGrid && onGrid(n.split);
+  for (int k = 0; k < 3; k++) out.planesOnGrid = out.planesOnGrid && onGrid(rootLo[k]) && onGrid(rootHi[k]);
   out.leaves.assign(nr + out.gaps, RopeLeafHost{});
   const std::vector<ExaKdNode> &rn = out.nodes;
   struct Item { int32_t ref; float lo[3], hi[3]; int32_t rope[6]; };

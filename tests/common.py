@@ -53,6 +53,7 @@ class Case:
         self.contour = contour
         self.tf_filter = tf_filter    # None = default (CUDA 1.8 fixed-point filter weight); 0 = full-precision weight
         self.meshes = meshes          # list of (verts[n,3], tris[m,3]), world space
+        self.prep_edit = None         # callable(prep): changes the host-prepared scene before the renderer is made from it
         nf = len(scene.fields)
         self.nprim = nf if multi else 1
         self.colormap_channel = 0 if (multi or nf < 2) else 1
@@ -121,6 +122,8 @@ class Case:
         from owlexabrick_amd import binding
         prep = binding.Prep(self.scene, num_region_fields=len(self.scene.fields) if self.multi else 1,
                             allow_empty_cells=self.allow_empty_cells)
+        if self.prep_edit is not None:
+            self.prep_edit(prep)
         R = binding.Renderer(prep, device=device, multiFieldDvr=self.multi)
         if self.meshes:
             R.setTriangles(*self._merged_meshes())
@@ -192,9 +195,63 @@ RGBA_MAX_LSB = 1
 # at most the remaining transmittance (0.02) times its colour.  Allowed for at most FLIP_FRACTION
 # of the pixels (2 pixels in a frame too small for that to be a whole pixel: 2 of 14 000 random frames had two — one of
 # them, seed 803 of the odd-TF-domain family, is pinned in tests/test_gpu_fuzz.py; the floor only ever matters below
-# 6 000 pixels, above that FLIP_FRACTION allows three or more anyway); every other pixel must meet ACCUM_ATOL/RTOL.
+# 10 000 pixels, above that FLIP_FRACTION allows two or more anyway); every other pixel must meet ACCUM_ATOL/RTOL.
+# FLIP_FRACTION: the largest rate observed on a whole frame is 18 of 4 194 304 pixels (4.3e-6, C4 against the oracle,
+# profiles/parity_error_profile.txt); no fixed case or fresh random seed has a flip, seed 803 has its two (the floor).
 FLIP_BOUND = 0.021
-FLIP_FRACTION = 5e-4
+FLIP_FRACTION = 2e-4
+
+# Error profile (compare(), ulp_profile()): the ulp distance of two float32 values a, b is |a - b| / ulp(max(|a|, |b|, 2^-20)),
+# taken over every component of every pixel that is not a flip (a pixel is a flip when a component exceeds the per-pixel
+# tolerance above).  Bounds: the largest distance measured on the MI355X (profiles/parity_error_profile.txt, one line per
+# comparison) times 4, rounded up to a power of two.  A change that needs a looser bound re-measures, replaces that file and
+# says why in its commit message.
+# The distances are thousands of ulps, not the 2 of a transcendental: they sit in colour components of about 1e-6 (dark
+# TF colours, faint volumes), next to the 2^-20 floor, where the absolute difference of a few 1e-9 left by a 1-ulp difference
+# in powf near 1 (the opacity correction 1 - powf(1 - a, dt) cancels) is thousands of ulps of the component.  The same
+# metric between the oracle and the oracle with its powf moved by 1 ulp gives 13 569 (ex3) and 21 002 (ex4_grad) ulp.
+# The per-case fraction of bit-identical pixels (exact_px, tests/test_gpu_parity.py) is the finer detector.
+ULP_FLOOR = 2.0 ** -20
+# fast_math = 0 (library powf, the counting variant), the fixed cases: 9 903 ulp (gen_exajet in test_hip_matches_oracle and
+# test_hip_matches_oracle_with_empty_cells) x 4 = 39 612 -> 2^16
+MAX_ULP_TIGHT = 65536
+# fast_math = 1 (the defaults a caller gets), the fixed cases and whole frames: max 9 903 ulp (gen_exajet in
+# test_shipped_defaults_within_stated_tolerance; the whole frames reach 9 836, C3) x 4 -> 2^16; 99.9th percentile 6 595 ulp
+# (gen_exajet, same test) x 4 = 26 381 -> 2^15
+MAX_ULP_SHIPPED = 65536
+ULP_P999_SHIPPED = 32768
+# the seeded random families of tests/gpu_fuzz.py (both legs; fresh seeds 1000-1299 of four families, and the suite's own
+# seeds): max 115 829 ulp, 99.9th percentile 78 170 ulp (rich family, seed 1256: contour planes at opacity scales of a few
+# hundredths, faint everywhere) x 4 -> 2^19 for both
+FUZZ_MAX_ULP = 524288
+FUZZ_ULP_P999 = 524288
+# An AO ray that flips hit / miss (cosf / sinf differ by ulps between libm and OCML) changes its pixel's shadow term by 1/2 of
+# one of the two AO samples: the surface term ambient + baseColor |cos| (1 - shadow) (exabrick.cu:1646-1648) moves by
+# baseColor |cos| / 2 <= 1/2 (colours are at most 1), behind whatever the volume in front leaves of it.  Per frame.
+AO_FLIP_BOUND = 0.5
+
+
+def ulp_profile(ref_acc, acc, flip_px=None):
+    """exact_px: fraction of pixels whose float32 accum (all components) is bit-identical; max_ulp / ulp_p999: the largest / the
+    99.9th percentile ulp distance over all components of the pixels that are not flips (flip_px: boolean per pixel)"""
+    a = np.asarray(ref_acc, dtype=np.float32)
+    b = np.asarray(acc, dtype=np.float32)
+    exact_px = float(np.all(a.view(np.uint32) == b.view(np.uint32), axis=-1).mean()) if a.size else 1.0
+    if flip_px is not None:
+        a, b = a[~flip_px], b[~flip_px]
+    if a.size == 0:
+        return dict(exact_px=exact_px, max_ulp=0.0, ulp_p999=0.0)
+    m = np.maximum(np.maximum(np.abs(a), np.abs(b)), np.float32(ULP_FLOOR))
+    ulps = (np.abs(a.astype(np.float64) - b.astype(np.float64)) / np.spacing(m).astype(np.float64)).ravel()
+    # NaN on either side: an infinite distance (fails every bound) rather than one a max() would drop
+    ulps[np.isnan(ulps)] = np.inf
+    return dict(exact_px=exact_px, max_ulp=float(ulps.max()), ulp_p999=float(np.percentile(ulps, 99.9)))
+
+
+def error_profile_line(r):
+    """the error profile of a compare() / ulp_profile() result in one line (the tests print it: a GPU run's log holds the numbers)"""
+    return (f"PROFILE {r.get('what', '')}: exact_px {r['exact_px']:.6f} max_ulp {r['max_ulp']:.6g} ulp_p999 {r['ulp_p999']:.6g} "
+            f"flips {r.get('flip_pixels', '-')}")
 
 
 def compare(oracle_out, hip_out, what=""):
@@ -205,8 +262,10 @@ def compare(oracle_out, hip_out, what=""):
     o8 = harness.unpack_rgba8(o_rgba).astype(np.int32)
     h8 = harness.unpack_rgba8(h_rgba).astype(np.int32)
     d8 = np.abs(o8 - h8)
-    nflip = int(((da > tol).any(axis=-1)).sum())
+    flip_px = (da > tol).any(axis=-1)
+    nflip = int(flip_px.sum())
     flips_ok = nflip <= max(2, int(FLIP_FRACTION * da.shape[0] * da.shape[1])) and float(da.max()) <= FLIP_BOUND
     return dict(what=what, accum_max=float(da.max()), accum_bad=int((da > tol).sum()), flip_pixels=nflip, flips_ok=flips_ok,
                 rgba_max=int(d8.max()), rgba_bad=int((d8 > RGBA_MAX_LSB).sum()),
-                rgba_diff_px=int((d8.max(axis=-1) > 0).sum()), exact=bool(np.array_equal(o_acc, h_acc)))
+                rgba_diff_px=int((d8.max(axis=-1) > 0).sum()), exact=bool(np.array_equal(o_acc, h_acc)),
+                **ulp_profile(o_acc, h_acc, flip_px))

@@ -9,11 +9,43 @@ import time
 
 import numpy as np
 
-from common import compare
-from common import ACCUM_ATOL, FLIP_BOUND
+from common import compare, error_profile_line
+from common import ACCUM_ATOL, AO_FLIP_BOUND, FLIP_BOUND, FUZZ_MAX_ULP, FUZZ_ULP_P999
 from fuzz_cases import random_case, random_deep_case, random_rich_case
 
 STAT_KEYS = ["segments", "sample_evals", "samples", "brick_visits", "corner_loads", "iso_segments", "iso_evals"]
+
+# AO legs (the rich family): pixels that differ by more than frames x ACCUM_ATOL (fast_math 0) / frames x FLIP_BOUND (defaults),
+# per pixel and frame — the largest rate over fresh seeds 1000-1299 and the suite's seeds is 0 for both
+# (profiles/parity_error_profile.txt: "rich: worst AO ...").  Allowed: twice that, at least 2 pixels (and never more than the
+# earlier 0.3 %).
+AO_OBSERVED_RATE = {"tight": 0.0, "shipped": 0.0}
+
+# the largest error profile seen by this process, per kind of leg (the sweep prints it at the end)
+WORST = {}
+
+
+def _note(kind, **vals):
+    w = WORST.setdefault(kind, {})
+    for k, v in vals.items():
+        w[k] = max(w.get(k, v), v)
+
+
+def _check_ao(o, h, frames, kind, leg, bad, r):
+    da = np.abs(o[1].astype(np.float64) - h[1].astype(np.float64)).max(axis=-1)
+    limit = frames * (ACCUM_ATOL if kind == "tight" else FLIP_BOUND)
+    n, px = int((da > limit).sum()), da.size * frames
+    print(f"PROFILE {leg} AO {kind}: {n} of {da.size} pixels x {frames} frames beyond {limit:g}, max |d accum| {da.max():.3g}")
+    _note(f"AO {kind}", rate=n / px, count=n, max_d_per_frame=float(da.max()) / frames)
+    if n > max(2, 0.003 * px) or n > max(2, int(2 * AO_OBSERVED_RATE[kind] * px)):
+        bad.append(f"{leg} (AO): {n} pixels beyond {limit:g}: {r}")
+    if da.max() > frames * (AO_FLIP_BOUND + FLIP_BOUND):
+        bad.append(f"{leg} (AO): a pixel moved by {da.max():.3g}, more than an AO flip can: {r}")
+    # the work must still be the same up to those few rays (a walk that loses segments shows here first)
+    keys = STAT_KEYS if kind == "tight" else ("samples", "brick_visits", "segments")
+    loose = [(k, o[2][k], h[2][k]) for k in keys if abs(o[2][k] - h[2][k]) > 0.01 * o[2][k] + 64]
+    if loose:
+        bad.append(f"{leg} (AO): counters {loose}")
 
 
 def check(seed, rich=False, clipbox=False, holes=False):
@@ -57,16 +89,14 @@ def check(seed, rich=False, clipbox=False, holes=False):
     for accel in (1, 2, 0):              # kd-tree stack walk, kd-tree rope walk, LBVH restart
         case.accel = accel
         h = case.run_hip(stats=True, frames=frames)
-        r = compare(o, h)
+        r = compare(o, h, f"seed {seed} accel {accel} fast_math 0")
         if case.ao:      # AO directions go through cosf/sinf (libm vs OCML): a few rays may flip hit/miss
-            da = np.abs(o[1] - h[1]).max(axis=-1)
-            if (da > frames * ACCUM_ATOL).sum() > max(2, 0.003 * da.size * frames):
-                bad.append(f"accel {accel} (AO): {r}")
-            # the work must still be the same up to those few rays (a walk that loses segments shows here first)
-            loose = [(k, o[2][k], h[2][k]) for k in STAT_KEYS if abs(o[2][k] - h[2][k]) > 0.01 * o[2][k] + 64]
-            if loose:
-                bad.append(f"accel {accel} (AO): counters {loose}")
+            _check_ao(o, h, frames, "tight", f"accel {accel}", bad, r)
             continue
+        print(error_profile_line(r))
+        _note("fast_math 0", max_ulp=r["max_ulp"], ulp_p999=r["ulp_p999"], flips=r["flip_pixels"])
+        if r["max_ulp"] > FUZZ_MAX_ULP:          # on the pixels that are not termination flips
+            bad.append(f"accel {accel}: {r['max_ulp']:.0f} ulp > {FUZZ_MAX_ULP}: {r}")
         # a ray whose opacity crosses 0.98 within an ulp of powf may stop one sample earlier or later on one side
         # (tests/common.py: FLIP_BOUND, FLIP_FRACTION; 2 of 2000 seeds have such a pixel): then the pixel is bounded
         # by the flip tolerance and the counters by a few samples, otherwise everything is exact
@@ -90,13 +120,16 @@ def check(seed, rich=False, clipbox=False, holes=False):
             bad.append(f"accel {accel}: shipped kernel differs from the counting variant")
     case.accel, case.fast_math = None, None       # the defaults a caller gets (the module chooses the walk per frame)
     h = case.run_hip(stats=True, frames=frames)
-    r = compare(o, h)
+    r = compare(o, h, f"seed {seed} defaults")
     if case.ao:
-        da = np.abs(o[1] - h[1]).max(axis=-1)
-        if (da > FLIP_BOUND * frames).sum() > max(2, 0.003 * da.size * frames):
-            bad.append(f"defaults (AO): {r}")
-    elif not (r["flips_ok"] and r["rgba_bad"] <= 3 * r["flip_pixels"]):
+        _check_ao(o, h, frames, "shipped", "defaults", bad, r)
+        return bad, desc
+    print(error_profile_line(r))
+    _note("defaults", max_ulp=r["max_ulp"], ulp_p999=r["ulp_p999"], flips=r["flip_pixels"])
+    if not (r["flips_ok"] and r["rgba_bad"] <= 3 * r["flip_pixels"]):
         bad.append(f"defaults: {r}")
+    if r["max_ulp"] > FUZZ_MAX_ULP or r["ulp_p999"] > FUZZ_ULP_P999:
+        bad.append(f"defaults: {r['max_ulp']:.0f} ulp (p99.9 {r['ulp_p999']:.0f}) > {FUZZ_MAX_ULP} ({FUZZ_ULP_P999}): {r}")
     return bad, desc
 
 
@@ -116,5 +149,7 @@ if __name__ == "__main__":
                 break
         elif seed % 10 == 0:
             print(f"seed {seed} ok ({time.time() - t0:.0f}s)", flush=True)
+    for kind, w in sorted(WORST.items()):
+        print(f"worst {kind}: " + ", ".join(f"{k} {v:.6g}" for k, v in sorted(w.items())), flush=True)
     print(f"{last - first + 1 - fails if keep or not fails else '?'} passed, {fails} failed, {time.time() - t0:.0f}s", flush=True)
     sys.exit(1 if fails else 0)

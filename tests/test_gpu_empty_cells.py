@@ -4,7 +4,7 @@ the module refuses the per-axis form for such a scene."""
 import numpy as np
 import pytest
 
-from common import Case, band_xf, compare
+from common import MAX_ULP_TIGHT, Case, band_xf, compare, error_profile_line
 from owlexabrick_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -43,8 +43,10 @@ def test_hip_matches_oracle_with_empty_cells(name, accel):
     case.accel, case.fast_math = accel, 0
     o = case.run_oracle()
     h = case.run_hip(stats=True)
-    r = compare(o, h, name)
+    r = compare(o, h, f"{name} {accel} empty cells fast_math 0")
+    print(error_profile_line(r))
     assert r["accum_bad"] == 0 and r["rgba_bad"] == 0, r
+    assert r["max_ulp"] <= MAX_ULP_TIGHT, r
     assert {k: o[2][k] for k in STAT_KEYS} == {k: h[2][k] for k in STAT_KEYS}
     assert np.isfinite(h[1]).all() and np.abs(h[1]).max() < 10.0          # no poison value in a pixel
     assert o[1][..., :3].sum() > 0

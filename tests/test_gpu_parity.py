@@ -7,7 +7,8 @@ import sys
 import numpy as np
 import pytest
 
-from common import ACCUM_ATOL, FLIP_BOUND, Case, ROOT, band_xf, compare, po
+from common import (ACCUM_ATOL, AO_FLIP_BOUND, FLIP_BOUND, MAX_ULP_SHIPPED, MAX_ULP_TIGHT, ULP_P999_SHIPPED, Case, ROOT, band_xf,
+                    compare, error_profile_line, po)
 from owlexabrick_amd import binding, harness, scenes
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +109,47 @@ CASES = {
 }
 
 
+# The AO cases of the matrix: an AO ray that flips hit / miss (cosf / sinf differ by ulps between libm and OCML) moves its pixel
+# by at most AO_FLIP_BOUND (tests/common.py).  Pixels that differ, per case, the largest over the three walks and both forms
+# (profiles/parity_error_profile.txt): "tight" = beyond ACCUM_ATOL with fast_math 0, "shipped" = beyond FLIP_BOUND with the
+# defaults.  Allowed: twice that, at least 2 (and never more than the earlier 0.3 % of the pixels).
+# Observed: no pixel in either case, either kind (largest |d accum| 2.4e-7).
+AO_OBSERVED = {"amr_xfm_iso_ao": {"tight": 0, "shipped": 0},
+               "amr_mesh_ao": {"tight": 0, "shipped": 0}}
+
+# Fraction of bit-identical pixels per case, the smallest over the three walks and both forms (profiles/parity_error_profile.txt):
+# (fast_math 0 in test_hip_matches_oracle, defaults in test_shipped_defaults_within_stated_tolerance).  Required: at least half
+# of it.  The kernels and the oracle execute the same operation sequence, so most pixels are bit-identical; a change of the
+# arithmetic shows here long before the ulp bounds see it (the opacity correction moved by one ulp drops ex3 from 0.83 to 0.22).
+EXACT_PX_OBSERVED = {
+    "amr": (0.8076, 0.6165), "amr_2ch": (0.7480, 0.4630), "amr_2ch_colormap": (0.7641, 0.4732),
+    "amr_2ch_iso_both": (0.7359, 0.6107), "amr_2ch_iso_ch1": (0.7572, 0.4766), "amr_band": (0.8521, 0.6559),
+    "amr_clip": (0.8971, 0.7732), "amr_contour": (0.5967, 0.4400), "amr_contour_iso": (0.7652, 0.7526),
+    "amr_dt025_scale": (0.4626, 0.4626), "amr_far_camera_tiny_components": (0.3268, 0.1003), "amr_grad": (0.8235, 0.4228),
+    "amr_inside": (0.7031, 0.2873), "amr_iso": (0.8280, 0.4438), "amr_mesh": (0.5329, 0.3428),
+    "amr_mesh_iso_contour": (0.7298, 0.7152), "amr_noskip": (0.8521, 0.6559), "amr_ragged": (0.8369, 0.4746),
+    "amr_rays_in_an_x_plane": (1.0000, 1.0000), "amr_rays_parallel_to_x_planes": (0.9076, 0.2796), "amr_xfm": (0.9048, 0.7310),
+    "amr_xfm_iso": (0.9070, 0.7400), "c1_64": (0.4564, 0.4539), "c1_64_grad_iso": (0.4641, 0.4017), "ex0": (1.0000, 1.0000),
+    "ex1_grad": (0.7591, 0.5562), "ex2": (0.7577, 0.7477), "ex3": (0.8309, 0.4129), "ex3_contour": (0.8328, 0.4150),
+    "ex3_grad": (0.8328, 0.3844), "ex3_iso": (0.8374, 0.3883), "ex4_grad": (0.7663, 0.5470), "ex4_iso_noshade": (0.8053, 0.6911),
+    "ex4_two_isos": (0.8341, 0.6652), "gen_exajet": (0.4730, 0.4730),
+}
+
+
+def _check_ao(o, h, name, kind):
+    da = np.abs(o[1].astype(np.float64) - h[1].astype(np.float64)).max(axis=-1)
+    limit = ACCUM_ATOL if kind == "tight" else FLIP_BOUND
+    n = int((da > limit).sum())
+    print(f"PROFILE {name} AO {kind}: {n} of {da.size} pixels beyond {limit:g}, max |d accum| {da.max():.3g}")
+    assert n <= max(2, 0.003 * da.size), (name, kind, n)
+    assert n <= max(2, 2 * AO_OBSERVED[name][kind]), (name, kind, n)
+    assert da.max() <= AO_FLIP_BOUND + FLIP_BOUND, (name, kind, float(da.max()))     # one AO flip, a termination flip at most
+    # the work up to those few rays is the same (the slack of tests/gpu_fuzz.py for AO)
+    keys = STAT_KEYS if kind == "tight" else ("samples", "brick_visits", "segments")
+    loose = [(k, o[2][k], h[2][k]) for k in keys if abs(o[2][k] - h[2][k]) > 0.01 * o[2][k] + 64]
+    assert not loose, (name, kind, loose)
+
+
 @pytest.mark.parametrize("form", [0, 1], ids=["source_order", "per_axis"])
 @pytest.mark.parametrize("accel", [1, 0, 2], ids=["kd", "lbvh", "rope"])
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -119,12 +161,13 @@ def test_hip_matches_oracle(name, accel, form):
     case.fast_math = 0          # library powf: the work counters must then match sample for sample
     o = case.run_oracle()
     h = case.run_hip(stats=True)
-    r = compare(o, h, name)
+    r = compare(o, h, f"{name} {accel} {form} fast_math 0")
     if case.ao:      # AO directions go through cosf/sinf (libm vs OCML): a few rays may flip hit/miss
-        da = np.abs(o[1] - h[1]).max(axis=-1)
-        assert (da > ACCUM_ATOL).sum() <= max(2, 0.003 * da.size), r
+        _check_ao(o, h, name, "tight")
         return
+    print(error_profile_line(r))
     assert r["accum_bad"] == 0 and r["rgba_bad"] == 0, r
+    assert r["max_ulp"] <= MAX_ULP_TIGHT and r["exact_px"] >= 0.5 * EXACT_PX_OBSERVED[name][0], r
     assert {k: o[2][k] for k in STAT_KEYS} == {k: h[2][k] for k in STAT_KEYS}   # identical work, sample for sample
     assert h[2]["diag"][8] == 0        # kd interval == the reference's slab test, every leaf
 
@@ -152,12 +195,14 @@ def test_shipped_defaults_within_stated_tolerance(name, accel, form):
     case = CASES[name]()
     case.accel, case.basis_form = accel, form
     o, h = case.run_oracle(), case.run_hip(stats=True)
-    r = compare(o, h, name)
+    r = compare(o, h, f"{name} {accel} {form} defaults")
     if case.ao:      # AO directions go through cosf/sinf (libm vs OCML): a few rays may flip hit/miss
-        da = np.abs(o[1] - h[1]).max(axis=-1)
-        assert (da > FLIP_BOUND).sum() <= max(2, 0.003 * da.size), r
+        _check_ao(o, h, name, "shipped")
         return
+    print(error_profile_line(r))
     assert r["flips_ok"] and r["rgba_bad"] <= 3 * r["flip_pixels"], r
+    assert r["max_ulp"] <= MAX_ULP_SHIPPED and r["ulp_p999"] <= ULP_P999_SHIPPED, r
+    assert r["exact_px"] >= 0.5 * EXACT_PX_OBSERVED[name][1], r
     for k in ("samples", "brick_visits", "segments"):
         assert abs(o[2][k] - h[2][k]) <= 1e-3 * o[2][k] + 2, (k, o[2][k], h[2][k])
 
@@ -177,8 +222,10 @@ def test_tf_filter_fixed_point_weight_matches_oracle_in_both_modes(accel):
     for mode in (1, 0):
         case = Case(_amr(), W=96, H=96, grad=1, xf=_step_tf(40), tf_filter=mode, accel=accel, fast_math=0, opacity_scale=0.5)
         o, h = case.run_oracle(), case.run_hip(stats=True)
-        r = compare(o, h, f"step tf, filter {mode}")
+        r = compare(o, h, f"step tf, filter {mode}, accel {accel}")
+        print(error_profile_line(r))
         assert r["accum_bad"] == 0 and r["rgba_bad"] == 0, r
+        assert r["max_ulp"] <= MAX_ULP_TIGHT, r
         assert {k: o[2][k] for k in STAT_KEYS} == {k: h[2][k] for k in STAT_KEYS}
         acc[mode] = h[1]
     d = np.abs(acc[0] - acc[1])

@@ -57,9 +57,14 @@ def _node_boxes(P, r):
 def test_leaf_boxes_and_links(name, sc):
     P = binding.Prep(sc)
     r = P.ropes()
+    assert r["flags"] == 3                                        # boxes == domains, planes on the short division's grid
+    _check_leaves_and_links(P, r)
+    P.close()
+
+
+def _check_leaves_and_links(P, r):
     reg = P.regions()
     nr = len(reg)
-    assert r["flags"] == 3                                        # boxes == domains, planes on the short division's grid
     assert np.array_equal(r["boxes"][:nr, :3], reg["dom_lo"]) and np.array_equal(r["boxes"][:nr, 3:], reg["dom_hi"])
     assert np.array_equal(r["region"][:nr], np.arange(nr)) and (r["region"][nr:] == -1).all()
     assert len(r["nodes"]) == P.scene.numKdNodes
@@ -91,7 +96,73 @@ def test_leaf_boxes_and_links(name, sc):
                 n = nodes[t]
                 b = int(n["axis"])
                 assert b != a and lo[b] < n["split"] < hi[b], (i, f, t)
+
+
+def split_a_gap_off_grid(P):
+    """give the prep's kd-tree one node more: the largest gap (an empty child slot) split in two by a plane that is not a
+    multiple of 2^-10 — a caller's own tree, whose region leaves still have exactly their domains as boxes.  Returns the plane"""
+    r = P.ropes()
+    _, nbox = _node_boxes(P, r)
+    kd = P.kd_nodes()
+    best = None
+    for i, n in enumerate(kd):
+        for side in ("left", "right"):
+            if n[side] != binding.KD_EMPTY:
+                continue
+            lo, hi = nbox[i][0].copy(), nbox[i][1].copy()
+            a = int(n["axis"]) & 3
+            (hi if side == "left" else lo)[a] = n["split"]
+            vol = float(np.prod(hi.astype(np.float64) - lo))
+            if best is None or vol > best[0]:
+                best = (vol, i, side, lo, hi)
+    assert best is not None, "the scene's kd-tree has no gap"
+    _, i, side, lo, hi = best
+    b = int(np.argmax(hi - lo))                                   # across the gap's longest extent
+    plane = np.float32(0.5 * (float(lo[b]) + float(hi[b])) + 2.0 ** -10 / 3)
+    assert lo[b] < plane < hi[b] and plane * 1024 != np.round(plane * 1024)
+    nodes = np.concatenate([kd, np.zeros(1, dtype=binding.KDNODE_DTYPE)])
+    nodes[-1] = (plane, b, binding.KD_EMPTY, binding.KD_EMPTY)
+    nodes[i][side] = len(kd)                                      # after its parent, as the module requires
+    P.set_kd_tree(nodes, int(P.scene.kdRoot))
+    return float(plane)
+
+
+def _grids_case():
+    from fuzz_cases import random_case
+    return random_case(7, grids=True)[0]                          # random brick partition with holes: gaps in the tree
+
+
+def test_a_split_plane_off_the_grid_turns_the_short_division_off():
+    """the rope walk divides by the kd-tree's split planes in its descent, not only by the leaves' faces: a tree with a plane off
+    the short division's grid (here one that splits a gap, so that every region leaf keeps its domain) must get flags == 1 —
+    boxes match, short division off — and links that are still right"""
+    P = binding.Prep(_grids_case().scene)
+    plane = split_a_gap_off_grid(P)
+    r = P.ropes()
+    assert r["flags"] == 1, r["flags"]
+    assert np.isin(np.float32(plane), r["nodes"]["split"])
+    _check_leaves_and_links(P, r)
     P.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("walk", [2, 1], ids=["rope", "stack"])
+def test_tree_with_an_off_grid_split_renders_what_the_oracle_renders(walk):
+    """the scene of the test above on the GPU (the oracle finds its regions without any tree): with the short division off,
+    the rope walk — and the stack walk — give the oracle's frame under the tight rule of tests/common.py, the same work
+    counters, and no leaf whose interval differs from the slab test"""
+    from common import MAX_ULP_TIGHT, compare, error_profile_line
+    case = _grids_case()
+    case.accel, case.fast_math = walk, 0
+    case.prep_edit = split_a_gap_off_grid
+    o, h = case.run_oracle(), case.run_hip(stats=True)
+    r = compare(o, h, f"grids 7 with an off-grid split, walk {walk}")
+    print(error_profile_line(r))
+    assert r["accum_bad"] == 0 and r["rgba_bad"] == 0 and r["max_ulp"] <= MAX_ULP_TIGHT, r
+    keys = ["segments", "sample_evals", "samples", "brick_visits", "corner_loads", "iso_segments", "iso_evals"]
+    assert {k: o[2][k] for k in keys} == {k: h[2][k] for k in keys}
+    assert h[2]["diag"][8] == 0
+    assert (h[2]["walk_leaf_visits"] > 0) == (walk == 2) and o[2]["samples"] > 0
 
 
 def _rope_walk(r, root, rootbox, o, d, tmin=0.0):
