@@ -286,6 +286,61 @@ int exa_hip_write_accum(ExaHipRenderer *, const float *src4);
  * (programs/exabrick.cu:285-312, 373-402), one byte per region; for tests */
 int exa_hip_read_activity(ExaHipRenderer *, int32_t which /*0 volume, 1 iso*/, uint8_t *dst);
 
+/* ---- point probes: the reconstructed field at arbitrary points and on uniform grids (new relative to the reference,
+ * whose samplePoint / samplePointWithDerivative, programs/exabrick.cu:781-806,883-928, only run inside its programs) ----
+ *
+ * Spaces.  Positions are in voxel space (the bricks' coordinates) unless EXA_SAMPLE_WORLD_SPACE is given: then they are
+ * mapped with the voxelSpaceTransform of the last exa_hip_set_frame_state, in xfmPoint's operation order
+ * x*vx + (y*vy + (z*vz + p)), nothing contracted; world space before any frame state is an error.
+ *
+ * Region lookup.  A result depends only on the scene, the position, the option basis_form and (world space) the
+ * transform — not on the transfer function, region activity, iso values, the camera or any other option:
+ *   - outside the closed root box [kdLo, kdHi] of the region kd-tree (the union of the region domains), or with a NaN or
+ *     infinite coordinate: status -1;
+ *   - else descend from the root: at an inner node `right` if p[axis] >= split, else `left` (activity bits ignored).  So a
+ *     point belongs to the half-open kd cell [lo, hi) on every axis, except on the upper faces of the root box, which are
+ *     closed: a point on a face between a region and a gap above it gets -1 (the region's hat basis ends on that face;
+ *     there is no backtracking);
+ *   - EXA_KD_EMPTY: -1; a leaf: region ~ref if p lies in that region's closed domain, else -1 (a caller's own tree,
+ *     exa_prep_set_kd_tree, stays honest);
+ *   - the descent is bounded; a tripped bound sets the module's loop-guard flag, and a synchronous call fails with 3.
+ * A scene without a kd tree (ExaHipScene.kdNodes == NULL, more than one region) is refused: its LBVH is refit to the region
+ * activity and cannot answer an activity-free lookup.
+ *
+ * Value.  samplePoint through the march headers in the handle's current basis_form (a scene marked allowEmptyCells: the
+ * form-0 sums with the poison test).  sumW <= 1e-20 gives status -2 (the reference's samplePoint returns false).  Status
+ * is per point AND channel: in an empty-cells scene the poison test skips corners channel by channel
+ * (exabrick.cu:614-618), so one channel can vanish where another does not.
+ *
+ * Gradient (EXA_SAMPLE_GRADIENT): the reference's numerator sumW*sumD - sumWV*sumDC (exabrick.cu:916-921), bit for bit as
+ * samplePointWithDerivative returns it; with EXA_SAMPLE_GRADIENT_NORMALIZED as well it is divided by sumW*sumW on the
+ * device: the true gradient of the reconstruction.  Gradients are taken with respect to VOXEL-space coordinates, also for
+ * world-space positions.
+ *
+ * Fill.  Where status < 0, value and gradient components of that point and channel are `fill`.
+ *
+ * Arrays.  n == 0 does nothing.  Host arrays go through a device buffer of bounded size (64 MiB), in chunks.  Synchronous
+ * unless the pointers are device pointers and async != 0 (as exa_hip_render); hipStream: a hipStream_t or NULL.  A handle
+ * of exa_hip_create_multi runs the call on devices[0], and device pointers are memory of that device.  A pending
+ * brick_order change is applied first, as render does.  Unknown flag bits are an error. */
+#define EXA_SAMPLE_WORLD_SPACE          1
+#define EXA_SAMPLE_GRADIENT             2
+#define EXA_SAMPLE_GRADIENT_NORMALIZED  4   /* with EXA_SAMPLE_GRADIENT only */
+/* channels: numChannels (1..EXA_MAX_CHANNELS) entries in [0, numFields), repeats allowed; values n x numChannels;
+ * gradients n x numChannels x 3 (read only with EXA_SAMPLE_GRADIENT, may be NULL otherwise); status n x numChannels:
+ * region id, -1 (no region), -2 (sumW <= 1e-20), or NULL */
+int exa_hip_sample_points(ExaHipRenderer *, const float *points /* n x 3 */, uint64_t n,
+                          const int32_t *channels, int32_t numChannels, int32_t flags, float fill,
+                          float *values, float *gradients, int32_t *status,
+                          int32_t pointersAreDevice, void *hipStream, int32_t async);
+/* the field on a uniform grid of dims[0] x dims[1] x dims[2] cell centres of the box [lo, hi] (finite, hi > lo and
+ * dims >= 1 on every axis): per axis p = lo + (float(i) + 0.5f) * ((hi - lo) / float(n)) in float32, nothing contracted,
+ * then the world mapping if flags = EXA_SAMPLE_WORLD_SPACE (the only flag).  out[(z*ny + y)*nx + x] (64-bit index, x
+ * fastest), fill where the status would be < 0: bit for bit what exa_hip_sample_points gives at those positions. */
+int exa_hip_resample(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                     int32_t channel, int32_t flags, float fill,
+                     float *out /* dims[0]*dims[1]*dims[2] floats */, int32_t dstIsDevice, void *hipStream, int32_t async);
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,
@@ -320,6 +375,9 @@ int exa_hip_read_activity(ExaHipRenderer *, int32_t which /*0 volume, 1 iso*/, u
  * work counters, 2 only phase_cycles, from the shipped code plus a clock read at every phase change; "walk_probe" 1 = the
  * counting variant also records every wave's SET of visited kd nodes (128 KiB of device memory per wave) and reports its
  * size summed over the waves as walk_union_nodes (a diagnostic of how coherent the 64 walks of a wave are);
+ * "sample_patch" / "sample_uniform" = the patch shape of exa_hip_resample's grid kernel (0 64x1x1, 1 16x4x1, 2 8x8x1,
+ * 3 4x4x4 (default) grid points per wave) and whether its waves descend the kd tree and read a shared region's brick headers together
+ * (1, default) or lane by lane (0): same values bit for bit either way;
  * "profile_marker" N = launch an empty kernel (profileMarkerKernel) on the null stream now: a bracket in a profiler's
  * dispatch list, no effect on any frame.
  * "walk" selects how the DVR march of the kd path finds its segments: 1 = the ordered walk of the region kd-tree with a

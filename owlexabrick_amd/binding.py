@@ -95,7 +95,12 @@ ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa
                "exa_hip_advance_tracer", "exa_hip_read_traces", "exa_hip_set_params", "exa_hip_set_shard", "exa_hip_output_pixels",
                "exa_hip_untile", "exa_hip_render", "exa_hip_render_stats", "exa_hip_get_stats",
                "exa_hip_read_accum", "exa_hip_write_accum", "exa_hip_read_activity",
-               "exa_hip_set_option", "exa_hip_last_error"]
+               "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample"]
+
+# exa_hip_sample_points / exa_hip_resample flags (include/exa_hip.h)
+SAMPLE_WORLD_SPACE = 1
+SAMPLE_GRADIENT = 2
+SAMPLE_GRADIENT_NORMALIZED = 4
 
 _lib = None
 
@@ -150,6 +155,9 @@ def lib():
         L.exa_hip_set_option.argtypes = [vp, C.c_char_p, C.c_int32]
         L.exa_hip_last_error.restype = C.c_char_p
         L.exa_hip_last_error.argtypes = [vp]
+        L.exa_hip_sample_points.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp,
+                                            C.c_int32, vp, C.c_int32]
+        L.exa_hip_resample.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp, C.c_int32]
         _lib = L
     return _lib
 
@@ -416,3 +424,70 @@ class Renderer:
     def untile(self, gathered_ptr, shard_stride, world, out_ptr, stream=None):
         self._check(lib().exa_hip_untile(self.h, C.c_void_p(gathered_ptr), shard_stride, world,
                                          C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
+
+    # ---- point probes (exa_hip_sample_points / exa_hip_resample; include/exa_hip.h states the contract) ----
+    def _probe_world(self, world):
+        if world:                       # the voxelSpaceTransform lives in the frame state the module holds
+            self._push_state()
+        return SAMPLE_WORLD_SPACE if world else 0
+
+    def samplePoints(self, points, channels=(0,), gradient=False, normalized=False, world=False, fill=float("nan"),
+                     stream=None, async_=False):
+        """the reconstructed field at points [n,3] (voxel space, or world space with world=True).  Returns
+        (values [n, len(channels)], gradients [n, len(channels), 3] or None, status [n, len(channels)]): status = region id,
+        -1 outside every region, -2 where the basis weights vanish; value and gradient are `fill` where status < 0.
+        gradient: the reference's numerator sumW*sumD - sumWV*sumDC; normalized: divided by sumW^2 (the true gradient),
+        both with respect to voxel-space coordinates.  A numpy array takes the host path; a contiguous float32 torch CUDA
+        tensor (memory of the handle's first device) the device path, with torch tensors out (async_ on `stream`)."""
+        chans = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+        flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradient or normalized else 0)
+        flags |= SAMPLE_GRADIENT_NORMALIZED if normalized else 0
+        k = chans.size
+        if getattr(points, "is_cuda", False):
+            import torch
+            if points.dtype != torch.float32 or not points.is_contiguous() or points.numel() % 3:
+                raise TypeError("points: a contiguous float32 tensor [n, 3]")
+            n = points.numel() // 3
+            values = torch.empty((n, k), dtype=torch.float32, device=points.device)
+            grads = torch.empty((n, k, 3), dtype=torch.float32, device=points.device) if flags & SAMPLE_GRADIENT else None
+            status = torch.empty((n, k), dtype=torch.int32, device=points.device)
+            self._check(lib().exa_hip_sample_points(self.h, _dev_ptr(points), n, chans.ctypes.data, k, flags, float(fill),
+                                                    _dev_ptr(values), _dev_ptr(grads), _dev_ptr(status), 1,
+                                                    C.c_void_p(stream or 0), int(async_)))
+            return values, grads, status
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        values = np.empty((n, k), dtype=np.float32)
+        grads = np.empty((n, k, 3), dtype=np.float32) if flags & SAMPLE_GRADIENT else None
+        status = np.empty((n, k), dtype=np.int32)
+        self._check(lib().exa_hip_sample_points(self.h, pts.ctypes.data, n, chans.ctypes.data, k, flags, float(fill),
+                                                values.ctypes.data, grads.ctypes.data if grads is not None else None,
+                                                status.ctypes.data, 0, None, 0))
+        return values, grads, status
+
+    def resample(self, lo, hi, dims, channel=0, world=False, fill=float("nan"), out_ptr=None, stream=None, async_=False):
+        """the field at the cell centres of a uniform dims[0] x dims[1] x dims[2] grid over the box [lo, hi] (voxel space, or
+        world space with world=True).  Without out_ptr returns a float32 array [nz, ny, nx] (x fastest); out_ptr (a device
+        pointer or a contiguous float32 torch CUDA tensor) takes the device path and returns None."""
+        flags = self._probe_world(world)
+        lo3 = (C.c_float * 3)(*[float(v) for v in lo])
+        hi3 = (C.c_float * 3)(*[float(v) for v in hi])
+        d3 = (C.c_int32 * 3)(*[int(v) for v in dims])
+        if out_ptr is not None:
+            self._check(lib().exa_hip_resample(self.h, lo3, hi3, d3, int(channel), flags, float(fill), _dev_ptr(out_ptr), 1,
+                                               C.c_void_p(stream or 0), int(async_)))
+            return None
+        out = np.empty(tuple(max(int(d), 0) for d in dims[::-1]), dtype=np.float32)     # the module checks the dims
+        self._check(lib().exa_hip_resample(self.h, lo3, hi3, d3, int(channel), flags, float(fill), out.ctypes.data, 0, None, 0))
+        return out
+
+
+def _dev_ptr(x):
+    """a device pointer from an int, None, or a contiguous torch CUDA tensor of 4-byte elements"""
+    if x is None:
+        return None
+    if isinstance(x, int):
+        return C.c_void_p(x)
+    if not (getattr(x, "is_cuda", False) and x.is_contiguous() and x.element_size() == 4):
+        raise TypeError("a device pointer or a contiguous float32 / int32 torch CUDA tensor is expected")
+    return C.c_void_p(x.data_ptr())

@@ -227,6 +227,39 @@ struct RenderArgs {
   uint32_t          *tileCost;      // != null: per tile id, brick visits of the tile's longest ray (launch-order feedback)
 };
 
+// The point probes (exa_hip_sample_points / exa_hip_resample, exa_sample_kernels.h): the region is found by descending the
+// region kd-tree on the position alone (no activity bits), the value is samplePoint on the march headers.  One launch covers
+// `count` points, or the box [box0, box1) of grid indices in compact patches of 64 points per wave.
+struct SampleArgs {
+  const int4        *leafHdr;       // march headers along the leaf list (DeviceScene::leafHdr)
+  const float       *scalars;
+  const KdNodeDev   *kdNodes;       // the region kd-tree (NULL for a one-region tree whose root is the leaf)
+  const RegionRec   *regionRec;     // closed domain + leaf-list range of every region
+  int32_t            kdRoot;
+  int32_t            maxSteps;      // bound of the descent (every path is shorter: children come after their parent)
+  float              kdLo[3], kdHi[3];
+  int32_t           *errorFlag;     // set when the bound trips
+  int32_t            world;         // positions in world space: mapped with fs' voxelSpaceTransform (xfmPoint)
+  int32_t            normalized;    // gradients divided by sumW * sumW
+  float              fill;          // value / gradient of a point and channel whose status is < 0
+  ExaHipFrameState   fs;
+  int32_t            numChannels;
+  unsigned long long fieldOffset[EXA_MAX_CHANNELS];   // channelOffset of each requested channel
+  // points: n x 3 floats in, n x numChannels values / status and n x numChannels x 3 gradients (may be NULL) out
+  const float       *points;
+  unsigned long long count;
+  float             *values, *gradients;
+  int32_t           *status;
+  // grid: position lo + (i + 0.5) * step per axis, output index (x - box0.x) + (y - box0.y) * strideY + (z - box0.z) * strideZ
+  float              lo[3], step[3];
+  int32_t            box0[3], box1[3];
+  unsigned long long patchesX, patchesY, numPatches;   // patches of the box along x, y, and in all
+  unsigned long long strideY, strideZ;
+  float             *out;
+};
+// patch shapes of the grid kernel (x, y, z extents; 64 points each)
+enum { kSamplePatchShapes = 4 };
+
 // ---- exa_lbvh.hip: LBVH topology over numPrims boxes (6 floats each, device), built on the device ----
 hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNode *nodes, int32_t *levelIds,
                                    std::vector<uint32_t> &internalNodesPerDepth, hipStream_t s);
@@ -250,7 +283,11 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
   hipError_t launchRenderKdWide(const RenderArgs &a, int numTiles, int lanesPerRay, bool grad, bool fast, bool surf,    \
                                 hipStream_t s);                                                                         \
   /* computeTraces (exabrick.cu:1531-1574): one thread per trace, run before the frame kernel */                        \
-  hipError_t launchComputeTraces(const RenderArgs &a, float *traces, int count, hipStream_t s);
+  hipError_t launchComputeTraces(const RenderArgs &a, float *traces, int count, hipStream_t s);                        \
+  /* the point probes (exa_sample_f*.o): a.count points; the grid box of a, in patch shape `shape` (0 64x1x1,         \
+     1 16x4x1, 2 8x8x1, 3 4x4x4), wave-uniform descent and brick headers where a patch allows (uniform) or per lane */  \
+  hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s);                                      \
+  hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);
 namespace form0 { EXA_FORM_LAUNCHERS }
 namespace form1 { EXA_FORM_LAUNCHERS }
 // ... and once more in the source order with the reference's ALLOW_EMPTY_CELLS semantics (-DEXA_EMPTY_CELLS=1: a corner whose

@@ -38,6 +38,10 @@
 #ifndef EXA_TU_ROPE
 #define EXA_TU_ROPE 0
 #endif
+// The point probes likewise (-DEXA_TU_SAMPLE=1: exa_sample_f*.o, the kernels of exa_sample_kernels.h and nothing else).
+#ifndef EXA_TU_SAMPLE
+#define EXA_TU_SAMPLE 0
+#endif
 namespace exa {
 namespace EXA_FORM_NS {
 
@@ -748,6 +752,13 @@ __device__ __forceinline__ bool samplePoint(Ctx<STATS> &C, float &value, V3 &der
     derivatives = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
   return true;
 }
+
+#if EXA_TU_SAMPLE
+// the point probes (exa_hip_sample_points / exa_hip_resample) in translation units of their own (-DEXA_TU_SAMPLE=1:
+// exa_sample_f*.o hold these kernels and nothing else); everything below is the renderer
+#include "exa_sample_kernels.h"
+} // namespace EXA_FORM_NS
+#else
 
 // the sample's colour after gradient shading and its opacity after the correction; actual_dt != 0
 template <bool FAST, int STATS, bool HAVE_RCP = false, bool LEAN = false>
@@ -3482,4 +3493,5 @@ hipError_t launchProfileMarker(int tag, hipStream_t s)
   return hipGetLastError();
 }
 #endif // EXA_BASIS_FORM == 0 && !EXA_EMPTY_CELLS
+#endif // EXA_TU_SAMPLE
 } // namespace exa

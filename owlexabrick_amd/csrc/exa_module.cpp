@@ -391,6 +391,10 @@ struct ExaHipRenderer {
   int walkProbeOn = 0;                  // option walk_probe
   DevBuf<uint32_t> walkProbe;
   DevBuf<int32_t> errorFlag;
+  // point probes (exa_hip_sample_points / exa_hip_resample): the device copy of a chunk of host arrays (bounded, grown on
+  // demand), and the grid kernel's patch shape / wave-uniform path (options sample_patch, sample_uniform)
+  DevBuf<char> probeStage;
+  int samplePatch = 3, sampleUniform = 1;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 
@@ -1789,6 +1793,11 @@ int exa_hip_set_option(ExaHipRenderer *h, const char *key, int32_t value)
     }
     h->basisForm = value; return 0;
   }
+  if (!std::strcmp(key, "sample_patch")) {
+    if (value < 0 || value >= kSamplePatchShapes) { h->fail("exa_hip_set_option: sample_patch is 0 (64x1x1), 1 (16x4x1), 2 (8x8x1) or 3 (4x4x4)"); return 1; }
+    h->samplePatch = value; return 0;
+  }
+  if (!std::strcmp(key, "sample_uniform")) { h->sampleUniform = value != 0; return 0; }
   if (!std::strcmp(key, "interleave")) { h->interleave = value != 0; return 0; }
   if (!std::strcmp(key, "addr64")) { h->addr64 = value != 0; return 0; }
   if (!std::strcmp(key, "pack_records")) { h->packRecords = value != 0; return 0; }
@@ -2020,6 +2029,179 @@ int exa_hip_read_activity(ExaHipRenderer *h, int32_t which, uint8_t *dst)
   HIP_TRY(h, hipDeviceSynchronize());
   HIP_TRY(h, hipMemcpy(dst, which ? h->isoActive.p : h->volActive.p, h->sc.numRegions, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- point probes ----
+// Host arrays pass through the handle's staging buffer in chunks of at most kProbeStageBytes; a launch covers at most
+// kProbeLaunch points (a grid patch holds one point at the least: 64 x that many lanes stay below 2^32).
+static const uint64_t kProbeStageBytes = 64ull << 20, kProbeLaunch = 1ull << 24;
+
+static hipError_t launchProbePoints(const ExaHipRenderer *r, const SampleArgs &a, bool grad, hipStream_t s)
+{
+  return r->emptyCells ? form0e::launchSamplePoints(a, grad, s)
+                       : (r->basisForm ? form1::launchSamplePoints(a, grad, s) : form0::launchSamplePoints(a, grad, s));
+}
+static hipError_t launchProbeGrid(const ExaHipRenderer *r, const SampleArgs &a, hipStream_t s)
+{
+  const bool u = r->sampleUniform != 0;
+  return r->emptyCells ? form0e::launchSampleGrid(a, r->samplePatch, u, s)
+                       : (r->basisForm ? form1::launchSampleGrid(a, r->samplePatch, u, s) : form0::launchSampleGrid(a, r->samplePatch, u, s));
+}
+
+// what both probes share: the renderer that runs them (a multi-device handle: the one of devices[0]), the checks, a pending
+// brick order applied (render does the same: the probes read `begin` through the march headers the permutation patches)
+static int probeSetup(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, bool world, hipStream_t s, SampleArgs &a)
+{
+  if (!r->haveKd) {
+    h->fail(std::string(fn) + ": the scene has no region kd-tree (ExaHipScene.kdNodes): the probes locate a point's region with it "
+            "(the LBVH is refit to the region activity and cannot)");
+    return 1;
+  }
+  if (world && !r->haveFs) { h->fail(std::string(fn) + ": world space needs a frame state (the voxelSpaceTransform of exa_hip_set_frame_state)"); return 1; }
+  if (r->applyBrickOrder(s)) { h->fail(r->err); return 1; }
+  std::memset(&a, 0, sizeof(a));
+  a.leafHdr = r->leafHdr.p;
+  a.scalars = r->scalars.p;
+  a.kdNodes = r->kdNodes.p;
+  a.regionRec = r->regionRec.p;
+  a.kdRoot = r->kdRoot;
+  a.maxSteps = (int32_t)std::min<uint64_t>(r->kdNodes.n + 1, INT32_MAX);
+  for (int k = 0; k < 3; k++) { a.kdLo[k] = r->kdLo[k]; a.kdHi[k] = r->kdHi[k]; }
+  a.errorFlag = r->errorFlag.p;
+  a.world = world ? 1 : 0;
+  if (world) a.fs = r->fs;
+  return 0;
+}
+
+// after a synchronous probe: the descent's loop guard
+static int probeCheckGuard(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn)
+{
+  int32_t flag = 0;
+  HIP_TRY(h, hipMemcpy(&flag, r->errorFlag.p, sizeof(flag), hipMemcpyDeviceToHost));
+  if (flag) {
+    (void)hipMemset(r->errorFlag.p, 0, sizeof(int32_t));
+    h->fail(std::string(fn) + ": the kd descent's loop guard tripped (malformed kd-tree?)");
+    return 3;
+  }
+  return 0;
+}
+
+int exa_hip_sample_points(ExaHipRenderer *h, const float *points, uint64_t n, const int32_t *channels, int32_t numChannels,
+                          int32_t flags, float fill, float *values, float *gradients, int32_t *status,
+                          int32_t pointersAreDevice, void *hipStream, int32_t async)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_sample_points";
+  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED)) { h->fail(std::string(fn) + ": unknown flag bits"); return 1; }
+  const bool grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
+  if ((flags & EXA_SAMPLE_GRADIENT_NORMALIZED) && !grad) { h->fail(std::string(fn) + ": EXA_SAMPLE_GRADIENT_NORMALIZED needs EXA_SAMPLE_GRADIENT"); return 1; }
+  if (!channels || numChannels < 1 || numChannels > EXA_MAX_CHANNELS) { h->fail(std::string(fn) + ": 1..10 channels required"); return 1; }
+  for (int c = 0; c < numChannels; c++)
+    if (channels[c] < 0 || channels[c] >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  if (n == 0) return 0;
+  if (!points || !values || (grad && !gradients)) { h->fail(std::string(fn) + ": null array (points, values, or gradients with EXA_SAMPLE_GRADIENT)"); return 1; }
+  if (n > (UINT64_MAX / 12) / uint64_t(numChannels)) { h->fail(std::string(fn) + ": too many points"); return 1; }
+  ExaHipRenderer *r = h->children.empty() ? h : h->children[0];
+  DeviceGuard guard_(r->device);
+  HIP_TRY(h, guard_.err);
+  hipStream_t s = (hipStream_t)hipStream;
+  SampleArgs a;
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a)) return 1;
+  a.fill = fill;
+  a.normalized = (flags & EXA_SAMPLE_GRADIENT_NORMALIZED) ? 1 : 0;
+  a.numChannels = numChannels;
+  for (int c = 0; c < numChannels; c++) a.fieldOffset[c] = r->sc.channelOffset[channels[c]];
+  const uint64_t nch = uint64_t(numChannels);
+  if (pointersAreDevice) {
+    for (uint64_t at = 0; at < n; at += kProbeLaunch) {
+      a.count = std::min(kProbeLaunch, n - at);
+      a.points = points + 3 * at;
+      a.values = values + at * nch;
+      a.gradients = grad ? gradients + 3 * at * nch : nullptr;
+      a.status = status ? status + at * nch : nullptr;
+      HIP_TRY(h, launchProbePoints(r, a, grad, s));
+    }
+    if (async) return 0;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return probeCheckGuard(h, r, fn);
+  }
+  // host arrays: chunk by chunk through the staging buffer {points | values | gradients | status}
+  const uint64_t perPoint = 12 + nch * 4 * (1 + (grad ? 3 : 0) + (status ? 1 : 0));
+  const uint64_t chunk = std::max<uint64_t>(1, std::min(kProbeLaunch, kProbeStageBytes / perPoint));
+  const uint64_t need = std::min(n, chunk) * perPoint;
+  if (r->probeStage.n < need) HIP_TRY(h, r->probeStage.alloc(need));
+  for (uint64_t at = 0; at < n; at += chunk) {
+    const uint64_t m = std::min(chunk, n - at);
+    char *p = r->probeStage.p;
+    a.count = m;
+    a.points = reinterpret_cast<const float *>(p);
+    a.values = reinterpret_cast<float *>(p + 12 * m);
+    a.gradients = grad ? reinterpret_cast<float *>(p + 12 * m + 4 * m * nch) : nullptr;
+    a.status = status ? reinterpret_cast<int32_t *>(p + 12 * m + 4 * m * nch * (grad ? 4 : 1)) : nullptr;
+    HIP_TRY(h, hipMemcpyAsync(p, points + 3 * at, 12 * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launchProbePoints(r, a, grad, s));
+    HIP_TRY(h, hipMemcpyAsync(values + at * nch, a.values, 4 * m * nch, hipMemcpyDeviceToHost, s));
+    if (grad) HIP_TRY(h, hipMemcpyAsync(gradients + 3 * at * nch, a.gradients, 12 * m * nch, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status + at * nch, a.status, 4 * m * nch, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+  }
+  return probeCheckGuard(h, r, fn);
+}
+
+int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
+                     int32_t flags, float fill, float *out, int32_t dstIsDevice, void *hipStream, int32_t async)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_resample";
+  if (flags & ~EXA_SAMPLE_WORLD_SPACE) { h->fail(std::string(fn) + ": unknown flag bits (only EXA_SAMPLE_WORLD_SPACE applies)"); return 1; }
+  if (!lo || !hi || !dims || !out) { h->fail(std::string(fn) + ": null argument"); return 1; }
+  for (int k = 0; k < 3; k++) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
+    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
+  }
+  if (channel < 0 || channel >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  ExaHipRenderer *r = h->children.empty() ? h : h->children[0];
+  DeviceGuard guard_(r->device);
+  HIP_TRY(h, guard_.err);
+  hipStream_t s = (hipStream_t)hipStream;
+  SampleArgs a;
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a)) return 1;
+  a.fill = fill;
+  a.numChannels = 1;
+  a.fieldOffset[0] = r->sc.channelOffset[channel];
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  static const int kShape[kSamplePatchShapes][3] = { { 64, 1, 1 }, { 16, 4, 1 }, { 8, 8, 1 }, { 4, 4, 4 } };
+  const int *ps = kShape[r->samplePatch];
+  const uint64_t nx = uint64_t(dims[0]), ny = uint64_t(dims[1]), nz = uint64_t(dims[2]);
+  // boxes of at most kProbeLaunch points: whole slabs of z, else rows of one slice, else pieces of one row — each one
+  // contiguous in the output, so a host destination takes one copy per box
+  const uint64_t bx = std::min(nx, kProbeLaunch), by = std::min(ny, std::max<uint64_t>(1, kProbeLaunch / bx)),
+                 bz = std::min(nz, std::max<uint64_t>(1, kProbeLaunch / (bx * by)));
+  if (!dstIsDevice && r->probeStage.n < bx * by * bz * 4) HIP_TRY(h, r->probeStage.alloc(bx * by * bz * 4));
+  for (uint64_t z0 = 0; z0 < nz; z0 += bz)
+    for (uint64_t y0 = 0; y0 < ny; y0 += by)
+      for (uint64_t x0 = 0; x0 < nx; x0 += bx) {
+        const uint64_t ex = std::min(bx, nx - x0), ey = std::min(by, ny - y0), ez = std::min(bz, nz - z0);
+        a.box0[0] = int32_t(x0); a.box0[1] = int32_t(y0); a.box0[2] = int32_t(z0);
+        a.box1[0] = int32_t(x0 + ex); a.box1[1] = int32_t(y0 + ey); a.box1[2] = int32_t(z0 + ez);
+        a.patchesX = (ex + ps[0] - 1) / ps[0];
+        a.patchesY = (ey + ps[1] - 1) / ps[1];
+        a.numPatches = a.patchesX * a.patchesY * ((ez + ps[2] - 1) / ps[2]);
+        const uint64_t first = (z0 * ny + y0) * nx + x0;
+        if (dstIsDevice) {
+          a.out = out + first; a.strideY = nx; a.strideZ = nx * ny;
+        } else {
+          a.out = reinterpret_cast<float *>(r->probeStage.p); a.strideY = ex; a.strideZ = ex * ey;
+        }
+        HIP_TRY(h, launchProbeGrid(r, a, s));
+        if (!dstIsDevice) {
+          HIP_TRY(h, hipMemcpyAsync(out + first, a.out, ex * ey * ez * sizeof(float), hipMemcpyDeviceToHost, s));
+          HIP_TRY(h, hipStreamSynchronize(s));
+        }
+      }
+  if (dstIsDevice && async) return 0;
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return probeCheckGuard(h, r, fn);
 }
 
 } // extern "C"

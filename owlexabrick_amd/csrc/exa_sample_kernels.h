@@ -1,0 +1,184 @@
+// exa_sample_kernels.h — the point probes: exa_hip_sample_points (one lane per point) and exa_hip_resample (one wave per
+// compact patch of 64 grid points).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
+// -DEXA_TU_SAMPLE=1 (exa_sample_f0.o, exa_sample_f1.o, exa_sample_f0e.o), after samplePoint and the basis evaluations it
+// uses; nothing else of the renderer is compiled there.
+//
+// Contract (include/exa_hip.h): the region of a position comes from the region kd-tree alone — inside the closed root box,
+// `right` where p[axis] >= split, else `left`, down to a leaf, accepted if p lies in that region's closed domain — so a
+// result depends on the scene, the position, the basis form and (world space) the transform, never on the transfer
+// function, the activity bits or any other knob.  The value is samplePoint on the march headers (the sums of the DVR
+// march and of the oracle, bit for bit); status -2 where sumW <= 1e-20 (the reference's samplePoint returns false).
+
+// p inside the closed root box; false for a NaN coordinate
+__device__ __forceinline__ bool sampleInRoot(const SampleArgs &a, V3 p)
+{
+  return p.x >= a.kdLo[0] && p.x <= a.kdHi[0] && p.y >= a.kdLo[1] && p.y <= a.kdHi[1] && p.z >= a.kdLo[2] && p.z <= a.kdHi[2];
+}
+
+// the child of a node on p's side of its plane (only split, axis and children: the activity bits are masked)
+__device__ __forceinline__ int sampleKdChild(const KdNodeDev n, V3 p)
+{
+  const uint32_t axis = n.word & 3u;
+  const float c = axis == 0u ? p.x : (axis == 1u ? p.y : p.z);
+  return c >= n.split ? n.right : n.left;
+}
+
+// from subtree `ref` down to a leaf: the region id, or -1 (an empty child slot, or the bound tripped)
+__device__ __forceinline__ int sampleKdLeaf(const SampleArgs &a, int ref, V3 p, bool &tripped)
+{
+  for (int g = 0; ref >= 0; g++) {
+    if (g >= a.maxSteps) { tripped = true; return -1; }
+    ref = sampleKdChild(a.kdNodes[ref], p);
+  }
+  return ref == EXA_KD_EMPTY ? -1 : ~ref;
+}
+
+__device__ __forceinline__ bool sampleInDomain(const RegionRec &R, V3 p)
+{
+  return p.x >= R.lo[0] && p.x <= R.hi0 && p.y >= R.lo[1] && p.y <= R.hi1 && p.z >= R.lo[2] && p.z <= R.hi2;
+}
+
+// samplePoint's sums (exabrick.cu:781-806, 883-928) over the region's bricks, through the march headers: the loop of
+// samplePoint with fastSampler.  listBegin / listSize wave-uniform -> the headers are read once per wave.
+template <bool DERIV>
+__device__ __forceinline__ Basis sampleSums(const SampleArgs &a, int listBegin, int listSize, const float *field, V3 p)
+{
+  Ctx<0> C;                       // no counters
+  Basis B;
+  B.sumWV = 0.f; B.sumW = 0.f; B.sumD = mk(0.f, 0.f, 0.f); B.sumDC = mk(0.f, 0.f, 0.f);
+  for (int child = 0; child < listSize; child++) {
+    const size_t at = 2 * (size_t(listBegin) + size_t(child));
+    const int4 h0 = a.leafHdr[at], h1 = a.leafHdr[at + 1];
+    addBasisFast<DERIV, 0, false>(C, B, h0, h1, field, p);
+  }
+  return B;
+}
+
+// one lane per point, the region located once for all channels
+template <bool DERIV>
+__global__ __launch_bounds__(256) void samplePointsKernel(const SampleArgs a)
+{
+  const size_t i = size_t(blockIdx.x) * 256u + threadIdx.x;
+  if (i >= a.count) return;
+  V3 p = mk(a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]);
+  if (a.world) p = xfmPoint(a.fs, p);
+  bool tripped = false;
+  int region = sampleInRoot(a, p) ? sampleKdLeaf(a, a.kdRoot, p, tripped) : -1;
+  if (tripped) atomicExch(a.errorFlag, 1);
+  RegionRec R;
+  R.listBegin = 0; R.listSize = 0;
+  if (region >= 0) {
+    R = a.regionRec[region];
+    if (!sampleInDomain(R, p)) region = -1;
+  }
+  for (int c = 0; c < a.numChannels; c++) {
+    const size_t o = i * size_t(a.numChannels) + size_t(c);
+    int st = region;
+    float value = a.fill;
+    V3 grad = mk(a.fill, a.fill, a.fill);
+    if (region >= 0) {
+      const Basis B = sampleSums<DERIV>(a, R.listBegin, R.listSize, a.scalars + a.fieldOffset[c], p);
+      if (B.sumW <= 1e-20f) {
+        st = -2;
+      } else {
+        value = B.sumWV / B.sumW;
+        if (DERIV) {
+          grad = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
+          if (a.normalized) {
+            const float w2 = B.sumW * B.sumW;
+            grad = mk(grad.x / w2, grad.y / w2, grad.z / w2);
+          }
+        }
+      }
+    }
+    a.values[o] = value;
+    if (DERIV) { a.gradients[3 * o] = grad.x; a.gradients[3 * o + 1] = grad.y; a.gradients[3 * o + 2] = grad.z; }
+    if (a.status) a.status[o] = st;
+  }
+}
+
+// One wave per patch of PX x PY x PZ = 64 grid points (lane -> point x fastest).  UNIFORM: the wave descends the tree
+// together while all its lanes (those inside the root box) take the same side of every plane — the node index is
+// wave-uniform, one scalar load per node — then each lane on its own from there; when all lanes land in the same region,
+// its record and brick headers are read once per wave through a wave-uniform index.  Otherwise (and without UNIFORM) the
+// per-lane path of samplePointsKernel.  Both find the same region and add the same bricks in the same order: the grid
+// equals the points API bit for bit.
+template <int PX, int PY, int PZ, bool UNIFORM>
+__global__ __launch_bounds__(256) void sampleGridKernel(const SampleArgs a)
+{
+  static_assert(PX * PY * PZ == 64, "a patch is one wave");
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long wave = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (wave >= a.numPatches) return;
+  const unsigned long long wx = wave % a.patchesX, wyz = wave / a.patchesX;
+  const unsigned long long wy = wyz % a.patchesY, wz = wyz / a.patchesY;
+  const long long x = a.box0[0] + (long long)(wx * PX + lane % PX);
+  const long long y = a.box0[1] + (long long)(wy * PY + (lane / PX) % PY);
+  const long long z = a.box0[2] + (long long)(wz * PZ + lane / (PX * PY));
+  if (x >= a.box1[0] || y >= a.box1[1] || z >= a.box1[2]) return;
+  V3 p = mk(a.lo[0] + (float(x) + 0.5f) * a.step[0], a.lo[1] + (float(y) + 0.5f) * a.step[1], a.lo[2] + (float(z) + 0.5f) * a.step[2]);
+  if (a.world) p = xfmPoint(a.fs, p);
+  const bool inRoot = sampleInRoot(a, p);
+  bool tripped = false;
+  int region = -1;
+  if (inRoot) {
+    int ref = a.kdRoot;
+    if (UNIFORM) {
+      for (int g = 0; ref >= 0 && g < a.maxSteps; g++) {
+        const int u = __builtin_amdgcn_readfirstlane(ref);           // the same in every lane here
+        const int next = sampleKdChild(a.kdNodes[u], p);
+        if (anyLane(next != __builtin_amdgcn_readfirstlane(next))) break;   // the lanes part at this node
+        ref = next;
+      }
+    }
+    region = sampleKdLeaf(a, ref, p, tripped);
+  }
+  if (tripped) atomicExch(a.errorFlag, 1);
+  const float *field = a.scalars + a.fieldOffset[0];
+  const int r0 = __builtin_amdgcn_readfirstlane(region);
+  float value = a.fill;
+  int st = -1;
+  if (UNIFORM && r0 >= 0 && !anyLane(region != r0)) {
+    const RegionRec R = a.regionRec[r0];                               // wave-uniform index: one record per wave
+    if (sampleInDomain(R, p)) {
+      const Basis B = sampleSums<false>(a, R.listBegin, R.listSize, field, p);
+      st = B.sumW <= 1e-20f ? -2 : r0;
+      if (st >= 0) value = B.sumWV / B.sumW;
+    }
+  } else if (region >= 0) {
+    const RegionRec R = a.regionRec[region];
+    if (sampleInDomain(R, p)) {
+      const Basis B = sampleSums<false>(a, R.listBegin, R.listSize, field, p);
+      st = B.sumW <= 1e-20f ? -2 : region;
+      if (st >= 0) value = B.sumWV / B.sumW;
+    }
+  }
+  const size_t o = size_t(x - a.box0[0]) + size_t(y - a.box0[1]) * size_t(a.strideY) + size_t(z - a.box0[2]) * size_t(a.strideZ);
+  a.out[o] = value;
+}
+
+hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s)
+{
+  if (a.count == 0) return hipSuccess;
+  const dim3 grid((unsigned)((a.count + 255) / 256)), block(256);
+  if (grad) hipLaunchKernelGGL((samplePointsKernel<true>), grid, block, 0, s, a);
+  else      hipLaunchKernelGGL((samplePointsKernel<false>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s)
+{
+  if (a.numPatches == 0) return hipSuccess;
+  const dim3 grid((unsigned)((a.numPatches + 3) / 4)), block(256);
+#define EXA_SG(X, Y, Z) do { if (uniform) hipLaunchKernelGGL((sampleGridKernel<X, Y, Z, true>), grid, block, 0, s, a); \
+                             else hipLaunchKernelGGL((sampleGridKernel<X, Y, Z, false>), grid, block, 0, s, a); } while (0)
+  switch (shape) {
+  case 0: EXA_SG(64, 1, 1); break;
+  case 1: EXA_SG(16, 4, 1); break;
+  case 2: EXA_SG(8, 8, 1); break;
+  case 3: EXA_SG(4, 4, 4); break;
+  default: return hipErrorInvalidValue;
+  }
+#undef EXA_SG
+  return hipGetLastError();
+}

@@ -12,6 +12,11 @@
 //             [--option key=int]...          exa_hip_set_option, e.g. walk=1|2 (stack / rope walk of the region kd-tree), ao_overlap=0
 //             [--pipeline]                   frames go to two device buffers in turn, frame k's copy to the host overlaps
 //                                            frame k+1's march
+//             [--resample NX NY NZ file.raw] the field on a uniform grid of cell centres (exa_hip_resample) as plain float32,
+//                                            x fastest (the inverse of the reference's tools/fromVolume/raw2cells.cpp), with
+//             [--resample-box lx ly lz ux uy uz] [--resample-world] [--resample-channel c] [--resample-fill v]
+//                                            (box default: the voxel bounds, or the world bounds with --resample-world;
+//                                            fill default NaN); --frames 0 renders nothing
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -65,6 +70,11 @@ int main(int argc, char **argv)
     std::vector<float> contourPlanes;                             // 4 floats per --contourplane (normal, offset)
     std::vector<std::pair<std::string, int>> options;             // --option key=value
     std::vector<int> contourChans;
+    int resampleDims[3] = { 0, 0, 0 }, resampleChannel = 0;
+    std::string resampleName;
+    bool resampleWorld = false, haveResampleBox = false;
+    box3f resampleBox;
+    float resampleFill = NAN;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -104,6 +114,15 @@ int main(int argc, char **argv)
         }
         if (devices.empty()) throw std::runtime_error("--devices wants a comma-separated list of device indices");
       }
+      else if (a == "--resample") {
+        for (int k = 0; k < 3; k++) resampleDims[k] = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --resample NX NY NZ");
+        resampleName = argv[++i];
+      }
+      else if (a == "--resample-box") { resampleBox.lower = { f(), f(), f() }; resampleBox.upper = { f(), f(), f() }; haveResampleBox = true; }
+      else if (a == "--resample-world") resampleWorld = true;
+      else if (a == "--resample-channel") resampleChannel = (int)f();
+      else if (a == "--resample-fill") resampleFill = f();
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
       else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
@@ -183,6 +202,24 @@ int main(int argc, char **argv)
       const box3f wb = renderer.worldSpaceBounds;
       renderer.frameState.clipBox.coords.lower = wb.lower + clipBox.lower * wb.span();
       renderer.frameState.clipBox.coords.upper = wb.lower + clipBox.upper * wb.span();
+    }
+    if (!resampleName.empty()) {
+      const box3f box = haveResampleBox ? resampleBox : (resampleWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
+      const vec3i dims(resampleDims[0], resampleDims[1], resampleDims[2]);
+      if (dims.x < 1 || dims.y < 1 || dims.z < 1) throw std::runtime_error("--resample wants NX NY NZ >= 1");
+      std::vector<float> grid(size_t(dims.x) * size_t(dims.y) * size_t(dims.z));
+      // sampled with a NaN fill to count the points outside every region (a reconstructed value is never NaN for a field
+      // without NaNs), then the requested fill written in their place
+      renderer.resample(box, dims, resampleChannel, grid.data(), resampleWorld, NAN);
+      size_t invalid = 0;
+      for (float &v : grid)
+        if (std::isnan(v)) { v = resampleFill; invalid++; }
+      FILE *f = std::fopen(resampleName.c_str(), "wb");
+      if (!f || std::fwrite(grid.data(), sizeof(float), grid.size(), f) != grid.size()) throw std::runtime_error("cannot write " + resampleName);
+      std::fclose(f);
+      std::printf("resample %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channel %d invalid %zu\n", dims.x, dims.y, dims.z,
+                  box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z, resampleChannel, invalid);
+      if (frames == 0) return 0;
     }
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);

@@ -522,6 +522,25 @@ ExaHipStats Renderer::renderStats()
 
 void Renderer::setOption(const std::string &key, int value) { check(exa_hip_set_option(handle, key.c_str(), value), handle); }
 
+void Renderer::samplePoints(const vec3f *points, size_t n, const int *channels, int numChannels, float *values,
+                            float *gradients, int *status, bool worldSpace, bool normalized, float fill)
+{
+  static_assert(sizeof(vec3f) == 3 * sizeof(float), "points are 3 floats each");
+  if (worldSpace) pushState();
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0)
+                  | (gradients && normalized ? EXA_SAMPLE_GRADIENT_NORMALIZED : 0);
+  check(exa_hip_sample_points(handle, reinterpret_cast<const float *>(points), n, channels, numChannels, flags, fill, values,
+                              gradients, status, 0, nullptr, 0), handle);
+}
+
+void Renderer::resample(const box3f &box, vec3i dims, int channel, float *out, bool worldSpace, float fill)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z };
+  check(exa_hip_resample(handle, lo, hi, d, channel, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, 0, nullptr, 0), handle);
+}
+
 ExaHipStats Renderer::stats() const
 {
   ExaHipStats s;

@@ -184,6 +184,15 @@ struct Renderer {
   // beyond the stated float tolerance
   void setOption(const std::string &key, int value);
 
+  // point probes (exa_hip_sample_points / exa_hip_resample; include/exa_hip.h states the contract): the reconstructed field
+  // at `n` points (host arrays; values n x numChannels, gradients n x numChannels x 3 or NULL = none, status n x numChannels
+  // or NULL) and at the cell centres of a uniform dims.x x dims.y x dims.z grid over `box` (out: x fastest).  Positions in
+  // voxel space, or in world space through frameState.voxelSpaceTransform (the frame state is pushed first).
+  void samplePoints(const vec3f *points, size_t n, const int *channels, int numChannels, float *values,
+                    float *gradients = nullptr, int *status = nullptr, bool worldSpace = false, bool normalized = false,
+                    float fill = NAN);
+  void resample(const box3f &box, vec3i dims, int channel, float *out, bool worldSpace = false, float fill = NAN);
+
   ExaHipStats stats() const;
   ExaHipStats renderStats();                 // the same frame through the counting variant of the kernels
   size_t numRegions = 0, numLeafEntries = 0; // what Regions::buildFrom produced (exa/Regions.cpp:308-319 prints them)
