@@ -341,6 +341,62 @@ int exa_hip_resample(ExaHipRenderer *, const float lo[3], const float hi[3], con
                      int32_t channel, int32_t flags, float fill,
                      float *out /* dims[0]*dims[1]*dims[2] floats */, int32_t dstIsDevice, void *hipStream, int32_t async);
 
+/* ---- iso-surface extraction: the surface field == iso of one channel on a caller-chosen uniform lattice, as an indexed
+ * triangle mesh without duplicate vertices, consistently oriented, in a fixed order (two runs give the same bytes).  New
+ * relative to the reference, which only renders iso-surfaces implicitly.  Marching tetrahedra on the six-tetrahedra (Kuhn)
+ * split of every lattice cube along the diagonal (0,0,0)-(1,1,1): no ambiguous cases, and the split is translation
+ * invariant, so neighbouring cubes agree on every shared face diagonal and the surface is watertight by construction. ----
+ *
+ * Lattice.  lo, hi, dims (each >= 2 here) and flags as for exa_hip_resample: lattice point (i,j,k) lies at
+ * P = lo + (float(i) + 0.5f) * ((hi - lo) / float(n)) per axis, and its value V is exactly what
+ * exa_hip_resample(lo, hi, dims, channel, flags & EXA_SAMPLE_WORLD_SPACE, fill = NaN) returns there in the handle's current
+ * basis_form.  Linear index L = (k*ny + j)*nx + i.  At most 2^31 - 1 lattice points.
+ *
+ * Valid cubes.  Cube (i,j,k), i < nx-1, j < ny-1, k < nz-1, is valid if all 8 corner values are finite; an invalid cube
+ * emits nothing.  inside(v) = V(v) >= iso; iso must be finite.
+ *
+ * Tetrahedra.  Six per valid cube, one per permutation (a,b,c) of the axes in lexicographic order 012, 021, 102, 120, 201,
+ * 210, with the vertices v0 = cube origin, v1 = v0 + e_a, v2 = v1 + e_b, v3 = v2 + e_c.  Parity = inversions mod 2.
+ *
+ * Vertices.  Every tet edge joins lattice points p and q = p + d, d in {0,1}^3 \ {0}: seven edge kinds per lattice point,
+ * coded dx + 2*dy + 4*dz.  An edge crosses if inside(p) != inside(q).  Exactly one vertex per crossing edge that belongs to
+ * at least one valid cube, no others: t = (iso - V(p)) / (V(q) - V(p)), pos = P(p) + t * (P(q) - P(p)) per component in
+ * float32, every operation rounded separately.  Positions are in the caller's space (the space of lo / hi), never put
+ * through the world transform.  Order: ascending L(p), then ascending edge code.
+ *
+ * Triangles (tet-vertex indices 0..3; "x-y" = the vertex on the edge between tet vertices x and y).
+ *   - one inside vertex s, or one outside vertex s: the triangle (s-o0, s-o1, s-o2), the other three vertices ascending,
+ *     reversed iff parity(s,o0,o1,o2) XOR parity(perm) XOR (three inside);
+ *   - two inside (a < b), two outside (c < d): the quad q = [a-c, a-d, b-d, b-c], reversed iff parity(a,b,c,d) XOR
+ *     parity(perm), then the triangles (q0,q1,q2) and (q0,q2,q3).
+ * Every geometric normal (B-A)x(C-A) then points toward the lower-value side.  Order: ascending L of the cube origin, then
+ * the tet order, then the order above.  Zero-area triangles (a lattice value equal to iso) are kept.  Indices are int32.
+ *
+ * Gradients.  With EXA_SAMPLE_GRADIENT the module also keeps, per vertex, the gradient that exa_hip_sample_points(pos,
+ * flags = world? | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED, fill = NaN) returns there, bit for bit (the same
+ * kernel on the device vertex buffer).  The shading normal is -grad/|grad|; the normalisation is the caller's.
+ *
+ * Independence.  The result depends only on the scene, the lattice, channel, iso, basis_form and (world space) the
+ * transform — not on the transfer function, region activity, the camera, walk, accel, brick_order, sample_patch or
+ * sample_uniform.  A scene without a kd tree is refused, as the probes refuse it.  A multi-device handle runs on devices[0].
+ *
+ * Calls.  exa_hip_isosurface extracts synchronously on hipStream and returns the counts; the mesh stays in module-owned
+ * device memory until the next extraction (also a failed one), exa_hip_isosurface_release or exa_hip_destroy.  An empty
+ * surface returns 0 with zero counts.  The call needs 8 bytes of device memory per lattice point while it runs.  A lattice
+ * of more than 2^31 - 1 points, more than INT32_MAX vertices or triangles, a failed allocation, a NaN or infinite iso, a
+ * dim < 2, a bad channel and flag bits other than EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT are errors with a message.
+ * exa_hip_isosurface_read copies the mesh out: vertices numVertices x 3 floats, gradients numVertices x 3 floats (only after
+ * an extraction with EXA_SAMPLE_GRADIENT), triangles numTriangles x 3 int32; a NULL pointer skips that array; host arrays,
+ * or memory of the handle's first device with pointersAreDevice; an error before any extraction.
+ * exa_hip_isosurface_stage_ms: the device time of the last extraction's stages in ms — lattice values, cube pass (validity
+ * and triangle count per cube), point pass (mask of owned crossing edges per lattice point), scans, emit, gradients. */
+int exa_hip_isosurface(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
+                       float iso, int32_t flags, uint64_t *numVertices, uint64_t *numTriangles, void *hipStream);
+int exa_hip_isosurface_read(ExaHipRenderer *, float *vertices, float *gradients, int32_t *triangles,
+                            int32_t pointersAreDevice, void *hipStream);
+int exa_hip_isosurface_release(ExaHipRenderer *);
+int exa_hip_isosurface_stage_ms(ExaHipRenderer *, float ms[6]);
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,

@@ -95,7 +95,8 @@ ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa
                "exa_hip_advance_tracer", "exa_hip_read_traces", "exa_hip_set_params", "exa_hip_set_shard", "exa_hip_output_pixels",
                "exa_hip_untile", "exa_hip_render", "exa_hip_render_stats", "exa_hip_get_stats",
                "exa_hip_read_accum", "exa_hip_write_accum", "exa_hip_read_activity",
-               "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample"]
+               "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample",
+               "exa_hip_isosurface", "exa_hip_isosurface_read", "exa_hip_isosurface_release", "exa_hip_isosurface_stage_ms"]
 
 # exa_hip_sample_points / exa_hip_resample flags (include/exa_hip.h)
 SAMPLE_WORLD_SPACE = 1
@@ -158,6 +159,11 @@ def lib():
         L.exa_hip_sample_points.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp,
                                             C.c_int32, vp, C.c_int32]
         L.exa_hip_resample.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp, C.c_int32]
+        L.exa_hip_isosurface.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), vp]
+        L.exa_hip_isosurface_read.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
+        L.exa_hip_isosurface_release.argtypes = [vp]
+        L.exa_hip_isosurface_stage_ms.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -480,6 +486,51 @@ class Renderer:
         out = np.empty(tuple(max(int(d), 0) for d in dims[::-1]), dtype=np.float32)     # the module checks the dims
         self._check(lib().exa_hip_resample(self.h, lo3, hi3, d3, int(channel), flags, float(fill), out.ctypes.data, 0, None, 0))
         return out
+
+    # ---- iso-surface extraction (exa_hip_isosurface*; include/exa_hip.h states the contract) ----
+    def extractIsoSurface(self, lo, hi, dims, iso, channel=0, world=False, gradients=False, stream=None):
+        """extract the surface field == iso on the lattice of resample(lo, hi, dims) into module-owned device memory;
+        returns (numVertices, numTriangles).  readIsoSurface copies it out, releaseIsoSurface frees it."""
+        flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradients else 0)
+        lo3 = (C.c_float * 3)(*[float(v) for v in lo])
+        hi3 = (C.c_float * 3)(*[float(v) for v in hi])
+        d3 = (C.c_int32 * 3)(*[int(v) for v in dims])
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().exa_hip_isosurface(self.h, lo3, hi3, d3, int(channel), float(iso), flags, C.byref(nv), C.byref(nt),
+                                             C.c_void_p(stream or 0)))
+        self._iso_counts = (int(nv.value), int(nt.value), bool(gradients))
+        return self._iso_counts[:2]
+
+    def readIsoSurface(self):
+        """(verts float32 [n,3], tris int32 [m,3], grads float32 [n,3] or None) of the last extractIsoSurface"""
+        nv, nt, grad = getattr(self, "_iso_counts", (0, 0, False))
+        verts = np.empty((nv, 3), dtype=np.float32)
+        tris = np.empty((nt, 3), dtype=np.int32)
+        grads = np.empty((nv, 3), dtype=np.float32) if grad else None
+        self._check(lib().exa_hip_isosurface_read(self.h, verts.ctypes.data, grads.ctypes.data if grad else None,
+                                                  tris.ctypes.data, 0, None))
+        return verts, tris, grads
+
+    def releaseIsoSurface(self):
+        self._check(lib().exa_hip_isosurface_release(self.h))
+        self._iso_counts = (0, 0, False)
+
+    def isoSurfaceStageMs(self):
+        """device ms of the last extraction's stages: lattice values, cube pass, point pass, scans, emit, gradients"""
+        ms = (C.c_float * 6)()
+        self._check(lib().exa_hip_isosurface_stage_ms(self.h, ms))
+        return [float(v) for v in ms]
+
+    def isosurface(self, lo, hi, dims, iso, channel=0, world=False, gradients=False):
+        """the iso-surface field == iso of `channel` on the lattice of resample(lo, hi, dims), by marching tetrahedra:
+        (verts float32 [n,3] in the space of lo / hi, tris int32 [m,3], grads float32 [n,3] or None).  grads: what
+        samplePoints(verts, gradient=True, normalized=True) gives; the shading normal is -grad/|grad|.  The device copy
+        is released before returning."""
+        self.extractIsoSurface(lo, hi, dims, iso, channel=channel, world=world, gradients=gradients)
+        try:
+            return self.readIsoSurface()
+        finally:
+            self.releaseIsoSurface()
 
 
 def _dev_ptr(x):

@@ -3,6 +3,7 @@
 // exa/OptixRenderer.cpp does through OWL/OptiX; see include/exa_hip.h for the
 // per-entry citations.
 #include "exa_device.h"
+#include "exa_isomesh.h"
 #include "exa_ropes.h"
 
 #include <algorithm>
@@ -395,6 +396,12 @@ struct ExaHipRenderer {
   // demand), and the grid kernel's patch shape / wave-uniform path (options sample_patch, sample_uniform)
   DevBuf<char> probeStage;
   int samplePatch = 3, sampleUniform = 1;
+  // the mesh of the last exa_hip_isosurface (on a multi-device handle: in the renderer of devices[0]) and the time its
+  // stages took (lattice values, cube pass, point pass, scans, emit, gradients)
+  DevBuf<float> isoVertices, isoGradients;
+  DevBuf<int32_t> isoTriangles;
+  bool haveIsoMesh = false;
+  float isoStageMs[6] = { 0, 0, 0, 0, 0, 0 };
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 
@@ -2202,6 +2209,171 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
   if (dstIsDevice && async) return 0;
   HIP_TRY(h, hipStreamSynchronize(s));
   return probeCheckGuard(h, r, fn);
+}
+
+// ---- iso-surface extraction (exa_isomesh.hip) ----
+static void isoRelease(ExaHipRenderer *r)
+{
+  r->isoVertices.release(); r->isoGradients.release(); r->isoTriangles.release();
+  r->haveIsoMesh = false;
+}
+
+namespace {
+struct IsoEvents {
+  hipEvent_t ev[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
+  ~IsoEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+} // namespace
+
+int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                       int32_t flags, uint64_t *numVertices, uint64_t *numTriangles, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isosurface";
+  if (numVertices) *numVertices = 0;
+  if (numTriangles) *numTriangles = 0;
+  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT)) { h->fail(std::string(fn) + ": unknown flag bits (EXA_SAMPLE_WORLD_SPACE and EXA_SAMPLE_GRADIENT apply)"); return 1; }
+  if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument"); return 1; }
+  if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
+  for (int k = 0; k < 3; k++)
+    if (dims[k] < 2) { h->fail(std::string(fn) + ": dims must be >= 2 on every axis (a lattice of cubes)"); return 1; }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);
+  if (n > uint64_t(INT32_MAX)) { h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points"); return 1; }
+  ExaHipRenderer *r = h->children.empty() ? h : h->children[0];
+  DeviceGuard guard_(r->device);
+  HIP_TRY(h, guard_.err);
+  hipStream_t s = (hipStream_t)hipStream;
+  isoRelease(r);
+  for (float &ms : r->isoStageMs) ms = 0.f;
+  const bool world = (flags & EXA_SAMPLE_WORLD_SPACE) != 0, grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
+
+  IsoMeshArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.iso = iso;
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  // the work space of one extraction, freed when the call returns: values | chunkBase, totals | blockCount, blockBase |
+  // rel | cubeInfo, mask (every part aligned to its element)
+  auto fail = [&](hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    h->fail(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
+    return 1;
+  };
+  DevBuf<float> values;
+  DevBuf<char> work;
+  const size_t n64 = 2 * size_t(a.numChunks) + 2, n32 = 4 * size_t(a.numBlocks);
+  const size_t n16 = n + (n & 1), workBytes = n64 * 8 + n32 * 4 + n16 * 2 + 2 * n;
+  hipError_t e = values.alloc(n);
+  if (e == hipSuccess) e = work.alloc(workBytes);
+  if (e != hipSuccess) return fail(e, "no device memory for the lattice (4 bytes per point) and the work space (4 more)");
+  a.values = values.p;
+  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
+  a.totals = a.chunkBase + 2 * size_t(a.numChunks);
+  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  a.blockBase = a.blockCount + 2 * size_t(a.numBlocks);
+  a.rel = reinterpret_cast<uint16_t *>(work.p + n64 * 8 + n32 * 4);
+  a.cubeInfo = reinterpret_cast<uint8_t *>(work.p + n64 * 8 + n32 * 4 + n16 * 2);
+  a.mask = a.cubeInfo + n;
+
+  IsoEvents t;
+  HIP_TRY(h, t.create());
+  // the lattice: exa_hip_resample with a NaN fill into the device buffer (its checks of the box, the channel, the kd
+  // tree and the frame state apply; synchronous, with the loop guard's check)
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  if (int rc = exa_hip_resample(h, lo, hi, dims, channel, world ? EXA_SAMPLE_WORLD_SPACE : 0, NAN, values.p, 1, hipStream, 0)) {
+    h->fail(std::string(fn) + ": " + h->err);
+    return rc;
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  HIP_TRY(h, launchIsoCubePass(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[2], s));
+  HIP_TRY(h, launchIsoPointPass(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[3], s));
+  HIP_TRY(h, launchIsoScans(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[4], s));
+  uint64_t totals[2] = { 0, 0 };                 // vertices, triangles
+  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  if (totals[0] > uint64_t(INT32_MAX) || totals[1] > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": the surface has " + std::to_string(totals[0]) + " vertices and " + std::to_string(totals[1]) +
+            " triangles: more than INT32_MAX, the indices are int32 (extract it in parts)");
+    return 1;
+  }
+  if (totals[0] && totals[1]) {
+    e = r->isoVertices.alloc(3 * size_t(totals[0]));
+    if (e == hipSuccess) e = r->isoTriangles.alloc(3 * size_t(totals[1]));
+    if (e == hipSuccess && grad) e = r->isoGradients.alloc(3 * size_t(totals[0]));
+    if (e != hipSuccess) { isoRelease(r); return fail(e, "no device memory for the mesh"); }
+    a.vertices = r->isoVertices.p;
+    a.triangles = r->isoTriangles.p;
+    HIP_TRY(h, launchIsoEmit(a, s));
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[5], s));
+  if (grad && totals[0]) {
+    // the existing points kernel on the device vertex buffer; its values go into the lattice buffer, which is done with
+    // (a vertex sits on an edge between two lattice points: fewer than 7 per point, but the buffer holds only n floats)
+    DevBuf<float> scratch;
+    float *vals = values.p;
+    if (totals[0] > n) {
+      e = scratch.alloc(size_t(totals[0]));
+      if (e != hipSuccess) { isoRelease(r); return fail(e, "no device memory for the gradients"); }
+      vals = scratch.p;
+    }
+    const int32_t pf = (world ? EXA_SAMPLE_WORLD_SPACE : 0) | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
+    if (int rc = exa_hip_sample_points(h, r->isoVertices.p, totals[0], &channel, 1, pf, NAN, vals, r->isoGradients.p, nullptr, 1, hipStream, 0)) {
+      h->fail(std::string(fn) + ": " + h->err);
+      isoRelease(r);
+      return rc;
+    }
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[6], s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  for (int k = 0; k < 6; k++) HIP_TRY(h, hipEventElapsedTime(&r->isoStageMs[k], t.ev[k], t.ev[k + 1]));
+  r->haveIsoMesh = true;
+  if (numVertices) *numVertices = totals[0];
+  if (numTriangles) *numTriangles = totals[1];
+  return 0;
+}
+
+int exa_hip_isosurface_read(ExaHipRenderer *h, float *vertices, float *gradients, int32_t *triangles, int32_t pointersAreDevice,
+                            void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isosurface_read";
+  ExaHipRenderer *r = h->children.empty() ? h : h->children[0];
+  if (!r->haveIsoMesh) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
+  if (gradients && r->isoVertices.n && !r->isoGradients.n) { h->fail(std::string(fn) + ": the mesh was extracted without EXA_SAMPLE_GRADIENT"); return 1; }
+  DeviceGuard guard_(r->device);
+  HIP_TRY(h, guard_.err);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (vertices && r->isoVertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, r->isoVertices.p, r->isoVertices.n * sizeof(float), kind, s));
+  if (gradients && r->isoGradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, r->isoGradients.p, r->isoGradients.n * sizeof(float), kind, s));
+  if (triangles && r->isoTriangles.n) HIP_TRY(h, hipMemcpyAsync(triangles, r->isoTriangles.p, r->isoTriangles.n * sizeof(int32_t), kind, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+int exa_hip_isosurface_release(ExaHipRenderer *h)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = h->children.empty() ? h : h->children[0];
+  DeviceGuard guard_(r->device);
+  HIP_TRY(h, guard_.err);
+  isoRelease(r);
+  return 0;
+}
+
+int exa_hip_isosurface_stage_ms(ExaHipRenderer *h, float ms[6])
+{
+  if (!h || !ms) return 1;
+  const ExaHipRenderer *r = h->children.empty() ? h : h->children[0];
+  for (int k = 0; k < 6; k++) ms[k] = r->isoStageMs[k];
+  return 0;
 }
 
 } // extern "C"

@@ -17,6 +17,11 @@
 //             [--resample-box lx ly lz ux uy uz] [--resample-world] [--resample-channel c] [--resample-fill v]
 //                                            (box default: the voxel bounds, or the world bounds with --resample-world;
 //                                            fill default NaN); --frames 0 renders nothing
+//             [--isomesh ISO NX NY NZ file.tris] the iso-surface field == ISO on that lattice (exa_hip_isosurface: marching
+//                                            tetrahedra, indexed, oriented toward the lower values) in the triangle file format
+//                                            a config's `triangles` line reads, with
+//             [--isomesh-box lx ly lz ux uy uz] [--isomesh-world] [--isomesh-channel c]
+//                                            (box default as for --resample)
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -75,6 +80,11 @@ int main(int argc, char **argv)
     bool resampleWorld = false, haveResampleBox = false;
     box3f resampleBox;
     float resampleFill = NAN;
+    int isoDims[3] = { 0, 0, 0 }, isoChannel = 0;
+    float isoValue = 0.f;
+    std::string isoName;
+    bool isoWorld = false, haveIsoBox = false;
+    box3f isoBox;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -123,6 +133,15 @@ int main(int argc, char **argv)
       else if (a == "--resample-world") resampleWorld = true;
       else if (a == "--resample-channel") resampleChannel = (int)f();
       else if (a == "--resample-fill") resampleFill = f();
+      else if (a == "--isomesh") {
+        isoValue = f();
+        for (int k = 0; k < 3; k++) isoDims[k] = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --isomesh ISO NX NY NZ");
+        isoName = argv[++i];
+      }
+      else if (a == "--isomesh-box") { isoBox.lower = { f(), f(), f() }; isoBox.upper = { f(), f(), f() }; haveIsoBox = true; }
+      else if (a == "--isomesh-world") isoWorld = true;
+      else if (a == "--isomesh-channel") isoChannel = (int)f();
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
       else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
@@ -219,8 +238,17 @@ int main(int argc, char **argv)
       std::fclose(f);
       std::printf("resample %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channel %d invalid %zu\n", dims.x, dims.y, dims.z,
                   box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z, resampleChannel, invalid);
-      if (frames == 0) return 0;
     }
+    if (!isoName.empty()) {
+      const box3f box = haveIsoBox ? isoBox : (isoWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
+      const vec3i dims(isoDims[0], isoDims[1], isoDims[2]);
+      TriangleMesh::SP mesh = renderer.extractIsoSurface(box, dims, isoChannel, isoValue, isoWorld);
+      TriangleMesh::save(isoName, { mesh });
+      std::printf("isomesh %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channel %d iso %.9g vertices %zu triangles %zu\n", dims.x, dims.y,
+                  dims.z, box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z, isoChannel, isoValue,
+                  mesh->vertex.size(), mesh->index.size());
+    }
+    if (frames == 0 && (!resampleName.empty() || !isoName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

@@ -210,6 +210,24 @@ std::vector<TriangleMesh::SP> TriangleMesh::load(const std::string &fileName)
   return result;
 }
 
+void TriangleMesh::save(const std::string &fileName, const std::vector<SP> &meshes)
+{
+  static_assert(sizeof(vec3f) == 12 && sizeof(vec3i) == 12, "the file holds packed vec3f / vec3i");
+  std::ofstream out(fileName, std::ios::binary);
+  if (!out.good()) throw std::runtime_error("cannot write " + fileName);
+  for (const SP &m : meshes) {
+    if (!m) continue;
+    if (m->vertex.size() > size_t(INT32_MAX) || m->index.size() > size_t(INT32_MAX)) throw std::runtime_error("mesh too large for the triangle file format");
+    const int32_t nv = int32_t(m->vertex.size()), nt = int32_t(m->index.size());
+    out.write(reinterpret_cast<const char *>(&nv), sizeof(nv));
+    out.write(reinterpret_cast<const char *>(m->vertex.data()), std::streamsize(m->vertex.size() * sizeof(vec3f)));
+    out.write(reinterpret_cast<const char *>(&nt), sizeof(nt));
+    out.write(reinterpret_cast<const char *>(m->index.data()), std::streamsize(m->index.size() * sizeof(vec3i)));
+  }
+  out.flush();
+  if (!out.good()) throw std::runtime_error("cannot write " + fileName);
+}
+
 // ------------------------------------------------------------------ Config
 void Config::finalize()
 {
@@ -539,6 +557,27 @@ void Renderer::resample(const box3f &box, vec3i dims, int channel, float *out, b
   const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
   const int32_t d[3] = { dims.x, dims.y, dims.z };
   check(exa_hip_resample(handle, lo, hi, d, channel, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, 0, nullptr, 0), handle);
+}
+
+TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace,
+                                             std::vector<vec3f> *gradients)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z };
+  uint64_t nv = 0, nt = 0;
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0);
+  check(exa_hip_isosurface(handle, lo, hi, d, channel, iso, flags, &nv, &nt, nullptr), handle);
+  auto mesh = std::make_shared<TriangleMesh>();
+  mesh->vertex.resize(nv);
+  mesh->index.resize(nt);
+  if (gradients) gradients->resize(nv);
+  const int rc = exa_hip_isosurface_read(handle, reinterpret_cast<float *>(mesh->vertex.data()),
+                                         gradients ? reinterpret_cast<float *>(gradients->data()) : nullptr,
+                                         reinterpret_cast<int32_t *>(mesh->index.data()), 0, nullptr);
+  if (rc) check(rc, handle);
+  check(exa_hip_isosurface_release(handle), handle);
+  return mesh;
 }
 
 ExaHipStats Renderer::stats() const

@@ -116,6 +116,8 @@ struct TriangleMesh {
   std::vector<vec3f> vertex;
   std::vector<vec3i> index;
   static std::vector<SP> load(const std::string &fileName);                               // exa/TriangleMesh.cpp:21-71
+  // the same file format written: per mesh int32 nVerts, vec3f[nVerts], int32 nTris, vec3i[nTris] (the reference only reads it)
+  static void save(const std::string &fileName, const std::vector<SP> &meshes);
 };
 
 struct Config {
@@ -192,6 +194,14 @@ struct Renderer {
                     float *gradients = nullptr, int *status = nullptr, bool worldSpace = false, bool normalized = false,
                     float fill = NAN);
   void resample(const box3f &box, vec3i dims, int channel, float *out, bool worldSpace = false, float fill = NAN);
+
+  // the iso-surface field == iso of `channel` on the lattice of resample(box, dims) (dims >= 2) as an indexed triangle mesh
+  // by marching tetrahedra (exa_hip_isosurface; include/exa_hip.h states the contract): no duplicate vertices, normals
+  // (B-A)x(C-A) toward the lower values, positions in the space of `box`.  gradients: per vertex what samplePoints gives there
+  // with normalized = true (the shading normal is -grad/|grad|).  The mesh can go back in as a surface, or to a file
+  // (TriangleMesh::save).
+  TriangleMesh::SP extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace = false,
+                                     std::vector<vec3f> *gradients = nullptr);
 
   ExaHipStats stats() const;
   ExaHipStats renderStats();                 // the same frame through the counting variant of the kernels
