@@ -1,4 +1,4 @@
-// exa_device.h — device-side data layout shared by the module (exa_module.cpp)
+// exa_device.h — device-side data layout shared by the module (exa_renderer.h)
 // and the kernels (exa_kernels.hip).  gfx950 only.
 #pragma once
 #include "../../include/exa_hip.h"
@@ -102,7 +102,7 @@ struct DeviceScene {
   const int4       *bricks;        // ExaBrick as two int4: (lower.xyz,size.x) (size.yz,level,begin)
   const int32_t    *leafList;
   const int4       *leafHdr;       // march headers along the leaf list, two int4 per entry:
-                                   // (float(lower.xyz), 2^-level | size.xyz, begin), see exa_module.cpp
+                                   // (float(lower.xyz), 2^-level | size.xyz, begin), see exa_create.cpp
   const float      *scalars;
   const RegionInfo *regionInfo;
   const float2     *valueRange;    // per region

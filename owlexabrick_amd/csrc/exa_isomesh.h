@@ -1,4 +1,4 @@
-// exa_isomesh.h — iso-surface extraction on a lattice of sampled values (exa_hip_isosurface): what exa_module.cpp and
+// exa_isomesh.h — iso-surface extraction on a lattice of sampled values (exa_hip_isosurface): what exa_probe.cpp and
 // exa_isomesh.hip share.  Marching tetrahedra on the six-tetrahedra (Kuhn) split of every lattice cube along the diagonal
 // (0,0,0)-(1,1,1); include/exa_hip.h states the contract (tetrahedron order, vertex order, orientation).
 //

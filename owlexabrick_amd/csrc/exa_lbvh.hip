@@ -1,7 +1,7 @@
 // exa_lbvh.hip — device-side build of the LBVH over the brick regions (north_star: "a software LBVH over the
 // brick-regions replaces the OptiX BVH"; the reference builds its BVH inside OptiX, exa/OptixRenderer.cpp:614-721).
 //
-// Same tree as the host builder in exa_module.cpp (LbvhTopology), node for node and id for id:
+// Same tree as the host builder in exa_hostbvh.h (LbvhTopology), node for node and id for id:
 //   1. 63-bit Morton code of every region's box centre (21 bits per axis over the union box, double arithmetic)
 //   2. stable radix sort of (code, region)                      — hipCUB/rocPRIM, the only library call on this path
 //   3. topology level by level from the root: a node over the sorted range [lo, hi) splits after the last code

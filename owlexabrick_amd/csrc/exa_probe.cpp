@@ -1,0 +1,323 @@
+// exa_probe.cpp — reading the reconstructed field outside a frame: the point probes (exa_hip_sample_points,
+// exa_hip_resample; kernels in exa_sample_kernels.h) and the iso-surface extraction on a sampled lattice
+// (exa_hip_isosurface; exa_isomesh.hip).
+#include "exa_renderer.h"
+#include "exa_isomesh.h"
+
+#include <cmath>
+#include <cstring>
+
+extern "C" {
+
+// ---- point probes ----
+// Host arrays pass through the handle's staging buffer in chunks of at most kProbeStageBytes; a launch covers at most
+// kProbeLaunch points (a grid patch holds one point at the least: 64 x that many lanes stay below 2^32).
+static const uint64_t kProbeStageBytes = 64ull << 20, kProbeLaunch = 1ull << 24;
+// after a synchronous probe: the descent's loop guard (checkLoopGuard)
+static const char *const kDescentGuard = ": the kd descent's loop guard tripped (malformed kd-tree?)";
+
+// what both probes share: the renderer that runs them (a multi-device handle: the one of devices[0]), the checks, a pending
+// brick order applied (render does the same: the probes read `begin` through the march headers the permutation patches)
+static int probeSetup(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, bool world, hipStream_t s, SampleArgs &a)
+{
+  if (!r->haveKd) {
+    h->fail(std::string(fn) + ": the scene has no region kd-tree (ExaHipScene.kdNodes): the probes locate a point's region with it "
+            "(the LBVH is refit to the region activity and cannot)");
+    return 1;
+  }
+  if (world && !r->haveFs) { h->fail(std::string(fn) + ": world space needs a frame state (the voxelSpaceTransform of exa_hip_set_frame_state)"); return 1; }
+  if (r->applyBrickOrder(s)) { h->fail(r->err); return 1; }
+  std::memset(&a, 0, sizeof(a));
+  a.leafHdr = r->leafHdr.p;
+  a.scalars = r->scalars.p;
+  a.kdNodes = r->kdNodes.p;
+  a.regionRec = r->regionRec.p;
+  a.kdRoot = r->kdRoot;
+  a.maxSteps = (int32_t)std::min<uint64_t>(r->kdNodes.n + 1, INT32_MAX);
+  for (int k = 0; k < 3; k++) { a.kdLo[k] = r->kdLo[k]; a.kdHi[k] = r->kdHi[k]; }
+  a.errorFlag = r->errorFlag.p;
+  a.world = world ? 1 : 0;
+  if (world) a.fs = r->fs;
+  return 0;
+}
+
+
+int exa_hip_sample_points(ExaHipRenderer *h, const float *points, uint64_t n, const int32_t *channels, int32_t numChannels,
+                          int32_t flags, float fill, float *values, float *gradients, int32_t *status,
+                          int32_t pointersAreDevice, void *hipStream, int32_t async)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_sample_points";
+  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED)) { h->fail(std::string(fn) + ": unknown flag bits"); return 1; }
+  const bool grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
+  if ((flags & EXA_SAMPLE_GRADIENT_NORMALIZED) && !grad) { h->fail(std::string(fn) + ": EXA_SAMPLE_GRADIENT_NORMALIZED needs EXA_SAMPLE_GRADIENT"); return 1; }
+  if (!channels || numChannels < 1 || numChannels > EXA_MAX_CHANNELS) { h->fail(std::string(fn) + ": 1..10 channels required"); return 1; }
+  for (int c = 0; c < numChannels; c++)
+    if (channels[c] < 0 || channels[c] >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  if (n == 0) return 0;
+  if (!points || !values || (grad && !gradients)) { h->fail(std::string(fn) + ": null array (points, values, or gradients with EXA_SAMPLE_GRADIENT)"); return 1; }
+  if (n > (UINT64_MAX / 12) / uint64_t(numChannels)) { h->fail(std::string(fn) + ": too many points"); return 1; }
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  SampleArgs a;
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a)) return 1;
+  a.fill = fill;
+  a.normalized = (flags & EXA_SAMPLE_GRADIENT_NORMALIZED) ? 1 : 0;
+  a.numChannels = numChannels;
+  for (int c = 0; c < numChannels; c++) a.fieldOffset[c] = r->sc.channelOffset[channels[c]];
+  const uint64_t nch = uint64_t(numChannels);
+  if (pointersAreDevice) {
+    for (uint64_t at = 0; at < n; at += kProbeLaunch) {
+      a.count = std::min(kProbeLaunch, n - at);
+      a.points = points + 3 * at;
+      a.values = values + at * nch;
+      a.gradients = grad ? gradients + 3 * at * nch : nullptr;
+      a.status = status ? status + at * nch : nullptr;
+      HIP_TRY(h, EXA_FORM(r, launchSamplePoints)(a, grad, s));
+    }
+    if (async) return 0;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return checkLoopGuard(h, r, fn, kDescentGuard);
+  }
+  // host arrays: chunk by chunk through the staging buffer {points | values | gradients | status}
+  const uint64_t perPoint = 12 + nch * 4 * (1 + (grad ? 3 : 0) + (status ? 1 : 0));
+  const uint64_t chunk = std::max<uint64_t>(1, std::min(kProbeLaunch, kProbeStageBytes / perPoint));
+  const uint64_t need = std::min(n, chunk) * perPoint;
+  if (r->probeStage.n < need) HIP_TRY(h, r->probeStage.alloc(need));
+  for (uint64_t at = 0; at < n; at += chunk) {
+    const uint64_t m = std::min(chunk, n - at);
+    char *p = r->probeStage.p;
+    a.count = m;
+    a.points = reinterpret_cast<const float *>(p);
+    a.values = reinterpret_cast<float *>(p + 12 * m);
+    a.gradients = grad ? reinterpret_cast<float *>(p + 12 * m + 4 * m * nch) : nullptr;
+    a.status = status ? reinterpret_cast<int32_t *>(p + 12 * m + 4 * m * nch * (grad ? 4 : 1)) : nullptr;
+    HIP_TRY(h, hipMemcpyAsync(p, points + 3 * at, 12 * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, EXA_FORM(r, launchSamplePoints)(a, grad, s));
+    HIP_TRY(h, hipMemcpyAsync(values + at * nch, a.values, 4 * m * nch, hipMemcpyDeviceToHost, s));
+    if (grad) HIP_TRY(h, hipMemcpyAsync(gradients + 3 * at * nch, a.gradients, 12 * m * nch, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status + at * nch, a.status, 4 * m * nch, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+  }
+  return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
+                     int32_t flags, float fill, float *out, int32_t dstIsDevice, void *hipStream, int32_t async)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_resample";
+  if (flags & ~EXA_SAMPLE_WORLD_SPACE) { h->fail(std::string(fn) + ": unknown flag bits (only EXA_SAMPLE_WORLD_SPACE applies)"); return 1; }
+  if (!lo || !hi || !dims || !out) { h->fail(std::string(fn) + ": null argument"); return 1; }
+  for (int k = 0; k < 3; k++) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
+    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
+  }
+  if (channel < 0 || channel >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  SampleArgs a;
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a)) return 1;
+  a.fill = fill;
+  a.numChannels = 1;
+  a.fieldOffset[0] = r->sc.channelOffset[channel];
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  static const int kShape[kSamplePatchShapes][3] = { { 64, 1, 1 }, { 16, 4, 1 }, { 8, 8, 1 }, { 4, 4, 4 } };
+  const int *ps = kShape[r->samplePatch];
+  const uint64_t nx = uint64_t(dims[0]), ny = uint64_t(dims[1]), nz = uint64_t(dims[2]);
+  // boxes of at most kProbeLaunch points: whole slabs of z, else rows of one slice, else pieces of one row — each one
+  // contiguous in the output, so a host destination takes one copy per box
+  const uint64_t bx = std::min(nx, kProbeLaunch), by = std::min(ny, std::max<uint64_t>(1, kProbeLaunch / bx)),
+                 bz = std::min(nz, std::max<uint64_t>(1, kProbeLaunch / (bx * by)));
+  if (!dstIsDevice && r->probeStage.n < bx * by * bz * 4) HIP_TRY(h, r->probeStage.alloc(bx * by * bz * 4));
+  for (uint64_t z0 = 0; z0 < nz; z0 += bz)
+    for (uint64_t y0 = 0; y0 < ny; y0 += by)
+      for (uint64_t x0 = 0; x0 < nx; x0 += bx) {
+        const uint64_t ex = std::min(bx, nx - x0), ey = std::min(by, ny - y0), ez = std::min(bz, nz - z0);
+        a.box0[0] = int32_t(x0); a.box0[1] = int32_t(y0); a.box0[2] = int32_t(z0);
+        a.box1[0] = int32_t(x0 + ex); a.box1[1] = int32_t(y0 + ey); a.box1[2] = int32_t(z0 + ez);
+        a.patchesX = (ex + ps[0] - 1) / ps[0];
+        a.patchesY = (ey + ps[1] - 1) / ps[1];
+        a.numPatches = a.patchesX * a.patchesY * ((ez + ps[2] - 1) / ps[2]);
+        const uint64_t first = (z0 * ny + y0) * nx + x0;
+        if (dstIsDevice) {
+          a.out = out + first; a.strideY = nx; a.strideZ = nx * ny;
+        } else {
+          a.out = reinterpret_cast<float *>(r->probeStage.p); a.strideY = ex; a.strideZ = ex * ey;
+        }
+        HIP_TRY(h, EXA_FORM(r, launchSampleGrid)(a, r->samplePatch, r->sampleUniform != 0, s));
+        if (!dstIsDevice) {
+          HIP_TRY(h, hipMemcpyAsync(out + first, a.out, ex * ey * ez * sizeof(float), hipMemcpyDeviceToHost, s));
+          HIP_TRY(h, hipStreamSynchronize(s));
+        }
+      }
+  if (dstIsDevice && async) return 0;
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+// ---- iso-surface extraction (exa_isomesh.hip) ----
+static void isoRelease(ExaHipRenderer *r)
+{
+  r->isoVertices.release(); r->isoGradients.release(); r->isoTriangles.release();
+  r->haveIsoMesh = false;
+}
+
+namespace {
+struct IsoEvents {
+  hipEvent_t ev[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
+  ~IsoEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+} // namespace
+
+int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                       int32_t flags, uint64_t *numVertices, uint64_t *numTriangles, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isosurface";
+  if (numVertices) *numVertices = 0;
+  if (numTriangles) *numTriangles = 0;
+  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT)) { h->fail(std::string(fn) + ": unknown flag bits (EXA_SAMPLE_WORLD_SPACE and EXA_SAMPLE_GRADIENT apply)"); return 1; }
+  if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument"); return 1; }
+  if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
+  for (int k = 0; k < 3; k++)
+    if (dims[k] < 2) { h->fail(std::string(fn) + ": dims must be >= 2 on every axis (a lattice of cubes)"); return 1; }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);
+  if (n > uint64_t(INT32_MAX)) { h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points"); return 1; }
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  isoRelease(r);
+  for (float &ms : r->isoStageMs) ms = 0.f;
+  const bool world = (flags & EXA_SAMPLE_WORLD_SPACE) != 0, grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
+
+  IsoMeshArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.iso = iso;
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  // the work space of one extraction, freed when the call returns: values | chunkBase, totals | blockCount, blockBase |
+  // rel | cubeInfo, mask (every part aligned to its element)
+  auto fail = [&](hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    h->fail(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
+    return 1;
+  };
+  DevBuf<float> values;
+  DevBuf<char> work;
+  const size_t n64 = 2 * size_t(a.numChunks) + 2, n32 = 4 * size_t(a.numBlocks);
+  const size_t n16 = n + (n & 1), workBytes = n64 * 8 + n32 * 4 + n16 * 2 + 2 * n;
+  hipError_t e = values.alloc(n);
+  if (e == hipSuccess) e = work.alloc(workBytes);
+  if (e != hipSuccess) return fail(e, "no device memory for the lattice (4 bytes per point) and the work space (4 more)");
+  a.values = values.p;
+  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
+  a.totals = a.chunkBase + 2 * size_t(a.numChunks);
+  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  a.blockBase = a.blockCount + 2 * size_t(a.numBlocks);
+  a.rel = reinterpret_cast<uint16_t *>(work.p + n64 * 8 + n32 * 4);
+  a.cubeInfo = reinterpret_cast<uint8_t *>(work.p + n64 * 8 + n32 * 4 + n16 * 2);
+  a.mask = a.cubeInfo + n;
+
+  IsoEvents t;
+  HIP_TRY(h, t.create());
+  // the lattice: exa_hip_resample with a NaN fill into the device buffer (its checks of the box, the channel, the kd
+  // tree and the frame state apply; synchronous, with the loop guard's check)
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  if (int rc = exa_hip_resample(h, lo, hi, dims, channel, world ? EXA_SAMPLE_WORLD_SPACE : 0, NAN, values.p, 1, hipStream, 0)) {
+    h->fail(std::string(fn) + ": " + h->err);
+    return rc;
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  HIP_TRY(h, launchIsoCubePass(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[2], s));
+  HIP_TRY(h, launchIsoPointPass(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[3], s));
+  HIP_TRY(h, launchIsoScans(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[4], s));
+  uint64_t totals[2] = { 0, 0 };                 // vertices, triangles
+  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  if (totals[0] > uint64_t(INT32_MAX) || totals[1] > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": the surface has " + std::to_string(totals[0]) + " vertices and " + std::to_string(totals[1]) +
+            " triangles: more than INT32_MAX, the indices are int32 (extract it in parts)");
+    return 1;
+  }
+  if (totals[0] && totals[1]) {
+    e = r->isoVertices.alloc(3 * size_t(totals[0]));
+    if (e == hipSuccess) e = r->isoTriangles.alloc(3 * size_t(totals[1]));
+    if (e == hipSuccess && grad) e = r->isoGradients.alloc(3 * size_t(totals[0]));
+    if (e != hipSuccess) { isoRelease(r); return fail(e, "no device memory for the mesh"); }
+    a.vertices = r->isoVertices.p;
+    a.triangles = r->isoTriangles.p;
+    HIP_TRY(h, launchIsoEmit(a, s));
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[5], s));
+  if (grad && totals[0]) {
+    // the existing points kernel on the device vertex buffer; its values go into the lattice buffer, which is done with
+    // (a vertex sits on an edge between two lattice points: fewer than 7 per point, but the buffer holds only n floats)
+    DevBuf<float> scratch;
+    float *vals = values.p;
+    if (totals[0] > n) {
+      e = scratch.alloc(size_t(totals[0]));
+      if (e != hipSuccess) { isoRelease(r); return fail(e, "no device memory for the gradients"); }
+      vals = scratch.p;
+    }
+    const int32_t pf = (world ? EXA_SAMPLE_WORLD_SPACE : 0) | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
+    if (int rc = exa_hip_sample_points(h, r->isoVertices.p, totals[0], &channel, 1, pf, NAN, vals, r->isoGradients.p, nullptr, 1, hipStream, 0)) {
+      h->fail(std::string(fn) + ": " + h->err);
+      isoRelease(r);
+      return rc;
+    }
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[6], s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  for (int k = 0; k < 6; k++) HIP_TRY(h, hipEventElapsedTime(&r->isoStageMs[k], t.ev[k], t.ev[k + 1]));
+  r->haveIsoMesh = true;
+  if (numVertices) *numVertices = totals[0];
+  if (numTriangles) *numTriangles = totals[1];
+  return 0;
+}
+
+int exa_hip_isosurface_read(ExaHipRenderer *h, float *vertices, float *gradients, int32_t *triangles, int32_t pointersAreDevice,
+                            void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isosurface_read";
+  ExaHipRenderer *r = firstChild(h);
+  if (!r->haveIsoMesh) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
+  if (gradients && r->isoVertices.n && !r->isoGradients.n) { h->fail(std::string(fn) + ": the mesh was extracted without EXA_SAMPLE_GRADIENT"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (vertices && r->isoVertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, r->isoVertices.p, r->isoVertices.n * sizeof(float), kind, s));
+  if (gradients && r->isoGradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, r->isoGradients.p, r->isoGradients.n * sizeof(float), kind, s));
+  if (triangles && r->isoTriangles.n) HIP_TRY(h, hipMemcpyAsync(triangles, r->isoTriangles.p, r->isoTriangles.n * sizeof(int32_t), kind, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+int exa_hip_isosurface_release(ExaHipRenderer *h)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  isoRelease(r);
+  return 0;
+}
+
+int exa_hip_isosurface_stage_ms(ExaHipRenderer *h, float ms[6])
+{
+  if (!h || !ms) return 1;
+  const ExaHipRenderer *r = firstChild(h);
+  for (int k = 0; k < 6; k++) ms[k] = r->isoStageMs[k];
+  return 0;
+}
+
+} // extern "C"

@@ -13,7 +13,7 @@
 // (Popov, Günther, Seidel, Slusallek: "Stackless kd-tree traversal for high performance GPU ray tracing", 2007).  The top
 // levels are expanded serially, the subtrees below them by a pool of threads.
 //
-// Used by exa_module.cpp (which adds the march's packed region record and the activity flags and uploads the result) and by
+// Used by exa_frame.cpp (which adds the march's packed region record and the activity flags and uploads the result) and by
 // exa_prep.cpp's diagnostic entry point exa_prep_ropes (tests/test_ropes.py checks the links on the CPU).
 #pragma once
 #include "../../include/exa_hip.h"

@@ -99,6 +99,40 @@ def test_multi_device_async_into_device_buffers_and_state_changes():
     ref.close()
 
 
+def test_multi_device_options_triangles_tracer_and_child_errors():
+    """set_option, set_triangles and the tracer entries fan out to every device's renderer, and a child's error text
+    reaches the caller through the multi handle"""
+    case = MultiCase(_amr(), W=48, H=40, grad=1)
+    case.devices = [0, 0]
+    R = case.hip_renderer()
+    ref = Case(_amr(), W=48, H=40, grad=1).hip_renderer()
+    with pytest.raises(RuntimeError, match="wide_march is 0, 1, 2 or 4"):
+        R.setOption("wide_march", 3)
+    with pytest.raises(RuntimeError, match="unknown key no_such_key"):
+        R.setOption("no_such_key", 1)
+    lo, hi = (np.asarray(b, dtype=np.float32) for b in ref.voxelSpaceBounds)
+    ext = hi - lo
+    verts = lo + ext * np.array([[0.3, 0.3, 0.5], [0.7, 0.35, 0.45], [0.45, 0.7, 0.55]], dtype=np.float32)
+    seeds = lo + ext * np.array([[0.3, 0.3, 0.3], [0.6, 0.4, 0.5], [0.4, 0.6, 0.6], [0.5, 0.5, 0.4]], dtype=np.float32)
+    frames, flags, traces = [], [], []
+    for r in (R, ref):
+        r.setOption("walk", 2)
+        r.setTriangles(verts, [[0, 1, 2]])
+        r.resetTracer(seeds, channels=(0, 0, 0), numTimesteps=6, steplen=2.0, enabled=True)
+        f, g = [], []
+        for i in range(3):
+            r.updateFrameID(i)
+            f.append(r.render())
+            g.append(r.advanceTracer())
+        frames.append(f); flags.append(g); traces.append(r.readTraces())
+    for i in range(3):
+        assert np.array_equal(frames[0][i], frames[1][i]), i
+    assert np.array_equal(traces[0].view(np.uint32), traces[1].view(np.uint32))
+    assert flags[0] == flags[1]
+    R.close()
+    ref.close()
+
+
 def test_exarender_gpus_flag_and_pipelined_copy_out():
     sc = _amr()
     with tempfile.TemporaryDirectory() as d:

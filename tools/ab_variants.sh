@@ -25,7 +25,13 @@ if [ "$mode" = build ]; then
       wait
       ls "$d"/exa_kernels_f0.o "$d"/exa_kernels_f1.o "$d"/exa_kernels_f0e.o "$d"/exa_kernels_f0r.o "$d"/exa_kernels_f1r.o "$d"/exa_kernels_f0er.o > /dev/null &&
       /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $defs -c "$CS/exa_lbvh.hip" -o "$d/exa_lbvh.o" &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $defs -x hip -c "$CS/exa_module.cpp" -o "$d/exa_module.o" &&
+      for s in f0:-DEXA_BASIS_FORM=0 f1:-DEXA_BASIS_FORM=1 "f0e:-DEXA_BASIS_FORM=0 -DEXA_EMPTY_CELLS=1"; do      # the point probes' kernels
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $defs ${s#*:} -DEXA_TU_SAMPLE=1 -c "$CS/exa_kernels.hip" -o "$d/exa_sample_${s%%:*}.o" || exit 1
+      done &&
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $defs -c "$CS/exa_isomesh.hip" -o "$d/exa_isomesh.o" &&
+      for m in exa_create exa_frame exa_probe exa_module; do                                                        # the host side of the ABI
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $defs -x hip -c "$CS/$m.cpp" -o "$d/$m.o" || exit 1
+      done &&
       /opt/rocm/bin/hipcc $FLAGS -c "$CS/exa_prep.cpp" -o "$d/exa_prep.o" &&
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$LIBS/libexa_hip_$name.so" "$d"/*.o -lpthread &&
       rm -rf "$d" && echo "built $name ($defs)"

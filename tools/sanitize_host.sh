@@ -19,7 +19,8 @@ CS="$ROOT/owlexabrick_amd/csrc"
 /opt/rocm/bin/hipcc $SAN -std=c++17 -fPIC -ffp-contract=off -c "$CS/exa_prep.cpp" -o "$D/exa_prep.o"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan -o "$D/libexa_hip.so" \
     "$CS/exa_kernels_f0.o" "$CS/exa_kernels_f1.o" "$CS/exa_kernels_f0e.o" "$CS/exa_kernels_f0r.o" "$CS/exa_kernels_f1r.o" "$CS/exa_kernels_f0er.o" \
-    "$CS/exa_lbvh.o" "$CS/exa_module.o" "$D/exa_prep.o" -lpthread 2>/dev/null
+    "$CS/exa_sample_f0.o" "$CS/exa_sample_f1.o" "$CS/exa_sample_f0e.o" "$CS/exa_isomesh.o" "$CS/exa_lbvh.o" \
+    "$CS/exa_create.o" "$CS/exa_frame.o" "$CS/exa_probe.o" "$CS/exa_module.o" "$D/exa_prep.o" -lpthread 2>/dev/null
 GCC_RT="$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so)"
 CLANG_RT=$(find /opt/rocm/lib/llvm/lib/clang -name "libclang_rt.asan-x86_64.so" | head -1)
 export ASAN_OPTIONS=detect_leaks=0
