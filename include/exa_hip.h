@@ -313,9 +313,14 @@ int exa_hip_read_activity(ExaHipRenderer *, int32_t which /*0 volume, 1 iso*/, u
  * (exabrick.cu:614-618), so one channel can vanish where another does not.
  *
  * Gradient (EXA_SAMPLE_GRADIENT): the reference's numerator sumW*sumD - sumWV*sumDC (exabrick.cu:916-921), bit for bit as
- * samplePointWithDerivative returns it; with EXA_SAMPLE_GRADIENT_NORMALIZED as well it is divided by sumW*sumW on the
- * device: the true gradient of the reconstruction.  Gradients are taken with respect to VOXEL-space coordinates, also for
- * world-space positions.
+ * samplePointWithDerivative returns it.  The derivative weights in it are taken per brick in that brick's own cell units
+ * (the reference compiles INV_CELL_WIDTH == 1, exabrick.cu:640-641): in a region whose bricks are at level L it is
+ * sumW*sumW * 2^L times the gradient, and in a region with bricks of several levels (every coarse-fine boundary) it is
+ * no voxel-space vector at all.  It is what the reference shades with, nothing more.
+ * With EXA_SAMPLE_GRADIENT_NORMALIZED as well the result is the gradient of the reconstruction sumWV/sumW with respect to
+ * VOXEL-space coordinates (also for world-space positions): every brick's derivative weights carry its 2^-level, and the
+ * numerator formed from those sums is divided by sumW*sumW on the device.  The value and the status are the same with
+ * and without the flag.
  *
  * Fill.  Where status < 0, value and gradient components of that point and channel are `fill`.
  *

@@ -442,7 +442,9 @@ class Renderer:
         """the reconstructed field at points [n,3] (voxel space, or world space with world=True).  Returns
         (values [n, len(channels)], gradients [n, len(channels), 3] or None, status [n, len(channels)]): status = region id,
         -1 outside every region, -2 where the basis weights vanish; value and gradient are `fill` where status < 0.
-        gradient: the reference's numerator sumW*sumD - sumWV*sumDC; normalized: divided by sumW^2 (the true gradient),
+        gradient: the reference's numerator sumW*sumD - sumWV*sumDC, its derivative weights in each brick's own cell units
+        (no voxel-space vector where bricks are coarse or of several levels); normalized: the gradient of sumWV/sumW with
+        respect to the voxel-space position (derivative weights times each brick's 2^-level, divided by sumW^2),
         both with respect to voxel-space coordinates.  A numpy array takes the host path; a contiguous float32 torch CUDA
         tensor (memory of the handle's first device) the device path, with torch tensors out (async_ on `stream`)."""
         chans = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)

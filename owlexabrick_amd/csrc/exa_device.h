@@ -240,7 +240,7 @@ struct SampleArgs {
   float              kdLo[3], kdHi[3];
   int32_t           *errorFlag;     // set when the bound trips
   int32_t            world;         // positions in world space: mapped with fs' voxelSpaceTransform (xfmPoint)
-  int32_t            normalized;    // gradients divided by sumW * sumW
+  int32_t            normalized;    // the gradient of sumWV / sumW in voxel space (samplePointsNormKernel)
   float              fill;          // value / gradient of a point and channel whose status is < 0
   ExaHipFrameState   fs;
   int32_t            numChannels;

@@ -399,7 +399,13 @@ __device__ __forceinline__ Pair loadPair(const float *__restrict__ p) { return *
 // leaves a sum unchanged (the sums start at +0 and can never become -0), so the
 // accumulators see bit-identical values.  The speculative read of an out-of-brick corner
 // is clamped onto a cell that an in-brick corner of the same sample reads as well.
-template <bool DERIV, int STATS, bool SMALL>
+//
+// VOXEL (the point probes' EXA_SAMPLE_GRADIENT_NORMALIZED only): the derivative weight of a corner is -+2^-level times the
+// other two axes' weights, the derivative with respect to the VOXEL-space position, where the reference (and every
+// other caller) takes -+1, the derivative with respect to the brick's own cell coordinate (INV_CELL_WIDTH == 1.f,
+// exabrick.cu:640-641).  2^-level is a power of two: every product with it is exact, so a brick's terms are the
+// reference's times 2^-level bit for bit.  sumW and sumWV do not depend on it.
+template <bool DERIV, int STATS, bool SMALL, bool VOXEL = false>
 __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4 b0, const int4 b1,
                                              const float *__restrict__ field, V3 pos)
 {
@@ -494,9 +500,10 @@ __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4
     B.sumW = __builtin_fmaf(zy, Sx, B.sumW);
     if (DERIV) {
       // d w / d x of a corner = -1 (low cell) or +1 (high cell) times the other two axes' weights, 0 outside the brick
-      const float mxl = vlx ? -1.f : 0.f, mxh = vhx ? 1.f : 0.f;
-      const float myl = vly ? -1.f : 0.f, myh = vhy ? 1.f : 0.f;
-      const float mzl = vlz ? -1.f : 0.f, mzh = vhz ? 1.f : 0.f;
+      const float dw = VOXEL ? invCw : 1.f;
+      const float mxl = vlx ? -dw : 0.f, mxh = vhx ? dw : 0.f;
+      const float myl = vly ? -dw : 0.f, myh = vhy ? dw : 0.f;
+      const float mzl = vlz ? -dw : 0.f, mzh = vhz ? dw : 0.f;
       const float dLL = __builtin_fmaf(mxh, s100, mxl * s000), dLH = __builtin_fmaf(mxh, s110, mxl * s010);
       const float dHL = __builtin_fmaf(mxh, s101, mxl * s001), dHH = __builtin_fmaf(mxh, s111, mxl * s011);
       const float DXl = __builtin_fmaf(wyh, dLH, wyl * dLL), DXh = __builtin_fmaf(wyh, dHH, wyl * dHL);
@@ -515,9 +522,10 @@ __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4
   const float zyLL = wzl * wyl, zyLH = wzl * wyh, zyHL = wzh * wyl, zyHH = wzh * wyh;
   if (DERIV) {
     // d/dx weight = +-(z*y), d/dy = +-(z*x), d/dz = +-(y*x), zero for an out-of-brick corner
-    const float mxl = vlx ? -1.f : 0.f, mxh = vhx ? 1.f : 0.f;
-    const float myl = vly ? -1.f : 0.f, myh = vhy ? 1.f : 0.f;
-    const float mzl = vlz ? -1.f : 0.f, mzh = vhz ? 1.f : 0.f;
+    const float dw = VOXEL ? invCw : 1.f;
+    const float mxl = vlx ? -dw : 0.f, mxh = vhx ? dw : 0.f;
+    const float myl = vly ? -dw : 0.f, myh = vhy ? dw : 0.f;
+    const float mzl = vlz ? -dw : 0.f, mzh = vhz ? dw : 0.f;
     const float zxLL = wzl * wxl, zxLH = wzl * wxh, zxHL = wzh * wxl, zxHH = wzh * wxh;   // [z][x]
     const float yxLL = wyl * wxl, yxLH = wyl * wxh, yxHL = wyh * wxl, yxHH = wyh * wxh;   // [y][x]
     // The derivative weight of a corner is +-(product of the other two axes' weights) or 0: dx_ = zy * mx with

@@ -8,6 +8,9 @@
 // result depends on the scene, the position, the basis form and (world space) the transform, never on the transfer
 // function, the activity bits or any other knob.  The value is samplePoint on the march headers (the sums of the DVR
 // march and of the oracle, bit for bit); status -2 where sumW <= 1e-20 (the reference's samplePoint returns false).
+// The gradient is the reference's numerator sumW * sumD - sumWV * sumDC, whose derivative weights are per brick in that
+// brick's cell units; EXA_SAMPLE_GRADIENT_NORMALIZED takes them in voxel units instead (addBasisFast<.., VOXEL>: each
+// brick's terms times its 2^-level) and divides by sumW^2: the gradient of sumWV / sumW with respect to the position.
 
 // p inside the closed root box; false for a NaN coordinate
 __device__ __forceinline__ bool sampleInRoot(const SampleArgs &a, V3 p)
@@ -40,7 +43,7 @@ __device__ __forceinline__ bool sampleInDomain(const RegionRec &R, V3 p)
 
 // samplePoint's sums (exabrick.cu:781-806, 883-928) over the region's bricks, through the march headers: the loop of
 // samplePoint with fastSampler.  listBegin / listSize wave-uniform -> the headers are read once per wave.
-template <bool DERIV>
+template <bool DERIV, bool VOXEL = false>
 __device__ __forceinline__ Basis sampleSums(const SampleArgs &a, int listBegin, int listSize, const float *field, V3 p)
 {
   Ctx<0> C;                       // no counters
@@ -49,14 +52,14 @@ __device__ __forceinline__ Basis sampleSums(const SampleArgs &a, int listBegin, 
   for (int child = 0; child < listSize; child++) {
     const size_t at = 2 * (size_t(listBegin) + size_t(child));
     const int4 h0 = a.leafHdr[at], h1 = a.leafHdr[at + 1];
-    addBasisFast<DERIV, 0, false>(C, B, h0, h1, field, p);
+    addBasisFast<DERIV, 0, false, VOXEL>(C, B, h0, h1, field, p);
   }
   return B;
 }
 
-// one lane per point, the region located once for all channels
-template <bool DERIV>
-__global__ __launch_bounds__(256) void samplePointsKernel(const SampleArgs a)
+// one lane per point, the region located once for all channels.  NORM: the voxel-space gradient (see the head of this file)
+template <bool DERIV, bool NORM>
+__device__ __forceinline__ void samplePointsBody(const SampleArgs &a)
 {
   const size_t i = size_t(blockIdx.x) * 256u + threadIdx.x;
   if (i >= a.count) return;
@@ -77,14 +80,14 @@ __global__ __launch_bounds__(256) void samplePointsKernel(const SampleArgs a)
     float value = a.fill;
     V3 grad = mk(a.fill, a.fill, a.fill);
     if (region >= 0) {
-      const Basis B = sampleSums<DERIV>(a, R.listBegin, R.listSize, a.scalars + a.fieldOffset[c], p);
+      const Basis B = sampleSums<DERIV, NORM>(a, R.listBegin, R.listSize, a.scalars + a.fieldOffset[c], p);
       if (B.sumW <= 1e-20f) {
         st = -2;
       } else {
         value = B.sumWV / B.sumW;
         if (DERIV) {
           grad = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
-          if (a.normalized) {
+          if (NORM) {
             const float w2 = B.sumW * B.sumW;
             grad = mk(grad.x / w2, grad.y / w2, grad.z / w2);
           }
@@ -96,6 +99,10 @@ __global__ __launch_bounds__(256) void samplePointsKernel(const SampleArgs a)
     if (a.status) a.status[o] = st;
   }
 }
+
+template <bool DERIV>
+__global__ __launch_bounds__(256) void samplePointsKernel(const SampleArgs a) { samplePointsBody<DERIV, false>(a); }
+__global__ __launch_bounds__(256) void samplePointsNormKernel(const SampleArgs a) { samplePointsBody<true, true>(a); }
 
 // One wave per patch of PX x PY x PZ = 64 grid points (lane -> point x fastest).  UNIFORM: the wave descends the tree
 // together while all its lanes (those inside the root box) take the same side of every plane — the node index is
@@ -161,7 +168,8 @@ hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s)
 {
   if (a.count == 0) return hipSuccess;
   const dim3 grid((unsigned)((a.count + 255) / 256)), block(256);
-  if (grad) hipLaunchKernelGGL((samplePointsKernel<true>), grid, block, 0, s, a);
+  if (grad && a.normalized) hipLaunchKernelGGL(samplePointsNormKernel, grid, block, 0, s, a);
+  else if (grad) hipLaunchKernelGGL((samplePointsKernel<true>), grid, block, 0, s, a);
   else      hipLaunchKernelGGL((samplePointsKernel<false>), grid, block, 0, s, a);
   return hipGetLastError();
 }

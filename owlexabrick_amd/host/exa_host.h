@@ -189,7 +189,10 @@ struct Renderer {
   // point probes (exa_hip_sample_points / exa_hip_resample; include/exa_hip.h states the contract): the reconstructed field
   // at `n` points (host arrays; values n x numChannels, gradients n x numChannels x 3 or NULL = none, status n x numChannels
   // or NULL) and at the cell centres of a uniform dims.x x dims.y x dims.z grid over `box` (out: x fastest).  Positions in
-  // voxel space, or in world space through frameState.voxelSpaceTransform (the frame state is pushed first).
+  // voxel space, or in world space through frameState.voxelSpaceTransform (the frame state is pushed first).  gradients:
+  // the reference's numerator sumW*sumD - sumWV*sumDC (derivative weights in each brick's own cell units: what the
+  // reference shades with, no voxel-space vector on coarse or mixed-level regions); with normalized = true the gradient of
+  // the reconstruction with respect to the voxel-space position.
   void samplePoints(const vec3f *points, size_t n, const int *channels, int numChannels, float *values,
                     float *gradients = nullptr, int *status = nullptr, bool worldSpace = false, bool normalized = false,
                     float fill = NAN);

@@ -9,6 +9,7 @@ import pytest
 
 from common import Case
 from owlexabrick_amd import binding, scenes
+from probe_sets import brute_owner, grid_positions as _grid_positions, probe_points, region_levels, with_field_of_centres
 
 pytestmark = pytest.mark.gpu
 
@@ -17,55 +18,6 @@ FILL = np.float32(-12345.5)
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _domains(prep):
-    r = prep.regions()
-    return np.concatenate([np.stack(list(r["dom_lo"])), np.stack(list(r["dom_hi"]))], axis=1).astype(np.float32)
-
-
-def probe_points(prep, n_uniform=2500, seed=0):
-    """uniform in the bounds grown by 10 %, on integer and half-integer planes, on region faces, on brick corners, and a
-    few NaN / infinite coordinates"""
-    rng = np.random.default_rng(seed)
-    dom = _domains(prep)
-    lo, hi = dom[:, :3].min(axis=0), dom[:, 3:].max(axis=0)     # the root box
-    ext = hi - lo
-    glo, ghi = lo - 0.1 * ext, hi + 0.1 * ext
-    parts = [rng.uniform(glo, ghi, (n_uniform, 3))]
-    q = rng.uniform(glo, ghi, (800, 3))
-    m = rng.random(q.shape) < 0.6
-    q[m] = np.round(q[m] * 2.0) / 2.0                         # cell centres (level 0) and cell faces
-    parts.append(q)
-    pick = dom[rng.integers(len(dom), size=800)]
-    f = rng.uniform(pick[:, :3], pick[:, 3:])
-    ax = rng.integers(3, size=800)
-    side = rng.integers(2, size=800)
-    f[np.arange(800), ax] = pick[np.arange(800), ax + 3 * side]  # on a face of a region: shared, or against a gap
-    parts.append(f)
-    b = np.asarray(prep.bricks())
-    lower = np.stack(list(b["lower"])).astype(np.float32)
-    size = np.stack(list(b["size"])).astype(np.float32) * (2.0 ** b["level"].astype(np.float32))[:, None]
-    corner = rng.integers(2, size=(len(b), 3))
-    parts.append(lower + corner * size)
-    parts.append(np.array([[np.nan, 1, 1], [1, np.inf, 1], [1, 1, -np.inf], [np.nan] * 3], dtype=np.float32))
-    return np.ascontiguousarray(np.concatenate(parts).astype(np.float32))
-
-
-def brute_owner(prep, pts):
-    """the region whose domain holds p with the descent's half-open rule (lo <= p < hi; p == hi only on the root box's upper
-    faces), -1 for none; asserts there is at most one"""
-    dom = _domains(prep)
-    rlo, rhi = dom[:, :3].min(axis=0), dom[:, 3:].max(axis=0)
-    out = np.full(len(pts), -1, dtype=np.int64)
-    for s in range(0, len(pts), 512):
-        p = pts[s:s + 512, None, :]
-        upper = (p < dom[None, :, 3:]) | ((p == dom[None, :, 3:]) & (dom[None, :, 3:] == rhi))
-        own = np.all((p >= dom[None, :, :3]) & upper, axis=2)
-        cnt = own.sum(axis=1)
-        assert cnt.max(initial=0) <= 1, "overlapping region domains"
-        out[s:s + 512] = np.where(cnt == 1, own.argmax(axis=1), -1)
-    return out
 
 
 def _cases():
@@ -254,14 +206,29 @@ def test_normalized_gradient_of_a_linear_field():
     assert np.all(se >= 0)
     assert np.all(np.abs(gn[:, 0, 1]) > np.abs(g1[:, 0, 1]))      # sumW < 1: the numerator of d/dy is sumW^2 * slope.y
     np.testing.assert_allclose(gn[:, 0, 1], slope[1], rtol=1e-4)
-
-
-def _grid_positions(lo, hi, dims, world=None):
-    f = np.float32
-    lo, hi = np.asarray(lo, f), np.asarray(hi, f)
-    axes = [lo[k] + (np.arange(dims[k], dtype=f) + f(0.5)) * ((hi[k] - lo[k]) / f(dims[k])) for k in range(3)]
-    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
-    return np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1).astype(f)
+    R.close()
+    # three levels: inside a brick of level L, a cell width and more from the faces of its region, the weights sum to 1
+    # and the interpolant of a linear field is that field, whatever the cell width: the normalized gradient is the slope in
+    # VOXEL space, where the numerator is the slope per cell, 2^L times as much
+    scene = with_field_of_centres(scenes.amr(levels=3), lambda c: c @ slope + 2.0)
+    _, R = _renderer(scene)
+    combos = region_levels(R.prep)
+    dom = np.stack([np.stack(list(R.prep.regions()[k])) for k in ("dom_lo", "dom_hi")], axis=1).astype(np.float64)
+    for level in (0, 1, 2):
+        cw = float(1 << level)
+        ids = np.array([i for i, c in enumerate(combos) if c == (level,) and np.all(dom[i, 1] - dom[i, 0] > 2 * cw)])
+        assert len(ids) > 0, level
+        pick = dom[ids[rng.integers(len(ids), size=600)]]
+        pts = rng.uniform(pick[:, 0] + cw, pick[:, 1] - cw).astype(np.float32)
+        pts = pts[np.all((pts >= pick[:, 0] + cw) & (pts <= pick[:, 1] - cw), axis=1)]     # after the rounding to float32
+        assert len(pts) >= 500, level
+        v, gn, st = R.samplePoints(pts, channels=(1,), gradient=True, normalized=True)
+        _, g1, _ = R.samplePoints(pts, channels=(1,), gradient=True)
+        assert np.array_equal(st[:, 0], brute_owner(R.prep, pts)) and np.all(np.isin(st[:, 0], ids)), level
+        np.testing.assert_allclose(v[:, 0], pts.astype(np.float64) @ slope + 2.0, rtol=1e-5, atol=0)
+        np.testing.assert_allclose(gn[:, 0], np.broadcast_to(slope, (len(pts), 3)), rtol=1e-4, atol=0, err_msg=f"level {level}")
+        np.testing.assert_allclose(g1[:, 0], np.broadcast_to(slope * cw, (len(pts), 3)), rtol=1e-4, atol=0)
+    R.close()
 
 
 @pytest.mark.parametrize("world", [False, True], ids=["voxel", "world"])
