@@ -402,6 +402,56 @@ int exa_hip_isosurface_read(ExaHipRenderer *, float *vertices, float *gradients,
 int exa_hip_isosurface_release(ExaHipRenderer *);
 int exa_hip_isosurface_stage_ms(ExaHipRenderer *, float ms[6]);
 
+/* ---- histogram and value range of one channel's cells: the exact histogram of the cell values by cell count and by
+ * volume, the value range, the cell counts per level and the NaN / empty / out-of-range counts, optionally inside an integer
+ * voxel box.  New relative to the reference, whose viewer left the hook unbuilt (exa/viewer.cpp:1274-1276, setValueRange /
+ * setHistogram(computeHistogram(scalarField)) commented out).  One streaming pass over the channel on the device. ----
+ *
+ * Cell slots.  The call considers every slot (b, i) of every brick b of the scene, i < size.x*size.y*size.z, x fastest; the
+ * slot's value is scalars[channelOffset[channel] + begin_b + i], addressed in 64 bits.  Every brick slot is counted: a scene
+ * whose bricks share cells counts them once per brick.
+ *
+ * Box.  box = lo.xyz, hi.xyz in voxel coordinates, NULL = everything.  A slot is considered if its cell centre lies in the
+ * half-open box: per axis 2*box_lo <= 2*(lower + idx*2^level) + 2^level < 2*box_hi, in 64-bit integers.  box_lo == box_hi on
+ * an axis is an empty box: all zeros, no error.  box_lo > box_hi is an error.
+ *
+ * Classes, in this order.  empty: the scene is marked allowEmptyCells and the value equals EXA_EMPTY_CELL_POISON_VALUE;
+ * nan: the value is NaN; under: v < lo; over: v > hi; binned: everything else, with
+ * t = (v - lo) * (float(numBins) / (hi - lo)) in float32, every operation rounded separately, bin = min(numBins - 1, (int)t).
+ * +-Inf are under / over and count for min / max.  The call adds 1 to cells[bin] and, with volume != NULL, 8^level to
+ * volume[bin] (a level-L cell is 8^L finest voxels).  Counts are integers: the result is exact.
+ *
+ * Arguments.  Errors with a message: lo or hi not finite, lo >= hi; hi - lo or float(numBins) / (hi - lo) not finite in
+ * float32; numBins > EXA_HIST_MAX_BINS or < 0; cells == NULL with numBins > 0; a bad channel; a brick level outside 0..31.
+ * With volume != NULL the call is refused if the sum over all bricks of cells * 8^level does not fit 64 bits.
+ *
+ * Range only.  With numBins == 0, lo / hi / cells / volume are ignored, under = over = 0 and every non-empty non-NaN slot is
+ * binned: the pass a caller runs first to choose lo and hi.
+ *
+ * min / max.  Over the considered, non-empty, non-NaN values (under and over included), under the total order in which
+ * -0.0 < +0.0 (the sign-flip map of the bit pattern to an ordered uint32): the returned bits do not depend on the order in
+ * which the values arrive.  +INFINITY / -INFINITY if there is no such value.
+ *
+ * Independence.  The result depends only on the scene, channel, lo, hi, numBins and the box — not on the transfer function,
+ * region activity, the frame state, basis_form, brick_order, interleave or any other option; two calls give the same bytes.
+ * A pending brick_order change is applied first, as render and the probes do.  The call never looks at regions and works on
+ * scenes without a kd tree.  A multi-device handle runs it on devices[0].  Synchronous on hipStream; all outputs are host
+ * memory.  A failed call leaves the handle usable. */
+#define EXA_HIST_MAX_BINS   4096
+#define EXA_HIST_MAX_LEVELS 32
+typedef struct ExaHipFieldStats {
+  uint64_t slots;                     /* cell slots considered: = empty + nan + under + over + binned */
+  uint64_t empty, nan, under, over, binned;
+  uint64_t levelCells[EXA_HIST_MAX_LEVELS]; /* non-empty considered slots (NaN included) by brick level */
+  float    min, max;                  /* over considered, non-empty, non-NaN values; +INFINITY / -INFINITY if there is none */
+} ExaHipFieldStats;
+int exa_hip_histogram(ExaHipRenderer *, int32_t channel, float lo, float hi, int32_t numBins,
+                      const int32_t box[6] /* lo.xyz, hi.xyz in voxel coordinates; NULL = everything */,
+                      uint64_t *cells /* numBins */, uint64_t *volume /* numBins, or NULL */,
+                      ExaHipFieldStats *stats /* or NULL */, void *hipStream);
+/* the device time of the last exa_hip_histogram's kernel in ms (0 after a call with an empty box, or before any) */
+int exa_hip_histogram_ms(ExaHipRenderer *, float *ms);
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,

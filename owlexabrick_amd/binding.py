@@ -82,6 +82,23 @@ class ExaHipStats(C.Structure):
         return d
 
 
+# exa_hip_histogram (include/exa_hip.h)
+HIST_MAX_BINS = 4096
+HIST_MAX_LEVELS = 32
+
+
+class ExaHipFieldStats(C.Structure):
+    _fields_ = [("slots", C.c_uint64), ("empty", C.c_uint64), ("nan", C.c_uint64), ("under", C.c_uint64), ("over", C.c_uint64),
+                ("binned", C.c_uint64), ("levelCells", C.c_uint64 * HIST_MAX_LEVELS), ("min", C.c_float), ("max", C.c_float)]
+
+    def asdict(self):
+        """counts as ints, levelCells as a uint64 array, min / max as numpy float32 (their bits are part of the result)"""
+        d = {k: int(getattr(self, k)) for k in ("slots", "empty", "nan", "under", "over", "binned")}
+        d["levelCells"] = np.array(self.levelCells, dtype=np.uint64)
+        d["min"], d["max"] = np.float32(self.min), np.float32(self.max)
+        return d
+
+
 BRICK_DTYPE = np.dtype([("lower", "<i4", 3), ("size", "<i4", 3), ("level", "<i4"), ("begin", "<u4")])
 REGION_DTYPE = np.dtype([("dom_lo", "<f4", 3), ("dom_hi", "<f4", 3), ("vr_lo", "<f4"), ("vr_hi", "<f4"),
                          ("leafListBegin", "<i4"), ("leafListSize", "<i4"), ("finestLevelCellWidth", "<f4")])
@@ -96,7 +113,8 @@ ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa
                "exa_hip_untile", "exa_hip_render", "exa_hip_render_stats", "exa_hip_get_stats",
                "exa_hip_read_accum", "exa_hip_write_accum", "exa_hip_read_activity",
                "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample",
-               "exa_hip_isosurface", "exa_hip_isosurface_read", "exa_hip_isosurface_release", "exa_hip_isosurface_stage_ms"]
+               "exa_hip_isosurface", "exa_hip_isosurface_read", "exa_hip_isosurface_release", "exa_hip_isosurface_stage_ms",
+               "exa_hip_histogram", "exa_hip_histogram_ms"]
 
 # exa_hip_sample_points / exa_hip_resample flags (include/exa_hip.h)
 SAMPLE_WORLD_SPACE = 1
@@ -164,6 +182,8 @@ def lib():
         L.exa_hip_isosurface_read.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
         L.exa_hip_isosurface_release.argtypes = [vp]
         L.exa_hip_isosurface_stage_ms.argtypes = [vp, vp]
+        L.exa_hip_histogram_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.exa_hip_histogram.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.POINTER(ExaHipFieldStats), vp]
         _lib = L
     return _lib
 
@@ -533,6 +553,33 @@ class Renderer:
             return self.readIsoSurface()
         finally:
             self.releaseIsoSurface()
+
+    # ---- histogram and value range of a channel's cells (exa_hip_histogram; include/exa_hip.h states the contract) ----
+    def histogram(self, channel, lo, hi, bins, box=None, volume=True, stream=None):
+        """the exact histogram of the cell values of `channel` over [lo, hi] in `bins` bins: (cells uint64 [bins], volume
+        uint64 [bins] or None, stats dict).  cells counts cell slots, volume weights a level-L cell with 8^L finest voxels;
+        box = (lo.xyz, hi.xyz) in integer voxel coordinates restricts both to the cells whose centre lies in it.  bins = 0
+        is the range-only pass (fieldStats)."""
+        bins = int(bins)
+        n = min(max(bins, 0), HIST_MAX_BINS)                                   # the module checks bins
+        cells = np.zeros(n, dtype=np.uint64)
+        vol = np.zeros(n, dtype=np.uint64) if volume else None
+        b6 = (C.c_int32 * 6)(*[int(v) for v in box]) if box is not None else None
+        st = ExaHipFieldStats()
+        self._check(lib().exa_hip_histogram(self.h, int(channel), float(lo), float(hi), bins, b6, cells.ctypes.data,
+                                            vol.ctypes.data if volume else None, C.byref(st), C.c_void_p(stream or 0)))
+        return cells, vol, st.asdict()
+
+    def histogramMs(self):
+        """device ms of the last histogram / fieldStats call's kernel"""
+        ms = C.c_float(0)
+        self._check(lib().exa_hip_histogram_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def fieldStats(self, channel, box=None):
+        """value range (min, max), cell counts per level and the NaN / empty counts of `channel`, optionally inside a box: the
+        stats dict of the range-only pass"""
+        return self.histogram(channel, 0.0, 0.0, 0, box=box, volume=False)[2]
 
 
 def _dev_ptr(x):

@@ -1,7 +1,7 @@
 // exa_renderer.h — internal to the exa_hip_* module (not installed): the renderer behind the opaque ExaHipRenderer handle
 // of include/exa_hip.h and the helpers its translation units share.  exa_create.cpp builds and destroys a renderer,
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes and the iso-surface extraction,
-// exa_module.cpp the setters, options and read-backs.
+// exa_stats.cpp the histogram and value range of the cells, exa_module.cpp the setters, options and read-backs.
 #pragma once
 #include "exa_device.h"
 #include "exa_ropes.h"
@@ -262,6 +262,15 @@ struct ExaHipRenderer {
   DevBuf<int32_t> isoTriangles;
   bool haveIsoMesh = false;
   float isoStageMs[6] = { 0, 0, 0, 0, 0, 0 };
+  // exa_hip_histogram (on a multi-device handle: in the renderer of devices[0]): the work list of the pass — segments
+  // {brick, first cell} by level and the offsets of the runs, built by the first call (exa_stats.cpp) —, whether the scene's
+  // volume-weighted cell count fits 64 bits, the device copy of a call's result and the device time of its kernel
+  DevBuf<uint4> histSegs;
+  DevBuf<uint32_t> histRuns;
+  uint32_t histNumRuns = 0;
+  bool histPlanBuilt = false, histVolumeFits = true;
+  DevBuf<unsigned long long> histResult;
+  float histKernelMs = 0.f;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 

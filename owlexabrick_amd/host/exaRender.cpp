@@ -22,6 +22,12 @@
 //                                            a config's `triangles` line reads, with
 //             [--isomesh-box lx ly lz ux uy uz] [--isomesh-world] [--isomesh-channel c]
 //                                            (box default as for --resample)
+//             [--histogram BINS file.txt]    the exact histogram of a channel's cell values (exa_hip_histogram), one line
+//                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
+//             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
+//                                            (range default: min..max of the channel from a range-only pass — a constant field
+//                                            is refused; box: integer voxel coordinates, default everything); --frames 0
+//                                            renders nothing
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -85,6 +91,11 @@ int main(int argc, char **argv)
     std::string isoName;
     bool isoWorld = false, haveIsoBox = false;
     box3f isoBox;
+    int histBins = 0, histChannel = 0;
+    std::string histName;
+    bool haveHistRange = false, haveHistBox = false;
+    float histRange[2] = { 0, 1 };
+    box3i histBox;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -142,6 +153,17 @@ int main(int argc, char **argv)
       else if (a == "--isomesh-box") { isoBox.lower = { f(), f(), f() }; isoBox.upper = { f(), f(), f() }; haveIsoBox = true; }
       else if (a == "--isomesh-world") isoWorld = true;
       else if (a == "--isomesh-channel") isoChannel = (int)f();
+      else if (a == "--histogram") {
+        histBins = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --histogram BINS");
+        histName = argv[++i];
+      }
+      else if (a == "--histogram-channel") histChannel = (int)f();
+      else if (a == "--histogram-range") { histRange[0] = f(); histRange[1] = f(); haveHistRange = true; }
+      else if (a == "--histogram-box") {
+        auto n = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (int)std::strtol(argv[++i], nullptr, 10); };
+        histBox.lower = { n(), n(), n() }; histBox.upper = { n(), n(), n() }; haveHistBox = true;
+      }
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
       else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
@@ -248,7 +270,27 @@ int main(int argc, char **argv)
                   dims.z, box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z, isoChannel, isoValue,
                   mesh->vertex.size(), mesh->index.size());
     }
-    if (frames == 0 && (!resampleName.empty() || !isoName.empty())) return 0;
+    if (!histName.empty()) {
+      if (histBins < 1) throw std::runtime_error("--histogram wants BINS >= 1");
+      const box3i *box = haveHistBox ? &histBox : nullptr;
+      interval<float> range(histRange[0], histRange[1]);
+      if (!haveHistRange) {
+        const ExaHipFieldStats r = renderer.fieldStats(histChannel, box);
+        if (!(r.min < r.max)) throw std::runtime_error("--histogram: the field is constant (or has no value) there: give --histogram-range lo hi");
+        range = interval<float>(r.min, r.max);
+      }
+      std::vector<uint64_t> cells, volume;
+      ExaHipFieldStats st;
+      renderer.computeHistogram(histChannel, range, histBins, cells, &volume, &st, box);
+      FILE *f = std::fopen(histName.c_str(), "w");
+      if (!f) throw std::runtime_error("cannot write " + histName);
+      for (size_t b = 0; b < cells.size(); b++) std::fprintf(f, "%llu %llu\n", (unsigned long long)cells[b], (unsigned long long)volume[b]);
+      if (std::fclose(f)) throw std::runtime_error("cannot write " + histName);
+      std::printf("histogram channel %d bins %d range %.9g %.9g slots %llu empty %llu nan %llu under %llu over %llu binned %llu\n", histChannel,
+                  histBins, range.lower, range.upper, (unsigned long long)st.slots, (unsigned long long)st.empty, (unsigned long long)st.nan,
+                  (unsigned long long)st.under, (unsigned long long)st.over, (unsigned long long)st.binned);
+    }
+    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

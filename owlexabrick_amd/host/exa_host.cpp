@@ -580,6 +580,26 @@ TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int c
   return mesh;
 }
 
+void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
+                                std::vector<uint64_t> *volume, ExaHipFieldStats *stats, const box3i *box)
+{
+  const int32_t b[6] = { box ? box->lower.x : 0, box ? box->lower.y : 0, box ? box->lower.z : 0,
+                         box ? box->upper.x : 0, box ? box->upper.y : 0, box ? box->upper.z : 0 };
+  const size_t n = numBins > 0 && numBins <= EXA_HIST_MAX_BINS ? size_t(numBins) : 0;     // the module checks numBins
+  cells.assign(n, 0);
+  if (volume) volume->assign(n, 0);
+  check(exa_hip_histogram(handle, channel, range.lower, range.upper, numBins, box ? b : nullptr, cells.data(),
+                          volume ? volume->data() : nullptr, stats, nullptr), handle);
+}
+
+ExaHipFieldStats Renderer::fieldStats(int channel, const box3i *box)
+{
+  ExaHipFieldStats s;
+  std::vector<uint64_t> none;
+  computeHistogram(channel, interval<float>(0.f, 0.f), 0, none, nullptr, &s, box);
+  return s;
+}
+
 ExaHipStats Renderer::stats() const
 {
   ExaHipStats s;

@@ -149,6 +149,9 @@ struct FrameState {
   float xfOpacityScale = 1.f;
 };
 
+// an integer voxel box, half open (computeHistogram / fieldStats)
+struct box3i { vec3i lower, upper; };
+
 // exa::OptixRenderer's interface (exa/OptixRenderer.h:32-97) over the C ABI
 struct Renderer {
   typedef std::shared_ptr<Renderer> SP;
@@ -205,6 +208,16 @@ struct Renderer {
   // (TriangleMesh::save).
   TriangleMesh::SP extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace = false,
                                      std::vector<vec3f> *gradients = nullptr);
+
+  // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
+  // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
+  // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
+  // `range`, volume[b] (or NULL) = the same weighted with 8^level finest voxels per cell, stats (or NULL) = the counts by
+  // class and level and the value range; box (or NULL) restricts all of it to the cells whose centre lies in it.
+  // fieldStats is the range-only pass: what setValueRange wants, and how a caller chooses `range`.
+  void computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
+                        std::vector<uint64_t> *volume = nullptr, ExaHipFieldStats *stats = nullptr, const box3i *box = nullptr);
+  ExaHipFieldStats fieldStats(int channel, const box3i *box = nullptr);
 
   ExaHipStats stats() const;
   ExaHipStats renderStats();                 // the same frame through the counting variant of the kernels
