@@ -452,6 +452,82 @@ int exa_hip_histogram(ExaHipRenderer *, int32_t channel, float lo, float hi, int
 /* the device time of the last exa_hip_histogram's kernel in ms (0 after a call with an empty box, or before any) */
 int exa_hip_histogram_ms(ExaHipRenderer *, float *ms);
 
+/* ---- streamlines: field lines of the vector field formed by three channels, integrated from seed points with classical
+ * RK4 at a fixed step and handed out as packed polylines.  An extraction, not the viewer's animation: the reference's tracer
+ * (exa_hip_reset_tracer / exa_hip_advance_tracer) takes one step per rendered frame, forward only, at a trace count and
+ * length fixed at reset, and finds a position's region with a ray through the volume BVH, which is refit to the transfer
+ * function — its traces end where the volume is merely invisible.  Here a whole line is integrated on the device in one
+ * call, in either or both directions, and nothing a frame sets changes it. ----
+ *
+ * Space.  Voxel space only.  World-space seeds are not offered: the components of a vector field have no defined mapping
+ * under the voxelSpaceTransform.
+ *
+ * Evaluation E(q).  Exactly what exa_hip_sample_points(q, channels, 3, flags = 0) returns: one region lookup by the rules of
+ * the probes' block (closed root box, `>= split` goes right, no backtracking, closed-domain test at the leaf), then the three
+ * channels in the order given, in the handle's current basis_form (a scene marked allowEmptyCells: the form-0 sums with the
+ * poison test).  The outcome is LEFT if the lookup gives -1 (outside, a gap, a NaN or infinite coordinate); otherwise NOVALUE
+ * if any channel has status -2; otherwise the velocity v = (v0, v1, v2).  With EXA_STREAM_NORMALIZE,
+ * s = sqrtf((v0*v0 + v1*v1) + v2*v2), every operation rounded separately and the square root correctly rounded; if !(s > 0)
+ * or s is not finite the outcome is STAGNANT, otherwise the direction is d = v / s per component by true division.  Without
+ * the flag d = v.
+ *
+ * One direction from the seed p0.  hs = +step forward, -step backward.  The seed is vertex 0 of its direction.  E(p0) failing
+ * ends the direction with that reason and no further vertices.  Otherwise, up to maxSteps times, in float32 with nothing
+ * contracted:
+ *     k1 = hs*d(p)   k2 = hs*d(p + .5f*k1)   k3 = hs*d(p + .5f*k2)   k4 = hs*d(p + k3)
+ *     pn = p + (1/6.f) * (((k1 + 2.f*k2) + 2.f*k3) + k4)
+ * (the reference's step, exabrick.cu:1531-1574).  A failing stage ends the direction with that stage's reason: the stage order
+ * decides, within a stage the order is lookup, channels, speed.  pn bit-equal to p in all three components ends it STAGNANT.
+ * Then E(pn): a failure ends the direction with that reason and pn is NOT appended; otherwise pn is appended and its d is the
+ * next step's k1.  After maxSteps appended vertices the reason is MAXSTEPS.  So every vertex other than a failed seed has a
+ * value in all three channels.
+ *
+ * A line.  The backward direction's vertices in reverse (farthest first), the seed once, the forward direction's vertices.
+ * seedVertex[i] = number of backward vertices; line i is vertices offsets[i] .. offsets[i+1]; offsets[n] = numVertices.  A
+ * seed whose own evaluation fails is a one-vertex line (the seed as given) with that reason in every requested direction.
+ * reasons[2*i] is the backward, reasons[2*i+1] the forward direction's; EXA_STREAM_END_NONE for a direction not requested.
+ * velocities (only after an extraction with EXA_STREAM_VELOCITIES) holds the raw v, never normalised, of every vertex; NaN
+ * for a failed seed.
+ *
+ * Independence.  The bytes depend only on the scene, the seeds, channels, step, maxSteps, flags and basis_form — not on the
+ * transfer function, region activity, the frame state, walk, accel, brick_order, interleave, the number of seeds in the call
+ * or their order: line i of a batch equals the one-seed call.  A pending brick_order change is applied first.  A multi-device
+ * handle runs on devices[0].  A scene without a kd tree is refused, as the probes refuse it.
+ *
+ * Calls.  exa_hip_streamlines extracts synchronously on hipStream; seeds are host memory.  The lines stay in module-owned
+ * device memory until the next extraction (also a failed one), exa_hip_streamlines_release or exa_hip_destroy.  n == 0
+ * returns 0 with zero vertices.  Errors with a message, after which the handle stays usable: step not finite or <= 0;
+ * maxSteps < 1 or > EXA_STREAM_MAX_STEPS; no direction flag; unknown flag bits; a channel outside [0, numFields); more than
+ * INT32_MAX vertices in all; a failed allocation; the descent's loop guard (return code 3, as the probes).
+ * exa_hip_streamlines_read copies the last extraction out (host arrays, or memory of the handle's first device with
+ * pointersAreDevice); a NULL pointer skips that array; an error before any extraction, after a release, and for velocities
+ * without EXA_STREAM_VELOCITIES.  exa_hip_streamlines_ms: the device time of the last extraction's two kernels, summed.
+ *
+ * Memory.  Count, then emit: the integration is deterministic, so it runs twice — once storing per direction only the
+ * number of vertices and the reason, then, after a scan of the counts on the host, again storing every vertex at its packed
+ * position.  Peak device memory: the packed result (12 bytes per vertex, 24 with velocities, and 28 bytes per seed for
+ * offsets, seedVertex, reasons and counts) plus 12 bytes per seed for the seeds while the call runs; nothing grows with
+ * n * maxSteps. */
+#define EXA_STREAM_FORWARD     1
+#define EXA_STREAM_BACKWARD    2   /* both: one polyline through the seed */
+#define EXA_STREAM_NORMALIZE   4   /* step along v/|v|: `step` is an arc length in voxel units */
+#define EXA_STREAM_VELOCITIES  8   /* also keep v at every vertex */
+#define EXA_STREAM_MAX_STEPS   1048576   /* the cap of maxSteps (per direction) */
+/* why a direction ended */
+#define EXA_STREAM_END_NONE     0  /* direction not requested */
+#define EXA_STREAM_END_MAXSTEPS 1
+#define EXA_STREAM_END_LEFT     2  /* a position with probe status -1 (outside, a gap, NaN / infinite) */
+#define EXA_STREAM_END_NOVALUE  3  /* probe status -2 in one of the three channels */
+#define EXA_STREAM_END_STAGNANT 4
+int exa_hip_streamlines(ExaHipRenderer *, const float *seeds /* n x 3, voxel space, host */, uint64_t n,
+                        const int32_t channels[3], float step, int32_t maxSteps, int32_t flags,
+                        uint64_t *numVertices, void *hipStream);
+int exa_hip_streamlines_read(ExaHipRenderer *, float *vertices /* numVertices x 3 */, float *velocities /* same, or NULL */,
+                             uint64_t *offsets /* n + 1 */, uint32_t *seedVertex /* n */, int32_t *reasons /* n x 2: backward, forward */,
+                             int32_t pointersAreDevice, void *hipStream);
+int exa_hip_streamlines_release(ExaHipRenderer *);
+int exa_hip_streamlines_ms(ExaHipRenderer *, float *ms);   /* device time of the last extraction's kernels, summed */
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,

@@ -114,12 +114,21 @@ ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa
                "exa_hip_read_accum", "exa_hip_write_accum", "exa_hip_read_activity",
                "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample",
                "exa_hip_isosurface", "exa_hip_isosurface_read", "exa_hip_isosurface_release", "exa_hip_isosurface_stage_ms",
-               "exa_hip_histogram", "exa_hip_histogram_ms"]
+               "exa_hip_histogram", "exa_hip_histogram_ms",
+               "exa_hip_streamlines", "exa_hip_streamlines_read", "exa_hip_streamlines_release", "exa_hip_streamlines_ms"]
 
 # exa_hip_sample_points / exa_hip_resample flags (include/exa_hip.h)
 SAMPLE_WORLD_SPACE = 1
 SAMPLE_GRADIENT = 2
 SAMPLE_GRADIENT_NORMALIZED = 4
+
+# exa_hip_streamlines flags and end reasons (include/exa_hip.h)
+STREAM_FORWARD = 1
+STREAM_BACKWARD = 2
+STREAM_NORMALIZE = 4
+STREAM_VELOCITIES = 8
+STREAM_MAX_STEPS = 1 << 20
+STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREAM_END_STAGNANT = range(5)
 
 _lib = None
 
@@ -184,6 +193,10 @@ def lib():
         L.exa_hip_isosurface_stage_ms.argtypes = [vp, vp]
         L.exa_hip_histogram_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.exa_hip_histogram.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.POINTER(ExaHipFieldStats), vp]
+        L.exa_hip_streamlines.argtypes = [vp, vp, C.c_uint64, vp, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), vp]
+        L.exa_hip_streamlines_read.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp]
+        L.exa_hip_streamlines_release.argtypes = [vp]
+        L.exa_hip_streamlines_ms.argtypes = [vp, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -580,6 +593,59 @@ class Renderer:
         """value range (min, max), cell counts per level and the NaN / empty counts of `channel`, optionally inside a box: the
         stats dict of the range-only pass"""
         return self.histogram(channel, 0.0, 0.0, 0, box=box, volume=False)[2]
+
+    # ---- streamlines (exa_hip_streamlines*; include/exa_hip.h states the contract) ----
+    def extractStreamlines(self, seeds, channels=(0, 1, 2), step=0.5, max_steps=1000, forward=True, backward=False,
+                           normalize=False, velocities=False, stream=None):
+        """integrate the field lines of the vector field `channels` from seeds [n,3] (voxel space) into module-owned device
+        memory; returns the number of vertices.  readStreamlines copies them out, releaseStreamlines frees them."""
+        pts = np.ascontiguousarray(seeds, dtype=np.float32).reshape(-1, 3)
+        ch3 = (C.c_int32 * 3)(*[int(c) for c in channels])
+        flags = (STREAM_FORWARD if forward else 0) | (STREAM_BACKWARD if backward else 0)
+        flags |= (STREAM_NORMALIZE if normalize else 0) | (STREAM_VELOCITIES if velocities else 0)
+        nv = C.c_uint64(0)
+        self._stream_counts = (0, 0, False)
+        self._check(lib().exa_hip_streamlines(self.h, pts.ctypes.data, pts.shape[0], ch3, float(step), int(max_steps), flags,
+                                              C.byref(nv), C.c_void_p(stream or 0)))
+        self._stream_counts = (pts.shape[0], int(nv.value), bool(velocities))
+        return int(nv.value)
+
+    def readStreamlines(self):
+        """(vertices float32 [V,3], offsets uint64 [n+1], seed_vertex uint32 [n], reasons int32 [n,2] (backward, forward),
+        velocities float32 [V,3] or None) of the last extractStreamlines"""
+        n, nv, vel = getattr(self, "_stream_counts", (0, 0, False))
+        verts = np.empty((nv, 3), dtype=np.float32)
+        vels = np.empty((nv, 3), dtype=np.float32) if vel else None
+        offsets = np.empty(n + 1, dtype=np.uint64)
+        seed_vertex = np.empty(n, dtype=np.uint32)
+        reasons = np.empty((n, 2), dtype=np.int32)
+        self._check(lib().exa_hip_streamlines_read(self.h, verts.ctypes.data, vels.ctypes.data if vel else None,
+                                                   offsets.ctypes.data, seed_vertex.ctypes.data, reasons.ctypes.data, 0, None))
+        return verts, offsets, seed_vertex, reasons, vels
+
+    def releaseStreamlines(self):
+        self._check(lib().exa_hip_streamlines_release(self.h))
+        self._stream_counts = (0, 0, False)
+
+    def streamlinesMs(self):
+        """device ms of the last extraction's two kernels (count and emit), summed"""
+        ms = C.c_float(0)
+        self._check(lib().exa_hip_streamlines_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def streamlines(self, seeds, channels=(0, 1, 2), step=0.5, max_steps=1000, forward=True, backward=False, normalize=False,
+                    velocities=False):
+        """field lines of the vector field formed by three channels, by fixed-step RK4 from seeds [n,3] in voxel space:
+        (vertices [V,3], offsets [n+1], seed_vertex [n], reasons [n,2], velocities [V,3] or None).  Line i is
+        vertices[offsets[i]:offsets[i+1]]: the backward part reversed, the seed at seed_vertex[i], the forward part.
+        normalize: step along v/|v| (step is an arc length in voxels).  reasons: STREAM_END_* per direction (backward,
+        forward).  The device copy is released before returning."""
+        self.extractStreamlines(seeds, channels=channels, step=step, max_steps=max_steps, forward=forward, backward=backward,
+                                normalize=normalize, velocities=velocities)
+        try:
+            return self.readStreamlines()
+        finally:
+            self.releaseStreamlines()
 
 
 def _dev_ptr(x):

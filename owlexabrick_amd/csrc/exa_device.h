@@ -260,6 +260,27 @@ struct SampleArgs {
 // patch shapes of the grid kernel (x, y, z extents; 64 points each)
 enum { kSamplePatchShapes = 4 };
 
+// The streamline integrator (exa_hip_streamlines, exa_stream_kernels.h): one lane per (seed, requested direction), RK4 in voxel
+// space on the probes' lookup and sums.  Two launches per extraction: the first stores per direction the number of vertices
+// it appends and why it ended, the second (after the scan of the counts) integrates again and stores the vertices packed.
+struct StreamArgs {
+  SampleArgs         s;             // the lookup and the field (probeSetup); fieldOffset[0..2] = the three channels
+  const float       *seeds;         // numSeeds x 3, device
+  unsigned long long numSeeds;
+  unsigned long long laneBase;      // first lane of this launch; lane = seed * dirs + (dirs == 2 ? direction slot : 0)
+  unsigned long long numLanes;      // numSeeds * dirs
+  float              step;
+  int32_t            maxSteps;
+  int32_t            flags;         // EXA_STREAM_*
+  uint32_t          *counts;        // numSeeds x 2 (slot 0 backward, 1 forward): vertices appended after the seed
+  int32_t           *reasons;       // numSeeds x 2: EXA_STREAM_END_*
+  // the second launch only
+  const unsigned long long *offsets;     // numSeeds + 1: first vertex of every line
+  const uint32_t    *seedVertex;    // numSeeds: index of the seed within its line (= backward count)
+  float             *vertices;      // numVertices x 3
+  float             *velocities;    // numVertices x 3, or NULL
+};
+
 // ---- exa_lbvh.hip: LBVH topology over numPrims boxes (6 floats each, device), built on the device ----
 hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNode *nodes, int32_t *levelIds,
                                    std::vector<uint32_t> &internalNodesPerDepth, hipStream_t s);
@@ -287,7 +308,10 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
   /* the point probes (exa_sample_f*.o): a.count points; the grid box of a, in patch shape `shape` (0 64x1x1,         \
      1 16x4x1, 2 8x8x1, 3 4x4x4), wave-uniform descent and brick headers where a patch allows (uniform) or per lane */  \
   hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s);                                      \
-  hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);
+  hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);                          \
+  /* the streamline integrator (exa_stream_f*.o): lanes [a.laneBase, a.numLanes) of at most 2^24 per launch; emit = the  \
+     second launch, which stores the vertices */                                                                        \
+  hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);
 namespace form0 { EXA_FORM_LAUNCHERS }
 namespace form1 { EXA_FORM_LAUNCHERS }
 // ... and once more in the source order with the reference's ALLOW_EMPTY_CELLS semantics (-DEXA_EMPTY_CELLS=1: a corner whose

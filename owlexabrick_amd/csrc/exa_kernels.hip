@@ -42,6 +42,10 @@
 #ifndef EXA_TU_SAMPLE
 #define EXA_TU_SAMPLE 0
 #endif
+// The streamline integrator likewise (-DEXA_TU_STREAM=1: exa_stream_f*.o, the kernels of exa_stream_kernels.h and nothing else).
+#ifndef EXA_TU_STREAM
+#define EXA_TU_STREAM 0
+#endif
 namespace exa {
 namespace EXA_FORM_NS {
 
@@ -765,6 +769,10 @@ __device__ __forceinline__ bool samplePoint(Ctx<STATS> &C, float &value, V3 &der
 // the point probes (exa_hip_sample_points / exa_hip_resample) in translation units of their own (-DEXA_TU_SAMPLE=1:
 // exa_sample_f*.o hold these kernels and nothing else); everything below is the renderer
 #include "exa_sample_kernels.h"
+} // namespace EXA_FORM_NS
+#elif EXA_TU_STREAM
+// the streamline integrator (exa_hip_streamlines) in translation units of its own (-DEXA_TU_STREAM=1: exa_stream_f*.o)
+#include "exa_stream_kernels.h"
 } // namespace EXA_FORM_NS
 #else
 
@@ -3501,5 +3509,5 @@ hipError_t launchProfileMarker(int tag, hipStream_t s)
   return hipGetLastError();
 }
 #endif // EXA_BASIS_FORM == 0 && !EXA_EMPTY_CELLS
-#endif // EXA_TU_SAMPLE
+#endif // EXA_TU_SAMPLE, EXA_TU_STREAM
 } // namespace exa

@@ -7,18 +7,13 @@
 #include <cmath>
 #include <cstring>
 
-extern "C" {
-
-// ---- point probes ----
-// Host arrays pass through the handle's staging buffer in chunks of at most kProbeStageBytes; a launch covers at most
-// kProbeLaunch points (a grid patch holds one point at the least: 64 x that many lanes stay below 2^32).
-static const uint64_t kProbeStageBytes = 64ull << 20, kProbeLaunch = 1ull << 24;
 // after a synchronous probe: the descent's loop guard (checkLoopGuard)
-static const char *const kDescentGuard = ": the kd descent's loop guard tripped (malformed kd-tree?)";
+const char *const kDescentGuard = ": the kd descent's loop guard tripped (malformed kd-tree?)";
 
-// what both probes share: the renderer that runs them (a multi-device handle: the one of devices[0]), the checks, a pending
-// brick order applied (render does the same: the probes read `begin` through the march headers the permutation patches)
-static int probeSetup(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, bool world, hipStream_t s, SampleArgs &a)
+// what the probes (and exa_streamlines.cpp) share: the renderer that runs them (a multi-device handle: the one of devices[0]),
+// the checks, a pending brick order applied (render does the same: the probes read `begin` through the march headers the
+// permutation patches)
+int probeSetup(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, bool world, hipStream_t s, SampleArgs &a)
 {
   if (!r->haveKd) {
     h->fail(std::string(fn) + ": the scene has no region kd-tree (ExaHipScene.kdNodes): the probes locate a point's region with it "
@@ -41,6 +36,12 @@ static int probeSetup(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, bool
   return 0;
 }
 
+extern "C" {
+
+// ---- point probes ----
+// Host arrays pass through the handle's staging buffer in chunks of at most kProbeStageBytes; a launch covers at most
+// kProbeLaunch points (a grid patch holds one point at the least: 64 x that many lanes stay below 2^32).
+static const uint64_t kProbeStageBytes = 64ull << 20, kProbeLaunch = 1ull << 24;
 
 int exa_hip_sample_points(ExaHipRenderer *h, const float *points, uint64_t n, const int32_t *channels, int32_t numChannels,
                           int32_t flags, float fill, float *values, float *gradients, int32_t *status,

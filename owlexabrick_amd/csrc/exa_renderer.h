@@ -1,6 +1,7 @@
 // exa_renderer.h — internal to the exa_hip_* module (not installed): the renderer behind the opaque ExaHipRenderer handle
 // of include/exa_hip.h and the helpers its translation units share.  exa_create.cpp builds and destroys a renderer,
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes and the iso-surface extraction,
+// exa_streamlines.cpp the streamline extraction,
 // exa_stats.cpp the histogram and value range of the cells, exa_module.cpp the setters, options and read-backs.
 #pragma once
 #include "exa_device.h"
@@ -271,6 +272,15 @@ struct ExaHipRenderer {
   bool histPlanBuilt = false, histVolumeFits = true;
   DevBuf<unsigned long long> histResult;
   float histKernelMs = 0.f;
+  // the lines of the last exa_hip_streamlines (on a multi-device handle: in the renderer of devices[0]), packed, and the
+  // device time of its two kernels
+  DevBuf<float> streamVertices, streamVelocities;
+  DevBuf<unsigned long long> streamOffsets;
+  DevBuf<uint32_t> streamSeedVertex;
+  DevBuf<int32_t> streamReasons;
+  uint64_t streamSeeds = 0, streamNumVertices = 0;
+  bool haveStreamlines = false;
+  float streamKernelMs = 0.f;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 
@@ -345,3 +355,9 @@ inline uint32_t packLeafRec(int32_t listBegin, int32_t listSize, float width, ui
 // Reads and clears the loop guard of r's kernels; when it tripped, h (r or its multi-device handle) fails with fn + what
 // and the ABI's return code 3 comes back
 int checkLoopGuard(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, const char *what);
+
+// What the probes and the streamline integrator share (exa_probe.cpp): the checks (a kd tree; a frame state for world
+// space), a pending brick order applied, and the lookup / field part of the kernels' arguments; the message of the kd
+// descent's loop guard (checkLoopGuard)
+int probeSetup(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, bool world, hipStream_t s, SampleArgs &a);
+extern const char *const kDescentGuard;

@@ -12,34 +12,7 @@
 // brick's cell units; EXA_SAMPLE_GRADIENT_NORMALIZED takes them in voxel units instead (addBasisFast<.., VOXEL>: each
 // brick's terms times its 2^-level) and divides by sumW^2: the gradient of sumWV / sumW with respect to the position.
 
-// p inside the closed root box; false for a NaN coordinate
-__device__ __forceinline__ bool sampleInRoot(const SampleArgs &a, V3 p)
-{
-  return p.x >= a.kdLo[0] && p.x <= a.kdHi[0] && p.y >= a.kdLo[1] && p.y <= a.kdHi[1] && p.z >= a.kdLo[2] && p.z <= a.kdHi[2];
-}
-
-// the child of a node on p's side of its plane (only split, axis and children: the activity bits are masked)
-__device__ __forceinline__ int sampleKdChild(const KdNodeDev n, V3 p)
-{
-  const uint32_t axis = n.word & 3u;
-  const float c = axis == 0u ? p.x : (axis == 1u ? p.y : p.z);
-  return c >= n.split ? n.right : n.left;
-}
-
-// from subtree `ref` down to a leaf: the region id, or -1 (an empty child slot, or the bound tripped)
-__device__ __forceinline__ int sampleKdLeaf(const SampleArgs &a, int ref, V3 p, bool &tripped)
-{
-  for (int g = 0; ref >= 0; g++) {
-    if (g >= a.maxSteps) { tripped = true; return -1; }
-    ref = sampleKdChild(a.kdNodes[ref], p);
-  }
-  return ref == EXA_KD_EMPTY ? -1 : ~ref;
-}
-
-__device__ __forceinline__ bool sampleInDomain(const RegionRec &R, V3 p)
-{
-  return p.x >= R.lo[0] && p.x <= R.hi0 && p.y >= R.lo[1] && p.y <= R.hi1 && p.z >= R.lo[2] && p.z <= R.hi2;
-}
+#include "exa_sample_locate.h"   // sampleInRoot, sampleKdChild, sampleKdLeaf, sampleInDomain
 
 // samplePoint's sums (exabrick.cu:781-806, 883-928) over the region's bricks, through the march headers: the loop of
 // samplePoint with fastSampler.  listBegin / listSize wave-uniform -> the headers are read once per wave.

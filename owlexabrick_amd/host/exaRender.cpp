@@ -28,6 +28,13 @@
 //                                            (range default: min..max of the channel from a range-only pass — a constant field
 //                                            is refused; box: integer voxel coordinates, default everything); --frames 0
 //                                            renders nothing
+//             [--streamlines SEEDS.txt STEP MAXSTEPS out.lines] field lines of three channels from the seeds of SEEDS.txt (one
+//                                            `x y z` per line, voxel space) by fixed-step RK4 (exa_hip_streamlines); one text
+//                                            line per polyline: `seedVertex backwardReason forwardReason count` and the
+//                                            count vertices `x y z` (%.9g), with
+//             [--streamlines-channels a b c] [--streamlines-both] [--streamlines-backward] [--streamlines-normalize]
+//                                            (channels default 0 1 2; forward unless --streamlines-backward); --frames 0
+//                                            renders nothing
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -96,6 +103,11 @@ int main(int argc, char **argv)
     bool haveHistRange = false, haveHistBox = false;
     float histRange[2] = { 0, 1 };
     box3i histBox;
+    std::string streamSeedsName, streamName;
+    float streamStep = 0.f;
+    int streamMaxSteps = 0;
+    vec3i streamChannels(0, 1, 2);
+    bool streamBoth = false, streamBackward = false, streamNormalize = false;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -164,6 +176,18 @@ int main(int argc, char **argv)
         auto n = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (int)std::strtol(argv[++i], nullptr, 10); };
         histBox.lower = { n(), n(), n() }; histBox.upper = { n(), n(), n() }; haveHistBox = true;
       }
+      else if (a == "--streamlines") {
+        if (i + 1 >= argc) throw std::runtime_error("missing seed file after --streamlines");
+        streamSeedsName = argv[++i];
+        streamStep = f();
+        streamMaxSteps = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --streamlines SEEDS.txt STEP MAXSTEPS");
+        streamName = argv[++i];
+      }
+      else if (a == "--streamlines-channels") { streamChannels.x = (int)f(); streamChannels.y = (int)f(); streamChannels.z = (int)f(); }
+      else if (a == "--streamlines-both") streamBoth = true;
+      else if (a == "--streamlines-backward") streamBackward = true;
+      else if (a == "--streamlines-normalize") streamNormalize = true;
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
       else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
@@ -290,7 +314,30 @@ int main(int argc, char **argv)
                   histBins, range.lower, range.upper, (unsigned long long)st.slots, (unsigned long long)st.empty, (unsigned long long)st.nan,
                   (unsigned long long)st.under, (unsigned long long)st.over, (unsigned long long)st.binned);
     }
-    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty())) return 0;
+    if (!streamName.empty()) {
+      std::vector<vec3f> seeds;
+      FILE *f = std::fopen(streamSeedsName.c_str(), "r");
+      if (!f) throw std::runtime_error("cannot read " + streamSeedsName);
+      char word[3][64];
+      int got;
+      while ((got = std::fscanf(f, "%63s %63s %63s", word[0], word[1], word[2])) == 3)     // strtof: nan and inf are seeds too
+        seeds.push_back(vec3f(std::strtof(word[0], nullptr), std::strtof(word[1], nullptr), std::strtof(word[2], nullptr)));
+      std::fclose(f);
+      if (got != EOF) throw std::runtime_error(streamSeedsName + ": a seed is three numbers `x y z`");
+      const Renderer::Streamlines L = renderer.streamlines(seeds.data(), seeds.size(), streamChannels, streamStep, streamMaxSteps,
+                                                           streamBoth || !streamBackward, streamBoth || streamBackward, streamNormalize);
+      f = std::fopen(streamName.c_str(), "w");
+      if (!f) throw std::runtime_error("cannot write " + streamName);
+      for (size_t i = 0; i < seeds.size(); i++) {
+        std::fprintf(f, "%u %d %d %llu", L.seedVertex[i], L.reason[2 * i], L.reason[2 * i + 1], (unsigned long long)(L.offset[i + 1] - L.offset[i]));
+        for (uint64_t v = L.offset[i]; v < L.offset[i + 1]; v++) std::fprintf(f, " %.9g %.9g %.9g", L.vertex[v].x, L.vertex[v].y, L.vertex[v].z);
+        std::fprintf(f, "\n");
+      }
+      if (std::fclose(f)) throw std::runtime_error("cannot write " + streamName);
+      std::printf("streamlines seeds %zu channels %d %d %d step %.9g maxSteps %d vertices %zu\n", seeds.size(), streamChannels.x,
+                  streamChannels.y, streamChannels.z, streamStep, streamMaxSteps, L.vertex.size());
+    }
+    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

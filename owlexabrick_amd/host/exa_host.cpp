@@ -600,6 +600,29 @@ ExaHipFieldStats Renderer::fieldStats(int channel, const box3i *box)
   return s;
 }
 
+Renderer::Streamlines Renderer::streamlines(const vec3f *seeds, size_t n, vec3i channels, float step, int maxSteps, bool forward,
+                                            bool backward, bool normalize, bool velocities)
+{
+  static_assert(sizeof(vec3f) == 3 * sizeof(float), "seeds are 3 floats each");
+  const int flags = (forward ? EXA_STREAM_FORWARD : 0) | (backward ? EXA_STREAM_BACKWARD : 0)
+                  | (normalize ? EXA_STREAM_NORMALIZE : 0) | (velocities ? EXA_STREAM_VELOCITIES : 0);
+  const int32_t ch[3] = { channels.x, channels.y, channels.z };
+  uint64_t nv = 0;
+  check(exa_hip_streamlines(handle, reinterpret_cast<const float *>(seeds), n, ch, step, maxSteps, flags, &nv, nullptr), handle);
+  Streamlines L;
+  L.vertex.resize(nv);
+  if (velocities) L.velocity.resize(nv);
+  L.offset.resize(n + 1);
+  L.seedVertex.resize(n);
+  L.reason.resize(2 * n);
+  const int rc = exa_hip_streamlines_read(handle, reinterpret_cast<float *>(L.vertex.data()),
+                                          velocities ? reinterpret_cast<float *>(L.velocity.data()) : nullptr, L.offset.data(),
+                                          L.seedVertex.data(), L.reason.data(), 0, nullptr);
+  if (rc) check(rc, handle);
+  check(exa_hip_streamlines_release(handle), handle);
+  return L;
+}
+
 ExaHipStats Renderer::stats() const
 {
   ExaHipStats s;

@@ -219,6 +219,20 @@ struct Renderer {
                         std::vector<uint64_t> *volume = nullptr, ExaHipFieldStats *stats = nullptr, const box3i *box = nullptr);
   ExaHipFieldStats fieldStats(int channel, const box3i *box = nullptr);
 
+  // field lines of the vector field (channels.x, .y, .z) from `n` seeds in VOXEL space (exa_hip_streamlines; include/exa_hip.h
+  // states the contract): fixed-step RK4 on the device, forward, backward or both (one polyline through the seed), along
+  // v or, with normalize, along v/|v| (`step` is then an arc length in voxels).  Unlike the tracer above it does not depend
+  // on the transfer function, takes whole lines in one call and says why each direction ended.
+  struct Streamlines {
+    std::vector<vec3f> vertex;           // all lines, packed
+    std::vector<vec3f> velocity;         // per vertex the raw v (NaN for a failed seed); empty unless asked for
+    std::vector<uint64_t> offset;        // n + 1: line i = vertex[offset[i] .. offset[i+1])
+    std::vector<uint32_t> seedVertex;    // n: index of the seed within its line (= number of backward vertices)
+    std::vector<int32_t> reason;         // n x 2 EXA_STREAM_END_*: backward, forward
+  };
+  Streamlines streamlines(const vec3f *seeds, size_t n, vec3i channels, float step, int maxSteps, bool forward = true,
+                          bool backward = false, bool normalize = false, bool velocities = false);
+
   ExaHipStats stats() const;
   ExaHipStats renderStats();                 // the same frame through the counting variant of the kernels
   size_t numRegions = 0, numLeafEntries = 0; // what Regions::buildFrom produced (exa/Regions.cpp:308-319 prints them)
