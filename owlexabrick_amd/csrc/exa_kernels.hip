@@ -776,6 +776,114 @@ __device__ __forceinline__ bool samplePoint(Ctx<STATS> &C, float &value, V3 &der
 } // namespace EXA_FORM_NS
 #else
 
+// ------------------------------------------------------------------------
+// The dynamic LDS of a workgroup of kKdBlock lanes, described once: the kernels carve theirs by these offsets and the
+// launchers ask for `total`, so a carve cannot reach past what its launch reserved.
+//   tables        TF tables of EXA_NUM_XF_VALUES float4 each
+//   stack walk    per lane a short stack of 12-byte entries (the references, then {tn, tf}) and behind it the segment queue
+//                 of 12-byte entries (the regions, then {t0, t1}), each array with a stride of kKdBlock
+//   rope walk     no stack: the queue starts where the stack would, in 16-byte entries
+//   pad           extra bytes behind everything (occupancy probe)
+// ------------------------------------------------------------------------
+struct LdsLayout {
+  int stackEntries, queueEntries;
+  size_t stackRef, stackF, queue, queueT, total;      // byte offsets; the tables are at 0
+};
+constexpr LdsLayout ldsLayout(int tables, int stackEntries, int queueEntries, bool rope, size_t pad = 0)
+{
+  const size_t t = size_t(tables) * EXA_NUM_XF_VALUES * sizeof(float4);
+  const size_t q = rope ? t : t + size_t(stackEntries) * kKdBlock * 12;
+  return { stackEntries, queueEntries, t, t + size_t(stackEntries) * kKdBlock * 4, q, q + size_t(queueEntries) * kKdBlock * 4,
+           q + size_t(queueEntries) * kKdBlock * (rope ? 16 : 12) + pad };
+}
+// the kernels on the stack walk outside the march: surfaces pre-pass, AO rays, wide march (which leaves the queue unused)
+constexpr LdsLayout kdLds(int tables) { return ldsLayout(tables, kKdStack, kSegQueue, false); }
+// the march: its two-table variant (MULTI == 1) runs with a shorter stack, see renderFrameKdKernel
+constexpr LdsLayout marchLds(bool multi1, bool rope, int tables, size_t pad = 0)
+{
+  return rope ? ldsLayout(tables, 0, multi1 ? kRopeQueueMulti : kRopeQueue, true, pad)
+              : ldsLayout(tables, multi1 ? kKdStackMulti : kKdStack, kSegQueue, false, pad);
+}
+// renderFrameKernel (256 lanes): traceRegion's stack of kStackDepth references per lane (4 bytes each, no floats, no queue)
+constexpr LdsLayout lbvhLds(int tables)
+{
+  const size_t t = ldsLayout(tables, 0, 0, false).total, end = t + size_t(kStackDepth) * 256 * sizeof(int);
+  return { kStackDepth, 0, t, end, end, end, end };
+}
+// do `waves` workgroups (one wave per SIMD each) fit a CU's 160 KB: the occupancy a kernel's launch bounds ask for is only reached then
+constexpr bool ldsFits(const LdsLayout &L, int waves) { return L.total * size_t(waves) <= 160 * 1024; }
+// this lane's pointers into it (every array has a stride of kKdBlock; queue4: the rope walk's view of the queue)
+struct LdsPtrs { float4 *xf; int *stackRef; float *stackF; int *qRegion; float *qT; float4 *queue4; };
+__device__ __forceinline__ LdsPtrs carveLds(const LdsLayout &L)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  return { reinterpret_cast<float4 *>(smem), reinterpret_cast<int *>(smem + L.stackRef) + threadIdx.x,
+           reinterpret_cast<float *>(smem + L.stackF) + threadIdx.x, reinterpret_cast<int *>(smem + L.queue) + threadIdx.x,
+           reinterpret_cast<float *>(smem + L.queueT) + threadIdx.x, reinterpret_cast<float4 *>(smem + L.queue) + threadIdx.x };
+}
+// the thread's context points at the staged TF tables and at the lane's stack column (an instrumented kernel clears its
+// counters itself, behind its clock stamp)
+template <int STATS>
+__device__ __forceinline__ void initCtx(Ctx<STATS> &C, const RenderArgs &a, const LdsPtrs &lds)
+{
+  C.a = &a;
+  C.xfLds = lds.xf;
+  C.stack = lds.stackRef;
+  C.guardTripped = false;
+}
+// The start of a kernel with such a layout: the workgroup stages the TF tables in LDS, then the context is set up
+template <int STATS>
+__device__ __forceinline__ void kernelPrologue(Ctx<STATS> &C, const RenderArgs &a, const LdsPtrs &lds)
+{
+  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += kKdBlock) lds.xf[i] = a.xf[i];
+  __syncthreads();
+  initCtx(C, a, lds);
+}
+
+// framebuffer slot of pixel (px, py) = place (inX, inY) of tile `tile`: row-major for a whole frame, tile-major inside a shard
+__device__ __forceinline__ size_t slotOf(const RenderArgs &a, int tile, int inX, int inY, int px, int py)
+{ return (a.world == 1) ? size_t(px) + size_t(a.W) * py : size_t(tile / a.world) * kTilePixels + (inY * kTile + inX); }
+
+// ------------------------------------------------------------------------
+// exabrick.cu:1591-1594 and Camera.h:27-44: the pixel's random sequence and its jittered camera ray
+// ------------------------------------------------------------------------
+__device__ __forceinline__ Ray cameraRay(const RenderArgs &a, int px, int py, Lcg &rnd)
+{
+  const ExaHipFrameState &fs = a.fs;
+  rnd.init((uint32_t)(fs.frameID * a.W * a.H) + (uint32_t)px, (uint32_t)py);   // :1591-1592
+  const float sx = float(px) + rnd.next();                                      // :1594
+  const float sy = float(py) + rnd.next();
+  Ray ray;                                                                      // Camera.h:27-44
+  ray.org = mk(fs.cam_pos);
+  ray.dir = normalize((mk(fs.cam_dir00) + sx * mk(fs.cam_dirDu)) + sy * mk(fs.cam_dirDv));
+  ray.tmin = 1e-6f; ray.tmax = 1e8f;
+  return ray;
+}
+// exabrick.cu:1664-1668 (and :1416-1420 of traceIsoRay): the ray in voxel space, its direction normalized; returns dt_scale,
+// the length of a world-space unit along it
+__device__ __forceinline__ float toVoxelSpace(const ExaHipFrameState &fs, Ray &ray)
+{
+  ray.org = xfmPoint(fs, ray.org);
+  ray.dir = xfmVector(fs, ray.dir);
+  const float dt_scale = length(ray.dir);
+  ray.dir = normalize(ray.dir);
+  return dt_scale;
+}
+// exabrick.cu:1657-1673: the primary ray ends at the surface hit, is clipped against the clip box (clipRay :1258-1265) and
+// goes to voxel space, its interval along with it
+__device__ __forceinline__ void clipToVoxelSpace(const ExaHipFrameState &fs, Ray &ray, float surface_t_hit)
+{
+  ray.tmax = surface_t_hit;                                                     // :1657
+  if (fs.clipBox.enabled) {
+    float c0, c1;
+    boxTest(ray, mk(fs.clipBox.lo), mk(fs.clipBox.hi), c0, c1);
+    ray.tmin = c0; ray.tmax = c1;
+  }
+  const float dt_scale = toVoxelSpace(fs, ray);
+  ray.tmin = dt_scale * ray.tmin;                                               // alreadyIntegratedDistance
+  ray.tmax = ray.tmax * dt_scale;
+}
+
 // the sample's colour after gradient shading and its opacity after the correction; actual_dt != 0
 template <bool FAST, int STATS, bool HAVE_RCP = false, bool LEAN = false>
 __device__ __forceinline__ Color4 shadeSample(Ctx<STATS> &C, const Ray &ray, float actual_dt, float cellValue, V3 gradient,
@@ -1278,10 +1386,7 @@ template <int STATS>
 __device__ SurfaceHit traceIsoRay(Ctx<STATS> &C, Ray ray, float off)
 {
   const ExaHipFrameState &fs = C.a->fs;
-  ray.org = xfmPoint(fs, ray.org);
-  ray.dir = xfmVector(fs, ray.dir);
-  const float dt_scale = length(ray.dir);
-  ray.dir = normalize(ray.dir);
+  const float dt_scale = toVoxelSpace(fs, ray);                 // :1416-1420
   float alreadyIntegratedDistance = dt_scale * ray.tmin;
   IsoLast last;
   last.init(fs);
@@ -1349,20 +1454,15 @@ __device__ __forceinline__ void traceSurfaces(Ctx<STATS> &C, const Ray &ray, Sur
 template <bool GRAD, bool ISO, int STATS>
 __global__ __launch_bounds__(256) void renderFrameKernel(const RenderArgs a)
 {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *xfLds = reinterpret_cast<float4 *>(smem);
-  int *stackLds = reinterpret_cast<int *>(smem + size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4));
-  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += 256) xfLds[i] = a.xf[i];
+  const LdsPtrs lds = carveLds(lbvhLds(a.numXfChannels));
+  // (kernelPrologue and, below, clipToVoxelSpace and the surface shading stay written out here and in the pre-pass where a
+  // function moved a shipped variant's registers or spills: profiles/march_dedup_equivalence.txt)
+  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += 256) lds.xf[i] = a.xf[i];
   __syncthreads();
-
   Ctx<STATS> C;
-  C.a = &a;
-  C.xfLds = xfLds;
-  C.stack = stackLds + threadIdx.x;
-  C.guardTripped = false;
+  initCtx(C, a, lds);
   const unsigned long long clockBegin = clock64();                              // :1588
   if (STATS) for (int i = 0; i < ST_COUNT; i++) C.st[i] = 0;
-
   // tile -> pixel: wave w covers the 8x8 block (w&1, w>>1) of the 16x16 tile
   const int tile = a.tileMap[blockIdx.x];
   const int tx = tile % a.tilesX, ty = tile / a.tilesX;
@@ -1375,13 +1475,7 @@ __global__ __launch_bounds__(256) void renderFrameKernel(const RenderArgs a)
     const ExaHipFrameState &fs = a.fs;
     const int frameID = fs.frameID;
     Lcg rnd;
-    rnd.init((uint32_t)(frameID * a.W * a.H) + (uint32_t)px, (uint32_t)py);      // :1591-1592
-    const float sx = float(px) + rnd.next();                                      // :1594
-    const float sy = float(py) + rnd.next();
-    Ray ray;                                                                      // Camera.h:27-44
-    ray.org = mk(fs.cam_pos);
-    ray.dir = normalize((mk(fs.cam_dir00) + sx * mk(fs.cam_dirDu)) + sy * mk(fs.cam_dirDv));
-    ray.tmin = 1e-6f; ray.tmax = 1e8f;
+    Ray ray = cameraRay(a, px, py, rnd);
 
     SurfaceHit surface;
     surface.primID = -1; surface.t_hit = ray.tmax;
@@ -1468,9 +1562,7 @@ __global__ __launch_bounds__(256) void renderFrameKernel(const RenderArgs a)
     float cb = pixelColor.w * pixelColor.z + (1.f - pixelColor.w) * bgColor.z;
     if (fs.clockScale > 0.f) cr = clockHeat(fs.clockScale, clockBegin);          // :1703-1707
 
-    // framebuffer slot: row-major for a whole frame, tile-major inside a shard
-    const size_t slot = (a.world == 1) ? size_t(px) + size_t(a.W) * py
-                                       : size_t(tile / a.world) * kTilePixels + (inY * kTile + inX);
+    const size_t slot = slotOf(a, tile, inX, inY, px, py);
     if (frameID > 0) {                                                            // :1709-1710
       const float4 acc = a.accum[slot];
       cr += acc.x; cg += acc.y; cb += acc.z;
@@ -1497,7 +1589,7 @@ __global__ __launch_bounds__(256) void renderFrameKernel(const RenderArgs a)
 hipError_t launchRender(const RenderArgs &a, int numBlocks, bool grad, bool iso, bool stats, hipStream_t s)
 {
   if (numBlocks <= 0) return hipSuccess;
-  const size_t lds = size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4) + size_t(kStackDepth) * 256 * sizeof(int);
+  const size_t lds = lbvhLds(a.numXfChannels).total;
   const dim3 grid(numBlocks), block(256);
 #define EXA_LAUNCH(G, I, S) hipLaunchKernelGGL((renderFrameKernel<G, I, S>), grid, block, lds, s, a)
   if (stats) {
@@ -1581,6 +1673,64 @@ __device__ __forceinline__ void kdPop(Ctx<STATS> &C, KdWalk &w, const int root, 
   }
 }
 
+// The node stage of a step of the stack walk: one level down from the inner node w.ref.  `shift`: where the node's word holds
+// the two activity bits the walk goes by (2 volume, 4 iso).
+// There is no pop here: a node that leaves nothing to descend into marks the subtree EMPTY and the pop happens at the start of
+// the lane's next call, in front of that call's node stage — the same sequence of subtrees, with one inlined copy of the pop
+// instead of five for the wave's divergent lanes to run
+template <int KS, bool SMALL, int STATS>
+__device__ __forceinline__ void kdNodeStage(Ctx<STATS> &C, KdWalk &w, float *stackF, const Ray &ray, const KdNodeDev *nodes, const int shift)
+{
+  // SMALL: the node array is below 4 GiB — uniform base + 32-bit byte offset, no 64-bit address per lane
+  const int4 n = SMALL ? *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(nodes) + ((uint32_t)w.ref << 4))
+                       : *reinterpret_cast<const int4 *>(nodes + w.ref);
+  C.count(ST_NODES);
+  C.phase(ST_W_NODE);
+  C.probeNode(w.ref);
+  const float split = __int_as_float(n.x);
+  const int axis = n.y & 3;
+  const int bits = (n.y >> shift) & 3;                      // bit0 left active, bit1 right active
+  // select on VALUES (copies first): selecting between struct members by address makes the
+  // compiler index a scratch copy of the ray
+  const float ox = ray.org.x, oy = ray.org.y, oz = ray.org.z, dx = ray.dir.x, dy = ray.dir.y, dz = ray.dir.z;
+  float o = axis == 0 ? ox : oy, d = axis == 0 ? dx : dy;
+  o = axis == 2 ? oz : o;
+  d = axis == 2 ? dz : d;
+  if (d == 0.f) {
+    // parallel to the plane: only the side that strictly contains the origin can be hit
+    // (boxTest turns lo==o / hi==o into a miss, exabrick.cu:201-208 with NaN-ignoring min/max)
+    if (o < split && (bits & 1)) w.ref = n.z;
+    else if (o > split && (bits & 2)) w.ref = n.w;
+    else w.ref = EXA_KD_EMPTY;
+    return;
+  }
+  const float ts = (split - o) / d;                         // same expression as the slab test
+  const bool nearIsLeft = d > 0.f;
+  const int nearRef = nearIsLeft ? n.z : n.w, farRef = nearIsLeft ? n.w : n.z;
+  const bool nearAct = (bits & (nearIsLeft ? 1 : 2)) != 0, farAct = (bits & (nearIsLeft ? 2 : 1)) != 0;
+  if (ts >= w.tf) {                                          // plane behind the interval: near side only
+    w.ref = nearAct ? nearRef : EXA_KD_EMPTY;
+  } else if (ts <= w.tn) {                                   // plane before the interval: far side only
+    w.ref = farAct ? farRef : EXA_KD_EMPTY;
+  } else if (nearAct) {
+    if (farAct) {                                            // push far [ts,tf], go near [tn,ts]
+      const int head = w.pk.get(PK_SHEAD), count = w.pk.get(PK_SCOUNT);
+      C.stack[head * kKdBlock] = farRef;
+      stackF[(2 * head) * kKdBlock] = ts;
+      stackF[(2 * head + 1) * kKdBlock] = w.tf;
+      w.pk.template incWrap<KS>(PK_SHEAD);
+      if (count == KS) w.pk.setBit(PK_DROPPED); else w.pk.inc(PK_SCOUNT);
+    }
+    w.ref = nearRef;
+    w.tf = ts;
+  } else if (farAct) {
+    w.ref = farRef;
+    w.tn = ts;
+  } else {
+    w.ref = EXA_KD_EMPTY;
+  }
+}
+
 // Per-lane queue of accepted segments (region, t0, t1) in LDS.  Which segments a ray
 // gets depends only on the walk (each accepted leaf advances ray.tmin to t1*1.0000001f,
 // exabrick.cu:1698), not on the march, so a lane may walk ahead of its march.  The walk
@@ -1639,62 +1789,10 @@ __device__ __forceinline__ void kdStep(Ctx<STATS> &C, KdWalk &w, float &walkTmin
     if (!(ISOWALK && hit && t1 < w.tf)) w.ref = EXA_KD_EMPTY;
   }
   if (w.ref == EXA_KD_EMPTY || (w.ref != EXA_KD_DONE && !(w.tf > walkTmin))) kdPop<STATS, KS, SMALL>(C, w, root, stackF, nodes, ray);
-  // This is the only pop: a node that leaves nothing to descend into marks the subtree EMPTY and
-  // the pop happens here at the start of the lane's next call, in front of that call's node stage — the same
-  // sequence of subtrees, with one inlined copy of the pop instead of five for the wave's divergent lanes to run
-#define EXA_KD_POP_LATER() (w.ref = EXA_KD_EMPTY)
   // the popped subtree gets its own look at tmin / tmax in the next call
   if (w.ref < 0 || !(w.tf > walkTmin) || (ISOWALK && !(w.tn < walkTmax))) return;
-  // SMALL: the node array is below 4 GiB — uniform base + 32-bit byte offset, no 64-bit address per lane
-  const int4 n = SMALL ? *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(nodes) + ((uint32_t)w.ref << 4))
-                       : *reinterpret_cast<const int4 *>(nodes + w.ref);
-  C.count(ST_NODES);
-  C.phase(ST_W_NODE);
-  C.probeNode(w.ref);
-  const float split = __int_as_float(n.x);
-  const int axis = n.y & 3;
-  const int bits = (n.y >> (2 + 2 * which)) & 3;            // bit0 left active, bit1 right active
-  // select on VALUES (copies first): selecting between struct members by address makes the
-  // compiler index a scratch copy of the ray
-  const float ox = ray.org.x, oy = ray.org.y, oz = ray.org.z, dx = ray.dir.x, dy = ray.dir.y, dz = ray.dir.z;
-  float o = axis == 0 ? ox : oy, d = axis == 0 ? dx : dy;
-  o = axis == 2 ? oz : o;
-  d = axis == 2 ? dz : d;
-  if (d == 0.f) {
-    // parallel to the plane: only the side that strictly contains the origin can be hit
-    // (boxTest turns lo==o / hi==o into a miss, exabrick.cu:201-208 with NaN-ignoring min/max)
-    if (o < split && (bits & 1)) w.ref = n.z;
-    else if (o > split && (bits & 2)) w.ref = n.w;
-    else EXA_KD_POP_LATER();
-    return;
-  }
-  const float ts = (split - o) / d;                         // same expression as the slab test
-  const bool nearIsLeft = d > 0.f;
-  const int nearRef = nearIsLeft ? n.z : n.w, farRef = nearIsLeft ? n.w : n.z;
-  const bool nearAct = (bits & (nearIsLeft ? 1 : 2)) != 0, farAct = (bits & (nearIsLeft ? 2 : 1)) != 0;
-  if (ts >= w.tf) {                                          // plane behind the interval: near side only
-    if (nearAct) w.ref = nearRef; else EXA_KD_POP_LATER();
-  } else if (ts <= w.tn) {                                   // plane before the interval: far side only
-    if (farAct) w.ref = farRef; else EXA_KD_POP_LATER();
-  } else if (nearAct) {
-    if (farAct) {                                            // push far [ts,tf], go near [tn,ts]
-      const int head = w.pk.get(PK_SHEAD), count = w.pk.get(PK_SCOUNT);
-      C.stack[head * kKdBlock] = farRef;
-      stackF[(2 * head) * kKdBlock] = ts;
-      stackF[(2 * head + 1) * kKdBlock] = w.tf;
-      w.pk.template incWrap<KS>(PK_SHEAD);
-      if (count == KS) w.pk.setBit(PK_DROPPED); else w.pk.inc(PK_SCOUNT);
-    }
-    w.ref = nearRef;
-    w.tf = ts;
-  } else if (farAct) {
-    w.ref = farRef;
-    w.tn = ts;
-  } else {
-    EXA_KD_POP_LATER();
-  }
+  kdNodeStage<KS, SMALL, STATS>(C, w, stackF, ray, nodes, 2 + 2 * which);
 }
-#undef EXA_KD_POP_LATER
 
 // ------------------------------------------------------------------------
 // Rope walk: the same ordered sequence of leaves without a stack.  Every leaf of the region kd-tree (and every empty
@@ -1847,10 +1945,7 @@ __device__ SurfaceHit traceIsoRayKd(Ctx<STATS> &C, Ray ray, float off, float *st
 {
   const RenderArgs &a = *C.a;
   const ExaHipFrameState &fs = a.fs;
-  ray.org = xfmPoint(fs, ray.org);
-  ray.dir = xfmVector(fs, ray.dir);
-  const float dt_scale = length(ray.dir);
-  ray.dir = normalize(ray.dir);
+  const float dt_scale = toVoxelSpace(fs, ray);                 // :1416-1420
   float walkTmin = dt_scale * ray.tmin;
   float walkTmax = ray.tmax * dt_scale;                      // tmax of the first trace (:1434)
   IsoLast last;
@@ -1972,28 +2067,18 @@ __device__ __forceinline__ void traceSurfacesKd(Ctx<STATS> &C, const Ray &ray, S
 template <int STATS, bool ISO_ONLY, bool AO_DEFER>
 __global__ __launch_bounds__(kKdBlock, (ISO_ONLY ? EXA_PREPASS_ISO_WAVES : EXA_PREPASS_WAVES)) void surfacePrepassKdKernel(const RenderArgs a)
 {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *xfLds = reinterpret_cast<float4 *>(smem);
-  unsigned char *sp0 = smem + size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4);
-  int *stackRef = reinterpret_cast<int *>(sp0);
-  float *stackF = reinterpret_cast<float *>(sp0 + size_t(kKdStackEntries) * kKdBlock * 4) + threadIdx.x;
-  int *qRegion = reinterpret_cast<int *>(sp0 + size_t(kKdStack) * kKdBlock * 12) + threadIdx.x;
-  float *qT = reinterpret_cast<float *>(sp0 + size_t(kKdStack) * kKdBlock * 12 + size_t(kSegQueue) * kKdBlock * 4) + threadIdx.x;
-  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += kKdBlock) xfLds[i] = a.xf[i];
-  __syncthreads();
-
+  static_assert(ldsFits(kdLds(1), ISO_ONLY ? EXA_PREPASS_ISO_WAVES : EXA_PREPASS_WAVES), "LDS per workgroup x waves per SIMD exceeds the CU's 160 KB");
+  const LdsPtrs lds = carveLds(kdLds(a.numXfChannels));
   Ctx<STATS> C;
-  C.a = &a;
-  C.xfLds = xfLds;
-  C.stack = stackRef + threadIdx.x;
-  C.guardTripped = false;
+  kernelPrologue(C, a, lds);
+  float *stackF = lds.stackF, *qT = lds.qT;
+  int *qRegion = lds.qRegion;
   // The counting variant keeps the literal sampler: for the NaN positions the iso march produces where a field equals the
   // iso value over a whole step (tavg = 0/0, exabrick.cu:1047-1053; the reference's NaN guard is at :1088) the two
   // forms clamp the cell index differently (int(NaN) = 0 vs max(NaN, -1) = -1), which changes nothing in the sums
   // (NaN either way) but counts other cells as "read".
   C.fastSampler = a.fastSampler != 0 && STATS != 1;
   if (STATS) for (int i = 0; i < ST_COUNT; i++) C.st[i] = 0;
-
   // a workgroup is kKdBlock/64 waves; each wave renders one 8x8 block of a 16x16 tile
   const int wavesPerBlock = kKdBlock / 64;
   const int gwave = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6);
@@ -2006,15 +2091,8 @@ __global__ __launch_bounds__(kKdBlock, (ISO_ONLY ? EXA_PREPASS_ISO_WAVES : EXA_P
 
   if (inside) {
     const ExaHipFrameState &fs = a.fs;
-    const int frameID = fs.frameID;
     Lcg rnd;
-    rnd.init((uint32_t)(frameID * a.W * a.H) + (uint32_t)px, (uint32_t)py);      // :1591-1592
-    const float sx = float(px) + rnd.next();
-    const float sy = float(py) + rnd.next();
-    Ray ray;
-    ray.org = mk(fs.cam_pos);
-    ray.dir = normalize((mk(fs.cam_dir00) + sx * mk(fs.cam_dirDu)) + sy * mk(fs.cam_dirDv));
-    ray.tmin = 1e-6f; ray.tmax = 1e8f;
+    const Ray ray = cameraRay(a, px, py, rnd);
     // ---- surfaces first: implicit iso-surface hit, AO rays, background colour (:1601-1652) ----
     V3 bgColor = mk(0.f, 0.f, 0.f);
     float surface_t_hit = ray.tmax;
@@ -2070,8 +2148,7 @@ __global__ __launch_bounds__(kKdBlock, (ISO_ONLY ? EXA_PREPASS_ISO_WAVES : EXA_P
         }
       }
     }
-    const size_t slot = (a.world == 1) ? size_t(px) + size_t(a.W) * py
-                                       : size_t(tile / a.world) * kTilePixels + (inY * kTile + inX);
+    const size_t slot = slotOf(a, tile, inX, inY, px, py);
     a.surf[slot] = make_float4(bgColor.x, bgColor.y, bgColor.z, surface_t_hit);
     a.surfRnd[slot] = rnd.state;
     if (AO_DEFER) {
@@ -2216,20 +2293,12 @@ __global__ __launch_bounds__(256) void aoFinalizeKernel(const RenderArgs a)
 template <bool ISO_ONLY, bool SORTED>
 __global__ __launch_bounds__(kKdBlock, (ISO_ONLY ? EXA_AO_ISO_WAVES : EXA_PREPASS_WAVES)) void aoRaysKdKernel(const RenderArgs a)
 {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *xfLds = reinterpret_cast<float4 *>(smem);
-  unsigned char *sp0 = smem + size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4);
-  int *stackRef = reinterpret_cast<int *>(sp0);
-  float *stackF = reinterpret_cast<float *>(sp0 + size_t(kKdStackEntries) * kKdBlock * 4) + threadIdx.x;
-  int *qRegion = reinterpret_cast<int *>(sp0 + size_t(kKdStack) * kKdBlock * 12) + threadIdx.x;
-  float *qT = reinterpret_cast<float *>(sp0 + size_t(kKdStack) * kKdBlock * 12 + size_t(kSegQueue) * kKdBlock * 4) + threadIdx.x;
-  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += kKdBlock) xfLds[i] = a.xf[i];
-  __syncthreads();
+  static_assert(ldsFits(kdLds(1), ISO_ONLY ? EXA_AO_ISO_WAVES : EXA_PREPASS_WAVES), "LDS per workgroup x waves per SIMD exceeds the CU's 160 KB");
+  const LdsPtrs lds = carveLds(kdLds(a.numXfChannels));
   Ctx<0> C;
-  C.a = &a;
-  C.xfLds = xfLds;
-  C.stack = stackRef + threadIdx.x;
-  C.guardTripped = false;
+  kernelPrologue(C, a, lds);
+  float *stackF = lds.stackF, *qT = lds.qT;
+  int *qRegion = lds.qRegion;
   C.fastSampler = a.fastSampler != 0;
   const ExaHipFrameState &fs = a.fs;
   const unsigned numRays = 2u * a.aoCount[0];
@@ -2302,32 +2371,24 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
   // 25 KB instead of 28 KB of LDS and a sixth workgroup fits a CU (C3: 30.8 -> 29.4 ms; a shorter stack alone costs ~1 %:
   // a dropped entry is re-found by a restart from the root).  With three tables the sixth workgroup does not fit either
   // way and the 80-VGPR build only costs (3 channels on C4: +2 %): MULTI == 2 keeps 4 entries and 5 waves per SIMD.
-  constexpr int KSB = MULTI == 1 ? kKdStackMulti : kKdStack;                      // LDS: 12 bytes x KSB per lane for the stack
-  constexpr int KS = MULTI == 1 ? kKdStackMultiEntries : kKdStackEntries;         // entries the walk keeps there
+  constexpr int KS = marchLds(MULTI == 1, false, 0).stackEntries;                 // entries the stack walk keeps per lane
   // entries of the lane's segment queue: the rope walk keeps no stack and gives the queue that LDS as well
-  constexpr int QN = ROPE ? (MULTI == 1 ? kRopeQueueMulti : kRopeQueue) : kSegQueue;
-  // the occupancy a variant is compiled for is only reached if that many workgroups' LDS fit a CU (160 KB): one TF table (one
-  // primary channel) + the lane's queue, and for the stack walk its stack
-  static_assert(MULTI != 0 || (size_t(EXA_NUM_XF_VALUES) * sizeof(float4) + size_t(kKdBlock) * (ROPE ? QN * 16 : (KSB + QN) * 12))
-                                  * marchWaves(MULTI, STATS, SMALL, NCH, ROPE) <= 160 * 1024,
+  constexpr int QN = marchLds(MULTI == 1, ROPE, 0).queueEntries;
+  // the occupancy a variant is compiled for is only reached if that many workgroups' LDS fit a CU (160 KB): the fewest TF
+  // tables the variant is launched with (launchRenderKdT: one per primary channel; MULTI == 1: exactly two) + the lane's
+  // queue, and for the stack walk its stack
+  static_assert(ldsFits(marchLds(MULTI == 1, ROPE, NCH ? NCH : (MULTI ? 2 : 1)), marchWaves(MULTI, STATS, SMALL, NCH, ROPE)),
                 "LDS per workgroup x waves per SIMD exceeds the CU's 160 KB: shorten the queue or lower the occupancy");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *xfLds = reinterpret_cast<float4 *>(smem);
-  unsigned char *sp0 = smem + size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4);
-  int *stackRef = reinterpret_cast<int *>(sp0);
-  float *stackF = reinterpret_cast<float *>(sp0 + size_t(KS) * kKdBlock * 4) + threadIdx.x;
-  unsigned char *q0 = ROPE ? sp0 : sp0 + size_t(KSB) * kKdBlock * 12;
-  int *qRegion = reinterpret_cast<int *>(q0) + threadIdx.x;
-  float *qT = reinterpret_cast<float *>(q0 + size_t(QN) * kKdBlock * 4) + threadIdx.x;
-  float4 *queue4 = reinterpret_cast<float4 *>(sp0) + threadIdx.x;     // rope walk: 16-byte entries, one LDS access each
-  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += kKdBlock) xfLds[i] = a.xf[i];
+  const LdsPtrs lds = carveLds(marchLds(MULTI == 1, ROPE, a.numXfChannels));
+  float4 *queue4 = lds.queue4;                                        // rope walk: 16-byte entries, one LDS access each
+  float *stackF = lds.stackF, *qT = lds.qT;
+  int *qRegion = lds.qRegion;
+  // (kernelPrologue, written out: at 72 / 80 registers this kernel's allocation moves with where the compiler lays out the
+  // staging loop, and its variants are held to their registers, tests/test_kernel_resources.py)
+  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += kKdBlock) lds.xf[i] = a.xf[i];
   __syncthreads();
-
   Ctx<STATS> C;
-  C.a = &a;
-  C.xfLds = xfLds;
-  C.stack = stackRef + threadIdx.x;
-  C.guardTripped = false;
+  initCtx(C, a, lds);
   const unsigned long long clockBegin = clock64();                              // :1588
   if (STATS) for (int i = 0; i < ST_COUNT; i++) C.st[i] = 0;
   __shared__ unsigned long long lapMarks[STATS == 2 ? 8 * (kKdBlock / 64) : 1];
@@ -2339,7 +2400,6 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
     }
   }
 
-  // a workgroup is kKdBlock/64 waves; each wave renders one 8x8 block of a 16x16 tile
   const int wavesPerBlock = kKdBlock / 64;
   const int gwave = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6);
   const int tile = a.tileMap[gwave >> 2];
@@ -2355,39 +2415,20 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
     const ExaHipFrameState &fs = a.fs;
     const int frameID = fs.frameID;
     Lcg rnd;
-    rnd.init((uint32_t)(frameID * a.W * a.H) + (uint32_t)px, (uint32_t)py);      // :1591-1592
-    const float sx = float(px) + rnd.next();
-    const float sy = float(py) + rnd.next();
-    Ray ray;
-    ray.org = mk(fs.cam_pos);
-    ray.dir = normalize((mk(fs.cam_dir00) + sx * mk(fs.cam_dirDu)) + sy * mk(fs.cam_dirDv));
-    ray.tmin = 1e-6f; ray.tmax = 1e8f;
+    Ray ray = cameraRay(a, px, py, rnd);
     // ---- surfaces: results of the pre-pass launch (the background colour is fetched after the march) ----
     float surface_t_hit = ray.tmax;
     if (SURF) {
-      const size_t slot0 = (a.world == 1) ? size_t(px) + size_t(a.W) * py
-                                          : size_t(tile / a.world) * kTilePixels + (inY * kTile + inX);
+      const size_t slot0 = slotOf(a, tile, inX, inY, px, py);
       surface_t_hit = a.surf[slot0].w;
       rnd.state = a.surfRnd[slot0];
     }
     const float interleavedSamplingOffset = rnd.next();                           // :1655
-    ray.tmax = surface_t_hit;                                                     // :1657-1659
-    if (fs.clipBox.enabled) {
-      float c0, c1;
-      boxTest(ray, mk(fs.clipBox.lo), mk(fs.clipBox.hi), c0, c1);
-      ray.tmin = c0; ray.tmax = c1;
-    }
-    surface_t_hit = ray.tmax;
-    ray.org = xfmPoint(fs, ray.org);                                              // :1664-1668
+    clipToVoxelSpace(fs, ray, surface_t_hit);
     // the ray origin is the camera position in voxel space: the same value in every lane, so it lives in scalar registers
     ray.org.x = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ray.org.x)));
     ray.org.y = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ray.org.y)));
     ray.org.z = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ray.org.z)));
-    ray.dir = xfmVector(fs, ray.dir);
-    const float dt_scale = length(ray.dir);
-    ray.dir = normalize(ray.dir);
-    ray.tmin = dt_scale * ray.tmin;                                               // alreadyIntegratedDistance
-    ray.tmax = surface_t_hit * dt_scale;
 
     Color4 pixelColor; pixelColor.x = pixelColor.y = pixelColor.z = pixelColor.w = 0.f;
     const int numChannels = a.p.numPrimaryChannels;
@@ -2696,66 +2737,18 @@ __device__ __forceinline__ void kdCollectStep(Ctx<0> &C, KdWalk &w, const float 
     w.ref = EXA_KD_EMPTY;
   }
   if (w.ref == EXA_KD_EMPTY || (w.ref != EXA_KD_DONE && !(w.tf > winLo))) kdPop(C, w, root, stackF, nodes, ray);
-#define EXA_KD_POP_LATER() (w.ref = EXA_KD_EMPTY)
   if (w.ref < 0 || !(w.tf > winLo) || !(w.tn < winHi)) return;
-  const int4 n = *reinterpret_cast<const int4 *>(nodes + w.ref);
-  const float split = __int_as_float(n.x);
-  const int axis = n.y & 3;
-  const int bits = (n.y >> 2) & 3;                            // volume activity: bit0 left, bit1 right
-  const float ox = ray.org.x, oy = ray.org.y, oz = ray.org.z, dx = ray.dir.x, dy = ray.dir.y, dz = ray.dir.z;
-  float o = axis == 0 ? ox : oy, d = axis == 0 ? dx : dy;
-  o = axis == 2 ? oz : o;
-  d = axis == 2 ? dz : d;
-  if (d == 0.f) {
-    if (o < split && (bits & 1)) w.ref = n.z;
-    else if (o > split && (bits & 2)) w.ref = n.w;
-    else EXA_KD_POP_LATER();
-    return;
-  }
-  const float ts = (split - o) / d;
-  const bool nearIsLeft = d > 0.f;
-  const int nearRef = nearIsLeft ? n.z : n.w, farRef = nearIsLeft ? n.w : n.z;
-  const bool nearAct = (bits & (nearIsLeft ? 1 : 2)) != 0, farAct = (bits & (nearIsLeft ? 2 : 1)) != 0;
-  if (ts >= w.tf) {
-    if (nearAct) w.ref = nearRef; else EXA_KD_POP_LATER();
-  } else if (ts <= w.tn) {
-    if (farAct) w.ref = farRef; else EXA_KD_POP_LATER();
-  } else if (nearAct) {
-    if (farAct) {
-      const int head = w.pk.get(PK_SHEAD), count_ = w.pk.get(PK_SCOUNT);
-      C.stack[head * kKdBlock] = farRef;
-      stackF[(2 * head) * kKdBlock] = ts;
-      stackF[(2 * head + 1) * kKdBlock] = w.tf;
-      w.pk.template incWrap<kKdStackEntries>(PK_SHEAD);
-      if (count_ == kKdStackEntries) w.pk.setBit(PK_DROPPED); else w.pk.inc(PK_SCOUNT);
-    }
-    w.ref = nearRef;
-    w.tf = ts;
-  } else if (farAct) {
-    w.ref = farRef;
-    w.tn = ts;
-  } else {
-    EXA_KD_POP_LATER();
-  }
+  kdNodeStage<kKdStackEntries, false, 0>(C, w, stackF, ray, nodes, 2);   // volume activity
 }
-#undef EXA_KD_POP_LATER
 
 template <bool GRAD, bool FAST, bool SURF, int L, bool SMALL>
 __global__ __launch_bounds__(kKdBlock, 4) void renderFrameKdWideKernel(const RenderArgs a)
 {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *xfLds = reinterpret_cast<float4 *>(smem);
-  unsigned char *sp0 = smem + size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4);
-  int *stackRef = reinterpret_cast<int *>(sp0);
-  float *stackF = reinterpret_cast<float *>(sp0 + size_t(kKdStackEntries) * kKdBlock * 4) + threadIdx.x;
-  for (int i = threadIdx.x; i < a.numXfChannels * EXA_NUM_XF_VALUES; i += kKdBlock) xfLds[i] = a.xf[i];
-  __syncthreads();
-
+  static_assert(ldsFits(kdLds(1), 4), "LDS per workgroup x waves per SIMD exceeds the CU's 160 KB");   // one primary channel
+  const LdsPtrs lds = carveLds(kdLds(a.numXfChannels));
+  float *stackF = lds.stackF;
   Ctx<false> C;
-  C.a = &a;
-  C.xfLds = xfLds;
-  C.stack = stackRef + threadIdx.x;
-  C.guardTripped = false;
+  kernelPrologue(C, a, lds);
   const unsigned long long clockBegin = clock64();                              // :1588
 
   // these waves are the frame's critical path: let them issue ahead of the one-lane march they share SIMDs with
@@ -2776,34 +2769,15 @@ __global__ __launch_bounds__(kKdBlock, 4) void renderFrameKdWideKernel(const Ren
     const ExaHipFrameState &fs = a.fs;
     const int frameID = fs.frameID;
     Lcg rnd;
-    rnd.init((uint32_t)(frameID * a.W * a.H) + (uint32_t)px, (uint32_t)py);      // :1591-1592
-    const float sx = float(px) + rnd.next();
-    const float sy = float(py) + rnd.next();
-    Ray ray;
-    ray.org = mk(fs.cam_pos);
-    ray.dir = normalize((mk(fs.cam_dir00) + sx * mk(fs.cam_dirDu)) + sy * mk(fs.cam_dirDv));
-    ray.tmin = 1e-6f; ray.tmax = 1e8f;
-    const size_t slot = (a.world == 1) ? size_t(px) + size_t(a.W) * py
-                                       : size_t(tile / a.world) * kTilePixels + (inY * kTile + inX);
+    Ray ray = cameraRay(a, px, py, rnd);
+    const size_t slot = slotOf(a, tile, inX, inY, px, py);
     float surface_t_hit = ray.tmax;
     if (SURF) {
       surface_t_hit = a.surf[slot].w;
       rnd.state = a.surfRnd[slot];
     }
     const float interleavedSamplingOffset = rnd.next();                           // :1655
-    ray.tmax = surface_t_hit;                                                     // :1657-1659
-    if (fs.clipBox.enabled) {
-      float c0, c1;
-      boxTest(ray, mk(fs.clipBox.lo), mk(fs.clipBox.hi), c0, c1);
-      ray.tmin = c0; ray.tmax = c1;
-    }
-    surface_t_hit = ray.tmax;
-    ray.org = xfmPoint(fs, ray.org);                                              // :1664-1668
-    ray.dir = xfmVector(fs, ray.dir);
-    const float dt_scale = length(ray.dir);
-    ray.dir = normalize(ray.dir);
-    ray.tmin = dt_scale * ray.tmin;
-    ray.tmax = surface_t_hit * dt_scale;
+    clipToVoxelSpace(fs, ray, surface_t_hit);
 
     Color4 pixelColor; pixelColor.x = pixelColor.y = pixelColor.z = pixelColor.w = 0.f;
 
@@ -3029,7 +3003,7 @@ __global__ __launch_bounds__(256) void compositeKdKernel(const RenderArgs a)
   const int inX = threadIdx.x & 15, inY = threadIdx.x >> 4;
   const int px = tx * kTile + inX, py = ty * kTile + inY;
   if (!(px < a.W && py < a.H) || !(a.debugPixel < 0 || a.debugPixel == px + a.W * py)) return;
-  const size_t slot = (a.world == 1) ? size_t(px) + size_t(a.W) * py : size_t(tile / a.world) * kTilePixels + (inY * kTile + inX);
+  const size_t slot = slotOf(a, tile, inX, inY, px, py);
   const size_t colorSlot = a.colorRowMajor ? size_t(px) + size_t(a.W) * py : slot;
   const float4 pixelColor = a.pixOut[slot];
   const float4 bgColor = a.surf[slot];
@@ -3059,7 +3033,7 @@ hipError_t launchRenderKdWide(const RenderArgs &a, int numTiles, int lanesPerRay
 #if EXA_EMPTY_CELLS
   return hipErrorNotSupported;       // scenes with empty cells march one lane per ray (the module never asks for more)
 #else
-  const size_t lds = size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4) + size_t(kKdStack + kSegQueue) * kKdBlock * 12;
+  const size_t lds = kdLds(a.numXfChannels).total;
   const dim3 grid(numTiles * lanesPerRay), block(kKdBlock);
   const bool small = a.mul24 && a.addr32;                   // 24-bit address multiplies and 32-bit byte offsets are valid
 #define EXA_W4(G, F, S, L) do { if (small) hipLaunchKernelGGL((renderFrameKdWideKernel<G, F, S, L, true>), grid, block, lds, s, a); \
@@ -3077,17 +3051,24 @@ hipError_t launchRenderKdWide(const RenderArgs &a, int numTiles, int lanesPerRay
 #endif
 }
 
+// the frame has no triangle meshes, contour planes or streamlines: the pre-pass and the AO rays take their ISO_ONLY variants
+// (both launchers must decide alike: the variant sets the wave budget the AO grid is sized by)
+static bool isoOnly(const RenderArgs &a)
+{
+  bool only = a.numTris == 0 && a.numStreamPrims == 0;
+  for (int i = 0; i < EXA_MAX_CONTOUR_PLANES; i++) only = only && !a.fs.contour[i].enabled;
+  return only;
+}
+
 hipError_t launchSurfacePrepassKd(const RenderArgs &a, int numBlocks, bool stats, hipStream_t s)
 {
   if (numBlocks <= 0) return hipSuccess;
-  const size_t lds = size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4) + size_t(kKdStack + kSegQueue) * kKdBlock * 12;
+  const size_t lds = kdLds(a.numXfChannels).total;
   const dim3 grid(numBlocks * (256 / kKdBlock)), block(kKdBlock);
-  bool isoOnly = a.numTris == 0 && a.numStreamPrims == 0;
-  for (int i = 0; i < EXA_MAX_CONTOUR_PLANES; i++) isoOnly = isoOnly && !a.fs.contour[i].enabled;
   // the shipped variants hand their AO rays to aoRaysKdKernel (a.aoRecs / a.aoCount, cleared by the caller)
   const bool defer = !stats && a.aoRecs && a.aoCount;
   if (stats)        hipLaunchKernelGGL((surfacePrepassKdKernel<1, false, false>), grid, block, lds, s, a);
-  else if (isoOnly) { if (defer) hipLaunchKernelGGL((surfacePrepassKdKernel<0, true, true>), grid, block, lds, s, a);
+  else if (isoOnly(a)) { if (defer) hipLaunchKernelGGL((surfacePrepassKdKernel<0, true, true>), grid, block, lds, s, a);
                       else       hipLaunchKernelGGL((surfacePrepassKdKernel<0, true, false>), grid, block, lds, s, a); }
   else              { if (defer) hipLaunchKernelGGL((surfacePrepassKdKernel<0, false, true>), grid, block, lds, s, a);
                       else       hipLaunchKernelGGL((surfacePrepassKdKernel<0, false, false>), grid, block, lds, s, a); }
@@ -3099,13 +3080,12 @@ hipError_t launchSurfacePrepassKd(const RenderArgs &a, int numBlocks, bool stats
 hipError_t launchAoRaysKd(const RenderArgs &a, int numBlocks, hipStream_t s)
 {
   if (numBlocks <= 0) return hipSuccess;
-  const size_t lds = size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4) + size_t(kKdStack + kSegQueue) * kKdBlock * 12;
+  const size_t lds = kdLds(a.numXfChannels).total;
   const dim3 block(kKdBlock);
-  bool isoOnly = a.numTris == 0 && a.numStreamPrims == 0;
-  for (int i = 0; i < EXA_MAX_CONTOUR_PLANES; i++) isoOnly = isoOnly && !a.fs.contour[i].enabled;
+  const bool iso = isoOnly(a);
   const bool defer = a.aoRecs && a.aoCount;
   if (defer && a.fs.ao.enabled) {
-    const int maxBlocks = 256 * (isoOnly ? EXA_AO_ISO_WAVES : EXA_PREPASS_WAVES);      // what the device holds at once (workgroups per CU = waves per SIMD)
+    const int maxBlocks = 256 * (iso ? EXA_AO_ISO_WAVES : EXA_PREPASS_WAVES);      // what the device holds at once (workgroups per CU = waves per SIMD)
     const long long upper = ((long long)numBlocks * kTilePixels * 2 + kKdBlock - 1) / kKdBlock;
     const dim3 g2((unsigned)(upper < maxBlocks ? upper : maxBlocks));
     if (a.aoKeys) {
@@ -3115,11 +3095,11 @@ hipError_t launchAoRaysKd(const RenderArgs &a, int numBlocks, hipStream_t s)
       hipLaunchKernelGGL(aoKeyKernel, gs, b256, 0, s, a);
       hipLaunchKernelGGL(aoScanKernel, dim3(1), dim3(1024), 0, s, a.aoHist, a.aoBins);
       hipLaunchKernelGGL(aoScatterKernel, gs, b256, 0, s, a);
-      if (isoOnly) hipLaunchKernelGGL((aoRaysKdKernel<true, true>), g2, block, lds, s, a);
+      if (iso) hipLaunchKernelGGL((aoRaysKdKernel<true, true>), g2, block, lds, s, a);
       else         hipLaunchKernelGGL((aoRaysKdKernel<false, true>), g2, block, lds, s, a);
       hipLaunchKernelGGL(aoFinalizeKernel, gs, b256, 0, s, a);
     } else {
-      if (isoOnly) hipLaunchKernelGGL((aoRaysKdKernel<true, false>), g2, block, lds, s, a);
+      if (iso) hipLaunchKernelGGL((aoRaysKdKernel<true, false>), g2, block, lds, s, a);
       else         hipLaunchKernelGGL((aoRaysKdKernel<false, false>), g2, block, lds, s, a);
     }
   }
@@ -3139,26 +3119,25 @@ static hipError_t launchRenderKdT(const RenderArgs &a, int numBlocks, bool grad,
   // 0: one primary channel; 1: several with at most two TF tables (3-entry stack, 6 workgroups per CU); 2: several, more tables.
   // The instrumented variants exist for 0 and 2 only.
   const int mode = a.p.numPrimaryChannels > 1 ? ((a.numXfChannels <= 2 && !stats) ? 1 : 2) : 0;
-  // interleaved march: the module has built float[cell][numPrimaryChannels] (a.cellsIl); shipped kernel only
-  const int nch = (!EXA_EMPTY_CELLS && a.cellsIl && !stats && a.p.numPrimaryChannels >= 2 && a.p.numPrimaryChannels <= 4) ? a.p.numPrimaryChannels : 0;
-  // per lane: stack + queue entries of 12 bytes (stack walk), or the queue alone in 16-byte entries (rope walk)
-  const size_t perLane = ROPE ? size_t(mode == 1 && !nch ? kRopeQueueMulti : kRopeQueue) * 16
-                              : size_t((mode == 1 && !nch ? kKdStackMulti : kKdStack) + kSegQueue) * 12;
-  const size_t lds = size_t(a.numXfChannels) * EXA_NUM_XF_VALUES * sizeof(float4) + perLane * kKdBlock + EXA_LDS_PAD;
   const dim3 grid(numBlocks * (256 / kKdBlock)), block(kKdBlock);
   // the instrumented variants keep the general address arithmetic (fewer instantiations)
   // (the 32-bit rope variants also take for granted that the region records pack: see renderFrameKdKernel, PACKED_CT)
   const bool small = a.mul24 && a.addr32 && (!ROPE || (a.ropeAddr32 && a.leafBeginBits));
-#define EXA_LAUNCH(G, F, M, I, S, A) hipLaunchKernelGGL((renderFrameKdKernel<G, F, M, I, S, A, 0, ROPE>), grid, block, lds, s, a)
+  // the LDS a launch asks for is the layout of the MULTI it instantiates
+#define EXA_LAUNCH(G, F, M, I, S, A) hipLaunchKernelGGL((renderFrameKdKernel<G, F, M, I, S, A, 0, ROPE>), grid, block, \
+                                                        marchLds((M) == 1, ROPE, a.numXfChannels, EXA_LDS_PAD).total, s, a)
 #define EXA_PICK2(G, F, M, I) do { if (stats == 1) EXA_LAUNCH(G, F, (M ? 2 : 0), I, 1, false); else if (stats == 2) EXA_LAUNCH(G, F, (M ? 2 : 0), I, 2, false); \
                                    else if (small) EXA_LAUNCH(G, F, M, I, 0, true); else EXA_LAUNCH(G, F, M, I, 0, false); } while (0)
 #define EXA_PICK(G, F, M) do { if (surf) EXA_PICK2(G, F, M, true); else EXA_PICK2(G, F, M, false); } while (0)
 #define EXA_PICKM(G, F) do { if (mode == 0) EXA_PICK(G, F, 0); else if (mode == 1) EXA_PICK(G, F, 1); else EXA_PICK(G, F, 2); } while (0)
 #if !EXA_EMPTY_CELLS
+  // interleaved march: the module has built float[cell][numPrimaryChannels] (a.cellsIl); shipped kernel only
+  const int nch = (a.cellsIl && !stats && a.p.numPrimaryChannels >= 2 && a.p.numPrimaryChannels <= 4) ? a.p.numPrimaryChannels : 0;
   if (nch) {
     // LDS: nch TF tables + a 4-entry stack + the queue = 28 / 30 / 32 KB per workgroup (5 workgroups per CU)
     const bool smallIl = small && a.il32;
-#define EXA_IL4(G, F, I, A, N) hipLaunchKernelGGL((renderFrameKdKernel<G, F, 2, I, 0, A, N, ROPE>), grid, block, lds, s, a)
+#define EXA_IL4(G, F, I, A, N) hipLaunchKernelGGL((renderFrameKdKernel<G, F, 2, I, 0, A, N, ROPE>), grid, block, \
+                                                  marchLds(false, ROPE, a.numXfChannels, EXA_LDS_PAD).total, s, a)
 #define EXA_IL3(G, F, I, A) do { if (nch == 2) EXA_IL4(G, F, I, A, 2); else if (nch == 3) EXA_IL4(G, F, I, A, 3); else EXA_IL4(G, F, I, A, 4); } while (0)
 #define EXA_IL2(G, F, I) do { if (smallIl) EXA_IL3(G, F, I, true); else EXA_IL3(G, F, I, false); } while (0)
 #define EXA_IL1(G, F) do { if (surf) EXA_IL2(G, F, true); else EXA_IL2(G, F, false); } while (0)
