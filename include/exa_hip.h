@@ -528,6 +528,65 @@ int exa_hip_streamlines_read(ExaHipRenderer *, float *vertices /* numVertices x 
 int exa_hip_streamlines_release(ExaHipRenderer *);
 int exa_hip_streamlines_ms(ExaHipRenderer *, float *ms);   /* device time of the last extraction's kernels, summed */
 
+/* ---- projections: the field itself reduced along lines of sight — per pixel the sum, the number, the maximum and the
+ * minimum of the samples of one channel along a ray, as plain arrays: column density (sum*dt), the mean along the ray
+ * (sum/count), maximum- and minimum-intensity images.  New relative to the reference, whose only images are RGBA8 pictures
+ * through a transfer function.  One kernel forms the positions and reduces in registers; nothing of size pixels x samples
+ * exists. ----
+ *
+ * Spaces.  Without EXA_SAMPLE_WORLD_SPACE the rays are in voxel space.  With it they are in world space: every sample
+ * position goes through the voxelSpaceTransform of the frame state (xfmPoint) exactly as exa_hip_sample_points does it, and
+ * tmin / dt are world-space lengths.  A frame state must have been set.
+ *
+ * Positions.  Pixel (x, y), x < width, y < height; all arithmetic in float32, every operation rounded separately, nothing
+ * contracted, in exactly this association:
+ *     sx = float(x) + 0.5f                       sy = float(y) + 0.5f
+ *     o  = (org + sx*orgDu) + sy*orgDv           d  = (dir + sx*dirDu) + sy*dirDv          per component
+ *     with EXA_PROJECT_NORMALIZE: s = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z), correctly rounded, then d = d / s per component
+ *         by true division; a pixel with !(s > 0) or a non-finite s has no samples
+ *     t_i = tmin + (float(i) + 0.5f) * dt        for i = 0 .. numSamples-1
+ *     p_i = o + t_i * d                          per component
+ * One struct covers orthographic cameras (dirDu = dirDv = 0), pinhole cameras (orgDu = orgDv = 0) and anything affine in
+ * between.  Without the flag t and dt are multiples of |d|; with it they are arc lengths.
+ *
+ * Sample.  Sample i of a pixel is exactly what exa_hip_sample_points(p_i, {channel}, 1, flags & EXA_SAMPLE_WORLD_SPACE)
+ * returns, in the handle's current basis_form (a scene marked allowEmptyCells: the form-0 sums with the poison test): the
+ * same lookup and the same sums, bit for bit.  A sample is valid when its status is >= 0.
+ *
+ * Reduction.  Per pixel over the valid samples in ascending i: count = their number; sum = a double started at 0.0 with
+ * sum += (double)v per valid sample — invalid samples are skipped, not added as zero; the caller forms sum*dt and sum/count.
+ * vmax starts at -INFINITY, vmin at +INFINITY, maxIndex at -1, and per valid sample
+ *     if (v > vmax) { vmax = v; maxIndex = i; }        if (v < vmin) vmin = v;
+ * so a NaN value counts, poisons sum and never becomes max or min; of equal maxima the first wins (+0.0 does not replace
+ * -0.0).  Output index y*width + x; a NULL output pointer skips that array.
+ *
+ * Independence.  The bytes depend only on the scene, the ExaHipRays struct, the channel, the flags, basis_form and (world
+ * space) the transform — not on the transfer function, region activity, the camera of the frame state, walk, accel,
+ * brick_order, interleave, sample_patch or sample_uniform (which here, too, only selects whether a wave descends the tree
+ * and reads a shared region's headers together); two calls give the same bytes.  A pending brick_order change is applied
+ * first.  A scene without a kd tree is refused, as the probes refuse it.  A multi-device handle runs on devices[0].
+ *
+ * Calls.  Synchronous on hipStream.  Outputs are host arrays, which pass through the handle's bounded staging buffer tile
+ * by tile of the image, or with pointersAreDevice memory of the handle's first device.  Errors with a message, after which
+ * the handle stays usable: a NULL struct; a non-finite float in it; dt <= 0; numSamples < 1 or > EXA_PROJECT_MAX_SAMPLES;
+ * tmin + float(numSamples) * dt not finite in float32; width < 1, height < 1 or width*height > 2^31 - 1; a bad channel; flag
+ * bits other than EXA_SAMPLE_WORLD_SPACE | EXA_PROJECT_NORMALIZE; world space before any frame state; the descent's loop
+ * guard (return code 3, as the probes).  exa_hip_project_ms: the device time of the last call's kernel launches, summed
+ * (0 before any call and after a refused one). */
+#define EXA_PROJECT_NORMALIZE    4        /* rays run along d/|d|: t and dt are arc lengths */
+#define EXA_PROJECT_MAX_SAMPLES  1048576  /* cap of numSamples */
+typedef struct ExaHipRays {
+  float   org[3], orgDu[3], orgDv[3];   /* origin of pixel (x,y) */
+  float   dir[3], dirDu[3], dirDv[3];   /* direction of pixel (x,y) */
+  int32_t width, height;
+  float   tmin, dt;
+  int32_t numSamples;
+} ExaHipRays;
+int exa_hip_project(ExaHipRenderer *, const ExaHipRays *, int32_t channel, int32_t flags,
+                    double *sum, uint32_t *count, float *vmax, float *vmin, int32_t *maxIndex,
+                    int32_t pointersAreDevice, void *hipStream);
+int exa_hip_project_ms(ExaHipRenderer *, float *ms);   /* device time of the last call's kernel(s) */
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,

@@ -115,7 +115,8 @@ ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa
                "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample",
                "exa_hip_isosurface", "exa_hip_isosurface_read", "exa_hip_isosurface_release", "exa_hip_isosurface_stage_ms",
                "exa_hip_histogram", "exa_hip_histogram_ms",
-               "exa_hip_streamlines", "exa_hip_streamlines_read", "exa_hip_streamlines_release", "exa_hip_streamlines_ms"]
+               "exa_hip_streamlines", "exa_hip_streamlines_read", "exa_hip_streamlines_release", "exa_hip_streamlines_ms",
+               "exa_hip_project", "exa_hip_project_ms"]
 
 # exa_hip_sample_points / exa_hip_resample flags (include/exa_hip.h)
 SAMPLE_WORLD_SPACE = 1
@@ -129,6 +130,17 @@ STREAM_NORMALIZE = 4
 STREAM_VELOCITIES = 8
 STREAM_MAX_STEPS = 1 << 20
 STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREAM_END_STAGNANT = range(5)
+
+# exa_hip_project (include/exa_hip.h)
+PROJECT_NORMALIZE = 4
+PROJECT_MAX_SAMPLES = 1 << 20
+
+
+class ExaHipRays(C.Structure):
+    _fields_ = [("org", C.c_float * 3), ("orgDu", C.c_float * 3), ("orgDv", C.c_float * 3),
+                ("dir", C.c_float * 3), ("dirDu", C.c_float * 3), ("dirDv", C.c_float * 3),
+                ("width", C.c_int32), ("height", C.c_int32), ("tmin", C.c_float), ("dt", C.c_float), ("numSamples", C.c_int32)]
+
 
 _lib = None
 
@@ -197,6 +209,8 @@ def lib():
         L.exa_hip_streamlines_read.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp]
         L.exa_hip_streamlines_release.argtypes = [vp]
         L.exa_hip_streamlines_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.exa_hip_project.argtypes = [vp, C.POINTER(ExaHipRays), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp]
+        L.exa_hip_project_ms.argtypes = [vp, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -646,6 +660,37 @@ class Renderer:
             return self.readStreamlines()
         finally:
             self.releaseStreamlines()
+
+    # ---- projections along rays (exa_hip_project; include/exa_hip.h states the contract) ----
+    def project(self, org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples, channel=0, world=False,
+                normalize=False, stream=None):
+        """the field of `channel` reduced along one ray per pixel of a size = (width, height) image: pixel (x, y) has the origin
+        org + (x+.5)*orgDu + (y+.5)*orgDv and the direction dir + (x+.5)*dirDu + (y+.5)*dirDv (normalize: divided by its
+        length), its samples lie at tmin + (i+.5)*dt, i < num_samples, in voxel space or (world=True) in world space.
+        Returns a dict of arrays [height, width]: sum (float64: the valid samples added up; sum*dt is the line integral,
+        sum/count the mean), count (uint32), max, min (float32; -inf / +inf where count is 0) and max_index (int32: the
+        sample index of the first maximum, -1 for none)."""
+        flags = self._probe_world(world) | (PROJECT_NORMALIZE if normalize else 0)
+        rays = ExaHipRays()
+        for name, v in (("org", org), ("orgDu", orgDu), ("orgDv", orgDv), ("dir", dir), ("dirDu", dirDu), ("dirDv", dirDv)):
+            setattr(rays, name, (C.c_float * 3)(*[float(c) for c in v]))
+        rays.width, rays.height = int(size[0]), int(size[1])
+        rays.tmin, rays.dt, rays.numSamples = float(tmin), float(dt), int(num_samples)
+        shape = (max(rays.height, 0), max(rays.width, 0))                      # the module checks the size
+        if shape[0] * shape[1] > 2 ** 31 - 1:
+            shape = (0, 0)
+        out = dict(sum=np.empty(shape, np.float64), count=np.empty(shape, np.uint32), max=np.empty(shape, np.float32),
+                   min=np.empty(shape, np.float32), max_index=np.empty(shape, np.int32))
+        self._check(lib().exa_hip_project(self.h, C.byref(rays), int(channel), flags, out["sum"].ctypes.data,
+                                          out["count"].ctypes.data, out["max"].ctypes.data, out["min"].ctypes.data,
+                                          out["max_index"].ctypes.data, 0, C.c_void_p(stream or 0)))
+        return out
+
+    def projectMs(self):
+        """device ms of the last project call's kernel launches, summed"""
+        ms = C.c_float(0)
+        self._check(lib().exa_hip_project_ms(self.h, C.byref(ms)))
+        return float(ms.value)
 
 
 def _dev_ptr(x):

@@ -260,6 +260,23 @@ struct SampleArgs {
 // patch shapes of the grid kernel (x, y, z extents; 64 points each)
 enum { kSamplePatchShapes = 4 };
 
+// The projections (exa_hip_project, sampleRaysKernel in exa_sample_kernels.h): one wave per 8 x 8 pixels of the tile
+// [x0, x1) x [y0, y1) of the image, every lane one ray whose samples it reduces in registers.
+struct RayArgs {
+  SampleArgs         s;             // the lookup and the field (probeSetup); fieldOffset[0] = the channel
+  ExaHipRays         rays;
+  int32_t            normalize;     // EXA_PROJECT_NORMALIZE
+  int32_t            x0, y0, x1, y1;
+  uint32_t           patchesX;      // patches of the tile along x, and in all
+  unsigned long long numPatches;
+  // outputs (each may be NULL), addressed (x - x0) + (y - y0) * strideY
+  unsigned long long strideY;
+  double            *sum;
+  uint32_t          *count;
+  float             *vmax, *vmin;
+  int32_t           *maxIndex;
+};
+
 // The streamline integrator (exa_hip_streamlines, exa_stream_kernels.h): one lane per (seed, requested direction), RK4 in voxel
 // space on the probes' lookup and sums.  Two launches per extraction: the first stores per direction the number of vertices
 // it appends and why it ended, the second (after the scan of the counts) integrates again and stores the vertices packed.
@@ -309,6 +326,8 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
      1 16x4x1, 2 8x8x1, 3 4x4x4), wave-uniform descent and brick headers where a patch allows (uniform) or per lane */  \
   hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s);                                      \
   hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);                          \
+  /* the projections (exa_sample_f*.o): the tile of a, one wave per 8 x 8 pixels; uniform as for the grid */            \
+  hipError_t launchSampleRays(const RayArgs &a, bool uniform, hipStream_t s);                                        \
   /* the streamline integrator (exa_stream_f*.o): lanes [a.laneBase, a.numLanes) of at most 2^24 per launch; emit = the  \
      second launch, which stores the vertices */                                                                        \
   hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);

@@ -1,6 +1,6 @@
 // exa_probe.cpp — reading the reconstructed field outside a frame: the point probes (exa_hip_sample_points,
-// exa_hip_resample; kernels in exa_sample_kernels.h) and the iso-surface extraction on a sampled lattice
-// (exa_hip_isosurface; exa_isomesh.hip).
+// exa_hip_resample; kernels in exa_sample_kernels.h), the projections along rays (exa_hip_project; the same file) and the
+// iso-surface extraction on a sampled lattice (exa_hip_isosurface; exa_isomesh.hip).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -157,6 +157,110 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
   if (dstIsDevice && async) return 0;
   HIP_TRY(h, hipStreamSynchronize(s));
   return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+// ---- projections (sampleRaysKernel) ----
+namespace {
+struct ProjectEvents {
+  hipEvent_t ev[2] = { nullptr, nullptr };
+  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
+  ~ProjectEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+} // namespace
+
+// The image goes tile by tile: a tile is at most kProjectTileWidth pixels wide and holds at most kProbeLaunch pixels — host
+// outputs: at most what kProbeStageBytes of the staging buffer hold —, whole 8 x 8 patches except at the image's edges.
+static const uint64_t kProjectTileWidth = 4096;
+
+int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, int32_t flags, double *sum, uint32_t *count,
+                    float *vmax, float *vmin, int32_t *maxIndex, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_project";
+  ExaHipRenderer *r = firstChild(h);
+  r->projectKernelMs = 0.f;
+  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_PROJECT_NORMALIZE)) { h->fail(std::string(fn) + ": unknown flag bits (EXA_SAMPLE_WORLD_SPACE and EXA_PROJECT_NORMALIZE apply)"); return 1; }
+  if (!rays) { h->fail(std::string(fn) + ": null rays"); return 1; }
+  const float *vec[6] = { rays->org, rays->orgDu, rays->orgDv, rays->dir, rays->dirDu, rays->dirDv };
+  bool finite = std::isfinite(rays->tmin) && std::isfinite(rays->dt);
+  for (const float *v : vec)
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(v[k]);
+  if (!finite) { h->fail(std::string(fn) + ": a float of the rays is not finite"); return 1; }
+  if (!(rays->dt > 0.f)) { h->fail(std::string(fn) + ": dt must be > 0"); return 1; }
+  if (rays->numSamples < 1 || rays->numSamples > EXA_PROJECT_MAX_SAMPLES) { h->fail(std::string(fn) + ": numSamples must be in 1.." + std::to_string(EXA_PROJECT_MAX_SAMPLES)); return 1; }
+  const float tEnd = rays->tmin + float(rays->numSamples) * rays->dt;
+  if (!std::isfinite(tEnd)) { h->fail(std::string(fn) + ": tmin + numSamples * dt is not finite in float32"); return 1; }
+  if (rays->width < 1 || rays->height < 1 || uint64_t(rays->width) * uint64_t(rays->height) > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": width and height must be >= 1 and width * height <= 2^31 - 1");
+    return 1;
+  }
+  if (channel < 0 || channel >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  RayArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a.s)) return 1;
+  a.s.numChannels = 1;
+  a.s.fieldOffset[0] = r->sc.channelOffset[channel];
+  a.rays = *rays;
+  a.normalize = (flags & EXA_PROJECT_NORMALIZE) ? 1 : 0;
+
+  const uint64_t W = uint64_t(rays->width), H = uint64_t(rays->height);
+  const uint64_t perPixel = (sum ? 8 : 0) + (count ? 4 : 0) + (vmax ? 4 : 0) + (vmin ? 4 : 0) + (maxIndex ? 4 : 0);
+  const bool staged = !pointersAreDevice && perPixel > 0;
+  const uint64_t cap = staged ? std::min(kProbeLaunch, kProbeStageBytes / perPixel) : kProbeLaunch;
+  const uint64_t tw = std::min(W, kProjectTileWidth), th = std::min(H, std::max<uint64_t>(8, (cap / tw) & ~uint64_t(7)));
+  if (staged && r->probeStage.n < tw * th * perPixel) HIP_TRY(h, r->probeStage.alloc(tw * th * perPixel));
+  ProjectEvents t;
+  HIP_TRY(h, t.create());
+  float total = 0.f;
+  for (uint64_t y0 = 0; y0 < H; y0 += th)
+    for (uint64_t x0 = 0; x0 < W; x0 += tw) {
+      const uint64_t ex = std::min(tw, W - x0), ey = std::min(th, H - y0), first = y0 * W + x0;
+      a.x0 = int32_t(x0); a.y0 = int32_t(y0); a.x1 = int32_t(x0 + ex); a.y1 = int32_t(y0 + ey);
+      a.patchesX = uint32_t((ex + 7) / 8);
+      a.numPatches = uint64_t(a.patchesX) * ((ey + 7) / 8);
+      if (staged) {
+        // {sum | count | vmax | vmin | maxIndex} of the tile, rows of ex pixels; the doubles first: aligned
+        char *p = r->probeStage.p;
+        a.strideY = ex;
+        a.sum = sum ? reinterpret_cast<double *>(p) : nullptr;         p += sum ? 8 * ex * ey : 0;
+        a.count = count ? reinterpret_cast<uint32_t *>(p) : nullptr;   p += count ? 4 * ex * ey : 0;
+        a.vmax = vmax ? reinterpret_cast<float *>(p) : nullptr;        p += vmax ? 4 * ex * ey : 0;
+        a.vmin = vmin ? reinterpret_cast<float *>(p) : nullptr;        p += vmin ? 4 * ex * ey : 0;
+        a.maxIndex = maxIndex ? reinterpret_cast<int32_t *>(p) : nullptr;
+      } else {
+        a.strideY = W;
+        a.sum = sum ? sum + first : nullptr;
+        a.count = count ? count + first : nullptr;
+        a.vmax = vmax ? vmax + first : nullptr;
+        a.vmin = vmin ? vmin + first : nullptr;
+        a.maxIndex = maxIndex ? maxIndex + first : nullptr;
+      }
+      HIP_TRY(h, hipEventRecord(t.ev[0], s));
+      HIP_TRY(h, EXA_FORM(r, launchSampleRays)(a, r->sampleUniform != 0, s));
+      HIP_TRY(h, hipEventRecord(t.ev[1], s));
+      if (staged) {
+        if (sum) HIP_TRY(h, hipMemcpy2DAsync(sum + first, W * 8, a.sum, ex * 8, ex * 8, ey, hipMemcpyDeviceToHost, s));
+        if (count) HIP_TRY(h, hipMemcpy2DAsync(count + first, W * 4, a.count, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
+        if (vmax) HIP_TRY(h, hipMemcpy2DAsync(vmax + first, W * 4, a.vmax, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
+        if (vmin) HIP_TRY(h, hipMemcpy2DAsync(vmin + first, W * 4, a.vmin, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
+        if (maxIndex) HIP_TRY(h, hipMemcpy2DAsync(maxIndex + first, W * 4, a.maxIndex, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
+      }
+      HIP_TRY(h, hipStreamSynchronize(s));
+      float ms = 0.f;
+      HIP_TRY(h, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+      total += ms;
+    }
+  r->projectKernelMs = total;
+  return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+int exa_hip_project_ms(ExaHipRenderer *h, float *ms)
+{
+  if (!h || !ms) return 1;
+  *ms = firstChild(h)->projectKernelMs;
+  return 0;
 }
 
 // ---- iso-surface extraction (exa_isomesh.hip) ----

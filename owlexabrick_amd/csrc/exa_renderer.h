@@ -281,6 +281,8 @@ struct ExaHipRenderer {
   uint64_t streamSeeds = 0, streamNumVertices = 0;
   bool haveStreamlines = false;
   float streamKernelMs = 0.f;
+  // the device time of the last exa_hip_project's kernel launches, summed (in the renderer of devices[0])
+  float projectKernelMs = 0.f;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 

@@ -1,5 +1,6 @@
 // exa_sample_kernels.h — the point probes: exa_hip_sample_points (one lane per point) and exa_hip_resample (one wave per
-// compact patch of 64 grid points).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
+// compact patch of 64 grid points), and on the same lookup and sums the projections of exa_hip_project (one wave per 8 x 8
+// rays, reduced in registers).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
 // -DEXA_TU_SAMPLE=1 (exa_sample_f0.o, exa_sample_f1.o, exa_sample_f0e.o), after samplePoint and the basis evaluations it
 // uses; nothing else of the renderer is compiled there.
 //
@@ -135,6 +136,168 @@ __global__ __launch_bounds__(256) void sampleGridKernel(const SampleArgs a)
   }
   const size_t o = size_t(x - a.box0[0]) + size_t(y - a.box0[1]) * size_t(a.strideY) + size_t(z - a.box0[2]) * size_t(a.strideZ);
   a.out[o] = value;
+}
+
+// ---- exa_hip_project: the field reduced along rays ----
+// p_i of the contract: t_i = tmin + (float(i) + 0.5f) * dt, p_i = o + t_i * d, every operation rounded separately (the unit
+// is compiled without contraction).  The ONE position function of the march and of the bisections below.
+__device__ __forceinline__ V3 rayPos(const RayArgs &a, V3 o, V3 d, int i)
+{
+  const float t = a.rays.tmin + (float(i) + 0.5f) * a.rays.dt;
+  return o + t * d;
+}
+
+// sampleInRoot's six comparisons, dealt by the sign of the direction into the three a ray satisfies from some index on
+// (rayEntered) and the three it satisfies up to some index (rayNotLeft): sampleInRoot(p) == rayEntered(p) && rayNotLeft(p)
+__device__ __forceinline__ bool rayEntered(const SampleArgs &s, V3 d, V3 p)
+{
+  return (d.x >= 0.f ? p.x >= s.kdLo[0] : p.x <= s.kdHi[0]) && (d.y >= 0.f ? p.y >= s.kdLo[1] : p.y <= s.kdHi[1])
+      && (d.z >= 0.f ? p.z >= s.kdLo[2] : p.z <= s.kdHi[2]);
+}
+__device__ __forceinline__ bool rayNotLeft(const SampleArgs &s, V3 d, V3 p)
+{
+  return (d.x >= 0.f ? p.x <= s.kdHi[0] : p.x >= s.kdLo[0]) && (d.y >= 0.f ? p.y <= s.kdHi[1] : p.y >= s.kdLo[1])
+      && (d.z >= 0.f ? p.z <= s.kdHi[2] : p.z >= s.kdLo[2]);
+}
+
+// the reduction of one pixel, in registers
+struct RayAcc { double sum; uint32_t count; float vmax, vmin; int32_t maxIndex; };
+
+// one sample whose lane has a region: the closed-domain test and the sums of samplePointsBody, then the contract's updates
+__device__ __forceinline__ void rayAccumulate(const RayArgs &a, const RegionRec &R, const float *field, V3 p, int i, RayAcc &acc)
+{
+  if (!sampleInDomain(R, p)) return;
+  const Basis B = sampleSums<false>(a.s, R.listBegin, R.listSize, field, p);
+  if (B.sumW <= 1e-20f) return;                                         // status -2
+  const float v = B.sumWV / B.sumW;
+  acc.count++;
+  acc.sum += double(v);
+  if (v > acc.vmax) { acc.vmax = v; acc.maxIndex = i; }
+  if (v < acc.vmin) acc.vmin = v;
+}
+
+// One wave per 8 x 8 pixels, every lane one ray; the lanes step the sample index i together, so that at every i the wave's
+// 64 positions lie in a small patch of space and the grid kernel's UNIFORM scheme applies: a shared descent while the lanes
+// (those inside the root box) take the same side of every plane, one region record and one stream of brick headers per wave
+// when they land in one region, else lane by lane.  Both through sampleInRoot, sampleKdChild, sampleKdLeaf, sampleInDomain
+// and sampleSums<false>, as the points kernel: a sample equals exa_hip_sample_points bit for bit.
+//
+// SKIP (voxel space): indices whose position cannot lie in the root box are not marched.  For a lane with finite o and d
+// (any other lane has no position inside the finite root box at all: a non-finite o or d makes every p_i infinite or NaN)
+//   - t_i is non-decreasing in i: float(i) + 0.5f is exact below 2^23 and increasing, the product with dt > 0 and the sum
+//     with tmin are correctly rounded operations with one operand fixed, which are monotone; every t_i is finite, because
+//     |t_i| <= max(|tmin|, |tmin + float(numSamples) * dt|), which the call has checked;
+//   - per axis k, p_i.k = o.k + t_i * d.k is, for the same reason, non-decreasing in t_i where d.k >= 0 and non-increasing
+//     where d.k < 0 (d.k == +-0: constant; no NaN can arise, o.k being finite: an overflowing product gives o.k +- inf).
+// So each comparison of rayEntered is false up to some index and true from it on, hence so is their conjunction; each of
+// rayNotLeft is true up to some index and false from it on, hence so is theirs.  A bisection finds the first index `beg`
+// with rayEntered and the first index `end` without rayNotLeft exactly (numSamples evaluations of the same rayPos would
+// find the same two), and sampleInRoot(p_i) holds precisely for beg <= i < end (for no i if beg >= end).  A skipped index
+// is therefore one whose sample is invalid (status -1), which the reduction ignores; the marched ones are tested with
+// sampleInRoot itself as ever.  The wave marches the union [min beg, max end) of its lanes' ranges; a lane idles outside
+// its own.  In world space the transform mixes the axes and nothing of this holds: every index is marched.
+template <bool UNIFORM, bool SKIP>
+__global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long wave = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (wave >= a.numPatches) return;
+  const long long xl = a.x0 + (long long)(wave % a.patchesX) * 8 + (long long)(lane & 7u);
+  const long long yl = a.y0 + (long long)(wave / a.patchesX) * 8 + (long long)(lane >> 3);
+  const bool live = xl < a.x1 && yl < a.y1;        // a dead lane stays (the wave's shuffles and ballots see it) with no samples
+  const int x = int(xl), y = int(yl);              // a live lane's fit: x1, y1 are int32
+  const int n = a.rays.numSamples;
+  const float sx = float(x) + 0.5f, sy = float(y) + 0.5f;
+  const V3 o = (mk(a.rays.org) + sx * mk(a.rays.orgDu)) + sy * mk(a.rays.orgDv);
+  V3 d = (mk(a.rays.dir) + sx * mk(a.rays.dirDu)) + sy * mk(a.rays.dirDv);
+  int beg = 0, end = live ? n : 0;
+  if (a.normalize) {
+    // sqrtf and `/`: the compiler's correctly rounded expansions, as in the streamline integrator
+    const float s = sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z);
+    if (!(s > 0.f) || !(s <= FLT_MAX)) end = 0;
+    d = mk(d.x / s, d.y / s, d.z / s);
+  }
+  if (SKIP) {
+    const bool finite = fabsf(o.x) <= FLT_MAX && fabsf(o.y) <= FLT_MAX && fabsf(o.z) <= FLT_MAX
+                     && fabsf(d.x) <= FLT_MAX && fabsf(d.y) <= FLT_MAX && fabsf(d.z) <= FLT_MAX;
+    if (!finite) end = 0;
+    if (end > 0) {
+      // the first index with rayEntered, in [0, n]; then the first without rayNotLeft, in [beg, n]
+      int lo = 0, hi = n;
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (rayEntered(a.s, d, rayPos(a, o, d, mid))) hi = mid; else lo = mid + 1;
+      }
+      beg = lo;
+      hi = n;
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (rayNotLeft(a.s, d, rayPos(a, o, d, mid))) lo = mid + 1; else hi = mid;
+      }
+      end = lo;
+    }
+  }
+  if (end <= beg) { beg = n; end = 0; }
+  // the union of the wave's ranges
+  int wBeg = beg, wEnd = end;
+  for (int m = 32; m >= 1; m >>= 1) {
+    wBeg = min(wBeg, __shfl_xor(wBeg, m, 64));
+    wEnd = max(wEnd, __shfl_xor(wEnd, m, 64));
+  }
+  wBeg = __builtin_amdgcn_readfirstlane(wBeg);
+  wEnd = __builtin_amdgcn_readfirstlane(wEnd);
+
+  const float *field = a.s.scalars + a.s.fieldOffset[0];
+  RayAcc acc;
+  acc.sum = 0.0; acc.count = 0u; acc.vmax = -INFINITY; acc.vmin = INFINITY; acc.maxIndex = -1;
+  bool tripped = false;
+  for (int i = wBeg; i < wEnd; i++) {
+    V3 p = rayPos(a, o, d, i);
+    if (a.s.world) p = xfmPoint(a.s.fs, p);
+    int region = -1;
+    if (i >= beg && i < end && sampleInRoot(a.s, p)) {
+      int ref = a.s.kdRoot;
+      if (UNIFORM) {
+        for (int g = 0; ref >= 0 && g < a.s.maxSteps; g++) {
+          const int u = __builtin_amdgcn_readfirstlane(ref);           // the same in every lane here
+          const int next = sampleKdChild(a.s.kdNodes[u], p);
+          if (anyLane(next != __builtin_amdgcn_readfirstlane(next))) break;   // the lanes part at this node
+          ref = next;
+        }
+      }
+      region = sampleKdLeaf(a.s, ref, p, tripped);
+    }
+    if (region >= 0) {
+      const int r0 = __builtin_amdgcn_readfirstlane(region);           // of the lanes that have a region
+      if (UNIFORM && !anyLane(region != r0)) {
+        const RegionRec R = a.s.regionRec[r0];                           // wave-uniform index: one record per wave
+        rayAccumulate(a, R, field, p, i, acc);
+      } else {
+        const RegionRec R = a.s.regionRec[region];
+        rayAccumulate(a, R, field, p, i, acc);
+      }
+    }
+  }
+  if (tripped) atomicExch(a.s.errorFlag, 1);
+  if (!live) return;
+  const size_t at = size_t(x - a.x0) + size_t(y - a.y0) * size_t(a.strideY);
+  if (a.sum) a.sum[at] = acc.sum;
+  if (a.count) a.count[at] = acc.count;
+  if (a.vmax) a.vmax[at] = acc.vmax;
+  if (a.vmin) a.vmin[at] = acc.vmin;
+  if (a.maxIndex) a.maxIndex[at] = acc.maxIndex;
+}
+
+hipError_t launchSampleRays(const RayArgs &a, bool uniform, hipStream_t s)
+{
+  if (a.numPatches == 0) return hipSuccess;
+  const dim3 grid((unsigned)((a.numPatches + 3) / 4)), block(256);
+  const bool skip = a.s.world == 0;
+  if (uniform) { if (skip) hipLaunchKernelGGL((sampleRaysKernel<true, true>), grid, block, 0, s, a);
+                 else      hipLaunchKernelGGL((sampleRaysKernel<true, false>), grid, block, 0, s, a); }
+  else         { if (skip) hipLaunchKernelGGL((sampleRaysKernel<false, true>), grid, block, 0, s, a);
+                 else      hipLaunchKernelGGL((sampleRaysKernel<false, false>), grid, block, 0, s, a); }
+  return hipGetLastError();
 }
 
 hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s)

@@ -35,6 +35,12 @@
 //             [--streamlines-channels a b c] [--streamlines-both] [--streamlines-backward] [--streamlines-normalize]
 //                                            (channels default 0 1 2; forward unless --streamlines-backward); --frames 0
 //                                            renders nothing
+//             [--project CHANNEL DT NSAMPLES out.prj] the field of CHANNEL reduced along the camera's rays through the pixel
+//                                            centres of the --size image (exa_hip_project: world space, unit directions,
+//                                            samples at (i + .5) * DT, i < NSAMPLES): one text line `project W H channel C dt
+//                                            DT samples N`, then four raw little-endian planes of W x H, row y = 0 first:
+//                                            the line integral sum*dt (float32), the number of valid samples (uint32), their
+//                                            maximum and their minimum (float32; -inf / +inf for none); --frames 0 renders nothing
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -108,6 +114,9 @@ int main(int argc, char **argv)
     int streamMaxSteps = 0;
     vec3i streamChannels(0, 1, 2);
     bool streamBoth = false, streamBackward = false, streamNormalize = false;
+    std::string projectName;
+    int projectChannel = 0, projectSamples = 0;
+    float projectDt = 0.f;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -188,6 +197,13 @@ int main(int argc, char **argv)
       else if (a == "--streamlines-both") streamBoth = true;
       else if (a == "--streamlines-backward") streamBackward = true;
       else if (a == "--streamlines-normalize") streamNormalize = true;
+      else if (a == "--project") {
+        projectChannel = (int)f();
+        projectDt = f();
+        projectSamples = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --project CHANNEL DT NSAMPLES");
+        projectName = argv[++i];
+      }
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
       else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
@@ -337,7 +353,23 @@ int main(int argc, char **argv)
       std::printf("streamlines seeds %zu channels %d %d %d step %.9g maxSteps %d vertices %zu\n", seeds.size(), streamChannels.x,
                   streamChannels.y, streamChannels.z, streamStep, streamMaxSteps, L.vertex.size());
     }
-    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty())) return 0;
+    if (!projectName.empty()) {
+      const ExaHipRays rays = renderer.cameraRays(size, 0.f, projectDt, projectSamples);
+      const Renderer::Projection P = renderer.project(rays, projectChannel, true, true);
+      std::vector<float> integral(P.sum.size());
+      size_t hit = 0;
+      for (size_t k = 0; k < integral.size(); k++) { integral[k] = float(P.sum[k] * double(projectDt)); hit += P.count[k] != 0; }
+      FILE *f = std::fopen(projectName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + projectName);
+      std::fprintf(f, "project %d %d channel %d dt %.9g samples %d\n", size.x, size.y, projectChannel, projectDt, projectSamples);
+      const size_t n = integral.size();
+      const bool ok = std::fwrite(integral.data(), 4, n, f) == n && std::fwrite(P.count.data(), 4, n, f) == n
+                   && std::fwrite(P.max.data(), 4, n, f) == n && std::fwrite(P.min.data(), 4, n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + projectName);
+      std::printf("project %d %d channel %d dt %.9g samples %d pixels_hit %zu\n", size.x, size.y, projectChannel, projectDt,
+                  projectSamples, hit);
+    }
+    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

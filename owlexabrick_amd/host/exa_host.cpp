@@ -623,6 +623,31 @@ Renderer::Streamlines Renderer::streamlines(const vec3f *seeds, size_t n, vec3i 
   return L;
 }
 
+Renderer::Projection Renderer::project(const ExaHipRays &rays, int channel, bool worldSpace, bool normalize)
+{
+  if (worldSpace) pushState();
+  Projection P;
+  const size_t n = rays.width > 0 && rays.height > 0 && uint64_t(rays.width) * uint64_t(rays.height) <= uint64_t(INT32_MAX)
+                       ? size_t(rays.width) * size_t(rays.height) : 0;        // the module checks the size
+  P.sum.resize(n); P.count.resize(n); P.max.resize(n); P.min.resize(n); P.maxIndex.resize(n);
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
+  check(exa_hip_project(handle, &rays, channel, flags, P.sum.data(), P.count.data(), P.max.data(), P.min.data(),
+                        P.maxIndex.data(), 0, nullptr), handle);
+  return P;
+}
+
+ExaHipRays Renderer::cameraRays(vec2i size, float tmin, float dt, int numSamples) const
+{
+  ExaHipRays r;
+  std::memset(&r, 0, sizeof(r));
+  auto put = [](float *d, const vec3f &v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+  put(r.org, frameState.camera.pos);
+  put(r.dir, frameState.camera.dir00); put(r.dirDu, frameState.camera.dirDu); put(r.dirDv, frameState.camera.dirDv);
+  r.width = size.x; r.height = size.y;
+  r.tmin = tmin; r.dt = dt; r.numSamples = numSamples;
+  return r;
+}
+
 ExaHipStats Renderer::stats() const
 {
   ExaHipStats s;

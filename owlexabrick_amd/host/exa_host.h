@@ -233,8 +233,24 @@ struct Renderer {
   Streamlines streamlines(const vec3f *seeds, size_t n, vec3i channels, float step, int maxSteps, bool forward = true,
                           bool backward = false, bool normalize = false, bool velocities = false);
 
+  // the field of `channel` reduced along one ray per pixel (exa_hip_project; include/exa_hip.h states the contract): pixel
+  // (x, y) of the rays.width x rays.height image starts at org + (x+.5)*orgDu + (y+.5)*orgDv, runs along
+  // dir + (x+.5)*dirDu + (y+.5)*dirDv (normalize: divided by its length) and is sampled at tmin + (i+.5)*dt, i < numSamples,
+  // in voxel space or, with worldSpace, in world space (the frame state is pushed first).  Per pixel, row-major: sum of the
+  // valid samples (sum*dt: the line integral, sum/count: the mean), their count, maximum (-inf for none), minimum (+inf)
+  // and the sample index of the first maximum (-1).
+  struct Projection {
+    std::vector<double> sum;
+    std::vector<uint32_t> count;
+    std::vector<float> max, min;
+    std::vector<int32_t> maxIndex;
+  };
+  Projection project(const ExaHipRays &rays, int channel, bool worldSpace = false, bool normalize = false);
+  // the rays of the camera set with updateCamera, through the pixel centres of a size.x x size.y image (world space)
+  ExaHipRays cameraRays(vec2i size, float tmin, float dt, int numSamples) const;
+
   ExaHipStats stats() const;
-  ExaHipStats renderStats();                 // the same frame through the counting variant of the kernels
+  ExaHipStats renderStats();                // the same frame through the counting variant of the kernels
   size_t numRegions = 0, numLeafEntries = 0; // what Regions::buildFrom produced (exa/Regions.cpp:308-319 prints them)
 
   std::vector<ScalarField::SP> scalarFields;
