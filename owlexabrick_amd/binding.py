@@ -105,19 +105,6 @@ REGION_DTYPE = np.dtype([("dom_lo", "<f4", 3), ("dom_hi", "<f4", 3), ("vr_lo", "
 KDNODE_DTYPE = np.dtype([("split", "<f4"), ("axis", "<i4"), ("left", "<i4"), ("right", "<i4")])
 KD_EMPTY = -2 ** 31
 
-# every symbol include/exa_hip.h declares
-ABI_SYMBOLS = ["exa_prep_create", "exa_prep_create_ex", "exa_prep_destroy", "exa_prep_scene", "exa_prep_last_error", "exa_prep_ropes", "exa_prep_set_kd_tree",
-               "exa_hip_create", "exa_hip_create_multi", "exa_hip_destroy", "exa_hip_resize", "exa_hip_set_frame_state",
-               "exa_hip_set_xf", "exa_hip_set_triangles", "exa_hip_reset_tracer", "exa_hip_set_tracer_enabled",
-               "exa_hip_advance_tracer", "exa_hip_read_traces", "exa_hip_set_params", "exa_hip_set_shard", "exa_hip_output_pixels",
-               "exa_hip_untile", "exa_hip_render", "exa_hip_render_stats", "exa_hip_get_stats",
-               "exa_hip_read_accum", "exa_hip_write_accum", "exa_hip_read_activity",
-               "exa_hip_set_option", "exa_hip_last_error", "exa_hip_sample_points", "exa_hip_resample",
-               "exa_hip_isosurface", "exa_hip_isosurface_read", "exa_hip_isosurface_release", "exa_hip_isosurface_stage_ms",
-               "exa_hip_histogram", "exa_hip_histogram_ms",
-               "exa_hip_streamlines", "exa_hip_streamlines_read", "exa_hip_streamlines_release", "exa_hip_streamlines_ms",
-               "exa_hip_project", "exa_hip_project_ms"]
-
 # exa_hip_sample_points / exa_hip_resample flags (include/exa_hip.h)
 SAMPLE_WORLD_SPACE = 1
 SAMPLE_GRADIENT = 2
@@ -142,6 +129,58 @@ class ExaHipRays(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("tmin", C.c_float), ("dt", C.c_float), ("numSamples", C.c_int32)]
 
 
+_vp, _i32, _u64, _f32, _P = C.c_void_p, C.c_int32, C.c_uint64, C.c_float, C.POINTER
+
+# every symbol include/exa_hip.h declares: name -> (restype, None = the int return code; argtypes, None = takes none).  lib()
+# sets the prototypes from it
+_ABI = {
+    "exa_prep_create": (None, [_vp, _u64, _vp, _u64, _P(_vp), _P(_u64), _i32, _i32, _i32, _P(_vp)]),
+    "exa_prep_create_ex": (None, [_vp, _u64, _vp, _u64, _P(_vp), _P(_u64), _i32, _i32, _i32, _i32, _P(_vp)]),
+    "exa_prep_destroy": (None, [_vp]),
+    "exa_prep_ropes": (None, [_vp, _P(_u64), _P(_u64), _vp, _vp, _vp, _vp, _P(_i32)]),
+    "exa_prep_scene": (None, [_vp, _P(ExaHipScene)]),
+    "exa_prep_set_kd_tree": (None, [_vp, _vp, _u64, _i32]),
+    "exa_prep_last_error": (C.c_char_p, None),
+    "exa_hip_create": (None, [_P(ExaHipScene), _i32, _P(_vp)]),
+    "exa_hip_create_multi": (None, [_P(ExaHipScene), _P(_i32), _i32, _P(_vp)]),
+    "exa_hip_destroy": (None, [_vp]),
+    "exa_hip_resize": (None, [_vp, _i32, _i32]),
+    "exa_hip_set_frame_state": (None, [_vp, _P(ExaHipFrameState)]),
+    "exa_hip_set_xf": (None, [_vp, _i32, _vp]),
+    "exa_hip_set_params": (None, [_vp, _P(ExaHipParams)]),
+    "exa_hip_set_triangles": (None, [_vp, _vp, _u64, _vp, _u64]),
+    "exa_hip_reset_tracer": (None, [_vp, _P(ExaHipTracer), _vp]),
+    "exa_hip_set_tracer_enabled": (None, [_vp, _i32]),
+    "exa_hip_advance_tracer": (None, [_vp, _P(_i32)]),
+    "exa_hip_read_traces": (None, [_vp, _vp]),
+    "exa_hip_set_shard": (None, [_vp, _i32, _i32]),
+    "exa_hip_output_pixels": (C.c_uint64, [_vp]),
+    "exa_hip_untile": (None, [_vp, _vp, _u64, _i32, _vp, _vp]),
+    "exa_hip_render": (None, [_vp, _vp, _i32, _vp, _i32]),
+    "exa_hip_render_stats": (None, [_vp, _vp, _i32, _P(ExaHipStats)]),
+    "exa_hip_get_stats": (None, [_vp, _P(ExaHipStats)]),
+    "exa_hip_read_accum": (None, [_vp, _vp]),
+    "exa_hip_write_accum": (None, [_vp, _vp]),
+    "exa_hip_read_activity": (None, [_vp, _i32, _vp]),
+    "exa_hip_set_option": (None, [_vp, C.c_char_p, _i32]),
+    "exa_hip_last_error": (C.c_char_p, [_vp]),
+    "exa_hip_sample_points": (None, [_vp, _vp, _u64, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp, _i32]),
+    "exa_hip_resample": (None, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i32]),
+    "exa_hip_isosurface": (None, [_vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _P(_u64), _vp]),
+    "exa_hip_isosurface_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_isosurface_release": (None, [_vp]),
+    "exa_hip_isosurface_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
+    "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),
+    "exa_hip_streamlines_read": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_streamlines_release": (None, [_vp]),
+    "exa_hip_streamlines_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_project": (None, [_vp, _P(ExaHipRays), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_project_ms": (None, [_vp, _P(_f32)]),
+}
+ABI_SYMBOLS = list(_ABI)
+
 _lib = None
 
 
@@ -158,59 +197,12 @@ def lib():
                 raise RuntimeError(f"{LIB_PATH} not found and building it failed ({e}); run "
                                    "__graft_entry__.build(); there is no CPU fallback") from e
         L = C.CDLL(LIB_PATH)
-        vp = C.c_void_p
-        L.exa_prep_create.restype = C.c_int
-        L.exa_prep_create.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64),
-                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-        L.exa_prep_create_ex.restype = C.c_int
-        L.exa_prep_create_ex.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64),
-                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-        L.exa_prep_destroy.argtypes = [vp]
-        L.exa_prep_ropes.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp, vp, C.POINTER(C.c_int32)]
-        L.exa_prep_scene.argtypes = [vp, C.POINTER(ExaHipScene)]
-        L.exa_prep_set_kd_tree.argtypes = [vp, vp, C.c_uint64, C.c_int32]
-        L.exa_prep_last_error.restype = C.c_char_p
-        L.exa_hip_create.argtypes = [C.POINTER(ExaHipScene), C.c_int32, C.POINTER(vp)]
-        L.exa_hip_create_multi.argtypes = [C.POINTER(ExaHipScene), C.POINTER(C.c_int32), C.c_int32, C.POINTER(vp)]
-        L.exa_hip_destroy.argtypes = [vp]
-        L.exa_hip_resize.argtypes = [vp, C.c_int32, C.c_int32]
-        L.exa_hip_set_frame_state.argtypes = [vp, C.POINTER(ExaHipFrameState)]
-        L.exa_hip_set_xf.argtypes = [vp, C.c_int32, vp]
-        L.exa_hip_set_params.argtypes = [vp, C.POINTER(ExaHipParams)]
-        L.exa_hip_set_triangles.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
-        L.exa_hip_reset_tracer.argtypes = [vp, C.POINTER(ExaHipTracer), vp]
-        L.exa_hip_set_tracer_enabled.argtypes = [vp, C.c_int32]
-        L.exa_hip_advance_tracer.argtypes = [vp, C.POINTER(C.c_int32)]
-        L.exa_hip_read_traces.argtypes = [vp, vp]
-        L.exa_hip_set_shard.argtypes = [vp, C.c_int32, C.c_int32]
-        L.exa_hip_output_pixels.restype = C.c_uint64
-        L.exa_hip_output_pixels.argtypes = [vp]
-        L.exa_hip_untile.argtypes = [vp, vp, C.c_uint64, C.c_int32, vp, vp]
-        L.exa_hip_render.argtypes = [vp, vp, C.c_int32, vp, C.c_int32]
-        L.exa_hip_render_stats.argtypes = [vp, vp, C.c_int32, C.POINTER(ExaHipStats)]
-        L.exa_hip_get_stats.argtypes = [vp, C.POINTER(ExaHipStats)]
-        L.exa_hip_read_accum.argtypes = [vp, vp]
-        L.exa_hip_write_accum.argtypes = [vp, vp]
-        L.exa_hip_read_activity.argtypes = [vp, C.c_int32, vp]
-        L.exa_hip_set_option.argtypes = [vp, C.c_char_p, C.c_int32]
-        L.exa_hip_last_error.restype = C.c_char_p
-        L.exa_hip_last_error.argtypes = [vp]
-        L.exa_hip_sample_points.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp,
-                                            C.c_int32, vp, C.c_int32]
-        L.exa_hip_resample.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp, C.c_int32]
-        L.exa_hip_isosurface.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_uint64),
-                                         C.POINTER(C.c_uint64), vp]
-        L.exa_hip_isosurface_read.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
-        L.exa_hip_isosurface_release.argtypes = [vp]
-        L.exa_hip_isosurface_stage_ms.argtypes = [vp, vp]
-        L.exa_hip_histogram_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.exa_hip_histogram.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.POINTER(ExaHipFieldStats), vp]
-        L.exa_hip_streamlines.argtypes = [vp, vp, C.c_uint64, vp, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), vp]
-        L.exa_hip_streamlines_read.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp]
-        L.exa_hip_streamlines_release.argtypes = [vp]
-        L.exa_hip_streamlines_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.exa_hip_project.argtypes = [vp, C.POINTER(ExaHipRays), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp]
-        L.exa_hip_project_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        for name, (restype, argtypes) in _ABI.items():
+            fn = getattr(L, name)
+            if restype is not None:
+                fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
         _lib = L
     return _lib
 
@@ -327,6 +319,12 @@ class Renderer:
         if rc:
             raise RuntimeError(lib().exa_hip_last_error(self.h).decode())
 
+    def _ms(self, getter):
+        """the float that one of the `float *ms` getters reports"""
+        ms = C.c_float(0)
+        self._check(getter(self.h, C.byref(ms)))
+        return float(ms.value)
+
     def close(self):
         if getattr(self, "h", None):
             lib().exa_hip_destroy(self.h)
@@ -353,7 +351,7 @@ class Renderer:
     # ---- streamline tracer (OptixRenderer::setTracerEnabled / resetTracer / advanceTracer) ----
     def resetTracer(self, seeds, channels=(0, 1, 2), numTimesteps=100, steplen=1e-6, enabled=True):
         sd = np.ascontiguousarray(seeds, dtype=np.float32).reshape(-1, 3)
-        self._tracer = ExaHipTracer(int(enabled), (C.c_int32 * 3)(*channels), sd.shape[0], int(numTimesteps), float(steplen))
+        self._tracer = ExaHipTracer(int(enabled), _i3(channels), sd.shape[0], int(numTimesteps), float(steplen))
         self._check(lib().exa_hip_reset_tracer(self.h, C.byref(self._tracer), sd.ctypes.data))
 
     def setTracerEnabled(self, enable):
@@ -525,9 +523,7 @@ class Renderer:
         world space with world=True).  Without out_ptr returns a float32 array [nz, ny, nx] (x fastest); out_ptr (a device
         pointer or a contiguous float32 torch CUDA tensor) takes the device path and returns None."""
         flags = self._probe_world(world)
-        lo3 = (C.c_float * 3)(*[float(v) for v in lo])
-        hi3 = (C.c_float * 3)(*[float(v) for v in hi])
-        d3 = (C.c_int32 * 3)(*[int(v) for v in dims])
+        lo3, hi3, d3 = _f3(lo), _f3(hi), _i3(dims)
         if out_ptr is not None:
             self._check(lib().exa_hip_resample(self.h, lo3, hi3, d3, int(channel), flags, float(fill), _dev_ptr(out_ptr), 1,
                                                C.c_void_p(stream or 0), int(async_)))
@@ -541,9 +537,7 @@ class Renderer:
         """extract the surface field == iso on the lattice of resample(lo, hi, dims) into module-owned device memory;
         returns (numVertices, numTriangles).  readIsoSurface copies it out, releaseIsoSurface frees it."""
         flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradients else 0)
-        lo3 = (C.c_float * 3)(*[float(v) for v in lo])
-        hi3 = (C.c_float * 3)(*[float(v) for v in hi])
-        d3 = (C.c_int32 * 3)(*[int(v) for v in dims])
+        lo3, hi3, d3 = _f3(lo), _f3(hi), _i3(dims)
         nv, nt = C.c_uint64(0), C.c_uint64(0)
         self._check(lib().exa_hip_isosurface(self.h, lo3, hi3, d3, int(channel), float(iso), flags, C.byref(nv), C.byref(nt),
                                              C.c_void_p(stream or 0)))
@@ -599,9 +593,7 @@ class Renderer:
 
     def histogramMs(self):
         """device ms of the last histogram / fieldStats call's kernel"""
-        ms = C.c_float(0)
-        self._check(lib().exa_hip_histogram_ms(self.h, C.byref(ms)))
-        return float(ms.value)
+        return self._ms(lib().exa_hip_histogram_ms)
 
     def fieldStats(self, channel, box=None):
         """value range (min, max), cell counts per level and the NaN / empty counts of `channel`, optionally inside a box: the
@@ -614,7 +606,7 @@ class Renderer:
         """integrate the field lines of the vector field `channels` from seeds [n,3] (voxel space) into module-owned device
         memory; returns the number of vertices.  readStreamlines copies them out, releaseStreamlines frees them."""
         pts = np.ascontiguousarray(seeds, dtype=np.float32).reshape(-1, 3)
-        ch3 = (C.c_int32 * 3)(*[int(c) for c in channels])
+        ch3 = _i3(channels)
         flags = (STREAM_FORWARD if forward else 0) | (STREAM_BACKWARD if backward else 0)
         flags |= (STREAM_NORMALIZE if normalize else 0) | (STREAM_VELOCITIES if velocities else 0)
         nv = C.c_uint64(0)
@@ -643,9 +635,7 @@ class Renderer:
 
     def streamlinesMs(self):
         """device ms of the last extraction's two kernels (count and emit), summed"""
-        ms = C.c_float(0)
-        self._check(lib().exa_hip_streamlines_ms(self.h, C.byref(ms)))
-        return float(ms.value)
+        return self._ms(lib().exa_hip_streamlines_ms)
 
     def streamlines(self, seeds, channels=(0, 1, 2), step=0.5, max_steps=1000, forward=True, backward=False, normalize=False,
                     velocities=False):
@@ -673,7 +663,7 @@ class Renderer:
         flags = self._probe_world(world) | (PROJECT_NORMALIZE if normalize else 0)
         rays = ExaHipRays()
         for name, v in (("org", org), ("orgDu", orgDu), ("orgDv", orgDv), ("dir", dir), ("dirDu", dirDu), ("dirDv", dirDv)):
-            setattr(rays, name, (C.c_float * 3)(*[float(c) for c in v]))
+            setattr(rays, name, _f3(v))
         rays.width, rays.height = int(size[0]), int(size[1])
         rays.tmin, rays.dt, rays.numSamples = float(tmin), float(dt), int(num_samples)
         shape = (max(rays.height, 0), max(rays.width, 0))                      # the module checks the size
@@ -688,9 +678,15 @@ class Renderer:
 
     def projectMs(self):
         """device ms of the last project call's kernel launches, summed"""
-        ms = C.c_float(0)
-        self._check(lib().exa_hip_project_ms(self.h, C.byref(ms)))
-        return float(ms.value)
+        return self._ms(lib().exa_hip_project_ms)
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(c) for c in v])
+
+
+def _i3(v):
+    return (C.c_int32 * 3)(*[int(c) for c in v])
 
 
 def _dev_ptr(x):

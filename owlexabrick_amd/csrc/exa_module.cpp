@@ -236,9 +236,9 @@ int exa_hip_set_option(ExaHipRenderer *h, const char *key, int32_t value)
   }
   if (!std::strcmp(key, "sample_patch")) {
     if (value < 0 || value >= kSamplePatchShapes) { h->fail("exa_hip_set_option: sample_patch is 0 (64x1x1), 1 (16x4x1), 2 (8x8x1) or 3 (4x4x4)"); return 1; }
-    h->samplePatch = value; return 0;
+    h->probes.patch = value; return 0;
   }
-  if (!std::strcmp(key, "sample_uniform")) { h->sampleUniform = value != 0; return 0; }
+  if (!std::strcmp(key, "sample_uniform")) { h->probes.uniform = value != 0; return 0; }
   if (!std::strcmp(key, "interleave")) { h->interleave = value != 0; return 0; }
   if (!std::strcmp(key, "addr64")) { h->addr64 = value != 0; return 0; }
   if (!std::strcmp(key, "pack_records")) { h->packRecords = value != 0; return 0; }

@@ -43,18 +43,28 @@ extern "C" {
 // kProbeLaunch points (a grid patch holds one point at the least: 64 x that many lanes stay below 2^32).
 static const uint64_t kProbeStageBytes = 64ull << 20, kProbeLaunch = 1ull << 24;
 
+// the next `bytes` of the staging buffer for a part of a chunk, nullptr for a part the call does not have; the parts come in
+// an order that leaves each aligned to its element
+static char *carve(char *&at, bool wanted, uint64_t bytes)
+{
+  if (!wanted) return nullptr;
+  char *part = at;
+  at += bytes;
+  return part;
+}
+
 int exa_hip_sample_points(ExaHipRenderer *h, const float *points, uint64_t n, const int32_t *channels, int32_t numChannels,
                           int32_t flags, float fill, float *values, float *gradients, int32_t *status,
                           int32_t pointersAreDevice, void *hipStream, int32_t async)
 {
   if (!h) return 1;
   const char *fn = "exa_hip_sample_points";
-  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED)) { h->fail(std::string(fn) + ": unknown flag bits"); return 1; }
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED, "")) return 1;
   const bool grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
   if ((flags & EXA_SAMPLE_GRADIENT_NORMALIZED) && !grad) { h->fail(std::string(fn) + ": EXA_SAMPLE_GRADIENT_NORMALIZED needs EXA_SAMPLE_GRADIENT"); return 1; }
   if (!channels || numChannels < 1 || numChannels > EXA_MAX_CHANNELS) { h->fail(std::string(fn) + ": 1..10 channels required"); return 1; }
   for (int c = 0; c < numChannels; c++)
-    if (channels[c] < 0 || channels[c] >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+    if (!checkChannel(h, fn, channels[c])) return 1;
   if (n == 0) return 0;
   if (!points || !values || (grad && !gradients)) { h->fail(std::string(fn) + ": null array (points, values, or gradients with EXA_SAMPLE_GRADIENT)"); return 1; }
   if (n > (UINT64_MAX / 12) / uint64_t(numChannels)) { h->fail(std::string(fn) + ": too many points"); return 1; }
@@ -85,16 +95,16 @@ int exa_hip_sample_points(ExaHipRenderer *h, const float *points, uint64_t n, co
   const uint64_t perPoint = 12 + nch * 4 * (1 + (grad ? 3 : 0) + (status ? 1 : 0));
   const uint64_t chunk = std::max<uint64_t>(1, std::min(kProbeLaunch, kProbeStageBytes / perPoint));
   const uint64_t need = std::min(n, chunk) * perPoint;
-  if (r->probeStage.n < need) HIP_TRY(h, r->probeStage.alloc(need));
+  if (r->probes.stage.n < need) HIP_TRY(h, r->probes.stage.alloc(need));
   for (uint64_t at = 0; at < n; at += chunk) {
     const uint64_t m = std::min(chunk, n - at);
-    char *p = r->probeStage.p;
+    char *cut = r->probes.stage.p;
     a.count = m;
-    a.points = reinterpret_cast<const float *>(p);
-    a.values = reinterpret_cast<float *>(p + 12 * m);
-    a.gradients = grad ? reinterpret_cast<float *>(p + 12 * m + 4 * m * nch) : nullptr;
-    a.status = status ? reinterpret_cast<int32_t *>(p + 12 * m + 4 * m * nch * (grad ? 4 : 1)) : nullptr;
-    HIP_TRY(h, hipMemcpyAsync(p, points + 3 * at, 12 * m, hipMemcpyHostToDevice, s));
+    a.points = reinterpret_cast<const float *>(carve(cut, true, 12 * m));
+    a.values = reinterpret_cast<float *>(carve(cut, true, 4 * m * nch));
+    a.gradients = reinterpret_cast<float *>(carve(cut, grad, 12 * m * nch));
+    a.status = reinterpret_cast<int32_t *>(carve(cut, status != nullptr, 4 * m * nch));
+    HIP_TRY(h, hipMemcpyAsync(r->probes.stage.p, points + 3 * at, 12 * m, hipMemcpyHostToDevice, s));
     HIP_TRY(h, EXA_FORM(r, launchSamplePoints)(a, grad, s));
     HIP_TRY(h, hipMemcpyAsync(values + at * nch, a.values, 4 * m * nch, hipMemcpyDeviceToHost, s));
     if (grad) HIP_TRY(h, hipMemcpyAsync(gradients + 3 * at * nch, a.gradients, 12 * m * nch, hipMemcpyDeviceToHost, s));
@@ -109,13 +119,13 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
 {
   if (!h) return 1;
   const char *fn = "exa_hip_resample";
-  if (flags & ~EXA_SAMPLE_WORLD_SPACE) { h->fail(std::string(fn) + ": unknown flag bits (only EXA_SAMPLE_WORLD_SPACE applies)"); return 1; }
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE, " (only EXA_SAMPLE_WORLD_SPACE applies)")) return 1;
   if (!lo || !hi || !dims || !out) { h->fail(std::string(fn) + ": null argument"); return 1; }
   for (int k = 0; k < 3; k++) {
     if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
     if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
   }
-  if (channel < 0 || channel >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  if (!checkChannel(h, fn, channel)) return 1;
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
@@ -126,13 +136,13 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
   a.fieldOffset[0] = r->sc.channelOffset[channel];
   for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
   static const int kShape[kSamplePatchShapes][3] = { { 64, 1, 1 }, { 16, 4, 1 }, { 8, 8, 1 }, { 4, 4, 4 } };
-  const int *ps = kShape[r->samplePatch];
+  const int *ps = kShape[r->probes.patch];
   const uint64_t nx = uint64_t(dims[0]), ny = uint64_t(dims[1]), nz = uint64_t(dims[2]);
   // boxes of at most kProbeLaunch points: whole slabs of z, else rows of one slice, else pieces of one row — each one
   // contiguous in the output, so a host destination takes one copy per box
   const uint64_t bx = std::min(nx, kProbeLaunch), by = std::min(ny, std::max<uint64_t>(1, kProbeLaunch / bx)),
                  bz = std::min(nz, std::max<uint64_t>(1, kProbeLaunch / (bx * by)));
-  if (!dstIsDevice && r->probeStage.n < bx * by * bz * 4) HIP_TRY(h, r->probeStage.alloc(bx * by * bz * 4));
+  if (!dstIsDevice && r->probes.stage.n < bx * by * bz * 4) HIP_TRY(h, r->probes.stage.alloc(bx * by * bz * 4));
   for (uint64_t z0 = 0; z0 < nz; z0 += bz)
     for (uint64_t y0 = 0; y0 < ny; y0 += by)
       for (uint64_t x0 = 0; x0 < nx; x0 += bx) {
@@ -146,9 +156,9 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
         if (dstIsDevice) {
           a.out = out + first; a.strideY = nx; a.strideZ = nx * ny;
         } else {
-          a.out = reinterpret_cast<float *>(r->probeStage.p); a.strideY = ex; a.strideZ = ex * ey;
+          a.out = reinterpret_cast<float *>(r->probes.stage.p); a.strideY = ex; a.strideZ = ex * ey;
         }
-        HIP_TRY(h, EXA_FORM(r, launchSampleGrid)(a, r->samplePatch, r->sampleUniform != 0, s));
+        HIP_TRY(h, EXA_FORM(r, launchSampleGrid)(a, r->probes.patch, r->probes.uniform != 0, s));
         if (!dstIsDevice) {
           HIP_TRY(h, hipMemcpyAsync(out + first, a.out, ex * ey * ez * sizeof(float), hipMemcpyDeviceToHost, s));
           HIP_TRY(h, hipStreamSynchronize(s));
@@ -160,14 +170,6 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
 }
 
 // ---- projections (sampleRaysKernel) ----
-namespace {
-struct ProjectEvents {
-  hipEvent_t ev[2] = { nullptr, nullptr };
-  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
-  ~ProjectEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-};
-} // namespace
-
 // The image goes tile by tile: a tile is at most kProjectTileWidth pixels wide and holds at most kProbeLaunch pixels — host
 // outputs: at most what kProbeStageBytes of the staging buffer hold —, whole 8 x 8 patches except at the image's edges.
 static const uint64_t kProjectTileWidth = 4096;
@@ -178,8 +180,8 @@ int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, 
   if (!h) return 1;
   const char *fn = "exa_hip_project";
   ExaHipRenderer *r = firstChild(h);
-  r->projectKernelMs = 0.f;
-  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_PROJECT_NORMALIZE)) { h->fail(std::string(fn) + ": unknown flag bits (EXA_SAMPLE_WORLD_SPACE and EXA_PROJECT_NORMALIZE apply)"); return 1; }
+  r->project.kernelMs = 0.f;
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_PROJECT_NORMALIZE, " (EXA_SAMPLE_WORLD_SPACE and EXA_PROJECT_NORMALIZE apply)")) return 1;
   if (!rays) { h->fail(std::string(fn) + ": null rays"); return 1; }
   const float *vec[6] = { rays->org, rays->orgDu, rays->orgDv, rays->dir, rays->dirDu, rays->dirDv };
   bool finite = std::isfinite(rays->tmin) && std::isfinite(rays->dt);
@@ -194,7 +196,7 @@ int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, 
     h->fail(std::string(fn) + ": width and height must be >= 1 and width * height <= 2^31 - 1");
     return 1;
   }
-  if (channel < 0 || channel >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  if (!checkChannel(h, fn, channel)) return 1;
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   RayArgs a;
@@ -206,12 +208,19 @@ int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, 
   a.normalize = (flags & EXA_PROJECT_NORMALIZE) ? 1 : 0;
 
   const uint64_t W = uint64_t(rays->width), H = uint64_t(rays->height);
-  const uint64_t perPixel = (sum ? 8 : 0) + (count ? 4 : 0) + (vmax ? 4 : 0) + (vmin ? 4 : 0) + (maxIndex ? 4 : 0);
+  // the five optional outputs, named once: the caller's array, the element size and where the kernel stores the current
+  // tile; the doubles first, so that every part of the staging buffer {sum | count | vmax | vmin | maxIndex} is aligned
+  struct Output { char *user; uint64_t size; char *dev; };
+  Output outs[5] = { { reinterpret_cast<char *>(sum), 8, nullptr }, { reinterpret_cast<char *>(count), 4, nullptr },
+                     { reinterpret_cast<char *>(vmax), 4, nullptr }, { reinterpret_cast<char *>(vmin), 4, nullptr },
+                     { reinterpret_cast<char *>(maxIndex), 4, nullptr } };
+  uint64_t perPixel = 0;
+  for (const Output &o : outs) perPixel += o.user ? o.size : 0;
   const bool staged = !pointersAreDevice && perPixel > 0;
   const uint64_t cap = staged ? std::min(kProbeLaunch, kProbeStageBytes / perPixel) : kProbeLaunch;
   const uint64_t tw = std::min(W, kProjectTileWidth), th = std::min(H, std::max<uint64_t>(8, (cap / tw) & ~uint64_t(7)));
-  if (staged && r->probeStage.n < tw * th * perPixel) HIP_TRY(h, r->probeStage.alloc(tw * th * perPixel));
-  ProjectEvents t;
+  if (staged && r->probes.stage.n < tw * th * perPixel) HIP_TRY(h, r->probes.stage.alloc(tw * th * perPixel));
+  TimingEvents<2> t;
   HIP_TRY(h, t.create());
   float total = 0.f;
   for (uint64_t y0 = 0; y0 < H; y0 += th)
@@ -220,64 +229,38 @@ int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, 
       a.x0 = int32_t(x0); a.y0 = int32_t(y0); a.x1 = int32_t(x0 + ex); a.y1 = int32_t(y0 + ey);
       a.patchesX = uint32_t((ex + 7) / 8);
       a.numPatches = uint64_t(a.patchesX) * ((ey + 7) / 8);
-      if (staged) {
-        // {sum | count | vmax | vmin | maxIndex} of the tile, rows of ex pixels; the doubles first: aligned
-        char *p = r->probeStage.p;
-        a.strideY = ex;
-        a.sum = sum ? reinterpret_cast<double *>(p) : nullptr;         p += sum ? 8 * ex * ey : 0;
-        a.count = count ? reinterpret_cast<uint32_t *>(p) : nullptr;   p += count ? 4 * ex * ey : 0;
-        a.vmax = vmax ? reinterpret_cast<float *>(p) : nullptr;        p += vmax ? 4 * ex * ey : 0;
-        a.vmin = vmin ? reinterpret_cast<float *>(p) : nullptr;        p += vmin ? 4 * ex * ey : 0;
-        a.maxIndex = maxIndex ? reinterpret_cast<int32_t *>(p) : nullptr;
-      } else {
-        a.strideY = W;
-        a.sum = sum ? sum + first : nullptr;
-        a.count = count ? count + first : nullptr;
-        a.vmax = vmax ? vmax + first : nullptr;
-        a.vmin = vmin ? vmin + first : nullptr;
-        a.maxIndex = maxIndex ? maxIndex + first : nullptr;
-      }
+      // a staged tile: rows of ex pixels in the staging buffer; else straight into the caller's device arrays
+      char *cut = r->probes.stage.p;
+      a.strideY = staged ? ex : W;
+      for (Output &o : outs) o.dev = staged ? carve(cut, o.user != nullptr, o.size * ex * ey) : (o.user ? o.user + o.size * first : nullptr);
+      a.sum = reinterpret_cast<double *>(outs[0].dev);
+      a.count = reinterpret_cast<uint32_t *>(outs[1].dev);
+      a.vmax = reinterpret_cast<float *>(outs[2].dev);
+      a.vmin = reinterpret_cast<float *>(outs[3].dev);
+      a.maxIndex = reinterpret_cast<int32_t *>(outs[4].dev);
       HIP_TRY(h, hipEventRecord(t.ev[0], s));
-      HIP_TRY(h, EXA_FORM(r, launchSampleRays)(a, r->sampleUniform != 0, s));
+      HIP_TRY(h, EXA_FORM(r, launchSampleRays)(a, r->probes.uniform != 0, s));
       HIP_TRY(h, hipEventRecord(t.ev[1], s));
-      if (staged) {
-        if (sum) HIP_TRY(h, hipMemcpy2DAsync(sum + first, W * 8, a.sum, ex * 8, ex * 8, ey, hipMemcpyDeviceToHost, s));
-        if (count) HIP_TRY(h, hipMemcpy2DAsync(count + first, W * 4, a.count, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
-        if (vmax) HIP_TRY(h, hipMemcpy2DAsync(vmax + first, W * 4, a.vmax, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
-        if (vmin) HIP_TRY(h, hipMemcpy2DAsync(vmin + first, W * 4, a.vmin, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
-        if (maxIndex) HIP_TRY(h, hipMemcpy2DAsync(maxIndex + first, W * 4, a.maxIndex, ex * 4, ex * 4, ey, hipMemcpyDeviceToHost, s));
-      }
+      if (staged)
+        for (const Output &o : outs)
+          if (o.user) HIP_TRY(h, hipMemcpy2DAsync(o.user + o.size * first, W * o.size, o.dev, ex * o.size, ex * o.size, ey, hipMemcpyDeviceToHost, s));
       HIP_TRY(h, hipStreamSynchronize(s));
       float ms = 0.f;
-      HIP_TRY(h, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+      HIP_TRY(h, t.elapsed(0, 1, &ms));
       total += ms;
     }
-  r->projectKernelMs = total;
+  r->project.kernelMs = total;
   return checkLoopGuard(h, r, fn, kDescentGuard);
 }
 
 int exa_hip_project_ms(ExaHipRenderer *h, float *ms)
 {
   if (!h || !ms) return 1;
-  *ms = firstChild(h)->projectKernelMs;
+  *ms = firstChild(h)->project.kernelMs;
   return 0;
 }
 
 // ---- iso-surface extraction (exa_isomesh.hip) ----
-static void isoRelease(ExaHipRenderer *r)
-{
-  r->isoVertices.release(); r->isoGradients.release(); r->isoTriangles.release();
-  r->haveIsoMesh = false;
-}
-
-namespace {
-struct IsoEvents {
-  hipEvent_t ev[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
-  ~IsoEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-};
-} // namespace
-
 int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
                        int32_t flags, uint64_t *numVertices, uint64_t *numTriangles, void *hipStream)
 {
@@ -285,7 +268,7 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
   const char *fn = "exa_hip_isosurface";
   if (numVertices) *numVertices = 0;
   if (numTriangles) *numTriangles = 0;
-  if (flags & ~(EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT)) { h->fail(std::string(fn) + ": unknown flag bits (EXA_SAMPLE_WORLD_SPACE and EXA_SAMPLE_GRADIENT apply)"); return 1; }
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT, " (EXA_SAMPLE_WORLD_SPACE and EXA_SAMPLE_GRADIENT apply)")) return 1;
   if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument"); return 1; }
   if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
   for (int k = 0; k < 3; k++)
@@ -295,8 +278,9 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
-  isoRelease(r);
-  for (float &ms : r->isoStageMs) ms = 0.f;
+  r->isoMesh.release();
+  DropUnlessCommitted<ExaHipRenderer::IsoMesh> mesh(r->isoMesh);     // whatever fails from here on leaves no mesh
+  for (float &ms : r->isoMesh.stageMs) ms = 0.f;
   const bool world = (flags & EXA_SAMPLE_WORLD_SPACE) != 0, grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
 
   IsoMeshArgs a;
@@ -309,18 +293,13 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
   a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
   // the work space of one extraction, freed when the call returns: values | chunkBase, totals | blockCount, blockBase |
   // rel | cubeInfo, mask (every part aligned to its element)
-  auto fail = [&](hipError_t e, const char *what) {
-    (void)hipGetLastError();
-    h->fail(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
-    return 1;
-  };
   DevBuf<float> values;
   DevBuf<char> work;
   const size_t n64 = 2 * size_t(a.numChunks) + 2, n32 = 4 * size_t(a.numBlocks);
   const size_t n16 = n + (n & 1), workBytes = n64 * 8 + n32 * 4 + n16 * 2 + 2 * n;
   hipError_t e = values.alloc(n);
   if (e == hipSuccess) e = work.alloc(workBytes);
-  if (e != hipSuccess) return fail(e, "no device memory for the lattice (4 bytes per point) and the work space (4 more)");
+  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the work space (4 more)", e);
   a.values = values.p;
   a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
   a.totals = a.chunkBase + 2 * size_t(a.numChunks);
@@ -330,7 +309,7 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
   a.cubeInfo = reinterpret_cast<uint8_t *>(work.p + n64 * 8 + n32 * 4 + n16 * 2);
   a.mask = a.cubeInfo + n;
 
-  IsoEvents t;
+  TimingEvents<7> t;
   HIP_TRY(h, t.create());
   // the lattice: exa_hip_resample with a NaN fill into the device buffer (its checks of the box, the channel, the kd
   // tree and the frame state apply; synchronous, with the loop guard's check)
@@ -355,12 +334,12 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
     return 1;
   }
   if (totals[0] && totals[1]) {
-    e = r->isoVertices.alloc(3 * size_t(totals[0]));
-    if (e == hipSuccess) e = r->isoTriangles.alloc(3 * size_t(totals[1]));
-    if (e == hipSuccess && grad) e = r->isoGradients.alloc(3 * size_t(totals[0]));
-    if (e != hipSuccess) { isoRelease(r); return fail(e, "no device memory for the mesh"); }
-    a.vertices = r->isoVertices.p;
-    a.triangles = r->isoTriangles.p;
+    e = r->isoMesh.vertices.alloc(3 * size_t(totals[0]));
+    if (e == hipSuccess) e = r->isoMesh.triangles.alloc(3 * size_t(totals[1]));
+    if (e == hipSuccess && grad) e = r->isoMesh.gradients.alloc(3 * size_t(totals[0]));
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the mesh", e);
+    a.vertices = r->isoMesh.vertices.p;
+    a.triangles = r->isoMesh.triangles.p;
     HIP_TRY(h, launchIsoEmit(a, s));
   }
   HIP_TRY(h, hipEventRecord(t.ev[5], s));
@@ -371,20 +350,20 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
     float *vals = values.p;
     if (totals[0] > n) {
       e = scratch.alloc(size_t(totals[0]));
-      if (e != hipSuccess) { isoRelease(r); return fail(e, "no device memory for the gradients"); }
+      if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the gradients", e);
       vals = scratch.p;
     }
     const int32_t pf = (world ? EXA_SAMPLE_WORLD_SPACE : 0) | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
-    if (int rc = exa_hip_sample_points(h, r->isoVertices.p, totals[0], &channel, 1, pf, NAN, vals, r->isoGradients.p, nullptr, 1, hipStream, 0)) {
+    if (int rc = exa_hip_sample_points(h, r->isoMesh.vertices.p, totals[0], &channel, 1, pf, NAN, vals, r->isoMesh.gradients.p, nullptr, 1, hipStream, 0)) {
       h->fail(std::string(fn) + ": " + h->err);
-      isoRelease(r);
       return rc;
     }
   }
   HIP_TRY(h, hipEventRecord(t.ev[6], s));
   HIP_TRY(h, hipStreamSynchronize(s));
-  for (int k = 0; k < 6; k++) HIP_TRY(h, hipEventElapsedTime(&r->isoStageMs[k], t.ev[k], t.ev[k + 1]));
-  r->haveIsoMesh = true;
+  for (int k = 0; k < 6; k++) HIP_TRY(h, t.elapsed(k, k + 1, &r->isoMesh.stageMs[k]));
+  r->isoMesh.have = true;
+  mesh.commit();
   if (numVertices) *numVertices = totals[0];
   if (numTriangles) *numTriangles = totals[1];
   return 0;
@@ -396,14 +375,14 @@ int exa_hip_isosurface_read(ExaHipRenderer *h, float *vertices, float *gradients
   if (!h) return 1;
   const char *fn = "exa_hip_isosurface_read";
   ExaHipRenderer *r = firstChild(h);
-  if (!r->haveIsoMesh) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
-  if (gradients && r->isoVertices.n && !r->isoGradients.n) { h->fail(std::string(fn) + ": the mesh was extracted without EXA_SAMPLE_GRADIENT"); return 1; }
+  if (!r->isoMesh.have) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
+  if (gradients && r->isoMesh.vertices.n && !r->isoMesh.gradients.n) { h->fail(std::string(fn) + ": the mesh was extracted without EXA_SAMPLE_GRADIENT"); return 1; }
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (vertices && r->isoVertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, r->isoVertices.p, r->isoVertices.n * sizeof(float), kind, s));
-  if (gradients && r->isoGradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, r->isoGradients.p, r->isoGradients.n * sizeof(float), kind, s));
-  if (triangles && r->isoTriangles.n) HIP_TRY(h, hipMemcpyAsync(triangles, r->isoTriangles.p, r->isoTriangles.n * sizeof(int32_t), kind, s));
+  if (vertices && r->isoMesh.vertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, r->isoMesh.vertices.p, r->isoMesh.vertices.n * sizeof(float), kind, s));
+  if (gradients && r->isoMesh.gradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, r->isoMesh.gradients.p, r->isoMesh.gradients.n * sizeof(float), kind, s));
+  if (triangles && r->isoMesh.triangles.n) HIP_TRY(h, hipMemcpyAsync(triangles, r->isoMesh.triangles.p, r->isoMesh.triangles.n * sizeof(int32_t), kind, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   return 0;
 }
@@ -413,7 +392,7 @@ int exa_hip_isosurface_release(ExaHipRenderer *h)
   if (!h) return 1;
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
-  isoRelease(r);
+  r->isoMesh.release();
   return 0;
 }
 
@@ -421,7 +400,7 @@ int exa_hip_isosurface_stage_ms(ExaHipRenderer *h, float ms[6])
 {
   if (!h || !ms) return 1;
   const ExaHipRenderer *r = firstChild(h);
-  for (int k = 0; k < 6; k++) ms[k] = r->isoStageMs[k];
+  for (int k = 0; k < 6; k++) ms[k] = r->isoMesh.stageMs[k];
   return 0;
 }
 

@@ -1,8 +1,10 @@
 // exa_renderer.h — internal to the exa_hip_* module (not installed): the renderer behind the opaque ExaHipRenderer handle
 // of include/exa_hip.h and the helpers its translation units share.  exa_create.cpp builds and destroys a renderer,
-// exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes and the iso-surface extraction,
-// exa_streamlines.cpp the streamline extraction,
-// exa_stats.cpp the histogram and value range of the cells, exa_module.cpp the setters, options and read-backs.
+// exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes, the projections along rays and the
+// iso-surface extraction, exa_streamlines.cpp the streamline extraction, exa_stats.cpp the histogram and value range of
+// the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
+// one struct per call (ExaHipRenderer::probes, isoMesh, hist, lines, project); TimingEvents, DropUnlessCommitted and the
+// argument checks below the renderer are what their host code shares.
 #pragma once
 #include "exa_device.h"
 #include "exa_ropes.h"
@@ -50,13 +52,15 @@ template <typename T>
 struct DevBuf {
   T *p = nullptr;
   size_t n = 0;
+  // a failed allocation leaves the buffer empty, {nullptr, 0, 0}: a guard `if (buf.n < need)` asks again the next time
   hipError_t alloc(size_t count)
   {
     release();
-    n = count;
     if (count == 0) return hipSuccess;
     // 16 spare bytes: the pair load of a one-cell-wide row reads one float past the last brick
-    return hipMalloc((void **)&p, count * sizeof(T) + 16);
+    const hipError_t e = hipMalloc((void **)&p, count * sizeof(T) + 16);
+    if (e == hipSuccess) n = count; else p = nullptr;
+    return e;
   }
   hipError_t upload(const T *src, size_t count)
   {
@@ -78,6 +82,29 @@ struct DevBuf {
   size_t cap = 0;
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; cap = 0; }
   ~DevBuf() { release(); }
+};
+
+// the events around the timed stages of a synchronous call, destroyed when it returns
+template <int N>
+struct TimingEvents {
+  hipEvent_t ev[N] = {};
+  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
+  hipError_t elapsed(int i, int j, float *ms) const { return hipEventElapsedTime(ms, ev[i], ev[j]); }
+  ~TimingEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// A result that a call builds on the handle piece by piece (ExaHipRenderer::isoMesh, lines): whatever way the call
+// leaves, release() drops the pieces unless it got as far as commit().  Declared behind the call's DeviceGuard, so that
+// the buffers are freed on the handle's device.
+template <typename T>
+struct DropUnlessCommitted {
+  T &result;
+  bool committed = false;
+  explicit DropUnlessCommitted(T &r) : result(r) {}
+  ~DropUnlessCommitted() { if (!committed) result.release(); }
+  void commit() { committed = true; }
+  DropUnlessCommitted(const DropUnlessCommitted &) = delete;
+  DropUnlessCommitted &operator=(const DropUnlessCommitted &) = delete;
 };
 
 struct ExaHipRenderer {
@@ -255,34 +282,51 @@ struct ExaHipRenderer {
   DevBuf<int32_t> errorFlag;
   // point probes (exa_hip_sample_points / exa_hip_resample): the device copy of a chunk of host arrays (bounded, grown on
   // demand), and the grid kernel's patch shape / wave-uniform path (options sample_patch, sample_uniform)
-  DevBuf<char> probeStage;
-  int samplePatch = 3, sampleUniform = 1;
+  struct Probes {
+    DevBuf<char> stage;
+    int patch = 3, uniform = 1;
+  } probes;
   // the mesh of the last exa_hip_isosurface (on a multi-device handle: in the renderer of devices[0]) and the time its
   // stages took (lattice values, cube pass, point pass, scans, emit, gradients)
-  DevBuf<float> isoVertices, isoGradients;
-  DevBuf<int32_t> isoTriangles;
-  bool haveIsoMesh = false;
-  float isoStageMs[6] = { 0, 0, 0, 0, 0, 0 };
+  struct IsoMesh {
+    DevBuf<float> vertices, gradients;
+    DevBuf<int32_t> triangles;
+    bool have = false;
+    float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
+    void release() { vertices.release(); gradients.release(); triangles.release(); have = false; }
+  } isoMesh;
   // exa_hip_histogram (on a multi-device handle: in the renderer of devices[0]): the work list of the pass — segments
   // {brick, first cell} by level and the offsets of the runs, built by the first call (exa_stats.cpp) —, whether the scene's
   // volume-weighted cell count fits 64 bits, the device copy of a call's result and the device time of its kernel
-  DevBuf<uint4> histSegs;
-  DevBuf<uint32_t> histRuns;
-  uint32_t histNumRuns = 0;
-  bool histPlanBuilt = false, histVolumeFits = true;
-  DevBuf<unsigned long long> histResult;
-  float histKernelMs = 0.f;
+  struct Histogram {
+    DevBuf<uint4> segs;
+    DevBuf<uint32_t> runs;
+    uint32_t numRuns = 0;
+    bool planBuilt = false, volumeFits = true;
+    DevBuf<unsigned long long> result;
+    float kernelMs = 0.f;
+  } hist;
   // the lines of the last exa_hip_streamlines (on a multi-device handle: in the renderer of devices[0]), packed, and the
   // device time of its two kernels
-  DevBuf<float> streamVertices, streamVelocities;
-  DevBuf<unsigned long long> streamOffsets;
-  DevBuf<uint32_t> streamSeedVertex;
-  DevBuf<int32_t> streamReasons;
-  uint64_t streamSeeds = 0, streamNumVertices = 0;
-  bool haveStreamlines = false;
-  float streamKernelMs = 0.f;
+  struct Streamlines {
+    DevBuf<float> vertices, velocities;
+    DevBuf<unsigned long long> offsets;
+    DevBuf<uint32_t> seedVertex;
+    DevBuf<int32_t> reasons;
+    uint64_t seeds = 0, numVertices = 0;
+    bool have = false;
+    float kernelMs = 0.f;
+    void release()
+    {
+      vertices.release(); velocities.release(); offsets.release(); seedVertex.release(); reasons.release();
+      seeds = 0; numVertices = 0;
+      have = false;
+    }
+  } lines;
   // the device time of the last exa_hip_project's kernel launches, summed (in the renderer of devices[0])
-  float projectKernelMs = 0.f;
+  struct Projection {
+    float kernelMs = 0.f;
+  } project;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 
@@ -352,6 +396,28 @@ inline int levelOfWidth(float w) { int lv = 0; while (lv < 31 && float(1 << lv) 
 inline uint32_t packLeafRec(int32_t listBegin, int32_t listSize, float width, uint32_t bb, uint32_t sb)
 {
   return uint32_t(listBegin) | (uint32_t(listSize - 1) << bb) | (uint32_t(levelOfWidth(width)) << (bb + sb));
+}
+
+// Argument checks that three or more calls state, each with one wording: false after h has failed with it
+inline bool checkChannel(ExaHipRenderer *h, const char *fn, int32_t channel)
+{
+  if (channel >= 0 && channel < h->numFields) return true;
+  h->fail(std::string(fn) + ": channel out of range");
+  return false;
+}
+// hint: the call's own words in parentheses on what applies, or ""
+inline bool checkFlags(ExaHipRenderer *h, const char *fn, int32_t flags, int32_t known, const char *hint)
+{
+  if (!(flags & ~known)) return true;
+  h->fail(std::string(fn) + ": unknown flag bits" + hint);
+  return false;
+}
+// an allocation of a call failed with e: clears the runtime's sticky error, h fails with "fn: what: <e>"; returns 1
+inline int failNoMemory(ExaHipRenderer *h, const char *fn, const char *what, hipError_t e)
+{
+  (void)hipGetLastError();
+  h->fail(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
+  return 1;
 }
 
 // Reads and clears the loop guard of r's kernels; when it tripped, h (r or its multi-device handle) fails with fn + what

@@ -13,7 +13,7 @@
 // brick's cell units; EXA_SAMPLE_GRADIENT_NORMALIZED takes them in voxel units instead (addBasisFast<.., VOXEL>: each
 // brick's terms times its 2^-level) and divides by sumW^2: the gradient of sumWV / sumW with respect to the position.
 
-#include "exa_sample_locate.h"   // sampleInRoot, sampleKdChild, sampleKdLeaf, sampleInDomain
+#include "exa_sample_locate.h"   // sampleInRoot, sampleKdChild, sampleKdLeaf, sampleKdLeafWave, sampleInDomain
 
 // samplePoint's sums (exabrick.cu:781-806, 883-928) over the region's bricks, through the march headers: the loop of
 // samplePoint with fastSampler.  listBegin / listSize wave-uniform -> the headers are read once per wave.
@@ -78,6 +78,17 @@ template <bool DERIV>
 __global__ __launch_bounds__(256) void samplePointsKernel(const SampleArgs a) { samplePointsBody<DERIV, false>(a); }
 __global__ __launch_bounds__(256) void samplePointsNormKernel(const SampleArgs a) { samplePointsBody<true, true>(a); }
 
+// a sample whose region record is R: the closed-domain test and the sums of samplePointsBody; false, v untouched, outside the
+// domain (status -1) and where the basis weights vanish (status -2).  R by value: the whole record is read up front
+__device__ __forceinline__ bool sampleValue(const SampleArgs &a, const RegionRec R, const float *field, V3 p, float &v)
+{
+  if (!sampleInDomain(R, p)) return false;
+  const Basis B = sampleSums<false>(a, R.listBegin, R.listSize, field, p);
+  if (B.sumW <= 1e-20f) return false;
+  v = B.sumWV / B.sumW;
+  return true;
+}
+
 // One wave per patch of PX x PY x PZ = 64 grid points (lane -> point x fastest).  UNIFORM: the wave descends the tree
 // together while all its lanes (those inside the root box) take the same side of every plane — the node index is
 // wave-uniform, one scalar load per node — then each lane on its own from there; when all lanes land in the same region,
@@ -99,41 +110,15 @@ __global__ __launch_bounds__(256) void sampleGridKernel(const SampleArgs a)
   if (x >= a.box1[0] || y >= a.box1[1] || z >= a.box1[2]) return;
   V3 p = mk(a.lo[0] + (float(x) + 0.5f) * a.step[0], a.lo[1] + (float(y) + 0.5f) * a.step[1], a.lo[2] + (float(z) + 0.5f) * a.step[2]);
   if (a.world) p = xfmPoint(a.fs, p);
-  const bool inRoot = sampleInRoot(a, p);
   bool tripped = false;
   int region = -1;
-  if (inRoot) {
-    int ref = a.kdRoot;
-    if (UNIFORM) {
-      for (int g = 0; ref >= 0 && g < a.maxSteps; g++) {
-        const int u = __builtin_amdgcn_readfirstlane(ref);           // the same in every lane here
-        const int next = sampleKdChild(a.kdNodes[u], p);
-        if (anyLane(next != __builtin_amdgcn_readfirstlane(next))) break;   // the lanes part at this node
-        ref = next;
-      }
-    }
-    region = sampleKdLeaf(a, ref, p, tripped);
-  }
+  if (sampleInRoot(a, p)) region = sampleKdLeafWave<UNIFORM>(a, p, tripped);
   if (tripped) atomicExch(a.errorFlag, 1);
   const float *field = a.scalars + a.fieldOffset[0];
   const int r0 = __builtin_amdgcn_readfirstlane(region);
   float value = a.fill;
-  int st = -1;
-  if (UNIFORM && r0 >= 0 && !anyLane(region != r0)) {
-    const RegionRec R = a.regionRec[r0];                               // wave-uniform index: one record per wave
-    if (sampleInDomain(R, p)) {
-      const Basis B = sampleSums<false>(a, R.listBegin, R.listSize, field, p);
-      st = B.sumW <= 1e-20f ? -2 : r0;
-      if (st >= 0) value = B.sumWV / B.sumW;
-    }
-  } else if (region >= 0) {
-    const RegionRec R = a.regionRec[region];
-    if (sampleInDomain(R, p)) {
-      const Basis B = sampleSums<false>(a, R.listBegin, R.listSize, field, p);
-      st = B.sumW <= 1e-20f ? -2 : region;
-      if (st >= 0) value = B.sumWV / B.sumW;
-    }
-  }
+  if (UNIFORM && r0 >= 0 && !anyLane(region != r0)) sampleValue(a, a.regionRec[r0], field, p, value);   // wave-uniform index: one record per wave
+  else if (region >= 0) sampleValue(a, a.regionRec[region], field, p, value);
   const size_t o = size_t(x - a.box0[0]) + size_t(y - a.box0[1]) * size_t(a.strideY) + size_t(z - a.box0[2]) * size_t(a.strideZ);
   a.out[o] = value;
 }
@@ -163,13 +148,11 @@ __device__ __forceinline__ bool rayNotLeft(const SampleArgs &s, V3 d, V3 p)
 // the reduction of one pixel, in registers
 struct RayAcc { double sum; uint32_t count; float vmax, vmin; int32_t maxIndex; };
 
-// one sample whose lane has a region: the closed-domain test and the sums of samplePointsBody, then the contract's updates
+// one sample whose lane has a region: where it is valid (sampleValue), the contract's updates
 __device__ __forceinline__ void rayAccumulate(const RayArgs &a, const RegionRec &R, const float *field, V3 p, int i, RayAcc &acc)
 {
-  if (!sampleInDomain(R, p)) return;
-  const Basis B = sampleSums<false>(a.s, R.listBegin, R.listSize, field, p);
-  if (B.sumW <= 1e-20f) return;                                         // status -2
-  const float v = B.sumWV / B.sumW;
+  float v;
+  if (!sampleValue(a.s, R, field, p, v)) return;
   acc.count++;
   acc.sum += double(v);
   if (v > acc.vmax) { acc.vmax = v; acc.maxIndex = i; }
@@ -255,18 +238,7 @@ __global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
     V3 p = rayPos(a, o, d, i);
     if (a.s.world) p = xfmPoint(a.s.fs, p);
     int region = -1;
-    if (i >= beg && i < end && sampleInRoot(a.s, p)) {
-      int ref = a.s.kdRoot;
-      if (UNIFORM) {
-        for (int g = 0; ref >= 0 && g < a.s.maxSteps; g++) {
-          const int u = __builtin_amdgcn_readfirstlane(ref);           // the same in every lane here
-          const int next = sampleKdChild(a.s.kdNodes[u], p);
-          if (anyLane(next != __builtin_amdgcn_readfirstlane(next))) break;   // the lanes part at this node
-          ref = next;
-        }
-      }
-      region = sampleKdLeaf(a.s, ref, p, tripped);
-    }
+    if (i >= beg && i < end && sampleInRoot(a.s, p)) region = sampleKdLeafWave<UNIFORM>(a.s, p, tripped);
     if (region >= 0) {
       const int r0 = __builtin_amdgcn_readfirstlane(region);           // of the lanes that have a region
       if (UNIFORM && !anyLane(region != r0)) {

@@ -26,6 +26,24 @@ __device__ __forceinline__ int sampleKdLeaf(const SampleArgs &a, int ref, V3 p, 
   return ref == EXA_KD_EMPTY ? -1 : ~ref;
 }
 
+// the same for a wave whose positions lie close together (called by every lane that is inside the root box).  UNIFORM: the
+// wave descends from the root together while all these lanes take the same side of every plane, then each lane on its own
+// from where they part
+template <bool UNIFORM>
+__device__ __forceinline__ int sampleKdLeafWave(const SampleArgs &a, V3 p, bool &tripped)
+{
+  int ref = a.kdRoot;
+  if (UNIFORM) {
+    for (int g = 0; ref >= 0 && g < a.maxSteps; g++) {
+      const int u = __builtin_amdgcn_readfirstlane(ref);           // the same in every lane here
+      const int next = sampleKdChild(a.kdNodes[u], p);
+      if (anyLane(next != __builtin_amdgcn_readfirstlane(next))) break;   // the lanes part at this node
+      ref = next;
+    }
+  }
+  return sampleKdLeaf(a, ref, p, tripped);
+}
+
 __device__ __forceinline__ bool sampleInDomain(const RegionRec &R, V3 p)
 {
   return p.x >= R.lo[0] && p.x <= R.hi0 && p.y >= R.lo[1] && p.y <= R.hi1 && p.z >= R.lo[2] && p.z <= R.hi2;

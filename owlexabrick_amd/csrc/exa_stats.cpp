@@ -19,7 +19,7 @@ const uint64_t kHistTargetRuns = 4096, kHistRunMinCells = 4 * uint64_t(kHistSegC
 // volume-weighted total fits 64 bits.  The brick geometry comes back from the device's own list.
 int buildHistPlan(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn)
 {
-  if (r->histPlanBuilt) return 0;
+  if (r->hist.planBuilt) return 0;
   std::vector<ExaBrick> bricks(r->numBricks);
   HIP_TRY(h, hipMemcpy(bricks.data(), r->bricks.p, bricks.size() * sizeof(ExaBrick), hipMemcpyDeviceToHost));
   uint64_t segsOfLevel[kHistLevels] = {}, cellsOfLevel[kHistLevels] = {}, slots = 0;
@@ -73,20 +73,13 @@ int buildHistPlan(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn)
   }
   const uint32_t numRuns = uint32_t(runs.size());
   runs.push_back(uint32_t(numSegs));
-  HIP_TRY(h, r->histSegs.upload(reinterpret_cast<const uint4 *>(segs.data()), segs.size()));
-  HIP_TRY(h, r->histRuns.upload(runs.data(), runs.size()));
-  r->histNumRuns = numRuns;
-  r->histVolumeFits = fits;
-  r->histPlanBuilt = true;
+  HIP_TRY(h, r->hist.segs.upload(reinterpret_cast<const uint4 *>(segs.data()), segs.size()));
+  HIP_TRY(h, r->hist.runs.upload(runs.data(), runs.size()));
+  r->hist.numRuns = numRuns;
+  r->hist.volumeFits = fits;
+  r->hist.planBuilt = true;
   return 0;
 }
-
-// the two events around a call's kernel (exa_hip_histogram_ms)
-struct HistEvents {
-  hipEvent_t ev[2] = { nullptr, nullptr };
-  hipError_t create() { for (auto &e : ev) { hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
-  ~HistEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-};
 
 float keyToFloat(uint32_t key)
 {
@@ -103,7 +96,7 @@ extern "C" int exa_hip_histogram(ExaHipRenderer *h, int32_t channel, float lo, f
 {
   if (!h) return 1;
   const char *fn = "exa_hip_histogram";
-  if (channel < 0 || channel >= h->numFields) { h->fail(std::string(fn) + ": channel out of range"); return 1; }
+  if (!checkChannel(h, fn, channel)) return 1;
   if (numBins < 0 || numBins > EXA_HIST_MAX_BINS) { h->fail(std::string(fn) + ": numBins must be 0 (range only) .. 4096"); return 1; }
   float scale = 0.f;
   if (numBins > 0) {
@@ -126,38 +119,38 @@ extern "C" int exa_hip_histogram(ExaHipRenderer *h, int32_t channel, float lo, f
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   if (buildHistPlan(h, r, fn)) return 1;
-  if (volume && !r->histVolumeFits) { h->fail(std::string(fn) + ": the scene's volume in finest voxels (cells x 8^level over all bricks) does not fit 64 bits: pass volume = NULL"); return 1; }
+  if (volume && !r->hist.volumeFits) { h->fail(std::string(fn) + ": the scene's volume in finest voxels (cells x 8^level over all bricks) does not fit 64 bits: pass volume = NULL"); return 1; }
   if (r->applyBrickOrder(s)) { h->fail(r->err); return 1; }
 
   const size_t words = histResultWords(uint32_t(numBins)), statAt = 2 * size_t(numBins);
   std::vector<unsigned long long> res(words, 0ull);
   res[words - 1] = 0x00000000ffffffffull;                       // {min key, max key} of no value
-  r->histKernelMs = 0.f;
+  r->hist.kernelMs = 0.f;
   if (!emptyBox) {
-    HistEvents t;
+    TimingEvents<2> t;                                          // around the call's kernel (exa_hip_histogram_ms)
     HIP_TRY(h, t.create());
-    if (r->histResult.n < words) HIP_TRY(h, r->histResult.alloc(histResultWords(kHistMaxBins)));
+    if (r->hist.result.n < words) HIP_TRY(h, r->hist.result.alloc(histResultWords(kHistMaxBins)));
     HistArgs a;
     std::memset(&a, 0, sizeof(a));
     a.bricks = r->bricks.p;
     a.field = r->scalars.p + r->sc.channelOffset[channel];
-    a.segs = reinterpret_cast<const HistSeg *>(r->histSegs.p);
-    a.runBegin = r->histRuns.p;
-    a.numRuns = r->histNumRuns;
+    a.segs = reinterpret_cast<const HistSeg *>(r->hist.segs.p);
+    a.runBegin = r->hist.runs.p;
+    a.numRuns = r->hist.numRuns;
     a.numBins = numBins;
     a.lo = lo; a.hi = hi; a.scale = scale;
     a.emptyCells = r->emptyCells ? 1 : 0;
     a.hasBox = box ? 1 : 0;
     if (box) for (int k = 0; k < 6; k++) a.box[k] = box[k];
     a.withVolume = volume ? 1 : 0;
-    a.result = r->histResult.p;
-    HIP_TRY(h, hipMemcpyAsync(r->histResult.p, res.data(), words * sizeof(res[0]), hipMemcpyHostToDevice, s));
+    a.result = r->hist.result.p;
+    HIP_TRY(h, hipMemcpyAsync(r->hist.result.p, res.data(), words * sizeof(res[0]), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipEventRecord(t.ev[0], s));
     HIP_TRY(h, launchHistogram(a, s));
     HIP_TRY(h, hipEventRecord(t.ev[1], s));
-    HIP_TRY(h, hipMemcpyAsync(res.data(), r->histResult.p, words * sizeof(res[0]), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(res.data(), r->hist.result.p, words * sizeof(res[0]), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
-    HIP_TRY(h, hipEventElapsedTime(&r->histKernelMs, t.ev[0], t.ev[1]));
+    HIP_TRY(h, t.elapsed(0, 1, &r->hist.kernelMs));
   }
   for (int32_t i = 0; i < numBins; i++) {
     cells[i] = res[i];
@@ -183,6 +176,6 @@ extern "C" int exa_hip_histogram(ExaHipRenderer *h, int32_t channel, float lo, f
 extern "C" int exa_hip_histogram_ms(ExaHipRenderer *h, float *ms)
 {
   if (!h || !ms) return 1;
-  *ms = firstChild(h)->histKernelMs;
+  *ms = firstChild(h)->hist.kernelMs;
   return 0;
 }

@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+from analysis_steps import frame_perturbations, multi_handle, without_kd_tree
 from common import Case, band_xf
 from owlexabrick_amd import binding, scenes
 from histogram_ref import Slots, same_stats
@@ -212,31 +213,20 @@ def test_nothing_else_moves_the_result():
     R.updateXF(1, xf[:, 3], xf[:, :3], (0.2, 0.6), 0.5)
     R.render()
     same(R, "after a TF change")
-    R.setOption("brick_order", 1)
-    same(R, "brick_order 1, applied by the call itself")
+    for what in frame_perturbations(case, R):
+        same(R, what)
+    R.setOption("interleave", 1)
     R.render()
-    same(R, "brick_order 1 after a frame")
-    R.setOption("brick_order", 0)
-    same(R, "brick_order back to 0")
-    for il in (0, 1):
-        R.setOption("interleave", il)
-        R.render()
-        same(R, f"interleave {il}")
+    same(R, "interleave 1")
     for form in (0, 1):
         R.setOption("basis_form", form)
         R.render()
         same(R, f"basis_form {form}")
-    M = binding.Renderer(R.prep, devices=[0, 0])
+    M = multi_handle(R)
     same(M, "multi-device handle with a repeated device")
     M.close()
     R.close()
-
-    def drop_kd_tree(prep):
-        prep.scene.kdNodes = None
-        prep.scene.numKdNodes = 0
-
-    case.prep_edit = drop_kd_tree
-    N = case.hip_renderer()
+    N = without_kd_tree(case).hip_renderer()
     same(N, "scene without kd nodes")
     N.close()
 

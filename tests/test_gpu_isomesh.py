@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import isomesh_ref as ref
+from analysis_steps import bits as _bits, frame_perturbations, multi_handle, without_kd_tree
 from common import Case
 from owlexabrick_amd import binding, scenes
 
@@ -17,10 +18,6 @@ pytestmark = pytest.mark.gpu
 NAN = float("nan")
 DIMS = (37, 29, 23)
 XFM = dict(vx=[1.6, 0.5, -0.2], vy=[-0.4, 1.3, 0.3], vz=[0.25, -0.15, 0.9], p=[3.5, -1.25, 2.0])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _root_box(prep, grow=0.1):
@@ -154,19 +151,8 @@ def test_mesh_does_not_depend_on_frame_state_or_options():
             assert x.tobytes() == y.tobytes(), what
 
     same("two consecutive calls")
-    for c in range(3):                                         # every region inactive
-        R.updateXF(c, np.zeros(128, np.float32), case.xfs[c][:, :3], case.xf_domains[c], 1.0)
-    R.render()
-    assert not R.readActivity(0).any()
-    same("inactive TF")
-    for walk in (1, 2):
-        R.setOption("walk", walk)
-        R.render()
-        same(f"walk {walk}")
-    R.setOption("brick_order", 1)                              # pending: the extraction applies it
-    same("brick_order 1 before a render")
-    R.render()
-    same("brick_order 1 after a render")
+    for what in frame_perturbations(case, R):
+        same(what)
     for patch in range(4):
         R.setOption("sample_patch", patch)
         same(f"sample_patch {patch}")
@@ -225,14 +211,7 @@ def test_empty_surface_and_refused_arguments():
 
 
 def test_scene_without_kd_tree_is_refused():
-    case = Case(scenes.amr(levels=3), W=32, H=32)
-
-    def drop_kd_tree(prep):
-        prep.scene.kdNodes = None
-        prep.scene.numKdNodes = 0
-
-    case.prep_edit = drop_kd_tree
-    R = case.hip_renderer()
+    R = without_kd_tree(Case(scenes.amr(levels=3), W=32, H=32)).hip_renderer()
     rc, nv, nt, msg = _raw(R)
     assert rc != 0 and (nv, nt) == (0, 0) and "kd-tree" in msg, msg
     assert R.render().shape == (32, 32)                        # the handle still renders (through its LBVH)
@@ -257,7 +236,7 @@ def test_device_read_and_multi_device_handle_equal_the_host_read():
         assert x.cpu().numpy().tobytes() == y.tobytes()
     ms = R.isoSurfaceStageMs()
     assert len(ms) == 6 and all(m >= 0 for m in ms) and ms[0] > 0
-    M = binding.Renderer(R.prep, devices=[0, 0])
+    M = multi_handle(R)
     got = M.isosurface(lo, hi, DIMS, iso, channel=1, gradients=True)
     for x, y in zip(got, want):
         assert x.tobytes() == y.tobytes()

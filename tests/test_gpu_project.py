@@ -13,6 +13,7 @@ import pytest
 
 import probe_sets as ps
 import project_ref as pr
+from analysis_steps import frame_perturbations, multi_handle, without_kd_tree
 from common import Case
 from owlexabrick_amd import binding, harness, scenes
 
@@ -271,31 +272,14 @@ def test_bytes_do_not_depend_on_the_frame_state_or_options():
     same("two calls")
     R.render()
     same("after a frame")
-    for c in range(2):                                          # every region inactive
-        R.updateXF(c, np.zeros(128, f32), case.xfs[c][:, :3], case.xf_domains[c], 1.0)
-    R.render()
-    assert not R.readActivity(0).any()
-    same("transparent TF")
-    R.updateCamera([1, 2, 3], [0, 0, -1], [0.01, 0, 0], [0, 0.01, 0])
-    R.render()
-    same("another camera in the frame state")
+    for what in frame_perturbations(case, R):
+        same(what)
     for uniform in (0, 1):
         R.setOption("sample_uniform", uniform)
         same(f"sample_uniform {uniform}")
         for patch in range(4):
             R.setOption("sample_patch", patch)
             same(f"sample_patch {patch}")
-    for walk in (1, 2):
-        R.setOption("walk", walk)
-        R.render()
-        same(f"walk {walk}")
-    R.setOption("interleave", 0)
-    R.render()
-    same("interleave 0")
-    R.setOption("brick_order", 1)                               # pending: the call applies it
-    same("brick_order 1 before a frame")
-    R.render()
-    same("brick_order 1 after a frame")
     R.close()
 
 
@@ -330,8 +314,7 @@ def test_multi_device_handle_equals_single():
     case, R = setup(1)
     rays = pinhole_rays(R.prep, True)
     want = R.project(**rays, normalize=True)
-    M = binding.Renderer(R.prep, devices=[0, 0])
-    M.setOption("basis_form", 1)
+    M = multi_handle(R, 1)
     got = M.project(**rays, normalize=True)
     for k in KEYS:
         assert pr.same_bits(got[k], want[k]), k
@@ -441,10 +424,7 @@ def test_world_space_needs_a_frame_state():
 
 
 def test_scene_without_kd_tree_is_refused():
-    prep = binding.Prep(amr3())
-    prep.scene.kdNodes = None
-    prep.scene.numKdNodes = 0
-    R = binding.Renderer(prep)
+    R = binding.Renderer(without_kd_tree(binding.Prep(amr3())))
     with pytest.raises(RuntimeError, match="kd-tree"):
-        R.project(**pinhole_rays(prep, True), normalize=True)
+        R.project(**pinhole_rays(R.prep, True), normalize=True)
     R.close()

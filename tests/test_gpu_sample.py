@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+from analysis_steps import bits as _bits, frame_perturbations, multi_handle, without_kd_tree
 from common import Case
 from owlexabrick_amd import binding, scenes
 from probe_sets import brute_owner, grid_positions as _grid_positions, probe_points, region_levels, with_field_of_centres
@@ -14,10 +15,6 @@ from probe_sets import brute_owner, grid_positions as _grid_positions, probe_poi
 pytestmark = pytest.mark.gpu
 
 FILL = np.float32(-12345.5)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _cases():
@@ -116,30 +113,8 @@ def test_results_do_not_depend_on_frame_state_or_options():
         assert np.array_equal(_bits(got[1]), _bits(want[1])), what
         assert np.array_equal(got[2], want[2]), what
 
-    for c in range(3):                                         # every region inactive
-        R.updateXF(c, np.zeros(128, np.float32), case.xfs[c][:, :3], case.xf_domains[c], 1.0)
-    R.render()
-    assert not R.readActivity(0).any()
-    same("inactive TF")
-    R.updateIsoValues([0.5, 0.3], [0, 1], [1, 1])
-    R.render()
-    same("iso values")
-    for walk in (1, 2):
-        R.setOption("walk", walk)
-        R.render()
-        same(f"walk {walk}")
-    R.setOption("accel", 0)
-    R.render()
-    same("accel 0")
-    R.setOption("brick_order", 1)                              # pending: the probe applies it
-    same("brick_order 1 before a render")
-    R.render()
-    same("brick_order 1 after a render")
-    R.setOption("brick_order", 0)
-    R.render()
-    R.setOption("brick_order", 1)
-    R.render()                                                 # applied by the render this time
-    same("brick_order 1 applied by render")
+    for what in frame_perturbations(case, R):
+        same(what)
 
 
 def _xfm_np(m, w):
@@ -316,7 +291,7 @@ def test_multi_device_handle_equals_single():
     want = R.samplePoints(pts, channels=(0, 1), gradient=True)
     lo, hi = R.prep.voxel_bounds()
     gw = R.resample(lo, hi, (20, 18, 9), channel=1)
-    M = binding.Renderer(R.prep, devices=[0, 0])
+    M = multi_handle(R)
     got = M.samplePoints(pts, channels=(0, 1), gradient=True)
     for x, y in zip(want, got):
         assert np.array_equal(np.asarray(x).view(np.uint32), np.asarray(y).view(np.uint32))
@@ -325,10 +300,7 @@ def test_multi_device_handle_equals_single():
 
 
 def test_scene_without_kd_tree_is_refused():
-    prep = binding.Prep(scenes.amr(levels=3))
-    prep.scene.kdNodes = None
-    prep.scene.numKdNodes = 0
-    R = binding.Renderer(prep)
+    R = binding.Renderer(without_kd_tree(binding.Prep(scenes.amr(levels=3))))
     with pytest.raises(RuntimeError, match="kd-tree"):
         R.samplePoints(np.zeros((4, 3), np.float32))
     with pytest.raises(RuntimeError, match="kd-tree"):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import streamline_ref as sr
+from analysis_steps import bits as _bits, frame_perturbations, multi_handle, without_kd_tree
 from common import Case
 from owlexabrick_amd import binding, scenes
 from probe_sets import domains, root_box
@@ -15,10 +16,6 @@ from probe_sets import domains, root_box
 pytestmark = pytest.mark.gpu
 
 STEP, MAX_STEPS, N_UNIFORM = 0.5, 40, 48
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _ex3():
@@ -165,43 +162,21 @@ def test_lines_do_not_depend_on_the_batch_the_frame_state_or_options():
     same("reversed", seeds[::-1].copy(), lambda i: 256 - i)
     first = same("again")
     _same(same("two calls"), first, "two calls")
-    for c in range(3):                                          # every region inactive
-        R.updateXF(c, np.zeros(128, np.float32), case.xfs[c][:, :3], case.xf_domains[c], 1.0)
-    R.render()
-    assert not R.readActivity(0).any()
-    same("inactive TF")
-    for walk in (1, 2):
-        R.setOption("walk", walk)
-        R.render()
-        same(f"walk {walk}")
-    R.setOption("accel", 0)
-    R.render()
-    same("accel 0")
-    R.setOption("accel", 1)
-    R.setOption("interleave", 0)
-    R.render()
-    same("interleave 0")
-    R.setOption("brick_order", 1)                               # pending: the extraction applies it
-    same("brick_order 1 before a render")
-    R.render()
-    same("brick_order 1 after a render")
+    for what in frame_perturbations(case, R):
+        same(what)
     R.close()
 
 
 def test_multi_device_handle_equals_single():
     case, R, S, seeds, channels, ref = _setup(0, 1)
-    M = binding.Renderer(R.prep, devices=[0, 0])
-    M.setOption("basis_form", 1)
+    M = multi_handle(R, 1)
     got = M.streamlines(seeds, channels, STEP, MAX_STEPS, True, True, True, True)
     _same(got, ref[(True, True, True)], "multi")
     M.close()
 
 
 def test_scene_without_kd_tree_is_refused():
-    prep = binding.Prep(scenes.amr(levels=3, fields=3))
-    prep.scene.kdNodes = None
-    prep.scene.numKdNodes = 0
-    R = binding.Renderer(prep)
+    R = binding.Renderer(without_kd_tree(binding.Prep(scenes.amr(levels=3, fields=3))))
     with pytest.raises(RuntimeError, match="kd-tree"):
         R.streamlines(np.zeros((4, 3), np.float32))
     R.close()
