@@ -402,6 +402,71 @@ int exa_hip_isosurface_read(ExaHipRenderer *, float *vertices, float *gradients,
 int exa_hip_isosurface_release(ExaHipRenderer *);
 int exa_hip_isosurface_stage_ms(ExaHipRenderer *, float ms[6]);
 
+/* ---- derived flow quantities: speed, divergence, vorticity, its magnitude, the Q-criterion and helicity of the vector field
+ * formed by three channels, at points, on uniform grids and as iso-surfaces.  New relative to the reference.  Formed on the
+ * device from what exa_hip_sample_points returns, so that a scalar leaves the device instead of 12 floats per point. ----
+ *
+ * Inputs.  channels[3], each in [0, numFields), repeats allowed, and a quantity.  For a position p the region lookup is the
+ * probes' lookup, done once.  For c = 0..2, v[c] is the value and J[c][k] component k of the gradient that
+ * exa_hip_sample_points(p, channels, 3, world? | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED) returns for channel
+ * c, bit for bit, in the handle's current basis_form (a scene marked allowEmptyCells: the form-0 sums with the poison test).
+ *
+ * Voxel space.  J is the Jacobian with respect to VOXEL-space coordinates, also for world-space positions, exactly as
+ * EXA_SAMPLE_GRADIENT_NORMALIZED states: every quantity below is a voxel-space quantity (bringing it into world
+ * space through the transform is the caller's).
+ *
+ * Status per point: -1 no region; -2 if any of the three channels has status -2; otherwise the region id.  Where status < 0
+ * every component of the output is `fill`.
+ *
+ * Quantities.  All arithmetic is float32, every operation rounded separately, nothing contracted, associated exactly as
+ * written; sqrtf and `/` are correctly rounded.  NaN and infinities propagate by these formulas, nothing is special-cased.
+ * With w = (J21 - J12, J02 - J20, J10 - J01):
+ *   EXA_DERIVED_SPEED               1 component   sqrtf((v0*v0 + v1*v1) + v2*v2)
+ *   EXA_DERIVED_DIVERGENCE          1             (J00 + J11) + J22
+ *   EXA_DERIVED_VORTICITY           3             w
+ *   EXA_DERIVED_VORTICITY_MAGNITUDE 1             sqrtf((w.x*w.x + w.y*w.y) + w.z*w.z)
+ *   EXA_DERIVED_Q                   1             d = (J00*J00 + J11*J11) + J22*J22; o = (J01*J10 + J02*J20) + J12*J21;
+ *                                                 Q = -0.5f*d - o     (= -1/2 tr(J^2) = 1/2 (|Omega|^2 - |S|^2))
+ *   EXA_DERIVED_HELICITY            1             (v0*w.x + v1*w.y) + v2*w.z
+ *
+ * Independence.  As for the probes: the result depends on the scene, the positions or the lattice, the channels and the
+ * quantity, basis_form and (world space) the transform, and on nothing a frame sets; sample_patch and sample_uniform never
+ * change a bit.
+ *
+ * exa_hip_sample_derived: out n x components, status n or NULL.  Arrays, the chunks of host arrays, the async rule,
+ * multi-device handles, the refusal of a scene without a kd tree, a pending brick_order change and the loop guard's return
+ * code 3 are those of exa_hip_sample_points; n == 0 does nothing.  The only flag is EXA_SAMPLE_WORLD_SPACE (the gradient
+ * flags are errors here).
+ * exa_hip_resample_derived: the lattice, its positions and the checks of the box and dims are those of exa_hip_resample;
+ * out[((z*ny + y)*nx + x) * components + c], bit for bit what exa_hip_sample_derived gives at those positions.
+ * exa_hip_isosurface_derived: the contract of exa_hip_isosurface with the lattice value V = what
+ * exa_hip_resample_derived(lo, hi, dims, channels, quantity, flags, fill = NaN) returns.  One-component quantities only;
+ * EXA_SAMPLE_GRADIENT is refused (a normal of a derived surface would need second derivatives).  The mesh replaces any
+ * earlier mesh of either call and is read, released and timed with exa_hip_isosurface_read / _release / _stage_ms.
+ * exa_hip_derived_ms: the device time of the kernels of the last exa_hip_sample_derived / exa_hip_resample_derived call,
+ * summed; 0 before any call, after a refused one and after an asynchronous one.
+ * Errors with a message that starts with the function's name, after which the handle stays usable: an unknown quantity, a
+ * bad channel, null arrays, unknown flag bits, world space before a frame state, the box and dims errors of
+ * exa_hip_resample, the lattice and size errors of exa_hip_isosurface, a non-finite iso. */
+#define EXA_DERIVED_SPEED               0
+#define EXA_DERIVED_DIVERGENCE          1
+#define EXA_DERIVED_VORTICITY           2
+#define EXA_DERIVED_VORTICITY_MAGNITUDE 3
+#define EXA_DERIVED_Q                   4
+#define EXA_DERIVED_HELICITY            5
+#define EXA_DERIVED_QUANTITIES          6
+int exa_hip_sample_derived(ExaHipRenderer *, const float *points /* n x 3 */, uint64_t n, const int32_t channels[3],
+                           int32_t quantity, int32_t flags, float fill, float *out /* n x components */,
+                           int32_t *status /* n, or NULL */, int32_t pointersAreDevice, void *hipStream, int32_t async);
+int exa_hip_resample_derived(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                             const int32_t channels[3], int32_t quantity, int32_t flags, float fill,
+                             float *out /* dims[0]*dims[1]*dims[2]*components floats */, int32_t dstIsDevice,
+                             void *hipStream, int32_t async);
+int exa_hip_isosurface_derived(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                               const int32_t channels[3], int32_t quantity, float iso, int32_t flags,
+                               uint64_t *numVertices, uint64_t *numTriangles, void *hipStream);
+int exa_hip_derived_ms(ExaHipRenderer *, float *ms);
+
 /* ---- histogram and value range of one channel's cells: the exact histogram of the cell values by cell count and by
  * volume, the value range, the cell counts per level and the NaN / empty / out-of-range counts, optionally inside an integer
  * voxel box.  New relative to the reference, whose viewer left the hook unbuilt (exa/viewer.cpp:1274-1276, setValueRange /

@@ -122,6 +122,20 @@ STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREA
 PROJECT_NORMALIZE = 4
 PROJECT_MAX_SAMPLES = 1 << 20
 
+# exa_hip_*_derived quantities (include/exa_hip.h: EXA_DERIVED_*), by name, and the number of components of each
+DERIVED = {"speed": 0, "divergence": 1, "vorticity": 2, "vorticity_magnitude": 3, "q": 4, "helicity": 5}
+DERIVED_COMPONENTS = {0: 1, 1: 1, 2: 3, 3: 1, 4: 1, 5: 1}
+
+
+def derived_quantity(q):
+    """the number of a derived quantity given by name (a key of DERIVED, any letter case) or by number; an unknown number
+    passes through for the module to refuse, an unknown name is a ValueError"""
+    if isinstance(q, str):
+        if q.lower() not in DERIVED:
+            raise ValueError(f"unknown derived quantity {q!r} (one of {', '.join(DERIVED)})")
+        return DERIVED[q.lower()]
+    return int(q)
+
 
 class ExaHipRays(C.Structure):
     _fields_ = [("org", C.c_float * 3), ("orgDu", C.c_float * 3), ("orgDv", C.c_float * 3),
@@ -170,6 +184,10 @@ _ABI = {
     "exa_hip_isosurface_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_isosurface_release": (None, [_vp]),
     "exa_hip_isosurface_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_sample_derived": (None, [_vp, _vp, _u64, _vp, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _i32]),
+    "exa_hip_resample_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i32]),
+    "exa_hip_isosurface_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _P(_u64), _vp]),
+    "exa_hip_derived_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
     "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),
@@ -574,6 +592,75 @@ class Renderer:
             return self.readIsoSurface()
         finally:
             self.releaseIsoSurface()
+
+    # ---- derived flow quantities (exa_hip_*_derived; include/exa_hip.h states the contract) ----
+    def sampleDerived(self, points, quantity, channels=(0, 1, 2), world=False, fill=float("nan"), stream=None, async_=False):
+        """a quantity of the velocity gradient tensor of the vector field `channels` at points [n,3]: `quantity` by name (a
+        key of DERIVED) or number.  Returns (out [n], or [n, 3] for vorticity; status [n]).  Voxel-space quantities, also
+        for world-space positions.  A numpy array takes the host path, a contiguous float32 torch CUDA tensor the device
+        path with torch tensors out (async_ on `stream`), as samplePoints."""
+        q = derived_quantity(quantity)
+        k = DERIVED_COMPONENTS.get(q, 1)                                       # the module checks the quantity
+        flags, ch3 = self._probe_world(world), _i3(channels)
+        if getattr(points, "is_cuda", False):
+            import torch
+            if points.dtype != torch.float32 or not points.is_contiguous() or points.numel() % 3:
+                raise TypeError("points: a contiguous float32 tensor [n, 3]")
+            n = points.numel() // 3
+            out = torch.empty((n, k), dtype=torch.float32, device=points.device)
+            status = torch.empty(n, dtype=torch.int32, device=points.device)
+            self._check(lib().exa_hip_sample_derived(self.h, _dev_ptr(points), n, ch3, q, flags, float(fill), _dev_ptr(out),
+                                                     _dev_ptr(status), 1, C.c_void_p(stream or 0), int(async_)))
+            return (out if k == 3 else out.reshape(n)), status
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        out = np.empty((n, k), dtype=np.float32)
+        status = np.empty(n, dtype=np.int32)
+        self._check(lib().exa_hip_sample_derived(self.h, pts.ctypes.data, n, ch3, q, flags, float(fill), out.ctypes.data,
+                                                 status.ctypes.data, 0, None, 0))
+        return (out if k == 3 else out.reshape(n)), status
+
+    def resampleDerived(self, lo, hi, dims, quantity, channels=(0, 1, 2), world=False, fill=float("nan"), out_ptr=None,
+                        stream=None, async_=False):
+        """the quantity on the lattice of resample(lo, hi, dims): a float32 array [nz, ny, nx], or [nz, ny, nx, 3] for
+        vorticity; out_ptr (a device pointer or a contiguous float32 torch CUDA tensor) takes the device path and returns
+        None."""
+        q = derived_quantity(quantity)
+        k = DERIVED_COMPONENTS.get(q, 1)
+        flags = self._probe_world(world)
+        lo3, hi3, d3, ch3 = _f3(lo), _f3(hi), _i3(dims), _i3(channels)
+        if out_ptr is not None:
+            self._check(lib().exa_hip_resample_derived(self.h, lo3, hi3, d3, ch3, q, flags, float(fill), _dev_ptr(out_ptr), 1,
+                                                       C.c_void_p(stream or 0), int(async_)))
+            return None
+        shape = tuple(max(int(d), 0) for d in dims[::-1])                      # the module checks the dims
+        out = np.empty(shape + (3,) if k == 3 else shape, dtype=np.float32)
+        self._check(lib().exa_hip_resample_derived(self.h, lo3, hi3, d3, ch3, q, flags, float(fill), out.ctypes.data, 0, None, 0))
+        return out
+
+    def extractIsoSurfaceDerived(self, lo, hi, dims, iso, quantity, channels=(0, 1, 2), world=False, gradients=False,
+                                 stream=None):
+        """extractIsoSurface on the lattice of resampleDerived(lo, hi, dims, quantity, channels): (numVertices, numTriangles).
+        One-component quantities only; gradients=True is refused by the module."""
+        flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradients else 0)
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().exa_hip_isosurface_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), derived_quantity(quantity),
+                                                     float(iso), flags, C.byref(nv), C.byref(nt), C.c_void_p(stream or 0)))
+        self._iso_counts = (int(nv.value), int(nt.value), False)
+        return self._iso_counts[:2]
+
+    def isosurfaceDerived(self, lo, hi, dims, iso, quantity, channels=(0, 1, 2), world=False):
+        """the iso-surface quantity == iso on the lattice of resampleDerived(lo, hi, dims, quantity, channels), as isosurface:
+        (verts float32 [n,3], tris int32 [m,3]).  The device copy is released before returning."""
+        self.extractIsoSurfaceDerived(lo, hi, dims, iso, quantity, channels=channels, world=world)
+        try:
+            return self.readIsoSurface()[:2]
+        finally:
+            self.releaseIsoSurface()
+
+    def derivedMs(self):
+        """device ms of the kernels of the last sampleDerived / resampleDerived call, summed"""
+        return self._ms(lib().exa_hip_derived_ms)
 
     # ---- histogram and value range of a channel's cells (exa_hip_histogram; include/exa_hip.h states the contract) ----
     def histogram(self, channel, lo, hi, bins, box=None, volume=True, stream=None):

@@ -256,6 +256,10 @@ struct SampleArgs {
   unsigned long long patchesX, patchesY, numPatches;   // patches of the box along x, y, and in all
   unsigned long long strideY, strideZ;
   float             *out;
+  // derived quantities (exa_hip_sample_derived / exa_hip_resample_derived): fieldOffset[0..2] = the three channels; the points
+  // kernel stores count x components floats in `values` and count status, the grid kernel `components` floats per index of `out`
+  int32_t            quantity;      // EXA_DERIVED_*
+  int32_t            components;    // 1, or 3 for EXA_DERIVED_VORTICITY
 };
 // patch shapes of the grid kernel (x, y, z extents; 64 points each)
 enum { kSamplePatchShapes = 4 };
@@ -326,6 +330,9 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
      1 16x4x1, 2 8x8x1, 3 4x4x4), wave-uniform descent and brick headers where a patch allows (uniform) or per lane */  \
   hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s);                                      \
   hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);                          \
+  /* the same two for a.quantity of the three channels' velocity gradient tensor */                                     \
+  hipError_t launchSampleDerivedPoints(const SampleArgs &a, hipStream_t s);                                          \
+  hipError_t launchSampleDerivedGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);                   \
   /* the projections (exa_sample_f*.o): the tile of a, one wave per 8 x 8 pixels; uniform as for the grid */            \
   hipError_t launchSampleRays(const RayArgs &a, bool uniform, hipStream_t s);                                        \
   /* the streamline integrator (exa_stream_f*.o): lanes [a.laneBase, a.numLanes) of at most 2^24 per launch; emit = the  \

@@ -1,6 +1,7 @@
 // exa_probe.cpp — reading the reconstructed field outside a frame: the point probes (exa_hip_sample_points,
-// exa_hip_resample; kernels in exa_sample_kernels.h), the projections along rays (exa_hip_project; the same file) and the
-// iso-surface extraction on a sampled lattice (exa_hip_isosurface; exa_isomesh.hip).
+// exa_hip_resample; kernels in exa_sample_kernels.h), the quantities derived from three channels' velocity gradient tensor
+// (exa_hip_sample_derived, exa_hip_resample_derived) and the projections along rays (exa_hip_project) in the same file, and
+// the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -114,35 +115,133 @@ int exa_hip_sample_points(ExaHipRenderer *h, const float *points, uint64_t n, co
   return checkLoopGuard(h, r, fn, kDescentGuard);
 }
 
-int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
-                     int32_t flags, float fill, float *out, int32_t dstIsDevice, void *hipStream, int32_t async)
+// ---- derived quantities (sampleDerivedPointsKernel, sampleDerivedGridKernel) ----
+// the number of components of a quantity of three channels, 0 after h->fail for an unknown quantity or a bad channel
+static int derivedComponents(ExaHipRenderer *h, const char *fn, const int32_t *channels, int32_t quantity)
+{
+  if (quantity < 0 || quantity >= EXA_DERIVED_QUANTITIES) { h->fail(std::string(fn) + ": unknown quantity (EXA_DERIVED_*)"); return 0; }
+  if (!channels) { h->fail(std::string(fn) + ": null channels (three are required)"); return 0; }
+  for (int c = 0; c < 3; c++)
+    if (!checkChannel(h, fn, channels[c])) return 0;
+  return quantity == EXA_DERIVED_VORTICITY ? 3 : 1;
+}
+
+static void derivedArgs(SampleArgs &a, const ExaHipRenderer *r, const int32_t *channels, int32_t quantity, int components)
+{
+  a.numChannels = 3;
+  for (int c = 0; c < 3; c++) a.fieldOffset[c] = r->sc.channelOffset[channels[c]];
+  a.quantity = quantity;
+  a.components = components;
+}
+
+int exa_hip_sample_derived(ExaHipRenderer *h, const float *points, uint64_t n, const int32_t channels[3], int32_t quantity,
+                           int32_t flags, float fill, float *out, int32_t *status, int32_t pointersAreDevice, void *hipStream,
+                           int32_t async)
 {
   if (!h) return 1;
-  const char *fn = "exa_hip_resample";
+  const char *fn = "exa_hip_sample_derived";
+  ExaHipRenderer *r = firstChild(h);
+  r->derived.kernelMs = 0.f;
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE, " (only EXA_SAMPLE_WORLD_SPACE applies)")) return 1;
+  const int comps = derivedComponents(h, fn, channels, quantity);
+  if (!comps) return 1;
+  if (n == 0) return 0;
+  if (!points || !out) { h->fail(std::string(fn) + ": null array (points or out)"); return 1; }
+  if (n > UINT64_MAX / 12) { h->fail(std::string(fn) + ": too many points"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  SampleArgs a;
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a)) return 1;
+  a.fill = fill;
+  derivedArgs(a, r, channels, quantity, comps);
+  const uint64_t nc = uint64_t(comps);
+  TimingEvents<2> t;
+  HIP_TRY(h, t.create());
+  if (pointersAreDevice) {
+    if (!async) HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    for (uint64_t at = 0; at < n; at += kProbeLaunch) {
+      a.count = std::min(kProbeLaunch, n - at);
+      a.points = points + 3 * at;
+      a.values = out + at * nc;
+      a.status = status ? status + at : nullptr;
+      HIP_TRY(h, EXA_FORM(r, launchSampleDerivedPoints)(a, s));
+    }
+    if (async) return 0;
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, t.elapsed(0, 1, &r->derived.kernelMs));
+    return checkLoopGuard(h, r, fn, kDescentGuard);
+  }
+  // host arrays: chunk by chunk through the staging buffer {points | out | status}
+  const uint64_t perPoint = 12 + 4 * nc + (status ? 4 : 0);
+  const uint64_t chunk = std::max<uint64_t>(1, std::min(kProbeLaunch, kProbeStageBytes / perPoint));
+  const uint64_t need = std::min(n, chunk) * perPoint;
+  if (r->probes.stage.n < need) HIP_TRY(h, r->probes.stage.alloc(need));
+  float total = 0.f;
+  for (uint64_t at = 0; at < n; at += chunk) {
+    const uint64_t m = std::min(chunk, n - at);
+    char *cut = r->probes.stage.p;
+    a.count = m;
+    a.points = reinterpret_cast<const float *>(carve(cut, true, 12 * m));
+    a.values = reinterpret_cast<float *>(carve(cut, true, 4 * m * nc));
+    a.status = reinterpret_cast<int32_t *>(carve(cut, status != nullptr, 4 * m));
+    HIP_TRY(h, hipMemcpyAsync(r->probes.stage.p, points + 3 * at, 12 * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    HIP_TRY(h, EXA_FORM(r, launchSampleDerivedPoints)(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    HIP_TRY(h, hipMemcpyAsync(out + at * nc, a.values, 4 * m * nc, hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status + at, a.status, 4 * m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(h, t.elapsed(0, 1, &ms));
+    total += ms;
+  }
+  r->derived.kernelMs = total;
+  return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+// exa_hip_resample (quantity < 0: the one channel channels[0]) and exa_hip_resample_derived: the checks, the lattice and its
+// boxes are the same; the derived call stores `components` floats per lattice point and times its kernels
+static int resampleLattice(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                           const int32_t *channels, int32_t quantity, int32_t flags, float fill, float *out, int32_t dstIsDevice,
+                           void *hipStream, int32_t async)
+{
+  const bool derived = quantity >= 0;
   if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE, " (only EXA_SAMPLE_WORLD_SPACE applies)")) return 1;
   if (!lo || !hi || !dims || !out) { h->fail(std::string(fn) + ": null argument"); return 1; }
   for (int k = 0; k < 3; k++) {
     if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
     if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
   }
-  if (!checkChannel(h, fn, channel)) return 1;
+  int comps = 1;
+  if (derived) {
+    comps = derivedComponents(h, fn, channels, quantity);
+    if (!comps) return 1;
+  } else if (!checkChannel(h, fn, channels[0])) return 1;
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   SampleArgs a;
   if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a)) return 1;
   a.fill = fill;
-  a.numChannels = 1;
-  a.fieldOffset[0] = r->sc.channelOffset[channel];
+  if (derived) derivedArgs(a, r, channels, quantity, comps);
+  else { a.numChannels = 1; a.fieldOffset[0] = r->sc.channelOffset[channels[0]]; }
   for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
   static const int kShape[kSamplePatchShapes][3] = { { 64, 1, 1 }, { 16, 4, 1 }, { 8, 8, 1 }, { 4, 4, 4 } };
   const int *ps = kShape[r->probes.patch];
-  const uint64_t nx = uint64_t(dims[0]), ny = uint64_t(dims[1]), nz = uint64_t(dims[2]);
-  // boxes of at most kProbeLaunch points: whole slabs of z, else rows of one slice, else pieces of one row — each one
-  // contiguous in the output, so a host destination takes one copy per box
-  const uint64_t bx = std::min(nx, kProbeLaunch), by = std::min(ny, std::max<uint64_t>(1, kProbeLaunch / bx)),
-                 bz = std::min(nz, std::max<uint64_t>(1, kProbeLaunch / (bx * by)));
-  if (!dstIsDevice && r->probes.stage.n < bx * by * bz * 4) HIP_TRY(h, r->probes.stage.alloc(bx * by * bz * 4));
+  const uint64_t nx = uint64_t(dims[0]), ny = uint64_t(dims[1]), nz = uint64_t(dims[2]), nc = uint64_t(comps);
+  // boxes of at most kProbeLaunch points (a host destination: at most what kProbeStageBytes hold): whole slabs of z, else
+  // rows of one slice, else pieces of one row — each one contiguous in the output, so a host destination takes one copy per box
+  const uint64_t cap = dstIsDevice ? kProbeLaunch : std::min(kProbeLaunch, kProbeStageBytes / (4 * nc));
+  const uint64_t bx = std::min(nx, cap), by = std::min(ny, std::max<uint64_t>(1, cap / bx)),
+                 bz = std::min(nz, std::max<uint64_t>(1, cap / (bx * by)));
+  if (!dstIsDevice && r->probes.stage.n < bx * by * bz * nc * 4) HIP_TRY(h, r->probes.stage.alloc(bx * by * bz * nc * 4));
+  // the derived call's kernel time: a host destination synchronises box by box, a device destination once behind the last box
+  const bool timed = derived && !(dstIsDevice && async);
+  TimingEvents<2> t;
+  if (timed) HIP_TRY(h, t.create());
+  float total = 0.f, ms = 0.f;
+  if (timed && dstIsDevice) HIP_TRY(h, hipEventRecord(t.ev[0], s));
   for (uint64_t z0 = 0; z0 < nz; z0 += bz)
     for (uint64_t y0 = 0; y0 < ny; y0 += by)
       for (uint64_t x0 = 0; x0 < nx; x0 += bx) {
@@ -152,21 +251,53 @@ int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], co
         a.patchesX = (ex + ps[0] - 1) / ps[0];
         a.patchesY = (ey + ps[1] - 1) / ps[1];
         a.numPatches = a.patchesX * a.patchesY * ((ez + ps[2] - 1) / ps[2]);
-        const uint64_t first = (z0 * ny + y0) * nx + x0;
+        const uint64_t first = ((z0 * ny + y0) * nx + x0) * nc;
         if (dstIsDevice) {
           a.out = out + first; a.strideY = nx; a.strideZ = nx * ny;
         } else {
           a.out = reinterpret_cast<float *>(r->probes.stage.p); a.strideY = ex; a.strideZ = ex * ey;
         }
-        HIP_TRY(h, EXA_FORM(r, launchSampleGrid)(a, r->probes.patch, r->probes.uniform != 0, s));
+        if (timed && !dstIsDevice) HIP_TRY(h, hipEventRecord(t.ev[0], s));
+        if (derived) HIP_TRY(h, EXA_FORM(r, launchSampleDerivedGrid)(a, r->probes.patch, r->probes.uniform != 0, s));
+        else HIP_TRY(h, EXA_FORM(r, launchSampleGrid)(a, r->probes.patch, r->probes.uniform != 0, s));
         if (!dstIsDevice) {
-          HIP_TRY(h, hipMemcpyAsync(out + first, a.out, ex * ey * ez * sizeof(float), hipMemcpyDeviceToHost, s));
+          if (timed) HIP_TRY(h, hipEventRecord(t.ev[1], s));
+          HIP_TRY(h, hipMemcpyAsync(out + first, a.out, ex * ey * ez * nc * sizeof(float), hipMemcpyDeviceToHost, s));
           HIP_TRY(h, hipStreamSynchronize(s));
+          if (timed) { HIP_TRY(h, t.elapsed(0, 1, &ms)); total += ms; }
         }
       }
   if (dstIsDevice && async) return 0;
+  if (timed && dstIsDevice) HIP_TRY(h, hipEventRecord(t.ev[1], s));
   HIP_TRY(h, hipStreamSynchronize(s));
+  if (timed && dstIsDevice) HIP_TRY(h, t.elapsed(0, 1, &total));
+  if (derived) r->derived.kernelMs = total;
   return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+int exa_hip_resample(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
+                     int32_t flags, float fill, float *out, int32_t dstIsDevice, void *hipStream, int32_t async)
+{
+  if (!h) return 1;
+  return resampleLattice(h, "exa_hip_resample", lo, hi, dims, &channel, -1, flags, fill, out, dstIsDevice, hipStream, async);
+}
+
+int exa_hip_resample_derived(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                             int32_t quantity, int32_t flags, float fill, float *out, int32_t dstIsDevice, void *hipStream,
+                             int32_t async)
+{
+  if (!h) return 1;
+  firstChild(h)->derived.kernelMs = 0.f;
+  // a quantity below 0 would mean exa_hip_resample's one channel to resampleLattice
+  if (quantity < 0) { h->fail("exa_hip_resample_derived: unknown quantity (EXA_DERIVED_*)"); return 1; }
+  return resampleLattice(h, "exa_hip_resample_derived", lo, hi, dims, channels, quantity, flags, fill, out, dstIsDevice, hipStream, async);
+}
+
+int exa_hip_derived_ms(ExaHipRenderer *h, float *ms)
+{
+  if (!h || !ms) return 1;
+  *ms = firstChild(h)->derived.kernelMs;
+  return 0;
 }
 
 // ---- projections (sampleRaysKernel) ----
@@ -261,14 +392,13 @@ int exa_hip_project_ms(ExaHipRenderer *h, float *ms)
 }
 
 // ---- iso-surface extraction (exa_isomesh.hip) ----
-int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
-                       int32_t flags, uint64_t *numVertices, uint64_t *numTriangles, void *hipStream)
+// exa_hip_isosurface (quantity < 0: the lattice holds the one channel channels[0]) and exa_hip_isosurface_derived (it holds
+// the quantity of channels[0..2]; no gradients: the caller has refused the flag).  Filling the lattice is the one step in
+// which they differ; every later stage only ever looks at lattice values.  The flags are checked by the caller.
+static int isoExtract(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                      const int32_t *channels, int32_t quantity, float iso, int32_t flags, uint64_t *numVertices,
+                      uint64_t *numTriangles, void *hipStream)
 {
-  if (!h) return 1;
-  const char *fn = "exa_hip_isosurface";
-  if (numVertices) *numVertices = 0;
-  if (numTriangles) *numTriangles = 0;
-  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT, " (EXA_SAMPLE_WORLD_SPACE and EXA_SAMPLE_GRADIENT apply)")) return 1;
   if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument"); return 1; }
   if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
   for (int k = 0; k < 3; k++)
@@ -311,10 +441,12 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
 
   TimingEvents<7> t;
   HIP_TRY(h, t.create());
-  // the lattice: exa_hip_resample with a NaN fill into the device buffer (its checks of the box, the channel, the kd
-  // tree and the frame state apply; synchronous, with the loop guard's check)
+  // the lattice: exa_hip_resample, or exa_hip_resample_derived, with a NaN fill into the device buffer (its checks of the
+  // box, the channels, the quantity, the kd tree and the frame state apply; synchronous, with the loop guard's check)
   HIP_TRY(h, hipEventRecord(t.ev[0], s));
-  if (int rc = exa_hip_resample(h, lo, hi, dims, channel, world ? EXA_SAMPLE_WORLD_SPACE : 0, NAN, values.p, 1, hipStream, 0)) {
+  const int32_t wf = world ? EXA_SAMPLE_WORLD_SPACE : 0;
+  if (int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], wf, NAN, values.p, 1, hipStream, 0)
+                            : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, wf, NAN, values.p, 1, hipStream, 0)) {
     h->fail(std::string(fn) + ": " + h->err);
     return rc;
   }
@@ -354,7 +486,7 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
       vals = scratch.p;
     }
     const int32_t pf = (world ? EXA_SAMPLE_WORLD_SPACE : 0) | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
-    if (int rc = exa_hip_sample_points(h, r->isoMesh.vertices.p, totals[0], &channel, 1, pf, NAN, vals, r->isoMesh.gradients.p, nullptr, 1, hipStream, 0)) {
+    if (int rc = exa_hip_sample_points(h, r->isoMesh.vertices.p, totals[0], channels, 1, pf, NAN, vals, r->isoMesh.gradients.p, nullptr, 1, hipStream, 0)) {
       h->fail(std::string(fn) + ": " + h->err);
       return rc;
     }
@@ -367,6 +499,36 @@ int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], 
   if (numVertices) *numVertices = totals[0];
   if (numTriangles) *numTriangles = totals[1];
   return 0;
+}
+
+int exa_hip_isosurface(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                       int32_t flags, uint64_t *numVertices, uint64_t *numTriangles, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isosurface";
+  if (numVertices) *numVertices = 0;
+  if (numTriangles) *numTriangles = 0;
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT, " (EXA_SAMPLE_WORLD_SPACE and EXA_SAMPLE_GRADIENT apply)")) return 1;
+  return isoExtract(h, fn, lo, hi, dims, &channel, -1, iso, flags, numVertices, numTriangles, hipStream);
+}
+
+int exa_hip_isosurface_derived(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                               int32_t quantity, float iso, int32_t flags, uint64_t *numVertices, uint64_t *numTriangles,
+                               void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isosurface_derived";
+  if (numVertices) *numVertices = 0;
+  if (numTriangles) *numTriangles = 0;
+  if (flags & EXA_SAMPLE_GRADIENT) {
+    h->fail(std::string(fn) + ": EXA_SAMPLE_GRADIENT does not apply (a normal of a derived surface would need second derivatives)");
+    return 1;
+  }
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE, " (only EXA_SAMPLE_WORLD_SPACE applies)")) return 1;
+  const int comps = derivedComponents(h, fn, channels, quantity);
+  if (!comps) return 1;
+  if (comps != 1) { h->fail(std::string(fn) + ": a surface needs a one-component quantity (EXA_DERIVED_VORTICITY has three)"); return 1; }
+  return isoExtract(h, fn, lo, hi, dims, channels, quantity, iso, flags, numVertices, numTriangles, hipStream);
 }
 
 int exa_hip_isosurface_read(ExaHipRenderer *h, float *vertices, float *gradients, int32_t *triangles, int32_t pointersAreDevice,

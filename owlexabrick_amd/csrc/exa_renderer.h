@@ -327,6 +327,10 @@ struct ExaHipRenderer {
   struct Projection {
     float kernelMs = 0.f;
   } project;
+  // the device time of the kernels of the last exa_hip_sample_derived / exa_hip_resample_derived
+  struct Derived {
+    float kernelMs = 0.f;
+  } derived;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 

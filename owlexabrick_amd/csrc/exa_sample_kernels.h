@@ -1,6 +1,7 @@
 // exa_sample_kernels.h — the point probes: exa_hip_sample_points (one lane per point) and exa_hip_resample (one wave per
-// compact patch of 64 grid points), and on the same lookup and sums the projections of exa_hip_project (one wave per 8 x 8
-// rays, reduced in registers).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
+// compact patch of 64 grid points), and on the same lookup and sums the derived quantities of exa_hip_sample_derived /
+// exa_hip_resample_derived (the same two shapes of kernel over three channels) and the projections of exa_hip_project (one
+// wave per 8 x 8 rays, reduced in registers).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
 // -DEXA_TU_SAMPLE=1 (exa_sample_f0.o, exa_sample_f1.o, exa_sample_f0e.o), after samplePoint and the basis evaluations it
 // uses; nothing else of the renderer is compiled there.
 //
@@ -121,6 +122,108 @@ __global__ __launch_bounds__(256) void sampleGridKernel(const SampleArgs a)
   else if (region >= 0) sampleValue(a, a.regionRec[region], field, p, value);
   const size_t o = size_t(x - a.box0[0]) + size_t(y - a.box0[1]) * size_t(a.strideY) + size_t(z - a.box0[2]) * size_t(a.strideZ);
   a.out[o] = value;
+}
+
+// ---- exa_hip_sample_derived / exa_hip_resample_derived: quantities of the velocity gradient tensor ----
+// The three channels at p in the region whose record is R, one after the other through sampleSums<true, true> — value,
+// numerator and quotients exactly as samplePointsBody<true, true> forms them —, of which only v[c] and the three quotients
+// J[c] stay live, then the contract's table (include/exa_hip.h) in float32, every operation rounded separately (the unit is
+// compiled without contraction) and associated as written there.  Returns the status: `region`, -1 outside R's closed
+// domain, -2 where the weights of any channel vanish; q untouched where it is < 0.  a.quantity is wave-uniform.
+__device__ __forceinline__ int sampleDerived(const SampleArgs &a, const RegionRec R, int region, V3 p, float q[3])
+{
+  if (!sampleInDomain(R, p)) return -1;
+  float v[3];
+  V3 J[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const Basis B = sampleSums<true, true>(a, R.listBegin, R.listSize, a.scalars + a.fieldOffset[c], p);
+    if (B.sumW <= 1e-20f) return -2;
+    v[c] = B.sumWV / B.sumW;
+    const V3 g = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
+    const float w2 = B.sumW * B.sumW;
+    J[c] = mk(g.x / w2, g.y / w2, g.z / w2);
+  }
+  // J[c].x, .y, .z = J[c][0], [1], [2]
+  const V3 w = mk(J[2].y - J[1].z, J[0].z - J[2].x, J[1].x - J[0].y);
+  switch (a.quantity) {
+  case EXA_DERIVED_SPEED:
+    // sqrtf: the compiler's correctly rounded expansion, as in the streamline integrator
+    q[0] = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    break;
+  case EXA_DERIVED_DIVERGENCE:
+    q[0] = (J[0].x + J[1].y) + J[2].z;
+    break;
+  case EXA_DERIVED_VORTICITY:
+    q[0] = w.x; q[1] = w.y; q[2] = w.z;
+    break;
+  case EXA_DERIVED_VORTICITY_MAGNITUDE:
+    q[0] = sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z);
+    break;
+  case EXA_DERIVED_Q: {
+    const float d = (J[0].x * J[0].x + J[1].y * J[1].y) + J[2].z * J[2].z;
+    const float o = (J[0].y * J[1].x + J[0].z * J[2].x) + J[1].z * J[2].y;
+    q[0] = -0.5f * d - o;
+    break;
+  }
+  default:   // EXA_DERIVED_HELICITY (the host has checked the quantity)
+    q[0] = (v[0] * w.x + v[1] * w.y) + v[2] * w.z;
+    break;
+  }
+  return region;
+}
+
+// a.components floats of a point or lattice point: the quantity, or `fill` in every one of them where the status is < 0
+__device__ __forceinline__ void storeDerived(const SampleArgs &a, float *at, int st, const float q[3])
+{
+  at[0] = st >= 0 ? q[0] : a.fill;
+  if (a.components == 3) { at[1] = st >= 0 ? q[1] : a.fill; at[2] = st >= 0 ? q[2] : a.fill; }
+}
+
+// one lane per point: the lookup of samplePointsBody, once for the three channels
+__global__ __launch_bounds__(256) void sampleDerivedPointsKernel(const SampleArgs a)
+{
+  const size_t i = size_t(blockIdx.x) * 256u + threadIdx.x;
+  if (i >= a.count) return;
+  V3 p = mk(a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2]);
+  if (a.world) p = xfmPoint(a.fs, p);
+  bool tripped = false;
+  const int region = sampleInRoot(a, p) ? sampleKdLeaf(a, a.kdRoot, p, tripped) : -1;
+  if (tripped) atomicExch(a.errorFlag, 1);
+  float q[3] = { 0.f, 0.f, 0.f };
+  const int st = region >= 0 ? sampleDerived(a, a.regionRec[region], region, p, q) : -1;
+  storeDerived(a, a.values + i * size_t(a.components), st, q);
+  if (a.status) a.status[i] = st;
+}
+
+// sampleGridKernel's patches, shared descent and shared region record, with sampleDerived as the body: the lattice equals
+// sampleDerivedPointsKernel at its positions bit for bit.  Output index: that of sampleGridKernel times a.components
+template <int PX, int PY, int PZ, bool UNIFORM>
+__global__ __launch_bounds__(256) void sampleDerivedGridKernel(const SampleArgs a)
+{
+  static_assert(PX * PY * PZ == 64, "a patch is one wave");
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long wave = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (wave >= a.numPatches) return;
+  const unsigned long long wx = wave % a.patchesX, wyz = wave / a.patchesX;
+  const unsigned long long wy = wyz % a.patchesY, wz = wyz / a.patchesY;
+  const long long x = a.box0[0] + (long long)(wx * PX + lane % PX);
+  const long long y = a.box0[1] + (long long)(wy * PY + (lane / PX) % PY);
+  const long long z = a.box0[2] + (long long)(wz * PZ + lane / (PX * PY));
+  if (x >= a.box1[0] || y >= a.box1[1] || z >= a.box1[2]) return;
+  V3 p = mk(a.lo[0] + (float(x) + 0.5f) * a.step[0], a.lo[1] + (float(y) + 0.5f) * a.step[1], a.lo[2] + (float(z) + 0.5f) * a.step[2]);
+  if (a.world) p = xfmPoint(a.fs, p);
+  bool tripped = false;
+  int region = -1;
+  if (sampleInRoot(a, p)) region = sampleKdLeafWave<UNIFORM>(a, p, tripped);
+  if (tripped) atomicExch(a.errorFlag, 1);
+  const int r0 = __builtin_amdgcn_readfirstlane(region);
+  float q[3] = { 0.f, 0.f, 0.f };
+  int st = -1;
+  if (UNIFORM && r0 >= 0 && !anyLane(region != r0)) st = sampleDerived(a, a.regionRec[r0], region, p, q);   // wave-uniform index: one record per wave
+  else if (region >= 0) st = sampleDerived(a, a.regionRec[region], region, p, q);
+  const size_t o = size_t(x - a.box0[0]) + size_t(y - a.box0[1]) * size_t(a.strideY) + size_t(z - a.box0[2]) * size_t(a.strideZ);
+  storeDerived(a, a.out + o * size_t(a.components), st, q);
 }
 
 // ---- exa_hip_project: the field reduced along rays ----
@@ -282,19 +385,32 @@ hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s)
   return hipGetLastError();
 }
 
-hipError_t launchSampleGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s)
-{
-  if (a.numPatches == 0) return hipSuccess;
-  const dim3 grid((unsigned)((a.numPatches + 3) / 4)), block(256);
-#define EXA_SG(X, Y, Z) do { if (uniform) hipLaunchKernelGGL((sampleGridKernel<X, Y, Z, true>), grid, block, 0, s, a); \
-                             else hipLaunchKernelGGL((sampleGridKernel<X, Y, Z, false>), grid, block, 0, s, a); } while (0)
-  switch (shape) {
-  case 0: EXA_SG(64, 1, 1); break;
-  case 1: EXA_SG(16, 4, 1); break;
-  case 2: EXA_SG(8, 8, 1); break;
-  case 3: EXA_SG(4, 4, 4); break;
-  default: return hipErrorInvalidValue;
+// a launcher of a grid kernel K<PX, PY, PZ, UNIFORM>: one wave per patch of shape `shape`
+#define EXA_GRID_LAUNCHER(NAME, K)                                                                                       \
+  hipError_t NAME(const SampleArgs &a, int shape, bool uniform, hipStream_t s)                                           \
+  {                                                                                                                      \
+    if (a.numPatches == 0) return hipSuccess;                                                                            \
+    const dim3 grid((unsigned)((a.numPatches + 3) / 4)), block(256);                                                     \
+    switch (shape * 2 + (uniform ? 1 : 0)) {                                                                             \
+    case 0: hipLaunchKernelGGL((K<64, 1, 1, false>), grid, block, 0, s, a); break;                                       \
+    case 1: hipLaunchKernelGGL((K<64, 1, 1, true>), grid, block, 0, s, a); break;                                        \
+    case 2: hipLaunchKernelGGL((K<16, 4, 1, false>), grid, block, 0, s, a); break;                                       \
+    case 3: hipLaunchKernelGGL((K<16, 4, 1, true>), grid, block, 0, s, a); break;                                        \
+    case 4: hipLaunchKernelGGL((K<8, 8, 1, false>), grid, block, 0, s, a); break;                                        \
+    case 5: hipLaunchKernelGGL((K<8, 8, 1, true>), grid, block, 0, s, a); break;                                         \
+    case 6: hipLaunchKernelGGL((K<4, 4, 4, false>), grid, block, 0, s, a); break;                                        \
+    case 7: hipLaunchKernelGGL((K<4, 4, 4, true>), grid, block, 0, s, a); break;                                         \
+    default: return hipErrorInvalidValue;                                                                                \
+    }                                                                                                                    \
+    return hipGetLastError();                                                                                            \
   }
-#undef EXA_SG
+EXA_GRID_LAUNCHER(launchSampleGrid, sampleGridKernel)
+EXA_GRID_LAUNCHER(launchSampleDerivedGrid, sampleDerivedGridKernel)
+#undef EXA_GRID_LAUNCHER
+
+hipError_t launchSampleDerivedPoints(const SampleArgs &a, hipStream_t s)
+{
+  if (a.count == 0) return hipSuccess;
+  hipLaunchKernelGGL(sampleDerivedPointsKernel, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();
 }

@@ -22,7 +22,13 @@
 //                                            a config's `triangles` line reads, with
 //             [--isomesh-box lx ly lz ux uy uz] [--isomesh-world] [--isomesh-channel c]
 //                                            (box default as for --resample)
-//             [--histogram BINS file.txt]    the exact histogram of a channel's cell values (exa_hip_histogram), one line
+//             [--derived QUANTITY C0 C1 C2]  --resample and --isomesh work on a quantity of the velocity gradient tensor of the
+//                                            vector field of channels C0 C1 C2 instead of a channel (exa_hip_resample_derived,
+//                                            exa_hip_isosurface_derived; voxel-space quantities): speed, divergence, vorticity,
+//                                            vorticity_magnitude, q or helicity, or its number 0..5.  vorticity has three
+//                                            components, written interleaved by --resample and refused by --isomesh.  With it
+//                                            --resample-channel / --isomesh-channel are an error
+//             [--histogram BINS file.txt]   the exact histogram of a channel's cell values (exa_hip_histogram), one line
 //                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
 //             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
 //                                            (range default: min..max of the channel from a range-only pass — a constant field
@@ -74,6 +80,18 @@ void setupCamera(Renderer &r, vec3f origin, vec3f interest, vec3f up, float fovy
               lower_left.x, lower_left.y, lower_left.z, du.x, du.y, du.z, dv.x, dv.y, dv.z);
   r.updateCamera(origin, lower_left, du, dv);
 }
+
+// --derived QUANTITY: a name or a number; EXA_DERIVED_* (the module refuses an unknown number)
+int derivedQuantity(const std::string &s)
+{
+  static const char *const names[EXA_DERIVED_QUANTITIES] = { "speed", "divergence", "vorticity", "vorticity_magnitude", "q", "helicity" };
+  for (int q = 0; q < EXA_DERIVED_QUANTITIES; q++)
+    if (s == names[q]) return q;
+  char *end = nullptr;
+  const long q = std::strtol(s.c_str(), &end, 10);
+  if (end == s.c_str() || *end || q < 0) throw std::runtime_error("--derived wants speed, divergence, vorticity, vorticity_magnitude, q, helicity or a number, not " + s);
+  return (int)q;
+}
 } // namespace
 
 int main(int argc, char **argv)
@@ -117,6 +135,9 @@ int main(int argc, char **argv)
     std::string projectName;
     int projectChannel = 0, projectSamples = 0;
     float projectDt = 0.f;
+    int derived = -1;                                             // --derived: EXA_DERIVED_*
+    vec3i derivedChannels(0, 1, 2);
+    bool haveResampleChannel = false, haveIsoChannel = false;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -163,7 +184,7 @@ int main(int argc, char **argv)
       }
       else if (a == "--resample-box") { resampleBox.lower = { f(), f(), f() }; resampleBox.upper = { f(), f(), f() }; haveResampleBox = true; }
       else if (a == "--resample-world") resampleWorld = true;
-      else if (a == "--resample-channel") resampleChannel = (int)f();
+      else if (a == "--resample-channel") { resampleChannel = (int)f(); haveResampleChannel = true; }
       else if (a == "--resample-fill") resampleFill = f();
       else if (a == "--isomesh") {
         isoValue = f();
@@ -173,7 +194,12 @@ int main(int argc, char **argv)
       }
       else if (a == "--isomesh-box") { isoBox.lower = { f(), f(), f() }; isoBox.upper = { f(), f(), f() }; haveIsoBox = true; }
       else if (a == "--isomesh-world") isoWorld = true;
-      else if (a == "--isomesh-channel") isoChannel = (int)f();
+      else if (a == "--isomesh-channel") { isoChannel = (int)f(); haveIsoChannel = true; }
+      else if (a == "--derived") {
+        if (i + 1 >= argc) throw std::runtime_error("missing quantity after --derived");
+        derived = derivedQuantity(argv[++i]);
+        derivedChannels.x = (int)f(); derivedChannels.y = (int)f(); derivedChannels.z = (int)f();
+      }
       else if (a == "--histogram") {
         histBins = (int)f();
         if (i + 1 >= argc) throw std::runtime_error("missing file after --histogram BINS");
@@ -219,6 +245,8 @@ int main(int argc, char **argv)
       else throw std::runtime_error("unknown flag " + a);
     }
     if (cfgName.empty()) throw std::runtime_error("usage: exaRender cfg.exa [flags]");
+    if (derived != -1 && (haveResampleChannel || haveIsoChannel))
+      throw std::runtime_error("--derived takes its three channels itself: --resample-channel / --isomesh-channel do not go with it");
     Config::SP config = Config::parseConfigFile(cfgName);
     if (!config->bricks.sp) throw std::runtime_error("no bricks file specified");
     config->bricks.sp->allowEmptyCells = allowEmptyCells;
@@ -288,27 +316,35 @@ int main(int argc, char **argv)
       const box3f box = haveResampleBox ? resampleBox : (resampleWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
       const vec3i dims(resampleDims[0], resampleDims[1], resampleDims[2]);
       if (dims.x < 1 || dims.y < 1 || dims.z < 1) throw std::runtime_error("--resample wants NX NY NZ >= 1");
-      std::vector<float> grid(size_t(dims.x) * size_t(dims.y) * size_t(dims.z));
+      const size_t comps = derived == EXA_DERIVED_VORTICITY ? 3 : 1;
+      std::vector<float> grid(size_t(dims.x) * size_t(dims.y) * size_t(dims.z) * comps);
       // sampled with a NaN fill to count the points outside every region (a reconstructed value is never NaN for a field
       // without NaNs), then the requested fill written in their place
-      renderer.resample(box, dims, resampleChannel, grid.data(), resampleWorld, NAN);
-      size_t invalid = 0;
+      if (derived < 0) renderer.resample(box, dims, resampleChannel, grid.data(), resampleWorld, NAN);
+      else renderer.resampleDerived(box, dims, derivedChannels, derived, grid.data(), resampleWorld, NAN);
+      size_t invalid = 0;                                             // floats: `comps` per lattice point
       for (float &v : grid)
         if (std::isnan(v)) { v = resampleFill; invalid++; }
       FILE *f = std::fopen(resampleName.c_str(), "wb");
       if (!f || std::fwrite(grid.data(), sizeof(float), grid.size(), f) != grid.size()) throw std::runtime_error("cannot write " + resampleName);
       std::fclose(f);
-      std::printf("resample %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channel %d invalid %zu\n", dims.x, dims.y, dims.z,
-                  box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z, resampleChannel, invalid);
+      std::printf("resample %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g ", dims.x, dims.y, dims.z,
+                  box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z);
+      if (derived < 0) std::printf("channel %d invalid %zu\n", resampleChannel, invalid);
+      else std::printf("derived %d channels %d %d %d components %zu invalid %zu\n", derived, derivedChannels.x, derivedChannels.y,
+                       derivedChannels.z, comps, invalid);
     }
     if (!isoName.empty()) {
       const box3f box = haveIsoBox ? isoBox : (isoWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
       const vec3i dims(isoDims[0], isoDims[1], isoDims[2]);
-      TriangleMesh::SP mesh = renderer.extractIsoSurface(box, dims, isoChannel, isoValue, isoWorld);
+      TriangleMesh::SP mesh = derived < 0 ? renderer.extractIsoSurface(box, dims, isoChannel, isoValue, isoWorld)
+                                          : renderer.extractIsoSurfaceDerived(box, dims, derivedChannels, derived, isoValue, isoWorld);
       TriangleMesh::save(isoName, { mesh });
-      std::printf("isomesh %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channel %d iso %.9g vertices %zu triangles %zu\n", dims.x, dims.y,
-                  dims.z, box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z, isoChannel, isoValue,
-                  mesh->vertex.size(), mesh->index.size());
+      std::printf("isomesh %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g ", dims.x, dims.y, dims.z, box.lower.x, box.lower.y,
+                  box.lower.z, box.upper.x, box.upper.y, box.upper.z);
+      if (derived < 0) std::printf("channel %d ", isoChannel);
+      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
+      std::printf("iso %.9g vertices %zu triangles %zu\n", isoValue, mesh->vertex.size(), mesh->index.size());
     }
     if (!histName.empty()) {
       if (histBins < 1) throw std::runtime_error("--histogram wants BINS >= 1");

@@ -559,6 +559,20 @@ void Renderer::resample(const box3f &box, vec3i dims, int channel, float *out, b
   check(exa_hip_resample(handle, lo, hi, d, channel, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, 0, nullptr, 0), handle);
 }
 
+// the mesh of the last extraction (exa_hip_isosurface or exa_hip_isosurface_derived) out of the module, which then drops it
+static TriangleMesh::SP readIsoMesh(ExaHipRenderer *handle, uint64_t nv, uint64_t nt, std::vector<vec3f> *gradients)
+{
+  auto mesh = std::make_shared<TriangleMesh>();
+  mesh->vertex.resize(nv);
+  mesh->index.resize(nt);
+  if (gradients) gradients->resize(nv);
+  check(exa_hip_isosurface_read(handle, reinterpret_cast<float *>(mesh->vertex.data()),
+                                gradients ? reinterpret_cast<float *>(gradients->data()) : nullptr,
+                                reinterpret_cast<int32_t *>(mesh->index.data()), 0, nullptr), handle);
+  check(exa_hip_isosurface_release(handle), handle);
+  return mesh;
+}
+
 TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace,
                                              std::vector<vec3f> *gradients)
 {
@@ -568,16 +582,37 @@ TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int c
   uint64_t nv = 0, nt = 0;
   const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0);
   check(exa_hip_isosurface(handle, lo, hi, d, channel, iso, flags, &nv, &nt, nullptr), handle);
-  auto mesh = std::make_shared<TriangleMesh>();
-  mesh->vertex.resize(nv);
-  mesh->index.resize(nt);
-  if (gradients) gradients->resize(nv);
-  const int rc = exa_hip_isosurface_read(handle, reinterpret_cast<float *>(mesh->vertex.data()),
-                                         gradients ? reinterpret_cast<float *>(gradients->data()) : nullptr,
-                                         reinterpret_cast<int32_t *>(mesh->index.data()), 0, nullptr);
-  if (rc) check(rc, handle);
-  check(exa_hip_isosurface_release(handle), handle);
-  return mesh;
+  return readIsoMesh(handle, nv, nt, gradients);
+}
+
+void Renderer::sampleDerived(const vec3f *points, size_t n, vec3i channels, int quantity, float *out, int *status,
+                             bool worldSpace, float fill)
+{
+  if (worldSpace) pushState();
+  const int32_t ch[3] = { channels.x, channels.y, channels.z };
+  check(exa_hip_sample_derived(handle, reinterpret_cast<const float *>(points), n, ch, quantity,
+                               worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, status, 0, nullptr, 0), handle);
+}
+
+void Renderer::resampleDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float *out, bool worldSpace, float fill)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  check(exa_hip_resample_derived(handle, lo, hi, d, ch, quantity, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, 0, nullptr, 0),
+        handle);
+}
+
+TriangleMesh::SP Renderer::extractIsoSurfaceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso,
+                                                    bool worldSpace)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  uint64_t nv = 0, nt = 0;
+  check(exa_hip_isosurface_derived(handle, lo, hi, d, ch, quantity, iso, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, &nv, &nt, nullptr),
+        handle);
+  return readIsoMesh(handle, nv, nt, nullptr);
 }
 
 void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,

@@ -209,6 +209,18 @@ struct Renderer {
   TriangleMesh::SP extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace = false,
                                      std::vector<vec3f> *gradients = nullptr);
 
+  // quantities of the velocity gradient tensor of the vector field (channels.x, .y, .z): `quantity` = EXA_DERIVED_SPEED,
+  // _DIVERGENCE, _VORTICITY (three components, interleaved), _VORTICITY_MAGNITUDE, _Q or _HELICITY (exa_hip_sample_derived,
+  // exa_hip_resample_derived, exa_hip_isosurface_derived; include/exa_hip.h states the contract).  At points (out n x
+  // components, status n or NULL), on the lattice of resample(box, dims) (components floats per lattice point) and as the
+  // surface quantity == iso on that lattice (one-component quantities).  Voxel-space quantities, also with worldSpace.
+  void sampleDerived(const vec3f *points, size_t n, vec3i channels, int quantity, float *out, int *status = nullptr,
+                     bool worldSpace = false, float fill = NAN);
+  void resampleDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float *out, bool worldSpace = false,
+                       float fill = NAN);
+  TriangleMesh::SP extractIsoSurfaceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso,
+                                            bool worldSpace = false);
+
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
   // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
