@@ -33,7 +33,17 @@ extern "C" {
 
 /* ---- POD mirrors of the reference's shared host/device structs ---- */
 
-/* programs/Brick.h:31-71 */
+/* programs/Brick.h:31-71
+ *
+ * Coordinates are signed: a scene may lie anywhere, the origin inside it or far from it.  What bounds them is that every
+ * table derived from the bricks is float32.  With cw = 2^level, each of the planes
+ *     lower,  lower +- cw/2,  lower + size cw,  lower + (size +- 1/2) cw        (per axis)
+ * must be exactly representable in float32: for level-0 bricks that is |coordinate| < 2^23.  exa_prep_create[_ex] and
+ * exa_hip_create[_multi] refuse a scene that breaks this and name the brick and the plane.  exa_prep_create[_ex]
+ * furthermore refuses a scene in which the float32 arithmetic that chooses the regions' split planes (midpoints and
+ * distances of such planes, as the reference computes them) rounds so that another plane is chosen than exact
+ * arithmetic would choose: level-0 bricks beyond |coordinate| = 2^22.  Inside these limits the prepared tables of a scene
+ * moved by an integer vector are the tables of the scene, moved. */
 typedef struct ExaBrick {
   int32_t  lower[3];
   int32_t  size[3];

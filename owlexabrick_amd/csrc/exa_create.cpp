@@ -3,6 +3,7 @@
 // the constructor of exa/OptixRenderer.cpp does through OWL/OptiX; see include/exa_hip.h for the per-entry citations.
 #include "exa_renderer.h"
 #include "exa_hostbvh.h"
+#include "exa_coords.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -208,6 +209,10 @@ int exa_hip_create(const ExaHipScene *scene, int32_t device, ExaHipRenderer **ou
     const ExaBrick &B = scene->bricks[b];
     if (B.size[0] <= 0 || B.size[1] <= 0 || B.size[2] <= 0 || B.level < 0 || B.level > 30
         || uint64_t(B.begin) + volumeOf(B) > scene->totalCells) { h->fail("exa_hip_create: brick record out of range"); return bail(); }
+    int axis = 0;
+    double plane = 0.0;
+    // (next to the kd-tree's check below: a table that does not describe the scene is refused, not rendered)
+    if (!exa::brickPlanesAreFloats(B, &axis, &plane)) { h->fail(exa::brickPlaneMessage("exa_hip_create", b, B, axis, plane)); return bail(); }
   }
   for (int f = 0; f < scene->numFields; f++)
     if (scene->channelOffset[f] + scene->totalCells > uint64_t(scene->numFields) * scene->totalCells) { h->fail("exa_hip_create: channel offset out of range"); return bail(); }

@@ -9,6 +9,7 @@
 // offsets and every float are the same as the reference would produce.
 #include "../../include/exa_hip.h"
 #include "exa_ropes.h"
+#include "exa_coords.h"
 
 #include <algorithm>
 #include <atomic>
@@ -58,6 +59,16 @@ struct RegionChunk {
 struct RegionPartitioner {
   std::atomic<int> workersFree{0};
   static constexpr size_t kSpawnThreshold = 4096;   // prims; below this recurse inline
+  // The choice of a split plane below is float32 arithmetic on the planes (the reference's): box centre, span, distance.
+  // With coordinates that are large against the cell width those round, although every plane is a float32, and a rounded
+  // distance can pick another plane: the same cells somewhere else are then partitioned differently.  Each choice is
+  // made a second time in double, where those operations are exact; the first one that differs is recorded (axis, the
+  // two planes) and the caller refuses the scene.
+  std::atomic<bool> rounded{false};
+  std::atomic<bool> roundedClaimed{false};
+  int roundedAxis = 0;
+  float roundedPlane[2] = { 0.f, 0.f };
+  int32_t roundedBrick = -1;
 
   // exa/Regions.cpp:32-71 addLeaf
   static int32_t emitLeaf(const std::vector<BuildPrim> &prims, const float lo[3], const float hi[3],
@@ -88,11 +99,18 @@ struct RegionPartitioner {
     // candidate plane per axis: the brick-domain face strictly inside the box that is
     // closest to the box centre; first found wins ties (:84-107)
     float centre[3], bestPos[3], bestDist[3], span[3];
+    double centreD[3], bestDistD[3], spanD[3];                      // the same choice in exact arithmetic (see `rounded`)
+    float bestPosD[3];
+    int32_t bestBrick[3] = { -1, -1, -1 };
     for (int i = 0; i < 3; i++) {
       span[i] = dhi[i] - dlo[i];
       centre[i] = 0.5f * (dlo[i] + dhi[i]);
       bestPos[i] = dlo[i];
       bestDist[i] = span[i];
+      spanD[i] = double(dhi[i]) - double(dlo[i]);
+      centreD[i] = 0.5 * (double(dlo[i]) + double(dhi[i]));
+      bestPosD[i] = dlo[i];
+      bestDistD[i] = spanD[i];
     }
     for (const BuildPrim &bp : prims)
       for (int dim = 0; dim < 3; dim++) {
@@ -100,14 +118,24 @@ struct RegionPartitioner {
         for (int side = 0; side < 2; side++) {
           const float pos = face[side];
           if (pos <= dlo[dim] || pos >= dhi[dim]) continue;
+          const double distD = std::fabs(centreD[dim] - double(pos));
+          if (distD < bestDistD[dim]) { bestPosD[dim] = pos; bestDistD[dim] = distD; }
           const float dist = std::fabs(centre[dim] - pos);
           if (dist >= bestDist[dim]) continue;
           bestPos[dim] = pos;
           bestDist[dim] = dist;
+          bestBrick[dim] = bp.brickID;
         }
       }
     int widest = 0;                                                // arg_max(span) (:112)
     for (int i = 1; i < 3; i++) if (std::fabs(span[i]) > std::fabs(span[widest])) widest = i;
+    int widestD = 0;
+    for (int i = 1; i < 3; i++) if (std::fabs(spanD[i]) > std::fabs(spanD[widestD])) widestD = i;
+    for (int i = 0; i < 3; i++)
+      if ((bestPos[i] != bestPosD[i] || widest != widestD) && !roundedClaimed.exchange(true)) {
+        roundedAxis = i; roundedPlane[0] = bestPos[i]; roundedPlane[1] = bestPosD[i]; roundedBrick = bestBrick[i];
+        rounded = true;
+      }
     int splitDim = -1;
     float splitPos = 0.f;
     for (int i = 0; i < 3; i++) {                                  // (:113-123)
@@ -331,6 +359,10 @@ int exa_prep_create_ex(const int32_t *bricks7, uint64_t numBricks,
   for (uint64_t i = 0; i < numBricks; i++) {
     const ExaBrick &b = P->bricks[i];
     const float cw = float(1 << b.level);        // Brick::getDomain (programs/Brick.h:50-55)
+    int axis = 0;
+    double plane = 0.0;
+    if (b.level >= 0 && b.level <= 30 && !exa::brickPlanesAreFloats(b, &axis, &plane))
+      return fail(exa::brickPlaneMessage("exa_prep_create", i, b, axis, plane).c_str());
     for (int k = 0; k < 3; k++) {
       prims[i].lo[k] = float(b.lower[k]) - 0.5f * cw;
       prims[i].hi[k] = float(b.lower[k]) + (float(b.size[k]) + 0.5f) * cw;
@@ -343,6 +375,15 @@ int exa_prep_create_ex(const int32_t *bricks7, uint64_t numBricks,
   part.workersFree = numThreads - 1;
   RegionChunk all;
   P->kdRoot = part.partition(prims, blo, bhi, all);
+  if (part.rounded) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf,
+                  "exa_prep_create: coordinates too large for the cell width: choosing a split plane on the %c axis rounds in float32 "
+                  "(it picks %.9g, a face of brick %d, where exact arithmetic picks %.9g), so the regions would depend on where the "
+                  "scene lies",
+                  "xyz"[part.roundedAxis], double(part.roundedPlane[0]), part.roundedBrick, double(part.roundedPlane[1]));
+    return fail(buf);
+  }
   P->regions = std::move(all.regions);
   P->leafList = std::move(all.leafList);
   P->kdNodes = std::move(all.nodes);

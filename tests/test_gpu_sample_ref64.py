@@ -63,7 +63,12 @@ CASES = [(i, f) for i, c in enumerate(ps.REF_CASES) for f in c[2]]
 @pytest.mark.parametrize("idx,form", CASES, ids=[f"{ps.REF_CASES[i][0]}-f{f}" for i, f in CASES])
 def test_probe_against_the_float64_reference(idx, form):
     name, make, forms, empty = ps.REF_CASES[idx]
-    case = Case(make(), basis_form=form, allow_empty_cells=empty)
+    check_probe_against_the_float64_reference(Case(make(), basis_form=form, allow_empty_cells=empty), name, form, idx)
+
+
+def check_probe_against_the_float64_reference(case, name, form, idx):
+    """the probes of `case`'s scene at ps.ref_points (seeded by idx) and on a lattice against tests/probe_ref64.py: status
+    rule, K_VALUE, K_NUM, the normalized bound (shared with tests/test_gpu_translation.py, which moves the scene)"""
     R = case.hip_renderer()
     pts = ps.ref_points(R.prep, idx)
     assert len(pts) <= 5000
