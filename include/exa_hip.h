@@ -662,6 +662,65 @@ int exa_hip_project(ExaHipRenderer *, const ExaHipRays *, int32_t channel, int32
                     int32_t pointersAreDevice, void *hipStream);
 int exa_hip_project_ms(ExaHipRenderer *, float *ms);   /* device time of the last call's kernel(s) */
 
+/* ---- iso-crossings along rays: where along each ray of an image the field of one channel first crosses a value — the
+ * depth t, the position, the value and the gradient there, and the number of crossings of the whole ray, as plain arrays:
+ * picking, depth images to composite rasterised geometry with, position and normal images without a lattice and a mesh.
+ * New relative to the reference, whose implicit iso hit goes straight into an RGBA8 pixel and depends on the transfer
+ * function and the region activity.  One kernel marches the ray, refines the first crossing and samples the hit in
+ * registers; nothing of size pixels x samples exists. ----
+ *
+ * Positions.  The rays, o, d, t_i and p_i of a pixel are exactly those of exa_hip_project: the same struct, the same
+ * float32 association, EXA_PROJECT_NORMALIZE and its pixels without samples (!(s > 0) or a non-finite s), and
+ * EXA_SAMPLE_WORLD_SPACE as there.  These two are the only flag bits.
+ *
+ * Samples.  S_i is exactly what exa_hip_sample_points(p_i, {channel}, 1, flags & EXA_SAMPLE_WORLD_SPACE) returns in the
+ * handle's current basis_form (a scene marked allowEmptyCells: the form-0 sums with the poison test).  A sample is usable if
+ * its status is >= 0 and its value v_i is not NaN.  inside(v) = v >= iso, as in exa_hip_isosurface; iso must be finite.
+ *
+ * Crossings.  Index i in 1 .. numSamples-1 is a crossing if S_{i-1} and S_i are both usable and inside(v_{i-1}) !=
+ * inside(v_i).  A pair separated by an unusable sample never forms a crossing, and where the volume begins no cap is
+ * invented: a ray that enters the volume, or comes out of a gap or of NaN cells, already on the `>= iso` side has no crossing
+ * there.  This is deliberate: the call reports where the field crosses the value, not where the data begin.
+ *
+ * Per pixel, for the whole ray.  crossings = the number of crossing indices; index = the smallest one, -1 if there is none;
+ * side = +1 if v_{index-1} < iso (the ray enters the `>= iso` side), -1 otherwise, 0 without a crossing.
+ *
+ * Refinement of the first crossing.  From (ta, va) = (t_{index-1}, v_{index-1}) and (tb, vb) = (t_index, v_index), at most
+ * `refine` rounds (0 .. EXA_CROSS_MAX_REFINE), float32 with every operation rounded separately:
+ *     tm = 0.5f * (ta + tb);   if (tm == ta || tm == tb) stop
+ *     pm = o + tm * d          per component;   the sample at pm (as S_i);   if it is not usable, stop
+ *     if (inside(vm) == inside(va)) (ta, va) = (tm, vm);   else (tb, vb) = (tm, vm)
+ * and after the rounds
+ *     s = (iso - va) / (vb - va)        t = ta + s * (tb - ta)        position = o + t * d   per component
+ * in exactly this association, as exa_hip_isosurface interpolates along an edge.  position is in the caller's space (world
+ * space with the flag) and is never put through the transform.  Infinite samples propagate by these formulas (a NaN t and
+ * position where inf - inf or inf / inf arises); nothing is special-cased.
+ *
+ * Value and gradient at the hit.  value and gradient are what exa_hip_sample_points(position, {channel}, 1, (flags &
+ * EXA_SAMPLE_WORLD_SPACE) | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED, fill) returns there: the voxel-space gradient
+ * of the field; a shading normal -g/|g| is the caller's.  A pixel without a crossing has `fill` in t, position, value and
+ * gradient.
+ *
+ * Outputs.  Index y*width + x (position, gradient: three floats there); a NULL pointer skips that array.  With
+ * crossings == NULL a ray may stop at its first crossing; every other array holds the same bytes either way.
+ *
+ * Independence, calls and errors as exa_hip_project: the bytes depend only on the scene, the struct, the channel, iso,
+ * refine, the flags, fill, basis_form and (world space) the transform — not on the transfer function, region activity, the
+ * camera of the frame state, walk, accel, brick_order, interleave, sample_patch or sample_uniform; a pending brick_order
+ * change is applied first; a scene without a kd tree is refused; a multi-device handle runs on devices[0].  Synchronous on
+ * hipStream; host outputs pass through the staging buffer tile by tile, or with pointersAreDevice memory of the handle's
+ * first device.  Refused with a message, after which the handle stays usable: everything exa_hip_project refuses of its
+ * rays, channel and flags, world space before any frame state, a non-finite iso, refine outside 0 .. EXA_CROSS_MAX_REFINE; the
+ * descent's loop guard returns 3.  exa_hip_raycast_iso_ms: the device time of the last call's kernel launches, summed
+ * (0 before any call and after a refused one). */
+#define EXA_CROSS_MAX_REFINE 32
+int exa_hip_raycast_iso(ExaHipRenderer *, const ExaHipRays *, int32_t channel, float iso, int32_t refine, int32_t flags,
+                        float fill,
+                        float *t /* w*h */, float *position /* w*h*3 */, float *value /* w*h */, float *gradient /* w*h*3 */,
+                        int32_t *index /* w*h */, int32_t *side /* w*h */, uint32_t *crossings /* w*h */,
+                        int32_t pointersAreDevice, void *hipStream);
+int exa_hip_raycast_iso_ms(ExaHipRenderer *, float *ms);
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,

@@ -122,6 +122,10 @@ STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREA
 PROJECT_NORMALIZE = 4
 PROJECT_MAX_SAMPLES = 1 << 20
 
+# exa_hip_raycast_iso (include/exa_hip.h)
+CROSS_MAX_REFINE = 32
+RAYCAST_KEYS = ("t", "position", "value", "gradient", "index", "side", "crossings")
+
 # exa_hip_*_derived quantities (include/exa_hip.h: EXA_DERIVED_*), by name, and the number of components of each
 DERIVED = {"speed": 0, "divergence": 1, "vorticity": 2, "vorticity_magnitude": 3, "q": 4, "helicity": 5}
 DERIVED_COMPONENTS = {0: 1, 1: 1, 2: 3, 3: 1, 4: 1, 5: 1}
@@ -196,6 +200,8 @@ _ABI = {
     "exa_hip_streamlines_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_project": (None, [_vp, _P(ExaHipRays), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_project_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_raycast_iso": (None, [_vp, _P(ExaHipRays), _i32, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_raycast_iso_ms": (None, [_vp, _P(_f32)]),
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -748,14 +754,7 @@ class Renderer:
         sum/count the mean), count (uint32), max, min (float32; -inf / +inf where count is 0) and max_index (int32: the
         sample index of the first maximum, -1 for none)."""
         flags = self._probe_world(world) | (PROJECT_NORMALIZE if normalize else 0)
-        rays = ExaHipRays()
-        for name, v in (("org", org), ("orgDu", orgDu), ("orgDv", orgDv), ("dir", dir), ("dirDu", dirDu), ("dirDv", dirDv)):
-            setattr(rays, name, _f3(v))
-        rays.width, rays.height = int(size[0]), int(size[1])
-        rays.tmin, rays.dt, rays.numSamples = float(tmin), float(dt), int(num_samples)
-        shape = (max(rays.height, 0), max(rays.width, 0))                      # the module checks the size
-        if shape[0] * shape[1] > 2 ** 31 - 1:
-            shape = (0, 0)
+        rays, shape = _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples)
         out = dict(sum=np.empty(shape, np.float64), count=np.empty(shape, np.uint32), max=np.empty(shape, np.float32),
                    min=np.empty(shape, np.float32), max_index=np.empty(shape, np.int32))
         self._check(lib().exa_hip_project(self.h, C.byref(rays), int(channel), flags, out["sum"].ctypes.data,
@@ -766,6 +765,46 @@ class Renderer:
     def projectMs(self):
         """device ms of the last project call's kernel launches, summed"""
         return self._ms(lib().exa_hip_project_ms)
+
+    # ---- iso-crossings along rays (exa_hip_raycast_iso; include/exa_hip.h states the contract) ----
+    def raycast_iso(self, org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples, iso, refine=8, channel=0,
+                    world=False, normalize=False, fill=float("nan"), outputs=RAYCAST_KEYS, stream=None):
+        """where the field of `channel` first crosses `iso` along the rays of project (same arguments, same sample positions):
+        a dict of arrays [height, width] — t (float32: the depth of the first crossing after `refine` rounds of bisection
+        and a linear interpolation), position [.., 3] (in the caller's space), value and gradient [.., 3] (the point probe's
+        value and voxel-space gradient at position), index (int32: the sample index behind the first crossing, -1 for none),
+        side (int32: +1 entering the >= iso side, -1 leaving it, 0 for none), crossings (uint32: crossings of the whole ray).
+        t, position, value and gradient are `fill` without a crossing.  outputs: the keys wanted; the others are skipped."""
+        unknown = [k for k in outputs if k not in RAYCAST_KEYS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown} (of {', '.join(RAYCAST_KEYS)})")
+        flags = self._probe_world(world) | (PROJECT_NORMALIZE if normalize else 0)
+        rays, shape = _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples)
+        kinds = dict(t=((), np.float32), position=((3,), np.float32), value=((), np.float32), gradient=((3,), np.float32),
+                     index=((), np.int32), side=((), np.int32), crossings=((), np.uint32))
+        out = {k: np.empty(shape + kinds[k][0], kinds[k][1]) for k in RAYCAST_KEYS if k in outputs}
+        ptr = [out[k].ctypes.data if k in out else None for k in RAYCAST_KEYS]
+        self._check(lib().exa_hip_raycast_iso(self.h, C.byref(rays), int(channel), float(iso), int(refine), flags, float(fill),
+                                              *ptr, 0, C.c_void_p(stream or 0)))
+        return out
+
+    def raycastIsoMs(self):
+        """device ms of the last raycast_iso call's kernel launches, summed"""
+        return self._ms(lib().exa_hip_raycast_iso_ms)
+
+
+def _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples):
+    """(the ExaHipRays of these arguments, the shape (height, width) of a per-pixel output — (0, 0) for a size the module
+    refuses)"""
+    rays = ExaHipRays()
+    for name, v in (("org", org), ("orgDu", orgDu), ("orgDv", orgDv), ("dir", dir), ("dirDu", dirDu), ("dirDv", dirDv)):
+        setattr(rays, name, _f3(v))
+    rays.width, rays.height = int(size[0]), int(size[1])
+    rays.tmin, rays.dt, rays.numSamples = float(tmin), float(dt), int(num_samples)
+    shape = (max(rays.height, 0), max(rays.width, 0))                      # the module checks the size
+    if shape[0] * shape[1] > 2 ** 31 - 1:
+        shape = (0, 0)
+    return rays, shape
 
 
 def _f3(v):

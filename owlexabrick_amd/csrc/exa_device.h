@@ -281,6 +281,18 @@ struct RayArgs {
   int32_t           *maxIndex;
 };
 
+// The iso-crossings along rays (exa_hip_raycast_iso, sampleCrossingsKernel in exa_sample_kernels.h): the rays, the tile and
+// the patches of the projections, every lane one ray whose first crossing of `iso` it finds, refines and samples in registers.
+struct CrossArgs {
+  RayArgs            r;             // the lookup, the field, the rays and the tile; r.s.fill = the call's fill; the projections' outputs unused
+  float              iso;
+  int32_t            refine;        // rounds of bisection of the first crossing's bracket, 0 .. EXA_CROSS_MAX_REFINE
+  // outputs (each may be NULL), addressed as those of RayArgs; position and gradient hold 3 floats per pixel
+  float             *t, *position, *value, *gradient;
+  int32_t           *index, *side;
+  uint32_t          *crossings;     // NULL: a lane may stop at its first crossing
+};
+
 // The streamline integrator (exa_hip_streamlines, exa_stream_kernels.h): one lane per (seed, requested direction), RK4 in voxel
 // space on the probes' lookup and sums.  Two launches per extraction: the first stores per direction the number of vertices
 // it appends and why it ended, the second (after the scan of the counts) integrates again and stores the vertices packed.
@@ -335,6 +347,8 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
   hipError_t launchSampleDerivedGrid(const SampleArgs &a, int shape, bool uniform, hipStream_t s);                   \
   /* the projections (exa_sample_f*.o): the tile of a, one wave per 8 x 8 pixels; uniform as for the grid */            \
   hipError_t launchSampleRays(const RayArgs &a, bool uniform, hipStream_t s);                                        \
+  /* the iso-crossings along the same rays (exa_sample_f*.o): the tile of a.r, one wave per 8 x 8 pixels */             \
+  hipError_t launchSampleCrossings(const CrossArgs &a, bool uniform, hipStream_t s);                                 \
   /* the streamline integrator (exa_stream_f*.o): lanes [a.laneBase, a.numLanes) of at most 2^24 per launch; emit = the  \
      second launch, which stores the vertices */                                                                        \
   hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);

@@ -1,12 +1,14 @@
 // exa_probe.cpp — reading the reconstructed field outside a frame: the point probes (exa_hip_sample_points,
 // exa_hip_resample; kernels in exa_sample_kernels.h), the quantities derived from three channels' velocity gradient tensor
-// (exa_hip_sample_derived, exa_hip_resample_derived) and the projections along rays (exa_hip_project) in the same file, and
+// (exa_hip_sample_derived, exa_hip_resample_derived), the projections along rays (exa_hip_project) and the iso-crossings along
+// the same rays (exa_hip_raycast_iso) in the same file, and
 // the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
 #include <cmath>
 #include <cstring>
+#include <functional>
 
 // after a synchronous probe: the descent's loop guard (checkLoopGuard)
 const char *const kDescentGuard = ": the kd descent's loop guard tripped (malformed kd-tree?)";
@@ -300,18 +302,10 @@ int exa_hip_derived_ms(ExaHipRenderer *h, float *ms)
   return 0;
 }
 
-// ---- projections (sampleRaysKernel) ----
-// The image goes tile by tile: a tile is at most kProjectTileWidth pixels wide and holds at most kProbeLaunch pixels — host
-// outputs: at most what kProbeStageBytes of the staging buffer hold —, whole 8 x 8 patches except at the image's edges.
-static const uint64_t kProjectTileWidth = 4096;
-
-int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, int32_t flags, double *sum, uint32_t *count,
-                    float *vmax, float *vmin, int32_t *maxIndex, int32_t pointersAreDevice, void *hipStream)
+// ---- rays: the projections (sampleRaysKernel) and the iso-crossings (sampleCrossingsKernel) ----
+// what both calls refuse of their flags, rays and channel
+static int checkRays(ExaHipRenderer *h, const char *fn, const ExaHipRays *rays, int32_t channel, int32_t flags)
 {
-  if (!h) return 1;
-  const char *fn = "exa_hip_project";
-  ExaHipRenderer *r = firstChild(h);
-  r->project.kernelMs = 0.f;
   if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_PROJECT_NORMALIZE, " (EXA_SAMPLE_WORLD_SPACE and EXA_PROJECT_NORMALIZE apply)")) return 1;
   if (!rays) { h->fail(std::string(fn) + ": null rays"); return 1; }
   const float *vec[6] = { rays->org, rays->orgDu, rays->orgDv, rays->dir, rays->dirDu, rays->dirDv };
@@ -328,25 +322,40 @@ int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, 
     return 1;
   }
   if (!checkChannel(h, fn, channel)) return 1;
-  EXA_ON_DEVICE_OF(h, r);
-  hipStream_t s = (hipStream_t)hipStream;
-  RayArgs a;
+  return 0;
+}
+
+// after checkRays, on r's device: probeSetup and the rays' part of the kernels' arguments (the tile: rayTiles)
+static int rayArgs(ExaHipRenderer *h, ExaHipRenderer *r, const char *fn, const ExaHipRays *rays, int32_t channel, int32_t flags,
+                   hipStream_t s, RayArgs &a)
+{
   std::memset(&a, 0, sizeof(a));
   if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a.s)) return 1;
   a.s.numChannels = 1;
   a.s.fieldOffset[0] = r->sc.channelOffset[channel];
   a.rays = *rays;
   a.normalize = (flags & EXA_PROJECT_NORMALIZE) ? 1 : 0;
+  return 0;
+}
 
-  const uint64_t W = uint64_t(rays->width), H = uint64_t(rays->height);
-  // the five optional outputs, named once: the caller's array, the element size and where the kernel stores the current
-  // tile; the doubles first, so that every part of the staging buffer {sum | count | vmax | vmin | maxIndex} is aligned
-  struct Output { char *user; uint64_t size; char *dev; };
-  Output outs[5] = { { reinterpret_cast<char *>(sum), 8, nullptr }, { reinterpret_cast<char *>(count), 4, nullptr },
-                     { reinterpret_cast<char *>(vmax), 4, nullptr }, { reinterpret_cast<char *>(vmin), 4, nullptr },
-                     { reinterpret_cast<char *>(maxIndex), 4, nullptr } };
+// an optional output of one element per pixel: the caller's array (NULL: skipped), the element's size and where the kernel
+// stores the current tile
+struct RayOutput { char *user; uint64_t size; char *dev; };
+
+// The image goes tile by tile: a tile is at most kProjectTileWidth pixels wide and holds at most kProbeLaunch pixels — host
+// outputs: at most what kProbeStageBytes of the staging buffer hold —, whole 8 x 8 patches except at the image's edges.
+// Per tile: a's tile and every outs[k].dev set — a staged tile carves the staging buffer in the order of outs, which must
+// leave every part aligned to its element —, launchTile() between two events, a staged tile's copies, the synchronisation.
+// kernelMs: the device time between the events, summed.
+static const uint64_t kProjectTileWidth = 4096;
+
+static int rayTiles(ExaHipRenderer *h, ExaHipRenderer *r, RayArgs &a, RayOutput *outs, int numOuts, bool pointersAreDevice,
+                    hipStream_t s, float &kernelMs, const std::function<hipError_t()> &launchTile)
+{
+  const uint64_t W = uint64_t(a.rays.width), H = uint64_t(a.rays.height);
+  RayOutput *const outsEnd = outs + numOuts;
   uint64_t perPixel = 0;
-  for (const Output &o : outs) perPixel += o.user ? o.size : 0;
+  for (const RayOutput *o = outs; o != outsEnd; o++) perPixel += o->user ? o->size : 0;
   const bool staged = !pointersAreDevice && perPixel > 0;
   const uint64_t cap = staged ? std::min(kProbeLaunch, kProbeStageBytes / perPixel) : kProbeLaunch;
   const uint64_t tw = std::min(W, kProjectTileWidth), th = std::min(H, std::max<uint64_t>(8, (cap / tw) & ~uint64_t(7)));
@@ -363,31 +372,98 @@ int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, 
       // a staged tile: rows of ex pixels in the staging buffer; else straight into the caller's device arrays
       char *cut = r->probes.stage.p;
       a.strideY = staged ? ex : W;
-      for (Output &o : outs) o.dev = staged ? carve(cut, o.user != nullptr, o.size * ex * ey) : (o.user ? o.user + o.size * first : nullptr);
-      a.sum = reinterpret_cast<double *>(outs[0].dev);
-      a.count = reinterpret_cast<uint32_t *>(outs[1].dev);
-      a.vmax = reinterpret_cast<float *>(outs[2].dev);
-      a.vmin = reinterpret_cast<float *>(outs[3].dev);
-      a.maxIndex = reinterpret_cast<int32_t *>(outs[4].dev);
+      for (RayOutput *o = outs; o != outsEnd; o++)
+        o->dev = staged ? carve(cut, o->user != nullptr, o->size * ex * ey) : (o->user ? o->user + o->size * first : nullptr);
       HIP_TRY(h, hipEventRecord(t.ev[0], s));
-      HIP_TRY(h, EXA_FORM(r, launchSampleRays)(a, r->probes.uniform != 0, s));
+      HIP_TRY(h, launchTile());
       HIP_TRY(h, hipEventRecord(t.ev[1], s));
       if (staged)
-        for (const Output &o : outs)
-          if (o.user) HIP_TRY(h, hipMemcpy2DAsync(o.user + o.size * first, W * o.size, o.dev, ex * o.size, ex * o.size, ey, hipMemcpyDeviceToHost, s));
+        for (const RayOutput *o = outs; o != outsEnd; o++)
+          if (o->user) HIP_TRY(h, hipMemcpy2DAsync(o->user + o->size * first, W * o->size, o->dev, ex * o->size, ex * o->size, ey, hipMemcpyDeviceToHost, s));
       HIP_TRY(h, hipStreamSynchronize(s));
       float ms = 0.f;
       HIP_TRY(h, t.elapsed(0, 1, &ms));
       total += ms;
     }
-  r->project.kernelMs = total;
-  return checkLoopGuard(h, r, fn, kDescentGuard);
+  kernelMs = total;
+  return 0;
+}
+
+int exa_hip_project(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, int32_t flags, double *sum, uint32_t *count,
+                    float *vmax, float *vmin, int32_t *maxIndex, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_project";
+  ExaHipRenderer *r = firstChild(h);
+  r->project.kernelMs = 0.f;
+  if (checkRays(h, fn, rays, channel, flags)) return 1;
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  RayArgs a;
+  if (rayArgs(h, r, fn, rays, channel, flags, s, a)) return 1;
+  // the doubles first, so that every part of the staging buffer {sum | count | vmax | vmin | maxIndex} is aligned
+  RayOutput outs[5] = { { reinterpret_cast<char *>(sum), 8, nullptr }, { reinterpret_cast<char *>(count), 4, nullptr },
+                        { reinterpret_cast<char *>(vmax), 4, nullptr }, { reinterpret_cast<char *>(vmin), 4, nullptr },
+                        { reinterpret_cast<char *>(maxIndex), 4, nullptr } };
+  const int rc = rayTiles(h, r, a, outs, 5, pointersAreDevice != 0, s, r->project.kernelMs, [&]() {
+    a.sum = reinterpret_cast<double *>(outs[0].dev);
+    a.count = reinterpret_cast<uint32_t *>(outs[1].dev);
+    a.vmax = reinterpret_cast<float *>(outs[2].dev);
+    a.vmin = reinterpret_cast<float *>(outs[3].dev);
+    a.maxIndex = reinterpret_cast<int32_t *>(outs[4].dev);
+    return EXA_FORM(r, launchSampleRays)(a, r->probes.uniform != 0, s);
+  });
+  return rc ? rc : checkLoopGuard(h, r, fn, kDescentGuard);
 }
 
 int exa_hip_project_ms(ExaHipRenderer *h, float *ms)
 {
   if (!h || !ms) return 1;
   *ms = firstChild(h)->project.kernelMs;
+  return 0;
+}
+
+int exa_hip_raycast_iso(ExaHipRenderer *h, const ExaHipRays *rays, int32_t channel, float iso, int32_t refine, int32_t flags,
+                        float fill, float *t, float *position, float *value, float *gradient, int32_t *index, int32_t *side,
+                        uint32_t *crossings, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_raycast_iso";
+  ExaHipRenderer *r = firstChild(h);
+  r->raycast.kernelMs = 0.f;
+  if (checkRays(h, fn, rays, channel, flags)) return 1;
+  if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
+  if (refine < 0 || refine > EXA_CROSS_MAX_REFINE) { h->fail(std::string(fn) + ": refine must be in 0.." + std::to_string(EXA_CROSS_MAX_REFINE)); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  CrossArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (rayArgs(h, r, fn, rays, channel, flags, s, a.r)) return 1;
+  a.r.s.fill = fill;
+  a.iso = iso;
+  a.refine = refine;
+  // every element a multiple of 4 bytes: any order leaves the parts of the staging buffer aligned
+  RayOutput outs[7] = { { reinterpret_cast<char *>(t), 4, nullptr }, { reinterpret_cast<char *>(position), 12, nullptr },
+                        { reinterpret_cast<char *>(value), 4, nullptr }, { reinterpret_cast<char *>(gradient), 12, nullptr },
+                        { reinterpret_cast<char *>(index), 4, nullptr }, { reinterpret_cast<char *>(side), 4, nullptr },
+                        { reinterpret_cast<char *>(crossings), 4, nullptr } };
+  const int rc = rayTiles(h, r, a.r, outs, 7, pointersAreDevice != 0, s, r->raycast.kernelMs, [&]() {
+    a.t = reinterpret_cast<float *>(outs[0].dev);
+    a.position = reinterpret_cast<float *>(outs[1].dev);
+    a.value = reinterpret_cast<float *>(outs[2].dev);
+    a.gradient = reinterpret_cast<float *>(outs[3].dev);
+    a.index = reinterpret_cast<int32_t *>(outs[4].dev);
+    a.side = reinterpret_cast<int32_t *>(outs[5].dev);
+    a.crossings = reinterpret_cast<uint32_t *>(outs[6].dev);
+    return EXA_FORM(r, launchSampleCrossings)(a, r->probes.uniform != 0, s);
+  });
+  return rc ? rc : checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+int exa_hip_raycast_iso_ms(ExaHipRenderer *h, float *ms)
+{
+  if (!h || !ms) return 1;
+  *ms = firstChild(h)->raycast.kernelMs;
   return 0;
 }
 

@@ -327,6 +327,10 @@ struct ExaHipRenderer {
   struct Projection {
     float kernelMs = 0.f;
   } project;
+  // the same of the last exa_hip_raycast_iso
+  struct Raycast {
+    float kernelMs = 0.f;
+  } raycast;
   // the device time of the kernels of the last exa_hip_sample_derived / exa_hip_resample_derived
   struct Derived {
     float kernelMs = 0.f;

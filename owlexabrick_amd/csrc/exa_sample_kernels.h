@@ -1,7 +1,7 @@
 // exa_sample_kernels.h — the point probes: exa_hip_sample_points (one lane per point) and exa_hip_resample (one wave per
 // compact patch of 64 grid points), and on the same lookup and sums the derived quantities of exa_hip_sample_derived /
 // exa_hip_resample_derived (the same two shapes of kernel over three channels) and the projections of exa_hip_project (one
-// wave per 8 x 8 rays, reduced in registers).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
+// wave per 8 x 8 rays, reduced in registers) and the iso-crossings of exa_hip_raycast_iso along the same rays.  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
 // -DEXA_TU_SAMPLE=1 (exa_sample_f0.o, exa_sample_f1.o, exa_sample_f0e.o), after samplePoint and the basis evaluations it
 // uses; nothing else of the renderer is compiled there.
 //
@@ -32,7 +32,25 @@ __device__ __forceinline__ Basis sampleSums(const SampleArgs &a, int listBegin, 
   return B;
 }
 
-// one lane per point, the region located once for all channels.  NORM: the voxel-space gradient (see the head of this file)
+// one channel at p inside the closed domain of the region whose record is R: the value and (DERIV) the gradient of the points
+// API — NORM: the voxel-space one (see the head of this file); false, both untouched, where the basis weights vanish (status -2)
+template <bool DERIV, bool NORM>
+__device__ __forceinline__ bool sampleValueGrad(const SampleArgs &a, const RegionRec &R, const float *field, V3 p, float &value, V3 &grad)
+{
+  const Basis B = sampleSums<DERIV, NORM>(a, R.listBegin, R.listSize, field, p);
+  if (B.sumW <= 1e-20f) return false;
+  value = B.sumWV / B.sumW;
+  if (DERIV) {
+    grad = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
+    if (NORM) {
+      const float w2 = B.sumW * B.sumW;
+      grad = mk(grad.x / w2, grad.y / w2, grad.z / w2);
+    }
+  }
+  return true;
+}
+
+// one lane per point, the region located once for all channels
 template <bool DERIV, bool NORM>
 __device__ __forceinline__ void samplePointsBody(const SampleArgs &a)
 {
@@ -54,21 +72,7 @@ __device__ __forceinline__ void samplePointsBody(const SampleArgs &a)
     int st = region;
     float value = a.fill;
     V3 grad = mk(a.fill, a.fill, a.fill);
-    if (region >= 0) {
-      const Basis B = sampleSums<DERIV, NORM>(a, R.listBegin, R.listSize, a.scalars + a.fieldOffset[c], p);
-      if (B.sumW <= 1e-20f) {
-        st = -2;
-      } else {
-        value = B.sumWV / B.sumW;
-        if (DERIV) {
-          grad = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
-          if (NORM) {
-            const float w2 = B.sumW * B.sumW;
-            grad = mk(grad.x / w2, grad.y / w2, grad.z / w2);
-          }
-        }
-      }
-    }
+    if (region >= 0 && !sampleValueGrad<DERIV, NORM>(a, R, a.scalars + a.fieldOffset[c], p, value, grad)) st = -2;
     a.values[o] = value;
     if (DERIV) { a.gradients[3 * o] = grad.x; a.gradients[3 * o + 1] = grad.y; a.gradients[3 * o + 2] = grad.z; }
     if (a.status) a.status[o] = st;
@@ -228,12 +232,9 @@ __global__ __launch_bounds__(256) void sampleDerivedGridKernel(const SampleArgs 
 
 // ---- exa_hip_project: the field reduced along rays ----
 // p_i of the contract: t_i = tmin + (float(i) + 0.5f) * dt, p_i = o + t_i * d, every operation rounded separately (the unit
-// is compiled without contraction).  The ONE position function of the march and of the bisections below.
-__device__ __forceinline__ V3 rayPos(const RayArgs &a, V3 o, V3 d, int i)
-{
-  const float t = a.rays.tmin + (float(i) + 0.5f) * a.rays.dt;
-  return o + t * d;
-}
+// is compiled without contraction).  The ONE position function of the marches and of the bisections below.
+__device__ __forceinline__ float rayTime(const RayArgs &a, int i) { return a.rays.tmin + (float(i) + 0.5f) * a.rays.dt; }
+__device__ __forceinline__ V3 rayPos(const RayArgs &a, V3 o, V3 d, int i) { return o + rayTime(a, i) * d; }
 
 // sampleInRoot's six comparisons, dealt by the sign of the direction into the three a ray satisfies from some index on
 // (rayEntered) and the three it satisfies up to some index (rayNotLeft): sampleInRoot(p) == rayEntered(p) && rayNotLeft(p)
@@ -262,11 +263,8 @@ __device__ __forceinline__ void rayAccumulate(const RayArgs &a, const RegionRec 
   if (v < acc.vmin) acc.vmin = v;
 }
 
-// One wave per 8 x 8 pixels, every lane one ray; the lanes step the sample index i together, so that at every i the wave's
-// 64 positions lie in a small patch of space and the grid kernel's UNIFORM scheme applies: a shared descent while the lanes
-// (those inside the root box) take the same side of every plane, one region record and one stream of brick headers per wave
-// when they land in one region, else lane by lane.  Both through sampleInRoot, sampleKdChild, sampleKdLeaf, sampleInDomain
-// and sampleSums<false>, as the points kernel: a sample equals exa_hip_sample_points bit for bit.
+// A lane's pixel of the tile, its ray (o, d of the contract) and the sample indices to march: its own [beg, end) and the
+// union [wBeg, wEnd) of its wave's (wave-uniform).  One wave per 8 x 8 pixels, every lane one ray.
 //
 // SKIP (voxel space): indices whose position cannot lie in the root box are not marched.  For a lane with finite o and d
 // (any other lane has no position inside the finite root box at all: a non-finite o or d makes every p_i infinite or NaN)
@@ -282,15 +280,19 @@ __device__ __forceinline__ void rayAccumulate(const RayArgs &a, const RegionRec 
 // is therefore one whose sample is invalid (status -1), which the reduction ignores; the marched ones are tested with
 // sampleInRoot itself as ever.  The wave marches the union [min beg, max end) of its lanes' ranges; a lane idles outside
 // its own.  In world space the transform mixes the axes and nothing of this holds: every index is marched.
-template <bool UNIFORM, bool SKIP>
-__global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
+struct RayLane {
+  bool live;                  // a dead lane stays (the wave's shuffles and ballots see it) with no samples
+  int  x, y;
+  V3   o, d;
+  int  beg, end, wBeg, wEnd;
+};
+
+template <bool SKIP>
+__device__ __forceinline__ RayLane rayLane(const RayArgs &a, unsigned long long wave, unsigned lane)
 {
-  const unsigned lane = threadIdx.x & 63u;
-  const unsigned long long wave = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (wave >= a.numPatches) return;
   const long long xl = a.x0 + (long long)(wave % a.patchesX) * 8 + (long long)(lane & 7u);
   const long long yl = a.y0 + (long long)(wave / a.patchesX) * 8 + (long long)(lane >> 3);
-  const bool live = xl < a.x1 && yl < a.y1;        // a dead lane stays (the wave's shuffles and ballots see it) with no samples
+  const bool live = xl < a.x1 && yl < a.y1;
   const int x = int(xl), y = int(yl);              // a live lane's fit: x1, y1 are int32
   const int n = a.rays.numSamples;
   const float sx = float(x) + 0.5f, sy = float(y) + 0.5f;
@@ -330,18 +332,34 @@ __global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
     wBeg = min(wBeg, __shfl_xor(wBeg, m, 64));
     wEnd = max(wEnd, __shfl_xor(wEnd, m, 64));
   }
-  wBeg = __builtin_amdgcn_readfirstlane(wBeg);
-  wEnd = __builtin_amdgcn_readfirstlane(wEnd);
+  RayLane L;
+  L.live = live; L.x = x; L.y = y; L.o = o; L.d = d; L.beg = beg; L.end = end;
+  L.wBeg = __builtin_amdgcn_readfirstlane(wBeg);
+  L.wEnd = __builtin_amdgcn_readfirstlane(wEnd);
+  return L;
+}
 
+// The lanes step the sample index i together, so that at every i the wave's 64 positions lie in a small patch of space and
+// the grid kernel's UNIFORM scheme applies: a shared descent while the lanes (those inside the root box) take the same side
+// of every plane, one region record and one stream of brick headers per wave when they land in one region, else lane by
+// lane.  Both through sampleInRoot, sampleKdChild, sampleKdLeaf, sampleInDomain and sampleSums<false>, as the points kernel:
+// a sample equals exa_hip_sample_points bit for bit.
+template <bool UNIFORM, bool SKIP>
+__global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long wave = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (wave >= a.numPatches) return;
+  const RayLane L = rayLane<SKIP>(a, wave, lane);
   const float *field = a.s.scalars + a.s.fieldOffset[0];
   RayAcc acc;
   acc.sum = 0.0; acc.count = 0u; acc.vmax = -INFINITY; acc.vmin = INFINITY; acc.maxIndex = -1;
   bool tripped = false;
-  for (int i = wBeg; i < wEnd; i++) {
-    V3 p = rayPos(a, o, d, i);
+  for (int i = L.wBeg; i < L.wEnd; i++) {
+    V3 p = rayPos(a, L.o, L.d, i);
     if (a.s.world) p = xfmPoint(a.s.fs, p);
     int region = -1;
-    if (i >= beg && i < end && sampleInRoot(a.s, p)) region = sampleKdLeafWave<UNIFORM>(a.s, p, tripped);
+    if (i >= L.beg && i < L.end && sampleInRoot(a.s, p)) region = sampleKdLeafWave<UNIFORM>(a.s, p, tripped);
     if (region >= 0) {
       const int r0 = __builtin_amdgcn_readfirstlane(region);           // of the lanes that have a region
       if (UNIFORM && !anyLane(region != r0)) {
@@ -354,8 +372,8 @@ __global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
     }
   }
   if (tripped) atomicExch(a.s.errorFlag, 1);
-  if (!live) return;
-  const size_t at = size_t(x - a.x0) + size_t(y - a.y0) * size_t(a.strideY);
+  if (!L.live) return;
+  const size_t at = size_t(L.x - a.x0) + size_t(L.y - a.y0) * size_t(a.strideY);
   if (a.sum) a.sum[at] = acc.sum;
   if (a.count) a.count[at] = acc.count;
   if (a.vmax) a.vmax[at] = acc.vmax;
@@ -363,17 +381,119 @@ __global__ __launch_bounds__(256) void sampleRaysKernel(const RayArgs a)
   if (a.maxIndex) a.maxIndex[at] = acc.maxIndex;
 }
 
-hipError_t launchSampleRays(const RayArgs &a, bool uniform, hipStream_t s)
+// ---- exa_hip_raycast_iso: the first crossing of a value along the same rays ----
+// the point probe at the caller's position q, lane by lane (the lookup of samplePointsBody, the value of sampleValue): false,
+// v untouched, where the sample is not usable — status < 0, or a NaN value
+__device__ __forceinline__ bool crossSample(const SampleArgs &s, const float *field, V3 q, bool &tripped, float &v)
 {
-  if (a.numPatches == 0) return hipSuccess;
-  const dim3 grid((unsigned)((a.numPatches + 3) / 4)), block(256);
-  const bool skip = a.s.world == 0;
-  if (uniform) { if (skip) hipLaunchKernelGGL((sampleRaysKernel<true, true>), grid, block, 0, s, a);
-                 else      hipLaunchKernelGGL((sampleRaysKernel<true, false>), grid, block, 0, s, a); }
-  else         { if (skip) hipLaunchKernelGGL((sampleRaysKernel<false, true>), grid, block, 0, s, a);
-                 else      hipLaunchKernelGGL((sampleRaysKernel<false, false>), grid, block, 0, s, a); }
-  return hipGetLastError();
+  const V3 p = s.world ? xfmPoint(s.fs, q) : q;
+  if (!sampleInRoot(s, p)) return false;
+  const int region = sampleKdLeaf(s, s.kdRoot, p, tripped);
+  if (region < 0) return false;
+  float u;
+  if (!sampleValue(s, s.regionRec[region], field, p, u) || u != u) return false;
+  v = u;
+  return true;
 }
+
+// sampleRaysKernel's rays, patches, lookup and skipped indices — a skipped index is a sample with status -1, which is not
+// usable: skipping cannot change a byte — with the contract's crossings in place of the reduction.  The march keeps the
+// previous sample (usable, value, t), the bracket of the first crossing and the count in registers; without an array of
+// counts (a.crossings == NULL) a lane idles from its first crossing on and the wave stops when no lane is still looking.
+// Behind the march, where any lane of the wave has a crossing: that lane's bisection of the bracket, a point probe per
+// round on the per-lane lookup (the lanes' brackets have nothing to do with each other any more), the contract's
+// interpolation, and the value and voxel-space gradient at the hit as samplePointsNormKernel forms them (sampleValueGrad).
+template <bool UNIFORM, bool SKIP>
+__global__ __launch_bounds__(256) void sampleCrossingsKernel(const CrossArgs a)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long wave = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+  const RayArgs &ra = a.r;
+  const SampleArgs &s = ra.s;
+  if (wave >= ra.numPatches) return;
+  const RayLane L = rayLane<SKIP>(ra, wave, lane);
+  const float *field = s.scalars + s.fieldOffset[0];
+  const float iso = a.iso;
+  const bool all = a.crossings != nullptr;
+  bool tripped = false, prevOk = false;
+  float prevV = 0.f, prevT = 0.f;
+  float ta = 0.f, va = 0.f, tb = 0.f, vb = 0.f;   // the bracket of the first crossing
+  int index = -1;
+  uint32_t count = 0u;
+  for (int i = L.wBeg; i < L.wEnd; i++) {
+    if (!all && !anyLane(index < 0 && i < L.end)) break;
+    const float t = rayTime(ra, i);
+    V3 p = L.o + t * L.d;
+    if (s.world) p = xfmPoint(s.fs, p);
+    int region = -1;
+    if (i >= L.beg && i < L.end && (all || index < 0) && sampleInRoot(s, p)) region = sampleKdLeafWave<UNIFORM>(s, p, tripped);
+    float v = 0.f;
+    bool ok = false;
+    if (region >= 0) {
+      const int r0 = __builtin_amdgcn_readfirstlane(region);           // of the lanes that have a region
+      if (UNIFORM && !anyLane(region != r0)) ok = sampleValue(s, s.regionRec[r0], field, p, v);   // wave-uniform index: one record per wave
+      else ok = sampleValue(s, s.regionRec[region], field, p, v);
+    }
+    ok = ok && v == v;
+    if (ok && prevOk && (prevV >= iso) != (v >= iso)) {
+      count++;
+      if (index < 0) { index = i; ta = prevT; va = prevV; tb = t; vb = v; }
+    }
+    prevOk = ok; prevV = v; prevT = t;
+  }
+  const float fill = s.fill;
+  float tHit = fill, value = fill;
+  V3 pos = mk(fill, fill, fill), grad = mk(fill, fill, fill);
+  int side = 0;
+  if (anyLane(index >= 0)) {                      // wave-uniform: a wave without a crossing skips the tail
+    if (index >= 0) {
+      side = va < iso ? 1 : -1;
+      for (int round = 0; round < a.refine; round++) {
+        const float tm = 0.5f * (ta + tb);
+        if (tm == ta || tm == tb) break;
+        float vm;
+        if (!crossSample(s, field, L.o + tm * L.d, tripped, vm)) break;
+        if ((vm >= iso) == (va >= iso)) { ta = tm; va = vm; } else { tb = tm; vb = vm; }
+      }
+      const float w = (iso - va) / (vb - va);
+      tHit = ta + w * (tb - ta);
+      pos = L.o + tHit * L.d;
+      const V3 p = s.world ? xfmPoint(s.fs, pos) : pos;
+      const int region = sampleInRoot(s, p) ? sampleKdLeaf(s, s.kdRoot, p, tripped) : -1;
+      if (region >= 0) {
+        const RegionRec R = s.regionRec[region];
+        if (sampleInDomain(R, p)) sampleValueGrad<true, true>(s, R, field, p, value, grad);
+      }
+    }
+  }
+  if (tripped) atomicExch(s.errorFlag, 1);
+  if (!L.live) return;
+  const size_t at = size_t(L.x - ra.x0) + size_t(L.y - ra.y0) * size_t(ra.strideY);
+  if (a.t) a.t[at] = tHit;
+  if (a.position) { a.position[3 * at] = pos.x; a.position[3 * at + 1] = pos.y; a.position[3 * at + 2] = pos.z; }
+  if (a.value) a.value[at] = value;
+  if (a.gradient) { a.gradient[3 * at] = grad.x; a.gradient[3 * at + 1] = grad.y; a.gradient[3 * at + 2] = grad.z; }
+  if (a.index) a.index[at] = index;
+  if (a.side) a.side[at] = side;
+  if (a.crossings) a.crossings[at] = count;
+}
+
+// a launcher of a ray kernel K<UNIFORM, SKIP> on the tile of `rays` (the RayArgs of a): one wave per 8 x 8 pixels
+#define EXA_RAY_LAUNCHER(NAME, K, ARGS, rays)                                                                            \
+  hipError_t NAME(const ARGS &a, bool uniform, hipStream_t s)                                                            \
+  {                                                                                                                      \
+    if ((rays).numPatches == 0) return hipSuccess;                                                                       \
+    const dim3 grid((unsigned)(((rays).numPatches + 3) / 4)), block(256);                                                \
+    const bool skip = (rays).s.world == 0;                                                                               \
+    if (uniform) { if (skip) hipLaunchKernelGGL((K<true, true>), grid, block, 0, s, a);                                  \
+                   else      hipLaunchKernelGGL((K<true, false>), grid, block, 0, s, a); }                               \
+    else         { if (skip) hipLaunchKernelGGL((K<false, true>), grid, block, 0, s, a);                                 \
+                   else      hipLaunchKernelGGL((K<false, false>), grid, block, 0, s, a); }                              \
+    return hipGetLastError();                                                                                            \
+  }
+EXA_RAY_LAUNCHER(launchSampleRays, sampleRaysKernel, RayArgs, a)
+EXA_RAY_LAUNCHER(launchSampleCrossings, sampleCrossingsKernel, CrossArgs, a.r)
+#undef EXA_RAY_LAUNCHER
 
 hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s)
 {

@@ -47,6 +47,13 @@
 //                                            DT samples N`, then four raw little-endian planes of W x H, row y = 0 first:
 //                                            the line integral sum*dt (float32), the number of valid samples (uint32), their
 //                                            maximum and their minimum (float32; -inf / +inf for none); --frames 0 renders nothing
+//             [--raycast CHANNEL ISO DT NSAMPLES REFINE out.hit] where the field of CHANNEL first crosses ISO along the same
+//                                            rays (exa_hip_raycast_iso: world space, unit directions, REFINE rounds of
+//                                            bisection, NaN for no crossing): one text line `raycast W H channel C iso ISO dt
+//                                            DT samples N refine R`, then seven raw little-endian arrays of W x H elements,
+//                                            row y = 0 first: t (float32), position (3 float32), value (float32), gradient
+//                                            (3 float32), index (int32), side (int32), crossings (uint32); --frames 0 renders
+//                                            nothing
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -135,7 +142,10 @@ int main(int argc, char **argv)
     std::string projectName;
     int projectChannel = 0, projectSamples = 0;
     float projectDt = 0.f;
-    int derived = -1;                                             // --derived: EXA_DERIVED_*
+    std::string raycastName;
+    int raycastChannel = 0, raycastSamples = 0, raycastRefine = 0;
+    float raycastIso = 0.f, raycastDt = 0.f;
+    int derived = -1;                                            // --derived: EXA_DERIVED_*
     vec3i derivedChannels(0, 1, 2);
     bool haveResampleChannel = false, haveIsoChannel = false;
     for (int i = 1; i < argc; i++) {
@@ -229,6 +239,15 @@ int main(int argc, char **argv)
         projectSamples = (int)f();
         if (i + 1 >= argc) throw std::runtime_error("missing file after --project CHANNEL DT NSAMPLES");
         projectName = argv[++i];
+      }
+      else if (a == "--raycast") {
+        raycastChannel = (int)f();
+        raycastIso = f();
+        raycastDt = f();
+        raycastSamples = (int)f();
+        raycastRefine = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --raycast CHANNEL ISO DT NSAMPLES REFINE");
+        raycastName = argv[++i];
       }
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
@@ -405,7 +424,26 @@ int main(int argc, char **argv)
       std::printf("project %d %d channel %d dt %.9g samples %d pixels_hit %zu\n", size.x, size.y, projectChannel, projectDt,
                   projectSamples, hit);
     }
-    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty())) return 0;
+    if (!raycastName.empty()) {
+      const ExaHipRays rays = renderer.cameraRays(size, 0.f, raycastDt, raycastSamples);
+      const Renderer::IsoHits R = renderer.raycastIso(rays, raycastChannel, raycastIso, raycastRefine, true, true);
+      FILE *f = std::fopen(raycastName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + raycastName);
+      std::fprintf(f, "raycast %d %d channel %d iso %.9g dt %.9g samples %d refine %d\n", size.x, size.y, raycastChannel, raycastIso,
+                   raycastDt, raycastSamples, raycastRefine);
+      const size_t n = R.t.size();
+      const bool ok = std::fwrite(R.t.data(), 4, n, f) == n && std::fwrite(R.position.data(), 12, n, f) == n
+                   && std::fwrite(R.value.data(), 4, n, f) == n && std::fwrite(R.gradient.data(), 12, n, f) == n
+                   && std::fwrite(R.index.data(), 4, n, f) == n && std::fwrite(R.side.data(), 4, n, f) == n
+                   && std::fwrite(R.crossings.data(), 4, n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + raycastName);
+      size_t hit = 0;
+      for (int32_t k : R.index) hit += k >= 0;
+      std::printf("raycast %d %d channel %d iso %.9g dt %.9g samples %d refine %d pixels_hit %zu\n", size.x, size.y, raycastChannel,
+                  raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
+    }
+    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
+                        || !raycastName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

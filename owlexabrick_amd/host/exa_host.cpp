@@ -658,17 +658,38 @@ Renderer::Streamlines Renderer::streamlines(const vec3f *seeds, size_t n, vec3i 
   return L;
 }
 
+// the pixels of the rays' image, 0 for a size the module refuses (it checks the size)
+static size_t rayPixels(const ExaHipRays &rays)
+{
+  return rays.width > 0 && rays.height > 0 && uint64_t(rays.width) * uint64_t(rays.height) <= uint64_t(INT32_MAX)
+             ? size_t(rays.width) * size_t(rays.height) : 0;
+}
+
 Renderer::Projection Renderer::project(const ExaHipRays &rays, int channel, bool worldSpace, bool normalize)
 {
   if (worldSpace) pushState();
   Projection P;
-  const size_t n = rays.width > 0 && rays.height > 0 && uint64_t(rays.width) * uint64_t(rays.height) <= uint64_t(INT32_MAX)
-                       ? size_t(rays.width) * size_t(rays.height) : 0;        // the module checks the size
+  const size_t n = rayPixels(rays);
   P.sum.resize(n); P.count.resize(n); P.max.resize(n); P.min.resize(n); P.maxIndex.resize(n);
   const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
   check(exa_hip_project(handle, &rays, channel, flags, P.sum.data(), P.count.data(), P.max.data(), P.min.data(),
                         P.maxIndex.data(), 0, nullptr), handle);
   return P;
+}
+
+Renderer::IsoHits Renderer::raycastIso(const ExaHipRays &rays, int channel, float iso, int refine, bool worldSpace, bool normalize,
+                                       float fill)
+{
+  static_assert(sizeof(vec3f) == 3 * sizeof(float), "positions and gradients are 3 floats each");
+  if (worldSpace) pushState();
+  IsoHits R;
+  const size_t n = rayPixels(rays);
+  R.t.resize(n); R.value.resize(n); R.position.resize(n); R.gradient.resize(n); R.index.resize(n); R.side.resize(n); R.crossings.resize(n);
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
+  check(exa_hip_raycast_iso(handle, &rays, channel, iso, refine, flags, fill, R.t.data(), reinterpret_cast<float *>(R.position.data()),
+                            R.value.data(), reinterpret_cast<float *>(R.gradient.data()), R.index.data(), R.side.data(),
+                            R.crossings.data(), 0, nullptr), handle);
+  return R;
 }
 
 ExaHipRays Renderer::cameraRays(vec2i size, float tmin, float dt, int numSamples) const

@@ -258,6 +258,19 @@ struct Renderer {
     std::vector<int32_t> maxIndex;
   };
   Projection project(const ExaHipRays &rays, int channel, bool worldSpace = false, bool normalize = false);
+  // where the field of `channel` first crosses `iso` along the same rays (exa_hip_raycast_iso; include/exa_hip.h states the
+  // contract), per pixel, row-major: the depth t of the first crossing after `refine` rounds of bisection, the position
+  // there (in the rays' space), the point probe's value and voxel-space gradient at it (all four `fill` without a
+  // crossing), the sample index behind the crossing (-1), the side (+1 entering the >= iso side, -1 leaving it, 0) and the
+  // number of crossings of the whole ray.
+  struct IsoHits {
+    std::vector<float> t, value;
+    std::vector<vec3f> position, gradient;
+    std::vector<int32_t> index, side;
+    std::vector<uint32_t> crossings;
+  };
+  IsoHits raycastIso(const ExaHipRays &rays, int channel, float iso, int refine, bool worldSpace = false, bool normalize = false,
+                     float fill = NAN);
   // the rays of the camera set with updateCamera, through the pixel centres of a size.x x size.y image (world space)
   ExaHipRays cameraRays(vec2i size, float tmin, float dt, int numSamples) const;
 
