@@ -721,6 +721,74 @@ int exa_hip_raycast_iso(ExaHipRenderer *, const ExaHipRays *, int32_t channel, f
                         int32_t pointersAreDevice, void *hipStream);
 int exa_hip_raycast_iso_ms(ExaHipRenderer *, float *ms);
 
+/* ---- the field on a surface: per triangle of a mesh the sum and the number of the samples of up to four channels at
+ * quadrature points spread evenly over it, and its area-weighted normal — surface pressure on loaded geometry, force
+ * (the integral of p n dA), flux through an iso-surface or a cut, the area of an iso-surface, a second channel on the mesh
+ * that exa_hip_isosurface just left in device memory.  New relative to the reference.  The kernels form the positions and
+ * reduce in registers; nothing of size triangles x samples exists. ----
+ *
+ * All arithmetic below is float32 with every operation rounded separately and nothing contracted, unless it says double.
+ *
+ * Mesh.  Vertices are in the caller's space: voxel space, or world space with EXA_SAMPLE_WORLD_SPACE (every sample position
+ * then goes through the voxelSpaceTransform of the frame state exactly as exa_hip_sample_points does it).  Triangles are
+ * vertex indices.  With EXA_SURFACE_FROM_ISOSURFACE `vertices` and `triangles` must be NULL, the two counts are ignored and
+ * the mesh is the one of the last exa_hip_isosurface[_derived] of this handle, read where it lies and never copied to the
+ * host; without such a mesh the call is an error; the caller passes the same space flag the extraction had.
+ * numTriangles == 0 (and an empty mesh of the handle) does nothing and returns 0.
+ *
+ * Per triangle, with v0, v1, v2 its vertices, e1 = v1 - v0 and e2 = v2 - v0 per component:
+ *     areaNormal = 0.5f * (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x)
+ * whose length is the area and whose direction is the geometric normal (B-A)x(C-A) of the iso-surface contract; non-finite
+ * input propagates.  The edge lengths are sqrtf((dx*dx + dy*dy) + dz*dz), correctly rounded, of v1-v0, v2-v1 and v0-v2; L is
+ * their maximum, NaN if one of them is.  A triangle is valid if its three indices lie in [0, numVertices) and L is finite.
+ * One that is not has subdiv = 0, no samples, sum = +0.0 and count = 0, and areaNormal by the formula, or three NaN where an
+ * index is out of range.  The subdivision n of a valid triangle: spacing == 0: n = maxN; otherwise q = L / spacing (true
+ * division) and n = maxN if q >= float(maxN), else max(1, (int)ceilf(q)).  subdiv = n.
+ *
+ * Samples.  A valid triangle has n*n samples of equal weight, the centroids of its n*n congruent sub-triangles.  For
+ * sample k = 0 .. n*n-1, with a = k / n and b = k % n as integers:
+ *     a + b <  n :  fa = float(a) + T1          fb = float(b) + T1            T1 = 1.0f/3.0f (bits 0x3eaaaaab)
+ *     a + b >= n :  fa = float(n-1-a) + T2      fb = float(n-1-b) + T2        T2 = 2.0f/3.0f (bits 0x3f2aaaab)
+ *     b1 = fa / float(n)    b2 = fb / float(n)          (true division)
+ *     p_k = (v0 + b1*e1) + b2*e2                         per component
+ * Sample k of channel c is exactly what exa_hip_sample_points(p_k, channels, numChannels, flags & EXA_SAMPLE_WORLD_SPACE)
+ * returns for that channel, in the handle's current basis_form (a scene marked allowEmptyCells: the form-0 sums with the
+ * poison test), with one region lookup for all channels.  A sample is valid where its status is >= 0.
+ *
+ * Reduction, per triangle and channel; its shape is fixed, so that a wave can form it and any implementation gives the
+ * same bytes.  count = the number of valid samples.  Slot l = k % 64 holds a double P_l, started at +0.0; the valid samples
+ * with k % 64 == l are added to it in ascending k, P_l += (double)v_k, invalid ones are skipped.  Then, for o = 32, 16, 8, 4, 2,
+ * 1 in this order, P_l = P_l + P_{l+o} for every l < o; sum = P_0.  (So a lone -0.0 gives +0.0.)  A NaN value makes a NaN
+ * sum, whose payload and sign are not part of the contract.  The caller forms the mean sum/count, the integral
+ * mean*|areaNormal|, the force mean*areaNormal and the flux mean_c . areaNormal.
+ *
+ * Outputs.  sum and count: index triangle*numChannels + c; areaNormal: three floats per triangle; subdiv: one int.  A NULL
+ * output pointer skips that array.
+ *
+ * Independence.  The bytes depend only on the scene, the mesh, the channels, spacing, maxN, the space flag, basis_form and
+ * (world space) the transform — not on anything a frame sets, nor on sample_uniform or surface_pack; two calls give the same
+ * bytes.  A pending brick_order change is applied first.  A scene without a kd tree is refused.  A multi-device handle runs
+ * on devices[0].
+ *
+ * Calls.  Synchronous on hipStream.  A host mesh: the vertices are uploaded whole for the duration of the call (12 bytes of
+ * device memory per vertex); triangles and outputs pass through the handle's bounded staging buffer in chunks.  With
+ * pointersAreDevice all arrays are memory of the handle's first device.  Refused with a message that starts with
+ * "exa_hip_sample_triangles: ", after which the handle stays usable: numChannels outside 1 .. EXA_SURFACE_MAX_CHANNELS or a
+ * bad channel; maxN outside 1 .. EXA_SURFACE_MAX_N; a spacing that is negative or not finite; flag bits other than
+ * EXA_SAMPLE_WORLD_SPACE | EXA_SURFACE_FROM_ISOSURFACE; world space before any frame state; NULL mesh pointers without
+ * EXA_SURFACE_FROM_ISOSURFACE or non-NULL ones with it; the flag without a mesh; counts above INT32_MAX.  The descent's loop
+ * guard returns 3.  exa_hip_sample_triangles_ms: the device time of the last call's kernels, summed (0 before any call and
+ * after a refused one). */
+#define EXA_SURFACE_FROM_ISOSURFACE 8     /* flag: the mesh of the last exa_hip_isosurface[_derived] of this handle */
+#define EXA_SURFACE_MAX_N           64    /* cap of maxN: at most 4096 samples per triangle */
+#define EXA_SURFACE_MAX_CHANNELS    4
+int exa_hip_sample_triangles(ExaHipRenderer *, const float *vertices /* nV x 3 */, uint64_t numVertices,
+                             const int32_t *triangles /* nT x 3 */, uint64_t numTriangles,
+                             const int32_t *channels, int32_t numChannels, float spacing, int32_t maxN, int32_t flags,
+                             double *sum /* nT x C */, uint32_t *count /* nT x C */, float *areaNormal /* nT x 3 */,
+                             int32_t *subdiv /* nT */, int32_t pointersAreDevice, void *hipStream);
+int exa_hip_sample_triangles_ms(ExaHipRenderer *, float *ms);
+
 /* tuning knobs that never change results: "tile_order" = launch sequence of the 16x16 tiles:
  * 0 row-major, 1 row-major 8x8 supertiles per XCD, 2 pseudo-random, 3 centre-out, 4 Z-order
  * (default), 5/6/7 Z-order dealt to the XCDs in chunks of 16/64/256 tiles; "accel" 0 = LBVH with restart per segment,
@@ -758,6 +826,8 @@ int exa_hip_raycast_iso_ms(ExaHipRenderer *, float *ms);
  * "sample_patch" / "sample_uniform" = the patch shape of exa_hip_resample's grid kernel (0 64x1x1, 1 16x4x1, 2 8x8x1,
  * 3 4x4x4 (default) grid points per wave) and whether its waves descend the kd tree and read a shared region's brick headers together
  * (1, default) or lane by lane (0): same values bit for bit either way;
+ * "surface_pack" 1 (default) = exa_hip_sample_triangles packs triangles of at most 16 samples into shared waves (groups of
+ * 1, 4 or 16 lanes per triangle), 0 = every triangle gets a wave of its own: same bytes either way;
  * "profile_marker" N = launch an empty kernel (profileMarkerKernel) on the null stream now: a bracket in a profiler's
  * dispatch list, no effect on any frame.
  * "walk" selects how the DVR march of the kd path finds its segments: 1 = the ordered walk of the region kd-tree with a

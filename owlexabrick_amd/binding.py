@@ -122,6 +122,11 @@ STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREA
 PROJECT_NORMALIZE = 4
 PROJECT_MAX_SAMPLES = 1 << 20
 
+# exa_hip_sample_triangles (include/exa_hip.h)
+SURFACE_FROM_ISOSURFACE = 8
+SURFACE_MAX_N = 64
+SURFACE_MAX_CHANNELS = 4
+
 # exa_hip_raycast_iso (include/exa_hip.h)
 CROSS_MAX_REFINE = 32
 RAYCAST_KEYS = ("t", "position", "value", "gradient", "index", "side", "crossings")
@@ -139,6 +144,43 @@ def derived_quantity(q):
             raise ValueError(f"unknown derived quantity {q!r} (one of {', '.join(DERIVED)})")
         return DERIVED[q.lower()]
     return int(q)
+
+
+SURFACE_KEYS = ("sum", "count", "areaNormal", "subdiv")
+
+
+def surface_integrals(samples):
+    """From the dict of Renderer.sampleTriangles (numpy), in float64 and sequentially in ascending triangle order (no pairwise
+    sums: the same operations as exa::Renderer::surfaceIntegrals).  Per triangle: area [m] = |areaNormal|, mean [m, C] = sum /
+    count (NaN where count == 0), integral [m, C] = mean * area.  Totals over the valid triangles (subdiv > 0; the others are
+    counted in invalid_triangles), per channel: covered_area [C], uncovered_area [C] and uncovered_triangles [C] (count == 0),
+    total_integral [C] = the sum of mean * area and force [C, 3] = the sum of mean * areaNormal over the covered ones; with three
+    channels flux = the sum of (mean0 * n.x + mean1 * n.y) + mean2 * n.z over the triangles all three cover (else NaN).  The
+    samples ride along under "samples"."""
+    total, count = samples["sum"], samples["count"]
+    normal = samples["areaNormal"].astype(np.float64)
+    subdiv = samples["subdiv"]
+    m, nc = total.shape
+    with np.errstate(all="ignore"):
+        area = np.sqrt((normal[:, 0] * normal[:, 0] + normal[:, 1] * normal[:, 1]) + normal[:, 2] * normal[:, 2])
+        mean = np.where(count > 0, total / np.where(count > 0, count, 1).astype(np.float64), np.nan)
+        integral = mean * area[:, None]
+        valid = subdiv > 0
+        covered = valid[:, None] & (count > 0)
+        # np.cumsum adds along the axis in order, from +0.0
+        seq = lambda terms: np.concatenate([np.zeros((1,) + terms.shape[1:]), terms]).cumsum(axis=0)[-1]        # noqa: E731
+        covered_area = seq(np.where(covered, area[:, None], 0.0))
+        uncovered = valid[:, None] & (count == 0)
+        uncovered_area = seq(np.where(uncovered, area[:, None], 0.0))
+        total_integral = seq(np.where(covered, integral, 0.0))
+        force = seq(np.where(covered[:, :, None], mean[:, :, None] * normal[:, None, :], 0.0))
+        flux = float("nan")
+        if nc == 3:
+            every = covered.all(axis=1)
+            flux = float(seq(np.where(every, (mean[:, 0] * normal[:, 0] + mean[:, 1] * normal[:, 1]) + mean[:, 2] * normal[:, 2], 0.0)))
+    return dict(samples=samples, area=area, mean=mean, integral=integral, covered_area=covered_area, uncovered_area=uncovered_area,
+                uncovered_triangles=uncovered.sum(axis=0).astype(np.uint64), total_integral=total_integral, force=force, flux=flux,
+                invalid_triangles=int((~valid).sum()))
 
 
 class ExaHipRays(C.Structure):
@@ -202,6 +244,8 @@ _ABI = {
     "exa_hip_project_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_raycast_iso": (None, [_vp, _P(ExaHipRays), _i32, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_raycast_iso_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_sample_triangles": (None, [_vp, _vp, _u64, _vp, _u64, _vp, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_sample_triangles_ms": (None, [_vp, _P(_f32)]),
 }
 ABI_SYMBOLS = list(_ABI)
 
@@ -765,6 +809,56 @@ class Renderer:
     def projectMs(self):
         """device ms of the last project call's kernel launches, summed"""
         return self._ms(lib().exa_hip_project_ms)
+
+    # ---- the field on a triangle mesh (exa_hip_sample_triangles; include/exa_hip.h states the contract) ----
+    def sampleTriangles(self, vertices=None, triangles=None, channels=(0,), spacing=1.0, max_n=SURFACE_MAX_N, world=False,
+                        stream=None):
+        """up to four channels of the field on the triangles of a mesh: every triangle is cut into n x n congruent parts, n =
+        its longest edge over `spacing` rounded up, at most max_n (spacing 0: n = max_n), and sampled at their centroids.
+        Returns a dict: sum float64 [m, C] of the valid samples, count uint32 [m, C], areaNormal float32 [m, 3] (half the
+        cross product of the edges) and subdiv int32 [m] (n; 0: a bad index or a non-finite vertex, no samples).  vertices
+        [nv, 3] and triangles [m, 3] in voxel space (world=True: world space): numpy arrays take the host path, contiguous
+        float32 / int32 torch CUDA tensors the device path with torch tensors out; both None: the mesh the last
+        extractIsoSurface left in the module (world as the extraction had it), read on the device."""
+        ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+        nc = min(len(ch), SURFACE_MAX_CHANNELS)                                 # the module checks the number
+        flags = self._probe_world(world)
+        args = (ch.ctypes.data, len(ch), float(spacing), int(max_n))
+        if vertices is None and triangles is None:
+            nt = getattr(self, "_iso_counts", (0, 0, False))[1]
+            mesh, flags, device = (None, 0, None, 0), flags | SURFACE_FROM_ISOSURFACE, False
+        elif getattr(vertices, "is_cuda", False):
+            import torch
+            if (vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous()
+                    or not triangles.is_contiguous() or vertices.numel() % 3 or triangles.numel() % 3):
+                raise TypeError("vertices: a contiguous float32 tensor [nv, 3]; triangles: a contiguous int32 tensor [m, 3]")
+            nt = triangles.numel() // 3
+            mesh, device = (_dev_ptr(vertices), vertices.numel() // 3, _dev_ptr(triangles), nt), True
+            out = dict(sum=torch.empty((nt, nc), dtype=torch.float64, device=vertices.device),
+                       count=torch.empty((nt, nc), dtype=torch.int32, device=vertices.device),
+                       areaNormal=torch.empty((nt, 3), dtype=torch.float32, device=vertices.device),
+                       subdiv=torch.empty(nt, dtype=torch.int32, device=vertices.device))
+            self._check(lib().exa_hip_sample_triangles(self.h, *mesh, *args, flags, *[C.c_void_p(out[k].data_ptr()) for k in SURFACE_KEYS], 1,
+                                                       C.c_void_p(stream or 0)))
+            return out
+        else:
+            verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+            tris = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+            nt = tris.shape[0]
+            mesh = (verts.ctypes.data, verts.shape[0], tris.ctypes.data, nt)
+        out = dict(sum=np.zeros((nt, nc), np.float64), count=np.zeros((nt, nc), np.uint32), areaNormal=np.zeros((nt, 3), np.float32),
+                   subdiv=np.zeros(nt, np.int32))
+        self._check(lib().exa_hip_sample_triangles(self.h, *mesh, *args, flags, *[out[k].ctypes.data for k in SURFACE_KEYS], 0,
+                                                   C.c_void_p(stream or 0)))
+        return out
+
+    def sampleTrianglesMs(self):
+        """device ms of the last sampleTriangles call's kernels, summed"""
+        return self._ms(lib().exa_hip_sample_triangles_ms)
+
+    def surfaceIntegrals(self, vertices=None, triangles=None, channels=(0,), spacing=1.0, max_n=SURFACE_MAX_N, world=False):
+        """sampleTriangles (host path, or the module's iso mesh) and what a caller forms of it: surface_integrals(samples)"""
+        return surface_integrals(self.sampleTriangles(vertices, triangles, channels, spacing, max_n, world))
 
     # ---- iso-crossings along rays (exa_hip_raycast_iso; include/exa_hip.h states the contract) ----
     def raycast_iso(self, org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples, iso, refine=8, channel=0,

@@ -293,6 +293,28 @@ struct CrossArgs {
   uint32_t          *crossings;     // NULL: a lane may stop at its first crossing
 };
 
+// The field on a triangle mesh (exa_hip_sample_triangles, the sampleTriangles* kernels in exa_sample_kernels.h): `numTriangles`
+// triangles of one launch.  The first kernel (one lane per triangle) stores subdiv and areaNormal, the results of the invalid
+// triangles, and the valid ones' indices in `list`: those of at most 16 samples (with `pack`) from the front, the others
+// from the back; listCount[0], [1] count the two (zeroed before the launch).  The second kernel reduces the listed triangles.
+struct TriArgs {
+  SampleArgs         s;             // the lookup and the fields (probeSetup); numChannels, fieldOffset[0..3] = the channels
+  const float       *vertices;      // numVertices x 3, device
+  unsigned long long numVertices;
+  const int32_t     *triangles;     // numTriangles x 3, device
+  uint32_t           numTriangles;
+  float              spacing;
+  int32_t            maxN;
+  int32_t            pack;          // option "surface_pack"
+  int32_t           *list;          // numTriangles entries
+  uint32_t          *listCount;     // 2
+  // outputs of the launch's triangles (each may be NULL): numTriangles x numChannels, .. x numChannels, .. x 3, numTriangles
+  double            *sum;
+  uint32_t          *count;
+  float             *areaNormal;
+  int32_t           *subdiv;
+};
+
 // The streamline integrator (exa_hip_streamlines, exa_stream_kernels.h): one lane per (seed, requested direction), RK4 in voxel
 // space on the probes' lookup and sums.  Two launches per extraction: the first stores per direction the number of vertices
 // it appends and why it ended, the second (after the scan of the counts) integrates again and stores the vertices packed.
@@ -349,6 +371,8 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
   hipError_t launchSampleRays(const RayArgs &a, bool uniform, hipStream_t s);                                        \
   /* the iso-crossings along the same rays (exa_sample_f*.o): the tile of a.r, one wave per 8 x 8 pixels */             \
   hipError_t launchSampleCrossings(const CrossArgs &a, bool uniform, hipStream_t s);                                 \
+  /* the field on the triangles of a (exa_sample_f*.o): the two kernels of exa_hip_sample_triangles, in order */        \
+  hipError_t launchSampleTriangles(const TriArgs &a, bool uniform, hipStream_t s);                                   \
   /* the streamline integrator (exa_stream_f*.o): lanes [a.laneBase, a.numLanes) of at most 2^24 per launch; emit = the  \
      second launch, which stores the vertices */                                                                        \
   hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);

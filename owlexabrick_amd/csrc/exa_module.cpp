@@ -239,6 +239,7 @@ int exa_hip_set_option(ExaHipRenderer *h, const char *key, int32_t value)
     h->probes.patch = value; return 0;
   }
   if (!std::strcmp(key, "sample_uniform")) { h->probes.uniform = value != 0; return 0; }
+  if (!std::strcmp(key, "surface_pack")) { h->surface.pack = value != 0; return 0; }
   if (!std::strcmp(key, "interleave")) { h->interleave = value != 0; return 0; }
   if (!std::strcmp(key, "addr64")) { h->addr64 = value != 0; return 0; }
   if (!std::strcmp(key, "pack_records")) { h->packRecords = value != 0; return 0; }

@@ -1,7 +1,7 @@
 // exa_probe.cpp — reading the reconstructed field outside a frame: the point probes (exa_hip_sample_points,
 // exa_hip_resample; kernels in exa_sample_kernels.h), the quantities derived from three channels' velocity gradient tensor
 // (exa_hip_sample_derived, exa_hip_resample_derived), the projections along rays (exa_hip_project) and the iso-crossings along
-// the same rays (exa_hip_raycast_iso) in the same file, and
+// the same rays (exa_hip_raycast_iso) in the same file, the field on the triangles of a mesh (exa_hip_sample_triangles), and
 // the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
@@ -420,6 +420,107 @@ int exa_hip_project_ms(ExaHipRenderer *h, float *ms)
 {
   if (!h || !ms) return 1;
   *ms = firstChild(h)->project.kernelMs;
+  return 0;
+}
+
+// ---- the field on a triangle mesh (the sampleTriangles* kernels) ----
+// The triangles go in chunks of at most kProbeLaunch (with staged parts: at most what kProbeStageBytes hold) through the
+// staging buffer {the two list counters, 16 bytes | sum | list | triangles | count | areaNormal | subdiv}: the doubles in
+// front, so that every part is aligned to its element.  The list is always there; the triangles only for a host mesh, the
+// outputs only for host outputs (the mesh of the handle with host outputs: the one without the other).
+int exa_hip_sample_triangles(ExaHipRenderer *h, const float *vertices, uint64_t numVertices, const int32_t *triangles,
+                             uint64_t numTriangles, const int32_t *channels, int32_t numChannels, float spacing, int32_t maxN,
+                             int32_t flags, double *sum, uint32_t *count, float *areaNormal, int32_t *subdiv,
+                             int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_sample_triangles";
+  ExaHipRenderer *r = firstChild(h);
+  r->surface.kernelMs = 0.f;
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_SURFACE_FROM_ISOSURFACE, " (EXA_SAMPLE_WORLD_SPACE and EXA_SURFACE_FROM_ISOSURFACE apply)")) return 1;
+  if (!channels || numChannels < 1 || numChannels > EXA_SURFACE_MAX_CHANNELS) { h->fail(std::string(fn) + ": 1..4 channels required"); return 1; }
+  for (int c = 0; c < numChannels; c++)
+    if (!checkChannel(h, fn, channels[c])) return 1;
+  if (maxN < 1 || maxN > EXA_SURFACE_MAX_N) { h->fail(std::string(fn) + ": maxN must be in 1.." + std::to_string(EXA_SURFACE_MAX_N)); return 1; }
+  if (!std::isfinite(spacing) || spacing < 0.f) { h->fail(std::string(fn) + ": the spacing must be finite and >= 0"); return 1; }
+  const bool fromIso = (flags & EXA_SURFACE_FROM_ISOSURFACE) != 0;
+  if (fromIso) {
+    if (vertices || triangles) { h->fail(std::string(fn) + ": vertices and triangles must be NULL with EXA_SURFACE_FROM_ISOSURFACE"); return 1; }
+    if (!r->isoMesh.have) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
+    vertices = r->isoMesh.vertices.p;
+    triangles = r->isoMesh.triangles.p;
+    numVertices = r->isoMesh.vertices.n / 3;
+    numTriangles = r->isoMesh.triangles.n / 3;
+  } else {
+    if (numVertices > uint64_t(INT32_MAX) || numTriangles > uint64_t(INT32_MAX)) { h->fail(std::string(fn) + ": more than INT32_MAX vertices or triangles"); return 1; }
+    if (numTriangles && (!vertices || !triangles)) { h->fail(std::string(fn) + ": null vertices or triangles (without EXA_SURFACE_FROM_ISOSURFACE)"); return 1; }
+  }
+  if (numTriangles == 0) return 0;
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  TriArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (probeSetup(h, r, fn, (flags & EXA_SAMPLE_WORLD_SPACE) != 0, s, a.s)) return 1;
+  a.s.numChannels = numChannels;
+  for (int c = 0; c < numChannels; c++) a.s.fieldOffset[c] = r->sc.channelOffset[channels[c]];
+  a.spacing = spacing;
+  a.maxN = maxN;
+  a.pack = r->surface.pack;
+  const bool meshDev = fromIso || pointersAreDevice, outDev = pointersAreDevice != 0;
+  DevBuf<float> vbuf;                      // a host mesh: its vertices, for the duration of the call
+  if (!meshDev) {
+    const hipError_t e = vbuf.upload(vertices, 3 * size_t(numVertices));
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the vertices (12 bytes each)", e);
+    vertices = vbuf.p;
+  }
+  a.vertices = vertices;
+  a.numVertices = numVertices;
+  const uint64_t nch = uint64_t(numChannels);
+  const uint64_t perTri = 4 + (meshDev ? 0 : 12) + (outDev ? 0 : (sum ? 8 * nch : 0) + (count ? 4 * nch : 0) + (areaNormal ? 12 : 0) + (subdiv ? 4 : 0));
+  const uint64_t chunk = std::max<uint64_t>(1, std::min(kProbeLaunch, (kProbeStageBytes - 16) / perTri));
+  const uint64_t need = 16 + std::min(numTriangles, chunk) * perTri;
+  if (r->probes.stage.n < need) HIP_TRY(h, r->probes.stage.alloc(need));
+  TimingEvents<2> t;
+  HIP_TRY(h, t.create());
+  float total = 0.f;
+  for (uint64_t at = 0; at < numTriangles; at += chunk) {
+    const uint64_t m = std::min(chunk, numTriangles - at);
+    char *cut = r->probes.stage.p;
+    a.numTriangles = uint32_t(m);
+    a.listCount = reinterpret_cast<uint32_t *>(carve(cut, true, 16));
+    double *dSum = reinterpret_cast<double *>(carve(cut, !outDev && sum, 8 * m * nch));
+    a.list = reinterpret_cast<int32_t *>(carve(cut, true, 4 * m));
+    int32_t *dTri = reinterpret_cast<int32_t *>(carve(cut, !meshDev, 12 * m));
+    uint32_t *dCount = reinterpret_cast<uint32_t *>(carve(cut, !outDev && count, 4 * m * nch));
+    float *dNormal = reinterpret_cast<float *>(carve(cut, !outDev && areaNormal, 12 * m));
+    int32_t *dSubdiv = reinterpret_cast<int32_t *>(carve(cut, !outDev && subdiv, 4 * m));
+    a.triangles = meshDev ? triangles + 3 * at : dTri;
+    a.sum = outDev ? (sum ? sum + at * nch : nullptr) : dSum;
+    a.count = outDev ? (count ? count + at * nch : nullptr) : dCount;
+    a.areaNormal = outDev ? (areaNormal ? areaNormal + 3 * at : nullptr) : dNormal;
+    a.subdiv = outDev ? (subdiv ? subdiv + at : nullptr) : dSubdiv;
+    if (!meshDev) HIP_TRY(h, hipMemcpyAsync(dTri, triangles + 3 * at, 12 * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(a.listCount, 0, 16, s));
+    HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    HIP_TRY(h, EXA_FORM(r, launchSampleTriangles)(a, r->probes.uniform != 0, s));
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    if (dSum) HIP_TRY(h, hipMemcpyAsync(sum + at * nch, dSum, 8 * m * nch, hipMemcpyDeviceToHost, s));
+    if (dCount) HIP_TRY(h, hipMemcpyAsync(count + at * nch, dCount, 4 * m * nch, hipMemcpyDeviceToHost, s));
+    if (dNormal) HIP_TRY(h, hipMemcpyAsync(areaNormal + 3 * at, dNormal, 12 * m, hipMemcpyDeviceToHost, s));
+    if (dSubdiv) HIP_TRY(h, hipMemcpyAsync(subdiv + at, dSubdiv, 4 * m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(h, t.elapsed(0, 1, &ms));
+    total += ms;
+  }
+  r->surface.kernelMs = total;
+  return checkLoopGuard(h, r, fn, kDescentGuard);
+}
+
+int exa_hip_sample_triangles_ms(ExaHipRenderer *h, float *ms)
+{
+  if (!h || !ms) return 1;
+  *ms = firstChild(h)->surface.kernelMs;
   return 0;
 }
 

@@ -3,7 +3,7 @@
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes, the projections along rays and the
 // iso-surface extraction, exa_streamlines.cpp the streamline extraction, exa_stats.cpp the histogram and value range of
 // the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
-// one struct per call (ExaHipRenderer::probes, isoMesh, hist, lines, project); TimingEvents, DropUnlessCommitted and the
+// one struct per call (ExaHipRenderer::probes, isoMesh, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
 // argument checks below the renderer are what their host code shares.
 #pragma once
 #include "exa_device.h"
@@ -327,6 +327,11 @@ struct ExaHipRenderer {
   struct Projection {
     float kernelMs = 0.f;
   } project;
+  // the same of the last exa_hip_sample_triangles, and whether it packs small triangles into shared waves (option surface_pack)
+  struct Surface {
+    float kernelMs = 0.f;
+    int pack = 1;
+  } surface;
   // the same of the last exa_hip_raycast_iso
   struct Raycast {
     float kernelMs = 0.f;

@@ -1,7 +1,8 @@
 // exa_sample_kernels.h — the point probes: exa_hip_sample_points (one lane per point) and exa_hip_resample (one wave per
 // compact patch of 64 grid points), and on the same lookup and sums the derived quantities of exa_hip_sample_derived /
 // exa_hip_resample_derived (the same two shapes of kernel over three channels) and the projections of exa_hip_project (one
-// wave per 8 x 8 rays, reduced in registers) and the iso-crossings of exa_hip_raycast_iso along the same rays.  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
+// wave per 8 x 8 rays, reduced in registers), the iso-crossings of exa_hip_raycast_iso along the same rays and the field reduced
+// over the triangles of a mesh of exa_hip_sample_triangles (small triangles packed into shared waves, large ones a wave each).  Included by exa_kernels.hip inside namespace exa::EXA_FORM_NS when it is compiled with
 // -DEXA_TU_SAMPLE=1 (exa_sample_f0.o, exa_sample_f1.o, exa_sample_f0e.o), after samplePoint and the basis evaluations it
 // uses; nothing else of the renderer is compiled there.
 //
@@ -494,6 +495,263 @@ __global__ __launch_bounds__(256) void sampleCrossingsKernel(const CrossArgs a)
 EXA_RAY_LAUNCHER(launchSampleRays, sampleRaysKernel, RayArgs, a)
 EXA_RAY_LAUNCHER(launchSampleCrossings, sampleCrossingsKernel, CrossArgs, a.r)
 #undef EXA_RAY_LAUNCHER
+
+// ---- exa_hip_sample_triangles: the field reduced over the triangles of a mesh ----
+// A triangle as the kernels see it: v0, the two edges of the contract and its subdivision n (0: not valid, no samples).
+struct TriGeom { V3 v0, e1, e2; int n; };
+
+// n of the contract (include/exa_hip.h): the longest edge over the spacing, rounded up, in 1 .. maxN; 0 where a length is not
+// finite (L, the maximum with a NaN propagated, is finite exactly where all three are).  sqrtf, `/`: correctly rounded
+__device__ __forceinline__ int sampleTrianglesSubdiv(V3 v0, V3 v1, V3 v2, float spacing, int maxN)
+{
+  const V3 a = v1 - v0, b = v2 - v1, c = v0 - v2;
+  const float la = sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z), lb = sqrtf((b.x * b.x + b.y * b.y) + b.z * b.z),
+              lc = sqrtf((c.x * c.x + c.y * c.y) + c.z * c.z);
+  if (!(la <= FLT_MAX && lb <= FLT_MAX && lc <= FLT_MAX)) return 0;
+  if (spacing == 0.f) return maxN;
+  const float q = fmaxf(fmaxf(la, lb), lc) / spacing;
+  if (q >= float(maxN)) return maxN;
+  return max(1, (int)ceilf(q));
+}
+
+// triangle t of the launch, whose indices the first kernel has found in range
+__device__ __forceinline__ TriGeom sampleTrianglesGeom(const TriArgs &a, int t)
+{
+  const int32_t *idx = a.triangles + 3 * size_t(t);
+  const V3 v0 = mk(a.vertices + 3 * size_t(idx[0])), v1 = mk(a.vertices + 3 * size_t(idx[1])), v2 = mk(a.vertices + 3 * size_t(idx[2]));
+  TriGeom g;
+  g.v0 = v0; g.e1 = v1 - v0; g.e2 = v2 - v0;
+  g.n = sampleTrianglesSubdiv(v0, v1, v2, a.spacing, a.maxN);
+  return g;
+}
+
+// p_k of the contract: the centroid of sub-triangle k of n * n, every operation rounded separately
+__device__ __forceinline__ V3 sampleTrianglesPos(const TriGeom &g, int k)
+{
+  const int n = max(g.n, 1), ka = k / n, kb = k - ka * n;
+  const bool upright = ka + kb < n;
+  const float fa = upright ? float(ka) + 1.0f / 3.0f : float(n - 1 - ka) + 2.0f / 3.0f;
+  const float fb = upright ? float(kb) + 1.0f / 3.0f : float(n - 1 - kb) + 2.0f / 3.0f;
+  const float b1 = fa / float(n), b2 = fb / float(n);
+  return (g.v0 + b1 * g.e1) + b2 * g.e2;
+}
+
+// the channels at p inside the region whose record is R, added to the lane's partial sums and counts where valid: the
+// closed-domain test and the sums of samplePointsBody
+__device__ __forceinline__ void sampleTrianglesAdd(const SampleArgs &s, const RegionRec R, V3 p, double P[EXA_SURFACE_MAX_CHANNELS],
+                                                   uint32_t cnt[EXA_SURFACE_MAX_CHANNELS])
+{
+  if (!sampleInDomain(R, p)) return;
+  for (int c = 0; c < s.numChannels; c++) {
+    const Basis B = sampleSums<false>(s, R.listBegin, R.listSize, s.scalars + s.fieldOffset[c], p);
+    if (B.sumW <= 1e-20f) continue;
+    const double v = double(B.sumWV / B.sumW);
+#pragma unroll
+    for (int k = 0; k < EXA_SURFACE_MAX_CHANNELS; k++)       // registers, not an indexed array
+      if (k == c) { P[k] += v; cnt[k]++; }
+  }
+}
+
+// The voxelSpaceTransform for the sampling kernels below, in LDS: as kernel arguments its twelve floats would stay in scalar
+// registers from the first sample to the last, which these kernels do not have to spare (they would spill some); read from
+// LDS at each sample they are vector registers for the length of xfmPoint.  Every thread of the block calls this, once
+__device__ __forceinline__ void sampleTrianglesStageXfm(const SampleArgs &s, float xfm[12])
+{
+  if (!s.world) return;                                                 // the same in every thread
+  const unsigned i = threadIdx.x;
+  if (i < 12u) {
+    const float *row = i < 3u ? s.fs.xfm_vx : (i < 6u ? s.fs.xfm_vy : (i < 9u ? s.fs.xfm_vz : s.fs.xfm_p));
+    xfm[i] = row[i % 3u];
+  }
+  __syncthreads();
+}
+
+// one sample per lane (`active`: the lane has one) at the caller's position q: the lookup of the grid and ray kernels — a shared
+// descent while the wave's lanes agree, one region record per wave where they land in one region, else lane by lane.  World
+// space: xfmPoint, operation for operation, on the staged transform
+template <bool UNIFORM>
+__device__ __forceinline__ void sampleTrianglesAt(const SampleArgs &s, const float xfm[12], bool active, V3 q, bool &tripped,
+                                                  double P[EXA_SURFACE_MAX_CHANNELS], uint32_t cnt[EXA_SURFACE_MAX_CHANNELS])
+{
+  V3 p = q;
+  if (s.world) p = q.x * mk(xfm) + (q.y * mk(xfm + 3) + (q.z * mk(xfm + 6) + mk(xfm + 9)));
+  int region = -1;
+  if (active && sampleInRoot(s, p)) region = sampleKdLeafWave<UNIFORM>(s, p, tripped);
+  if (region >= 0) {
+    const int r0 = __builtin_amdgcn_readfirstlane(region);             // of the lanes that have a region
+    if (UNIFORM && !anyLane(region != r0)) sampleTrianglesAdd(s, s.regionRec[r0], p, P, cnt);   // wave-uniform index: one record per wave
+    else sampleTrianglesAdd(s, s.regionRec[region], p, P, cnt);
+  }
+}
+
+// the steps o = first, first / 2, .. 1 of the contract's tree, P_l = P_l + P_{l+o} for l < o (the lanes from o on hold what
+// nobody reads); every lane of the wave takes part
+__device__ __forceinline__ void sampleTrianglesTree(int first, double P[EXA_SURFACE_MAX_CHANNELS], uint32_t cnt[EXA_SURFACE_MAX_CHANNELS])
+{
+  for (int o = first; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < EXA_SURFACE_MAX_CHANNELS; c++) {
+      P[c] = P[c] + __shfl_down(P[c], o, 64);
+      cnt[c] += __shfl_down(cnt[c], o, 64);
+    }
+  }
+}
+
+__device__ __forceinline__ void sampleTrianglesStore(const TriArgs &a, int t, const double P[EXA_SURFACE_MAX_CHANNELS],
+                                                     const uint32_t cnt[EXA_SURFACE_MAX_CHANNELS])
+{
+  const size_t at = size_t(t) * size_t(a.s.numChannels);
+#pragma unroll
+  for (int c = 0; c < EXA_SURFACE_MAX_CHANNELS; c++)
+    if (c < a.s.numChannels) {
+      if (a.sum) a.sum[at + c] = P[c];
+      if (a.count) a.count[at + c] = cnt[c];
+    }
+}
+
+// First kernel, one lane per triangle: areaNormal and subdiv, the results of a triangle that is not valid, and the valid ones
+// handed to the second kernel through a.list — at most 16 samples (with a.pack): from the front, its packed part; more: from
+// the back, its wide part.  A wave appends with one atomic per end; the order of the entries varies from run to
+// run and no byte depends on it (every result is stored by triangle).
+__global__ __launch_bounds__(256) void sampleTrianglesPrepKernel(const TriArgs a)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  const bool have = t < a.numTriangles;
+  int n = 0;
+  if (have) {
+    const int32_t *idx = a.triangles + 3 * size_t(t);
+    const int32_t i0 = idx[0], i1 = idx[1], i2 = idx[2];
+    const unsigned long long nv = a.numVertices;
+    V3 an = mk(NAN, NAN, NAN);
+    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && (unsigned long long)i0 < nv && (unsigned long long)i1 < nv && (unsigned long long)i2 < nv) {
+      const V3 v0 = mk(a.vertices + 3 * size_t(i0)), v1 = mk(a.vertices + 3 * size_t(i1)), v2 = mk(a.vertices + 3 * size_t(i2));
+      const V3 e1 = v1 - v0, e2 = v2 - v0;
+      an = 0.5f * cross(e1, e2);
+      n = sampleTrianglesSubdiv(v0, v1, v2, a.spacing, a.maxN);
+    }
+    if (a.areaNormal) { a.areaNormal[3 * size_t(t)] = an.x; a.areaNormal[3 * size_t(t) + 1] = an.y; a.areaNormal[3 * size_t(t) + 2] = an.z; }
+    if (a.subdiv) a.subdiv[t] = n;
+    if (n == 0) {
+      const double zero[EXA_SURFACE_MAX_CHANNELS] = { 0.0, 0.0, 0.0, 0.0 };
+      const uint32_t none[EXA_SURFACE_MAX_CHANNELS] = { 0u, 0u, 0u, 0u };
+      sampleTrianglesStore(a, int(t), zero, none);
+    }
+  }
+  const bool packed = n > 0 && a.pack && n <= 4, wide = n > 0 && !packed;
+  const unsigned long long mp = __builtin_amdgcn_ballot_w64(packed), mw = __builtin_amdgcn_ballot_w64(wide);
+  uint32_t bp = 0u, bw = 0u;
+  if (lane == 0u) {
+    if (mp) bp = atomicAdd(a.listCount, uint32_t(__popcll(mp)));
+    if (mw) bw = atomicAdd(a.listCount + 1, uint32_t(__popcll(mw)));
+  }
+  bp = __shfl(bp, 0, 64);
+  bw = __shfl(bw, 0, 64);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  if (packed) a.list[bp + uint32_t(__popcll(mp & below))] = int32_t(t);
+  if (wide) a.list[a.numTriangles - 1u - (bw + uint32_t(__popcll(mw & below)))] = int32_t(t);
+}
+
+// Packed: a wave takes 64 entries from the front of the list, a lane each, and serves them in three rounds by the size G of
+// the group of lanes a triangle needs — n = 1: G = 1, every lane its own triangle at once; n = 2: G = 4, sixteen triangles at a
+// time; n = 3, 4: G = 16, four at a time —, the owner's triangle handed to its group's lanes by shuffles.  A slot l of the
+// contract holds at most one sample here, P_l = +0.0 + v; the tree's steps above G add the +0.0 of the empty slots, which
+// changes no P_l (none is -0.0), then its steps below G run inside the group.
+template <bool UNIFORM>
+__device__ __forceinline__ void sampleTrianglesPacked(const TriArgs &a, const float xfm[12], bool &tripped)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  const uint32_t numPacked = a.listCount[0], waves = gridDim.x * 4u;
+  for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); (unsigned long long)w * 64u < numPacked; w += waves) {
+    const uint32_t i = w * 64u + lane;
+    int t = -1;
+    TriGeom g;
+    g.v0 = mk(0.f, 0.f, 0.f); g.e1 = g.v0; g.e2 = g.v0; g.n = 0;
+    if (i < numPacked) { t = a.list[i]; g = sampleTrianglesGeom(a, t); }
+    const int G = g.n == 0 ? 0 : (g.n == 1 ? 1 : (g.n == 2 ? 4 : 16));
+    if (anyLane(G == 1)) {
+      double P[EXA_SURFACE_MAX_CHANNELS] = { 0.0, 0.0, 0.0, 0.0 };
+      uint32_t cnt[EXA_SURFACE_MAX_CHANNELS] = { 0u, 0u, 0u, 0u };
+      sampleTrianglesAt<UNIFORM>(a.s, xfm, G == 1, sampleTrianglesPos(g, 0), tripped, P, cnt);
+      if (G == 1) sampleTrianglesStore(a, t, P, cnt);
+    }
+    for (int GG = 4; GG <= 16; GG *= 4) {
+      unsigned long long mask = __builtin_amdgcn_ballot_w64(G == GG);
+      const int per = 64 / GG, slot = int(lane) / GG, k = int(lane) % GG;
+      while (mask) {
+        // the owners of this round: the lowest `per` lanes of the mask, in order (wave-uniform arithmetic)
+        int owner = -1;
+        for (int j = 0; j < per && mask; j++) {
+          const int o = __ffsll(mask) - 1;
+          mask &= mask - 1ull;
+          if (slot == j) owner = o;
+        }
+        const int src = owner >= 0 ? owner : int(lane);
+        TriGeom h;
+        h.v0 = mk(__shfl(g.v0.x, src, 64), __shfl(g.v0.y, src, 64), __shfl(g.v0.z, src, 64));
+        h.e1 = mk(__shfl(g.e1.x, src, 64), __shfl(g.e1.y, src, 64), __shfl(g.e1.z, src, 64));
+        h.e2 = mk(__shfl(g.e2.x, src, 64), __shfl(g.e2.y, src, 64), __shfl(g.e2.z, src, 64));
+        h.n = __shfl(g.n, src, 64);
+        const int ht = __shfl(t, src, 64);
+        double P[EXA_SURFACE_MAX_CHANNELS] = { 0.0, 0.0, 0.0, 0.0 };
+        uint32_t cnt[EXA_SURFACE_MAX_CHANNELS] = { 0u, 0u, 0u, 0u };
+        sampleTrianglesAt<UNIFORM>(a.s, xfm, owner >= 0 && k < h.n * h.n, sampleTrianglesPos(h, k), tripped, P, cnt);
+        sampleTrianglesTree(GG / 2, P, cnt);
+        if (owner >= 0 && k == 0) sampleTrianglesStore(a, ht, P, cnt);
+      }
+    }
+  }
+}
+
+// Wide: a wave takes one entry from the back of the list and loops over its blocks of 64 samples, lane l holding the
+// contract's P_l and its count in registers — sample k = 64 j + l is added in block j, so in ascending k —, then the whole tree.
+template <bool UNIFORM>
+__device__ __forceinline__ void sampleTrianglesWide(const TriArgs &a, const float xfm[12], bool &tripped)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  const uint32_t numWide = a.listCount[1], waves = gridDim.x * 4u;
+  for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); w < numWide; w += waves) {
+    const int t = a.list[a.numTriangles - 1u - w];                     // the same in every lane; held per lane, as its triangle
+    const TriGeom g = sampleTrianglesGeom(a, t);
+    const int nn = g.n * g.n;
+    double P[EXA_SURFACE_MAX_CHANNELS] = { 0.0, 0.0, 0.0, 0.0 };
+    uint32_t cnt[EXA_SURFACE_MAX_CHANNELS] = { 0u, 0u, 0u, 0u };
+    for (int k0 = 0; k0 < nn; k0 += 64) {
+      const int k = k0 + int(lane);
+      sampleTrianglesAt<UNIFORM>(a.s, xfm, k < nn, sampleTrianglesPos(g, k), tripped, P, cnt);
+    }
+    sampleTrianglesTree(32, P, cnt);
+    if (lane == 0u) sampleTrianglesStore(a, t, P, cnt);
+  }
+}
+
+// Second kernel: the waves stride first over the packed part of the list, 64 entries each, then over the wide part, one entry
+// each — one launch, so that neither part waits for the other's last waves
+template <bool UNIFORM>
+__global__ __launch_bounds__(256) void sampleTrianglesKernel(const TriArgs a)
+{
+  __shared__ float xfm[12];
+  sampleTrianglesStageXfm(a.s, xfm);
+  bool tripped = false;
+  sampleTrianglesPacked<UNIFORM>(a, xfm, tripped);
+  sampleTrianglesWide<UNIFORM>(a, xfm, tripped);
+  if (tripped) atomicExch(a.s.errorFlag, 1);
+}
+
+// the two kernels on the triangles of a, in order; the one that samples runs as at most kSampleTrianglesBlocks blocks whose
+// waves stride over the list (the lengths of its two parts are known on the device only)
+static const unsigned kSampleTrianglesBlocks = 16384;
+
+hipError_t launchSampleTriangles(const TriArgs &a, bool uniform, hipStream_t s)
+{
+  const unsigned m = a.numTriangles;
+  if (m == 0) return hipSuccess;
+  const dim3 block(256), grid(std::min(m / 4u + 1u, kSampleTrianglesBlocks));
+  hipLaunchKernelGGL(sampleTrianglesPrepKernel, dim3((m + 255u) / 256u), block, 0, s, a);
+  if (uniform) hipLaunchKernelGGL((sampleTrianglesKernel<true>), grid, block, 0, s, a);
+  else         hipLaunchKernelGGL((sampleTrianglesKernel<false>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launchSamplePoints(const SampleArgs &a, bool grad, hipStream_t s)
 {

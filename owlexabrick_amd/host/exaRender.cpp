@@ -54,6 +54,20 @@
 //                                            row y = 0 first: t (float32), position (3 float32), value (float32), gradient
 //                                            (3 float32), index (int32), side (int32), crossings (uint32); --frames 0 renders
 //                                            nothing
+//             [--surface MESH C0[,C1,C2,C3] SPACING MAXN out.surf] up to four channels of the field on the triangles of MESH
+//                                            (exa_hip_sample_triangles: each triangle cut into n x n parts, n = longest edge /
+//                                            SPACING rounded up, at most MAXN, sampled at their centroids), a triangle file as
+//                                            --isomesh writes it (all its meshes), or the word `iso`: the mesh of this
+//                                            invocation's --isomesh, in its space, integrated where it lies on the device.  Text,
+//                                            floats as %.9g and doubles as %.17g: one line `surface triangles T channels C c0 ..
+//                                            spacing S maxN N world 0|1`; per triangle one line `subdiv nx ny nz area` (areaNormal
+//                                            and its length) followed per channel by `count sum mean integral` (mean = sum / count,
+//                                            integral = mean * area, nan for count 0); one line `invalid K` (triangles of subdiv 0,
+//                                            left out of the totals); per channel one line `total c covered_area A uncovered_area U
+//                                            uncovered_triangles K integral I force fx fy fz` (sums of mean * area and of mean *
+//                                            areaNormal, in double in triangle order); with three channels one line `flux F` (the
+//                                            sum of mean . areaNormal); with
+//             [--surface-world]              a MESH file's vertices are in world space; --frames 0 renders nothing
 #include "exa_host.h"
 
 #include <hip/hip_runtime.h>
@@ -143,6 +157,11 @@ int main(int argc, char **argv)
     int projectChannel = 0, projectSamples = 0;
     float projectDt = 0.f;
     std::string raycastName;
+    std::string surfaceName, surfaceMesh;
+    std::vector<int> surfaceChannels;
+    float surfaceSpacing = 0.f;
+    int surfaceMaxN = 0;
+    bool surfaceWorld = false;
     int raycastChannel = 0, raycastSamples = 0, raycastRefine = 0;
     float raycastIso = 0.f, raycastDt = 0.f;
     int derived = -1;                                            // --derived: EXA_DERIVED_*
@@ -249,6 +268,21 @@ int main(int argc, char **argv)
         if (i + 1 >= argc) throw std::runtime_error("missing file after --raycast CHANNEL ISO DT NSAMPLES REFINE");
         raycastName = argv[++i];
       }
+      else if (a == "--surface") {
+        if (i + 2 >= argc) throw std::runtime_error("missing mesh and channels after --surface");
+        surfaceMesh = argv[++i];
+        for (const char *c = argv[++i]; *c;) {
+          char *end = nullptr;
+          surfaceChannels.push_back((int)std::strtol(c, &end, 10));
+          if (end == c || (*end && *end != ',')) throw std::runtime_error("--surface: channels are C0[,C1,C2,C3]");
+          c = *end ? end + 1 : end;
+        }
+        surfaceSpacing = f();
+        surfaceMaxN = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --surface MESH CHANNELS SPACING MAXN");
+        surfaceName = argv[++i];
+      }
+      else if (a == "--surface-world") surfaceWorld = true;
       else if (a == "--pipeline") pipeline = true;
       else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
       else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
@@ -353,17 +387,58 @@ int main(int argc, char **argv)
       else std::printf("derived %d channels %d %d %d components %zu invalid %zu\n", derived, derivedChannels.x, derivedChannels.y,
                        derivedChannels.z, comps, invalid);
     }
+    size_t isoTriangles = 0;
     if (!isoName.empty()) {
       const box3f box = haveIsoBox ? isoBox : (isoWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
       const vec3i dims(isoDims[0], isoDims[1], isoDims[2]);
-      TriangleMesh::SP mesh = derived < 0 ? renderer.extractIsoSurface(box, dims, isoChannel, isoValue, isoWorld)
-                                          : renderer.extractIsoSurfaceDerived(box, dims, derivedChannels, derived, isoValue, isoWorld);
+      const bool keep = surfaceMesh == "iso";          // --surface iso reads the module's copy
+      TriangleMesh::SP mesh = derived < 0 ? renderer.extractIsoSurface(box, dims, isoChannel, isoValue, isoWorld, nullptr, keep)
+                                          : renderer.extractIsoSurfaceDerived(box, dims, derivedChannels, derived, isoValue, isoWorld, keep);
+      isoTriangles = mesh->index.size();
       TriangleMesh::save(isoName, { mesh });
       std::printf("isomesh %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g ", dims.x, dims.y, dims.z, box.lower.x, box.lower.y,
                   box.lower.z, box.upper.x, box.upper.y, box.upper.z);
       if (derived < 0) std::printf("channel %d ", isoChannel);
       else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
       std::printf("iso %.9g vertices %zu triangles %zu\n", isoValue, mesh->vertex.size(), mesh->index.size());
+    }
+    if (!surfaceName.empty()) {
+      const bool fromIso = surfaceMesh == "iso";
+      if (fromIso && isoName.empty()) throw std::runtime_error("--surface iso needs --isomesh in the same invocation");
+      Renderer::SurfaceSamples S;
+      const bool world = fromIso ? isoWorld : surfaceWorld;
+      if (fromIso) S = renderer.sampleIsoSurface(isoTriangles, surfaceChannels.data(), (int)surfaceChannels.size(), surfaceSpacing, surfaceMaxN, world);
+      else {
+        TriangleMesh all;                                // the file's meshes as one
+        for (const TriangleMesh::SP &m : TriangleMesh::load(surfaceMesh)) {
+          const int base = (int)all.vertex.size();
+          all.vertex.insert(all.vertex.end(), m->vertex.begin(), m->vertex.end());
+          for (const vec3i &t : m->index) all.index.push_back(vec3i(t.x + base, t.y + base, t.z + base));
+        }
+        S = renderer.sampleTriangles(all, surfaceChannels.data(), (int)surfaceChannels.size(), surfaceSpacing, surfaceMaxN, world);
+      }
+      const Renderer::SurfaceIntegrals I = Renderer::surfaceIntegrals(S);
+      const size_t nt = S.subdiv.size(), nc = surfaceChannels.size();
+      FILE *f = std::fopen(surfaceName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + surfaceName);
+      std::fprintf(f, "surface triangles %zu channels %zu", nt, nc);
+      for (int c : surfaceChannels) std::fprintf(f, " %d", c);
+      std::fprintf(f, " spacing %.9g maxN %d world %d\n", surfaceSpacing, surfaceMaxN, world ? 1 : 0);
+      for (size_t t = 0; t < nt; t++) {
+        std::fprintf(f, "%d %.9g %.9g %.9g %.17g", S.subdiv[t], S.areaNormal[t].x, S.areaNormal[t].y, S.areaNormal[t].z, I.area[t]);
+        for (size_t c = 0; c < nc; c++)
+          std::fprintf(f, " %u %.17g %.17g %.17g", S.count[t * nc + c], S.sum[t * nc + c], I.mean[t * nc + c], I.integral[t * nc + c]);
+        std::fprintf(f, "\n");
+      }
+      std::fprintf(f, "invalid %llu\n", (unsigned long long)I.invalidTriangles);
+      for (size_t c = 0; c < nc; c++)
+        std::fprintf(f, "total %d covered_area %.17g uncovered_area %.17g uncovered_triangles %llu integral %.17g force %.17g %.17g %.17g\n",
+                     surfaceChannels[c], I.coveredArea[c], I.uncoveredArea[c], (unsigned long long)I.uncoveredTriangles[c],
+                     I.totalIntegral[c], I.force[3 * c], I.force[3 * c + 1], I.force[3 * c + 2]);
+      if (nc == 3) std::fprintf(f, "flux %.17g\n", I.flux);
+      if (std::fclose(f)) throw std::runtime_error("cannot write " + surfaceName);
+      std::printf("surface triangles %zu channels %zu spacing %.9g maxN %d invalid %llu\n", nt, nc, surfaceSpacing, surfaceMaxN,
+                  (unsigned long long)I.invalidTriangles);
     }
     if (!histName.empty()) {
       if (histBins < 1) throw std::runtime_error("--histogram wants BINS >= 1");
@@ -443,7 +518,7 @@ int main(int argc, char **argv)
                   raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
-                        || !raycastName.empty())) return 0;
+                        || !raycastName.empty() || !surfaceName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

@@ -560,7 +560,8 @@ void Renderer::resample(const box3f &box, vec3i dims, int channel, float *out, b
 }
 
 // the mesh of the last extraction (exa_hip_isosurface or exa_hip_isosurface_derived) out of the module, which then drops it
-static TriangleMesh::SP readIsoMesh(ExaHipRenderer *handle, uint64_t nv, uint64_t nt, std::vector<vec3f> *gradients)
+// (unless it is to keep it)
+static TriangleMesh::SP readIsoMesh(ExaHipRenderer *handle, uint64_t nv, uint64_t nt, std::vector<vec3f> *gradients, bool keep = false)
 {
   auto mesh = std::make_shared<TriangleMesh>();
   mesh->vertex.resize(nv);
@@ -569,12 +570,12 @@ static TriangleMesh::SP readIsoMesh(ExaHipRenderer *handle, uint64_t nv, uint64_
   check(exa_hip_isosurface_read(handle, reinterpret_cast<float *>(mesh->vertex.data()),
                                 gradients ? reinterpret_cast<float *>(gradients->data()) : nullptr,
                                 reinterpret_cast<int32_t *>(mesh->index.data()), 0, nullptr), handle);
-  check(exa_hip_isosurface_release(handle), handle);
+  if (!keep) check(exa_hip_isosurface_release(handle), handle);
   return mesh;
 }
 
 TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace,
-                                             std::vector<vec3f> *gradients)
+                                             std::vector<vec3f> *gradients, bool keep)
 {
   if (worldSpace) pushState();
   const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
@@ -582,7 +583,7 @@ TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int c
   uint64_t nv = 0, nt = 0;
   const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0);
   check(exa_hip_isosurface(handle, lo, hi, d, channel, iso, flags, &nv, &nt, nullptr), handle);
-  return readIsoMesh(handle, nv, nt, gradients);
+  return readIsoMesh(handle, nv, nt, gradients, keep);
 }
 
 void Renderer::sampleDerived(const vec3f *points, size_t n, vec3i channels, int quantity, float *out, int *status,
@@ -604,7 +605,7 @@ void Renderer::resampleDerived(const box3f &box, vec3i dims, vec3i channels, int
 }
 
 TriangleMesh::SP Renderer::extractIsoSurfaceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso,
-                                                    bool worldSpace)
+                                                    bool worldSpace, bool keep)
 {
   if (worldSpace) pushState();
   const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
@@ -612,7 +613,7 @@ TriangleMesh::SP Renderer::extractIsoSurfaceDerived(const box3f &box, vec3i dims
   uint64_t nv = 0, nt = 0;
   check(exa_hip_isosurface_derived(handle, lo, hi, d, ch, quantity, iso, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, &nv, &nt, nullptr),
         handle);
-  return readIsoMesh(handle, nv, nt, nullptr);
+  return readIsoMesh(handle, nv, nt, nullptr, keep);
 }
 
 void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
@@ -690,6 +691,70 @@ Renderer::IsoHits Renderer::raycastIso(const ExaHipRays &rays, int channel, floa
                             R.value.data(), reinterpret_cast<float *>(R.gradient.data()), R.index.data(), R.side.data(),
                             R.crossings.data(), 0, nullptr), handle);
   return R;
+}
+
+// the results of numTriangles triangles and the call that fills them (mesh == nullptr: the mesh the module holds)
+static Renderer::SurfaceSamples sampleSurface(ExaHipRenderer *handle, const TriangleMesh *mesh, size_t numTriangles, const int *channels,
+                                              int numChannels, float spacing, int maxN, bool worldSpace)
+{
+  static_assert(sizeof(vec3f) == 12 && sizeof(vec3i) == 12, "vertices, indices and normals are packed");
+  Renderer::SurfaceSamples S;
+  S.numChannels = numChannels;
+  const size_t nc = numChannels > 0 && numChannels <= EXA_SURFACE_MAX_CHANNELS ? size_t(numChannels) : 0;   // the module checks it
+  S.sum.resize(numTriangles * nc); S.count.resize(numTriangles * nc); S.areaNormal.resize(numTriangles); S.subdiv.resize(numTriangles);
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (mesh ? 0 : EXA_SURFACE_FROM_ISOSURFACE);
+  std::vector<int32_t> ch(channels, channels + nc);
+  check(exa_hip_sample_triangles(handle, mesh ? reinterpret_cast<const float *>(mesh->vertex.data()) : nullptr, mesh ? mesh->vertex.size() : 0,
+                                 mesh ? reinterpret_cast<const int32_t *>(mesh->index.data()) : nullptr, mesh ? mesh->index.size() : 0,
+                                 nc ? ch.data() : nullptr, numChannels, spacing, maxN, flags, S.sum.data(), S.count.data(),
+                                 reinterpret_cast<float *>(S.areaNormal.data()), S.subdiv.data(), 0, nullptr), handle);
+  return S;
+}
+
+Renderer::SurfaceSamples Renderer::sampleTriangles(const TriangleMesh &mesh, const int *channels, int numChannels, float spacing,
+                                                   int maxN, bool worldSpace)
+{
+  if (worldSpace) pushState();
+  return sampleSurface(handle, &mesh, mesh.index.size(), channels, numChannels, spacing, maxN, worldSpace);
+}
+
+Renderer::SurfaceSamples Renderer::sampleIsoSurface(size_t numTriangles, const int *channels, int numChannels, float spacing, int maxN,
+                                                    bool worldSpace)
+{
+  if (worldSpace) pushState();
+  return sampleSurface(handle, nullptr, numTriangles, channels, numChannels, spacing, maxN, worldSpace);
+}
+
+Renderer::SurfaceIntegrals Renderer::surfaceIntegrals(const SurfaceSamples &S)
+{
+  const size_t nt = S.subdiv.size(), nc = size_t(S.numChannels);
+  SurfaceIntegrals I;
+  I.area.resize(nt); I.mean.resize(nt * nc); I.integral.resize(nt * nc);
+  I.coveredArea.assign(nc, 0.0); I.uncoveredArea.assign(nc, 0.0); I.totalIntegral.assign(nc, 0.0);
+  I.uncoveredTriangles.assign(nc, 0); I.force.assign(3 * nc, 0.0);
+  double flux = 0.0;
+  for (size_t t = 0; t < nt; t++) {
+    const double nx = S.areaNormal[t].x, ny = S.areaNormal[t].y, nz = S.areaNormal[t].z;
+    const double area = std::sqrt((nx * nx + ny * ny) + nz * nz);
+    I.area[t] = area;
+    bool all = true;
+    for (size_t c = 0; c < nc; c++) {
+      const uint32_t n = S.count[t * nc + c];
+      const double mean = n ? S.sum[t * nc + c] / double(n) : double(NAN);
+      I.mean[t * nc + c] = mean;
+      I.integral[t * nc + c] = mean * area;
+      all = all && n;
+      if (S.subdiv[t] <= 0) continue;
+      if (!n) { I.uncoveredArea[c] += area; I.uncoveredTriangles[c]++; continue; }
+      I.coveredArea[c] += area;
+      I.totalIntegral[c] += mean * area;
+      I.force[3 * c] += mean * nx; I.force[3 * c + 1] += mean * ny; I.force[3 * c + 2] += mean * nz;
+    }
+    if (S.subdiv[t] <= 0) { I.invalidTriangles++; continue; }
+    if (nc == 3 && all) flux += (I.mean[t * nc] * nx + I.mean[t * nc + 1] * ny) + I.mean[t * nc + 2] * nz;
+  }
+  if (nc == 3) I.flux = flux;
+  return I;
 }
 
 ExaHipRays Renderer::cameraRays(vec2i size, float tmin, float dt, int numSamples) const

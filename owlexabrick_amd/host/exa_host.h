@@ -206,8 +206,9 @@ struct Renderer {
   // (B-A)x(C-A) toward the lower values, positions in the space of `box`.  gradients: per vertex what samplePoints gives there
   // with normalized = true (the shading normal is -grad/|grad|).  The mesh can go back in as a surface, or to a file
   // (TriangleMesh::save).
+  // keep: the module keeps its device copy of the mesh (for sampleIsoSurface) until the next extraction.
   TriangleMesh::SP extractIsoSurface(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace = false,
-                                     std::vector<vec3f> *gradients = nullptr);
+                                     std::vector<vec3f> *gradients = nullptr, bool keep = false);
 
   // quantities of the velocity gradient tensor of the vector field (channels.x, .y, .z): `quantity` = EXA_DERIVED_SPEED,
   // _DIVERGENCE, _VORTICITY (three components, interleaved), _VORTICITY_MAGNITUDE, _Q or _HELICITY (exa_hip_sample_derived,
@@ -219,7 +220,7 @@ struct Renderer {
   void resampleDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float *out, bool worldSpace = false,
                        float fill = NAN);
   TriangleMesh::SP extractIsoSurfaceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso,
-                                            bool worldSpace = false);
+                                            bool worldSpace = false, bool keep = false);
 
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
@@ -271,6 +272,39 @@ struct Renderer {
   };
   IsoHits raycastIso(const ExaHipRays &rays, int channel, float iso, int refine, bool worldSpace = false, bool normalize = false,
                      float fill = NAN);
+  // up to four channels of the field on the triangles of a mesh (exa_hip_sample_triangles; include/exa_hip.h states the
+  // contract): every triangle is cut into n x n congruent parts, n = its longest edge over `spacing` rounded up, at most maxN
+  // (spacing 0: n = maxN), and sampled at their centroids.  Per triangle: subdiv = n (0: a bad index or a non-finite vertex,
+  // no samples), areaNormal = half the cross product of its edges, and per channel (index triangle * numChannels + c) the sum
+  // of the valid samples and their count.  Vertices in voxel space or, with worldSpace, in world space (the frame state is
+  // pushed first).  sampleIsoSurface: the same on the mesh an extraction with keep = true left in the module, read on the
+  // device (numTriangles: that mesh's, it sizes the result; worldSpace: as the extraction had it).  surfaceIntegrals forms,
+  // in double and in ascending triangle order, what a caller wants of them.
+  struct SurfaceSamples {
+    int numChannels = 0;
+    std::vector<double> sum;
+    std::vector<uint32_t> count;
+    std::vector<vec3f> areaNormal;
+    std::vector<int32_t> subdiv;
+  };
+  SurfaceSamples sampleTriangles(const TriangleMesh &mesh, const int *channels, int numChannels, float spacing, int maxN,
+                                 bool worldSpace = false);
+  SurfaceSamples sampleIsoSurface(size_t numTriangles, const int *channels, int numChannels, float spacing, int maxN,
+                                  bool worldSpace = false);
+  // Per triangle: area = |areaNormal|, and per channel mean = sum / count (NaN where count == 0) and integral = mean * area.
+  // Totals over the valid triangles (subdiv > 0; the others are counted in invalidTriangles), per channel: coveredArea and
+  // uncoveredArea / uncoveredTriangles (count == 0), integral = the sum of mean * area and force = the sum of mean * areaNormal
+  // over the covered ones; with three channels flux = the sum of (mean0 * n.x + mean1 * n.y) + mean2 * n.z over the triangles
+  // all three cover (else NaN).
+  struct SurfaceIntegrals {
+    std::vector<double> area, mean, integral;                   // numTriangles, x numChannels, x numChannels
+    std::vector<double> coveredArea, uncoveredArea, totalIntegral;   // numChannels each
+    std::vector<uint64_t> uncoveredTriangles;
+    std::vector<double> force;                                  // numChannels x 3
+    double flux = NAN;
+    uint64_t invalidTriangles = 0;
+  };
+  static SurfaceIntegrals surfaceIntegrals(const SurfaceSamples &S);
   // the rays of the camera set with updateCamera, through the pixel centres of a size.x x size.y image (world space)
   ExaHipRays cameraRays(vec2i size, float tmin, float dt, int numSamples) const;
 
