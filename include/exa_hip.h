@@ -477,6 +477,93 @@ int exa_hip_isosurface_derived(ExaHipRenderer *, const float lo[3], const float 
                                uint64_t *numVertices, uint64_t *numTriangles, void *hipStream);
 int exa_hip_derived_ms(ExaHipRenderer *, float *ms);
 
+/* ---- contour lines: the lines field == iso of one channel, or of a derived quantity, on a caller-chosen plane lattice that
+ * may be oblique, for several levels at once, as indexed segments without duplicate vertices, consistently oriented, in a
+ * fixed order (two runs give the same bytes).  The 2D sibling of exa_hip_isosurface; new relative to the reference, whose
+ * contour planes (ExaHipFrameState.contour) exist only as shaded pixels.  Marching triangles on the split of every lattice
+ * square along the diagonal (0,0)-(1,1): no ambiguous cases, and the split is translation invariant, so neighbouring
+ * squares agree on every shared edge.  All arithmetic is float32, every operation rounded separately, nothing contracted. ----
+ *
+ * Lattice.  nu, nv >= 2, nu*nv <= 2^31 - 1, every float of the plane finite.  Lattice point (i,j) lies at
+ * P = (origin + (float(i) + 0.5f) * du) + (float(j) + 0.5f) * dv per component (the association of ExaHipRays' origin);
+ * linear index L = j*nu + i.  du and dv are not checked for independence: a degenerate plane gives coincident points.
+ * Without EXA_SAMPLE_WORLD_SPACE the plane is in voxel space, with it in world space: the positions then go through the frame
+ * state's transform exactly as the probes do it.
+ *
+ * Values.  V(L) is exactly what exa_hip_sample_points(P, {channel}, 1, flags & EXA_SAMPLE_WORLD_SPACE, fill = NaN) returns;
+ * for exa_hip_isolines_derived what exa_hip_sample_derived(P, channels, quantity, the same flag, fill = NaN) returns
+ * (one-component quantities only; EXA_SAMPLE_GRADIENT is refused, as by exa_hip_isosurface_derived).  Both in the handle's
+ * current basis_form.
+ *
+ * Levels.  isos[0 .. numIsos), 1 <= numIsos <= EXA_ISOLINES_MAX_LEVELS, each finite, in any order, repeats allowed; each
+ * level is contoured independently.  inside(v) = v >= iso.
+ *
+ * Valid squares.  Square (i,j), i < nu-1, j < nv-1, is valid if its four corner values are finite; an invalid square emits
+ * nothing.
+ *
+ * Triangles.  Two per valid square, in this order: T0, the permutation (u,v): v0 = p, v1 = p + e_u, v2 = p + e_u + e_v,
+ * parity 0; T1, the permutation (v,u): v0 = p, v1 = p + e_v, v2 = p + e_u + e_v, parity 1.
+ *
+ * Vertices.  Every triangle edge joins lattice points p and q = p + d, d in {(1,0), (0,1), (1,1)}, coded dx + 2*dy.  An edge
+ * crosses if inside(V(p)) != inside(V(q)).  Exactly one vertex per crossing edge that belongs to at least one valid square,
+ * no others: t = (iso - V(p)) / (V(q) - V(p)), pos = P(p) + t * (P(q) - P(p)) per component,
+ * uv = ((float(i) + 0.5f) + t * float(dx), (float(j) + 0.5f) + t * float(dy)).  Positions are in the caller's space, never put
+ * through the transform.  Order within a level: ascending L(p), then ascending edge code.
+ *
+ * Segments (triangle-vertex indices 0..2; "x-y" = the vertex on the edge between triangle vertices x and y).  A triangle
+ * whose vertex s lies alone on its side emits the segment (s-o0, s-o1), o0 < o1 the other two, reversed iff
+ * parity(s,o0,o1) XOR parity(triangle) XOR (s is outside).  With u pointing right and v up the >= iso side then lies to the
+ * left of every segment.  Order within a level: ascending L of the square's origin, then T0 before T1.  Zero-length segments
+ * (a lattice value equal to iso) are kept.  Indices are int32 and global (they address the packed vertex array).
+ *
+ * Levels in the output.  Level l's vertices are vertexOffsets[l] .. vertexOffsets[l+1], its segments
+ * segmentOffsets[l] .. segmentOffsets[l+1]; the levels appear in the order given.  More than INT32_MAX vertices or segments
+ * in all is an error.
+ *
+ * Gradients.  With EXA_SAMPLE_GRADIENT (exa_hip_isolines only) the module also keeps, per vertex, the gradient that
+ * exa_hip_sample_points(pos, world? | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED, fill = NaN) returns there, bit
+ * for bit (the same kernel on the device vertex buffer).
+ *
+ * Values kept.  With EXA_ISOLINES_KEEP_VALUES the nu*nv lattice values stay with the result and exa_hip_isolines_read
+ * returns them: the slice image under the contours.  Without the flag a non-NULL `values` there is an error.
+ *
+ * Independence.  The result depends only on the scene, the plane, the channel(s) and the quantity, the levels, the flags,
+ * basis_form and (world space) the transform — on nothing a frame sets, nor on walk, accel, brick_order, sample_patch or
+ * sample_uniform.  Two calls give the same bytes.  A pending brick_order change is applied first.  A scene without a kd tree
+ * is refused.  A multi-device handle runs on devices[0].
+ *
+ * Calls.  Synchronous on hipStream.  The result lives in module-owned device memory until the next extraction (also a
+ * failed one), exa_hip_isolines_release or exa_hip_destroy; it is independent of the mesh of exa_hip_isosurface, neither
+ * call drops the other's result.  An empty result returns 0 with zero counts.  exa_hip_isolines_read: vertices V x 3, uv
+ * V x 2, gradients V x 3 (only after EXA_SAMPLE_GRADIENT), segments S x 2, both offset arrays numIsos + 1, values nu*nv
+ * (values[j*nu + i]); a NULL pointer skips that array; host arrays, or memory of the handle's first device with
+ * pointersAreDevice; an error before any extraction.  Errors carry a message that starts with the function's name and
+ * leave the handle usable: a NULL plane or NULL levels, a non-finite float, nu or nv < 2, too many lattice points, numIsos
+ * out of range, a bad channel or quantity, unknown flag bits, world space before a frame state, a failed allocation.  The
+ * descent's loop guard returns 3.
+ * exa_hip_isolines_stage_ms: the device time of the last extraction's stages in ms, summed over the levels — positions and
+ * values, square pass (validity and segment count per square), point pass (mask of owned crossing edges per lattice point),
+ * scans, emit, gradients.
+ *
+ * Memory.  While the values are formed: 4 bytes per lattice point for the values and 12 for the positions (the peak, 16);
+ * afterwards the values and a work space of 4 bytes per point, plus the packed result.  Nothing grows with nu*nv*numIsos:
+ * the levels run one after another over the shared values — a first round counts every level, a second repeats the passes
+ * and emits at the level's offsets (a single level is not repeated). */
+#define EXA_ISOLINES_KEEP_VALUES 16   /* flag: keep the lattice values for exa_hip_isolines_read */
+#define EXA_ISOLINES_MAX_LEVELS  256
+typedef struct ExaHipPlane { float origin[3], du[3], dv[3]; int32_t nu, nv; } ExaHipPlane;
+int exa_hip_isolines(ExaHipRenderer *, const ExaHipPlane *, int32_t channel, const float *isos, int32_t numIsos,
+                     int32_t flags, uint64_t *numVertices, uint64_t *numSegments, void *hipStream);
+int exa_hip_isolines_derived(ExaHipRenderer *, const ExaHipPlane *, const int32_t channels[3], int32_t quantity,
+                             const float *isos, int32_t numIsos, int32_t flags,
+                             uint64_t *numVertices, uint64_t *numSegments, void *hipStream);
+int exa_hip_isolines_read(ExaHipRenderer *, float *vertices /* V x 3 */, float *uv /* V x 2 */, float *gradients /* V x 3 */,
+                          int32_t *segments /* S x 2 */, uint64_t *vertexOffsets /* numIsos+1 */,
+                          uint64_t *segmentOffsets /* numIsos+1 */, float *values /* nu*nv */,
+                          int32_t pointersAreDevice, void *hipStream);
+int exa_hip_isolines_release(ExaHipRenderer *);
+int exa_hip_isolines_stage_ms(ExaHipRenderer *, float ms[6]);
+
 /* ---- histogram and value range of one channel's cells: the exact histogram of the cell values by cell count and by
  * volume, the value range, the cell counts per level and the NaN / empty / out-of-range counts, optionally inside an integer
  * voxel box.  New relative to the reference, whose viewer left the hook unbuilt (exa/viewer.cpp:1274-1276, setValueRange /

@@ -127,6 +127,10 @@ SURFACE_FROM_ISOSURFACE = 8
 SURFACE_MAX_N = 64
 SURFACE_MAX_CHANNELS = 4
 
+# exa_hip_isolines (include/exa_hip.h)
+ISOLINES_KEEP_VALUES = 16
+ISOLINES_MAX_LEVELS = 256
+
 # exa_hip_raycast_iso (include/exa_hip.h)
 CROSS_MAX_REFINE = 32
 RAYCAST_KEYS = ("t", "position", "value", "gradient", "index", "side", "crossings")
@@ -189,6 +193,10 @@ class ExaHipRays(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("tmin", C.c_float), ("dt", C.c_float), ("numSamples", C.c_int32)]
 
 
+class ExaHipPlane(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("nu", C.c_int32), ("nv", C.c_int32)]
+
+
 _vp, _i32, _u64, _f32, _P = C.c_void_p, C.c_int32, C.c_uint64, C.c_float, C.POINTER
 
 # every symbol include/exa_hip.h declares: name -> (restype, None = the int return code; argtypes, None = takes none).  lib()
@@ -234,6 +242,11 @@ _ABI = {
     "exa_hip_resample_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i32]),
     "exa_hip_isosurface_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _P(_u64), _vp]),
     "exa_hip_derived_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_isolines": (None, [_vp, _P(ExaHipPlane), _i32, _vp, _i32, _i32, _P(_u64), _P(_u64), _vp]),
+    "exa_hip_isolines_derived": (None, [_vp, _P(ExaHipPlane), _vp, _i32, _vp, _i32, _i32, _P(_u64), _P(_u64), _vp]),
+    "exa_hip_isolines_read": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_isolines_release": (None, [_vp]),
+    "exa_hip_isolines_stage_ms": (None, [_vp, _vp]),
     "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
     "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),
@@ -707,6 +720,78 @@ class Renderer:
             return self.readIsoSurface()[:2]
         finally:
             self.releaseIsoSurface()
+
+    # ---- contour lines on a plane lattice (exa_hip_isolines*; include/exa_hip.h states the contract) ----
+    def extractIsolines(self, origin, du, dv, size, isos, channel=0, world=False, gradients=False, values=False, quantity=None,
+                        channels=(0, 1, 2), stream=None):
+        """extract the lines field == iso, for every iso of `isos`, on the plane lattice of size = (nu, nv) whose point (i, j)
+        lies at origin + (i + 0.5) du + (j + 0.5) dv, into module-owned device memory; with a `quantity` the lines of that
+        derived quantity of `channels`.  Returns (numVertices, numSegments).  readIsolines copies the result out,
+        releaseIsolines frees it."""
+        flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradients else 0) | (ISOLINES_KEEP_VALUES if values else 0)
+        plane = ExaHipPlane(_f3(origin), _f3(du), _f3(dv), int(size[0]), int(size[1]))
+        levels = np.ascontiguousarray(isos, dtype=np.float32).reshape(-1)
+        nv, ns = C.c_uint64(0), C.c_uint64(0)
+        self._isolines = None
+        if quantity is None:
+            rc = lib().exa_hip_isolines(self.h, C.byref(plane), int(channel), levels.ctypes.data, len(levels), flags,
+                                        C.byref(nv), C.byref(ns), C.c_void_p(stream or 0))
+        else:
+            rc = lib().exa_hip_isolines_derived(self.h, C.byref(plane), _i3(channels), derived_quantity(quantity),
+                                                levels.ctypes.data, len(levels), flags, C.byref(nv), C.byref(ns),
+                                                C.c_void_p(stream or 0))
+        self._check(rc)
+        self._isolines = (int(nv.value), int(ns.value), len(levels), bool(gradients), (int(size[1]), int(size[0])) if values else None)
+        return self._isolines[:2]
+
+    def readIsolines(self):
+        """the last extractIsolines as a dict: vertices float32 [V,3], uv float32 [V,2], segments int32 [S,2] (global vertex
+        indices), vertex_offsets and segment_offsets uint64 [levels + 1], and gradients float32 [V,3] / values float32
+        [nv,nu] where the extraction kept them"""
+        if not getattr(self, "_isolines", None):
+            self._check(lib().exa_hip_isolines_read(self.h, None, None, None, None, None, None, None, 0, None))   # refused
+            raise RuntimeError("readIsolines: no extraction of this renderer to read")
+        nv, ns, nl, grad, shape = self._isolines
+        out = dict(vertices=np.empty((nv, 3), np.float32), uv=np.empty((nv, 2), np.float32), segments=np.empty((ns, 2), np.int32),
+                   vertex_offsets=np.empty(nl + 1, np.uint64), segment_offsets=np.empty(nl + 1, np.uint64))
+        if grad:
+            out["gradients"] = np.empty((nv, 3), np.float32)
+        if shape:
+            out["values"] = np.empty(shape, np.float32)
+        ptr = lambda k: out[k].ctypes.data if k in out else None                # noqa: E731
+        self._check(lib().exa_hip_isolines_read(self.h, ptr("vertices"), ptr("uv"), ptr("gradients"), ptr("segments"),
+                                                ptr("vertex_offsets"), ptr("segment_offsets"), ptr("values"), 0, None))
+        return out
+
+    def releaseIsolines(self):
+        self._check(lib().exa_hip_isolines_release(self.h))
+        self._isolines = None
+
+    def isolinesStageMs(self):
+        """device ms of the last extraction's stages, summed over the levels: positions and values, square pass, point pass,
+        scans, emit, gradients"""
+        ms = (C.c_float * 6)()
+        self._check(lib().exa_hip_isolines_stage_ms(self.h, ms))
+        return [float(v) for v in ms]
+
+    def isolines(self, origin, du, dv, size, isos, channel=0, world=False, gradients=False, values=False):
+        """the contour lines field == iso of `channel`, for every iso of `isos`, on the plane lattice of extractIsolines, by
+        marching triangles: the dict of readIsolines.  The >= iso side lies to the left of every segment (u right, v up);
+        level l owns vertices[vertex_offsets[l]:vertex_offsets[l+1]] and segments[segment_offsets[l]:segment_offsets[l+1]].
+        The device copy is released before returning."""
+        self.extractIsolines(origin, du, dv, size, isos, channel=channel, world=world, gradients=gradients, values=values)
+        try:
+            return self.readIsolines()
+        finally:
+            self.releaseIsolines()
+
+    def isolinesDerived(self, origin, du, dv, size, isos, quantity, channels=(0, 1, 2), world=False, values=False):
+        """isolines of a one-component derived quantity (a key of DERIVED, or its number) of the vector field `channels`"""
+        self.extractIsolines(origin, du, dv, size, isos, world=world, values=values, quantity=quantity, channels=channels)
+        try:
+            return self.readIsolines()
+        finally:
+            self.releaseIsolines()
 
     def derivedMs(self):
         """device ms of the kernels of the last sampleDerived / resampleDerived call, summed"""

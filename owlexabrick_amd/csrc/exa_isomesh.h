@@ -1,5 +1,5 @@
-// exa_isomesh.h — iso-surface extraction on a lattice of sampled values (exa_hip_isosurface): what exa_probe.cpp and
-// exa_isomesh.hip share.  Marching tetrahedra on the six-tetrahedra (Kuhn) split of every lattice cube along the diagonal
+// exa_isomesh.h — iso-surface extraction on a lattice of sampled values (exa_hip_isosurface), and contour lines on a plane
+// lattice (exa_hip_isolines, further down): what exa_probe.cpp and exa_isomesh.hip share.  Marching tetrahedra on the six-tetrahedra (Kuhn) split of every lattice cube along the diagonal
 // (0,0,0)-(1,1,1); include/exa_hip.h states the contract (tetrahedron order, vertex order, orientation).
 //
 // The pipeline, every kernel one lane per lattice point L = (k*ny + j)*nx + i, blocks of kIsoBlock consecutive L (a wave
@@ -46,5 +46,45 @@ hipError_t launchIsoCubePass(const IsoMeshArgs &a, hipStream_t s);
 hipError_t launchIsoPointPass(const IsoMeshArgs &a, hipStream_t s);
 hipError_t launchIsoScans(const IsoMeshArgs &a, hipStream_t s);
 hipError_t launchIsoEmit(const IsoMeshArgs &a, hipStream_t s);
+
+// ---- contour lines on a plane lattice (exa_hip_isolines): the 2D sibling, marching triangles on the split of every lattice
+// square along the diagonal (0,0)-(1,1).  One lane per lattice point L = j*nu + i, blocks of kIsoBlock consecutive L, one
+// level (iso) per round of passes over the shared values:
+//   positions     P(L) = (origin + (float(i) + 0.5f) * du) + (float(j) + 0.5f) * dv into a device buffer; the probes' kernels
+//                 fill the values from it
+//   square pass   squareInfo[L] = 0x80 | number of segments of the square with origin L (0 = not a square, or a corner value
+//                 is not finite), and the block's segment count
+//   point pass    mask[L] = bit (code-1) for every crossing triangle edge L -> L + (dx,dy), code = dx + 2 dy, that lies in a
+//                 valid square; rel[L] and the block's count as above
+//   scans         the iso-surface's (launchIsolineScans hands them the counts)
+//   emit          vertices and uv at vertexBase + chunkBase + blockBase + rel + popcount(mask below the edge's bit); segment
+//                 indices through the owning point's base and mask.  vertices, uv and segments point at the level's first
+//                 entry, vertexBase is the global index of its first vertex
+struct IsoLineArgs {
+  const float *values;        // the lattice, numPoints floats
+  uint32_t numPoints;         // nu*nv <= 2^31 - 1
+  uint32_t nu, nv;
+  float iso;
+  float origin[3], du[3], dv[3];
+  float *positions;           // the positions kernel: 3 floats per lattice point
+  uint8_t *squareInfo;        // numPoints
+  uint8_t *mask;              // numPoints
+  uint16_t *rel;              // numPoints
+  uint32_t numBlocks, numChunks;
+  uint32_t *blockCount;       // [2][numBlocks]: 0 = vertices, 1 = segments
+  uint32_t *blockBase;        // [2][numBlocks]
+  uint64_t *chunkBase;        // [2][numChunks]
+  uint64_t *totals;           // [2]
+  uint32_t vertexBase;
+  float *vertices;            // 3 floats per vertex
+  float *uv;                  // 2 floats per vertex
+  int32_t *segments;          // 2 indices per segment
+};
+
+hipError_t launchIsolinePositions(const IsoLineArgs &a, hipStream_t s);
+hipError_t launchIsolineSquarePass(const IsoLineArgs &a, hipStream_t s);
+hipError_t launchIsolinePointPass(const IsoLineArgs &a, hipStream_t s);
+hipError_t launchIsolineScans(const IsoLineArgs &a, hipStream_t s);
+hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s);
 
 } // namespace exa

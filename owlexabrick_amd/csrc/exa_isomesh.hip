@@ -1,7 +1,8 @@
 // exa_isomesh.hip — the kernels of exa_hip_isosurface: classify, count, scan, emit (exa_isomesh.h describes the pipeline,
 // include/exa_hip.h the contract).  A translation unit of its own: nothing of the renderer or of the probes is compiled
 // here, the lattice values arrive in a device buffer.  Compiled with -ffp-contract=off: a vertex position is
-// P(p) + t * (P(q) - P(p)) with every operation rounded separately.
+// P(p) + t * (P(q) - P(p)) with every operation rounded separately.  Behind them the kernels of exa_hip_isolines, the same
+// pipeline on the squares of a plane lattice (isoline...Kernel), which shares the block scan and the scans.
 #include "exa_isomesh.h"
 
 namespace exa {
@@ -320,7 +321,223 @@ __global__ __launch_bounds__(kIsoBlock) void isoEmitTrianglesKernel(const IsoMes
   emitTet<5>(inside, vb, mk, out);
 }
 
+// ---- contour lines on a plane lattice (exa_hip_isolines): marching triangles, the passes of exa_isomesh.h ----
+// the triangles of a square: T0 = permutation (u,v), corners 0, 1, 3 (dx + 2 dy), parity 0; T1 = (v,u), corners 0, 2, 3, parity 1
+constexpr int kTriCorner[2][3] = { { 0, 1, 3 }, { 0, 2, 3 } };
+
+__device__ __forceinline__ size_t lineCornerOffset(const IsoLineArgs &a, int m)
+{
+  return size_t(m & 1) + size_t(m >> 1) * a.nu;
+}
+
+// lattice point (i,j), component c: (origin + (float(i) + 0.5f) * du) + (float(j) + 0.5f) * dv
+__device__ __forceinline__ float linePosition(const IsoLineArgs &a, uint32_t i, uint32_t j, int c)
+{
+  return (a.origin[c] + (float(i) + 0.5f) * a.du[c]) + (float(j) + 0.5f) * a.dv[c];
+}
+
+template <int TRI>
+__device__ __forceinline__ uint32_t triPattern(uint32_t inside)
+{
+  return ((inside >> kTriCorner[TRI][0]) & 1u) | (((inside >> kTriCorner[TRI][1]) & 1u) << 1) | (((inside >> kTriCorner[TRI][2]) & 1u) << 2);
+}
+__device__ __forceinline__ uint32_t triSegments(uint32_t pat) { return (pat != 0u && pat != 7u) ? 1u : 0u; }
+
+__global__ __launch_bounds__(kIsoBlock) void isolinePositionsKernel(const IsoLineArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  const uint32_t i = L % a.nu, j = L / a.nu;
+  float *out = a.positions + 3 * size_t(L);
+  out[0] = linePosition(a, i, j, 0);
+  out[1] = linePosition(a, i, j, 1);
+  out[2] = linePosition(a, i, j, 2);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isolineSquareKernel(const IsoLineArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  uint32_t count = 0;
+  if (L < a.numPoints) {
+    const uint32_t i = L % a.nu, j = L / a.nu;
+    uint32_t info = 0;
+    if (i + 1 < a.nu && j + 1 < a.nv) {
+      const float *v = a.values + L;
+      bool finite = true;
+      uint32_t inside = 0;
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const float x = v[lineCornerOffset(a, m)];
+        finite = finite && __builtin_isfinite(x);
+        inside |= (x >= a.iso ? 1u : 0u) << m;
+      }
+      if (finite) {
+        count = triSegments(triPattern<0>(inside)) + triSegments(triPattern<1>(inside));
+        info = 0x80u | count;
+      }
+    }
+    a.squareInfo[L] = uint8_t(info);
+  }
+  uint32_t total;
+  (void)blockScan(count, total, lds);
+  if (threadIdx.x == 0) a.blockCount[a.numBlocks + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isolinePointKernel(const IsoLineArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  uint32_t mask = 0;
+  if (L < a.numPoints) {
+    const uint32_t i = L % a.nu, j = L / a.nu;
+    uint32_t squares = 0;                     // bit m: the square with origin p - m is valid (m = 3 holds no edge of p)
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+      if (i >= uint32_t(m & 1) && j >= uint32_t(m >> 1))
+        squares |= uint32_t(a.squareInfo[L - lineCornerOffset(a, m)] >> 7) << m;
+    if (squares) {
+      const float *v = a.values + L;
+      const bool inP = v[0] >= a.iso;
+#pragma unroll
+      for (int code = 1; code < 4; code++)
+        if (squares & edgeCubes(code)) {        // then q = p + code is a lattice point, and both values are finite
+          const bool inQ = v[lineCornerOffset(a, code)] >= a.iso;
+          if (inQ != inP) mask |= 1u << (code - 1);
+        }
+    }
+    a.mask[L] = uint8_t(mask);
+  }
+  uint32_t total;
+  const uint32_t before = blockScan(__popc(mask), total, lds);
+  if (L < a.numPoints) a.rel[L] = uint16_t(before);
+  if (threadIdx.x == 0) a.blockCount[blockIdx.x] = total;
+}
+
+__device__ __forceinline__ uint64_t lineBlockStart(const IsoLineArgs &a, uint32_t which, uint32_t block)
+{
+  return a.chunkBase[size_t(which) * a.numChunks + block / kIsoChunk] + a.blockBase[size_t(which) * a.numBlocks + block];
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isolineEmitVerticesKernel(const IsoLineArgs a)
+{
+  if (a.blockCount[blockIdx.x] == 0) return;          // the same for the whole block
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  const uint32_t mask = a.mask[L];
+  if (!mask) return;
+  const uint32_t i = L % a.nu, j = L / a.nu;
+  const float *v = a.values + L;
+  const float vp = v[0];
+  const float px = linePosition(a, i, j, 0), py = linePosition(a, i, j, 1), pz = linePosition(a, i, j, 2);
+  const float pu = float(i) + 0.5f, pv = float(j) + 0.5f;
+  const uint64_t first = lineBlockStart(a, 0, blockIdx.x) + a.rel[L];
+  float *out = a.vertices + 3 * first, *outUv = a.uv + 2 * first;
+#pragma unroll
+  for (int code = 1; code < 4; code++)
+    if (mask & (1u << (code - 1))) {
+      const uint32_t dx = uint32_t(code & 1), dy = uint32_t(code >> 1);
+      const float vq = v[lineCornerOffset(a, code)];
+      const float t = (a.iso - vp) / (vq - vp);
+      const float qx = linePosition(a, i + dx, j + dy, 0), qy = linePosition(a, i + dx, j + dy, 1), qz = linePosition(a, i + dx, j + dy, 2);
+      out[0] = px + t * (qx - px);
+      out[1] = py + t * (qy - py);
+      out[2] = pz + t * (qz - pz);
+      outUv[0] = pu + t * float(dx);
+      outUv[1] = pv + t * float(dy);
+      out += 3;
+      outUv += 2;
+    }
+}
+
+// vb[m], mk[m]: index of the first vertex and edge mask of the lattice point origin + m (m = 0, 1, 2: the owners of a
+// square's five triangle edges)
+template <int TRI>
+__device__ __forceinline__ void emitTri(uint32_t inside, const uint32_t (&vb)[3], const uint32_t (&mk)[3], int32_t *&out)
+{
+  const uint32_t pat = triPattern<TRI>(inside);
+  if (pat == 0u || pat == 7u) return;
+  int32_t e[3];                               // the vertices on the edges 01, 02, 12 of the triangle
+#pragma unroll
+  for (int n = 0; n < 3; n++) {
+    const int owner = kTriCorner[TRI][n == 2 ? 1 : 0];
+    const int code = kTriCorner[TRI][n == 0 ? 1 : 2] ^ owner;
+    e[n] = int32_t(vb[owner] + __popc(mk[owner] & ((1u << (code - 1)) - 1u)));
+  }
+  // s: the vertex alone on its side; the segment (s-o0, s-o1), o0 < o1, reversed iff parity(s,o0,o1) = s & 1 XOR the
+  // triangle's parity XOR (s is outside)
+  const uint32_t outside = __popc(pat) == 2u ? 1u : 0u;
+  const uint32_t single = outside ? (~pat & 7u) : pat;
+  const uint32_t s = single >> 1;             // 1, 2, 4 -> 0, 1, 2
+  const int32_t first = s == 2u ? e[1] : e[0], second = s == 0u ? e[1] : e[2];
+  const bool rev = (((s & 1u) ^ uint32_t(TRI) ^ outside) & 1u) != 0u;
+  out[0] = rev ? second : first;
+  out[1] = rev ? first : second;
+  out += 2;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isolineEmitSegmentsKernel(const IsoLineArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  if (a.blockCount[a.numBlocks + blockIdx.x] == 0) return;      // the same for the whole block
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  const uint32_t count = L < a.numPoints ? (a.squareInfo[L] & 0x7fu) : 0u;
+  uint32_t total;
+  const uint32_t before = blockScan(count, total, lds);
+  if (!count) return;
+  const float *v = a.values + L;
+  uint32_t inside = 0;
+#pragma unroll
+  for (int m = 0; m < 4; m++) inside |= (v[lineCornerOffset(a, m)] >= a.iso ? 1u : 0u) << m;
+  uint32_t vb[3], mk[3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    const uint32_t Lp = L + uint32_t(lineCornerOffset(a, m));
+    vb[m] = a.vertexBase + uint32_t(lineBlockStart(a, 0, Lp / kIsoBlock)) + a.rel[Lp];     // the vertex count fits 31 bits (checked before the emit)
+    mk[m] = a.mask[Lp];
+  }
+  int32_t *out = a.segments + 2 * (lineBlockStart(a, 1, blockIdx.x) + before);
+  emitTri<0>(inside, vb, mk, out);
+  emitTri<1>(inside, vb, mk, out);
+}
+
 } // namespace
+
+hipError_t launchIsolinePositions(const IsoLineArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isolinePositionsKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsolineSquarePass(const IsoLineArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isolineSquareKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsolinePointPass(const IsoLineArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isolinePointKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the iso-surface's scans over the block counts of the two passes: they read nothing of their arguments but these
+hipError_t launchIsolineScans(const IsoLineArgs &a, hipStream_t s)
+{
+  IsoMeshArgs m = {};
+  m.numBlocks = a.numBlocks; m.numChunks = a.numChunks;
+  m.blockCount = a.blockCount; m.blockBase = a.blockBase; m.chunkBase = a.chunkBase; m.totals = a.totals;
+  return launchIsoScans(m, s);
+}
+
+hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isolineEmitVerticesKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isolineEmitSegmentsKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launchIsoCubePass(const IsoMeshArgs &a, hipStream_t s)
 {

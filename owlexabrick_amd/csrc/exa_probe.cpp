@@ -2,7 +2,8 @@
 // exa_hip_resample; kernels in exa_sample_kernels.h), the quantities derived from three channels' velocity gradient tensor
 // (exa_hip_sample_derived, exa_hip_resample_derived), the projections along rays (exa_hip_project) and the iso-crossings along
 // the same rays (exa_hip_raycast_iso) in the same file, the field on the triangles of a mesh (exa_hip_sample_triangles), and
-// the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip).
+// the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip) with the
+// contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -740,6 +741,255 @@ int exa_hip_isosurface_stage_ms(ExaHipRenderer *h, float ms[6])
   if (!h || !ms) return 1;
   const ExaHipRenderer *r = firstChild(h);
   for (int k = 0; k < 6; k++) ms[k] = r->isoMesh.stageMs[k];
+  return 0;
+}
+
+// ---- contour lines on a plane lattice (exa_isomesh.hip) ----
+// exa_hip_isolines (quantity < 0: the lattice holds the one channel channels[0]) and exa_hip_isolines_derived (it holds the
+// quantity of channels[0..2]; no gradients: the caller has refused the flag).  The levels share the lattice values and the
+// work space of one level: a first round counts every level (square pass, point pass, scans), the packed arrays are
+// allocated for the sum, and a second round repeats the passes level by level and emits at the level's offsets — from the
+// last level to the first, so that the last one, whose passes the work space still holds, is not repeated.  The flags, the
+// channels and the quantity are checked by the caller.
+static int isolinesExtract(ExaHipRenderer *h, const char *fn, const ExaHipPlane *plane, const int32_t *channels, int32_t quantity,
+                           const float *isos, int32_t numIsos, int32_t flags, uint64_t *numVertices, uint64_t *numSegments,
+                           void *hipStream)
+{
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isolines.release();
+  DropUnlessCommitted<ExaHipRenderer::Isolines> lines(r->isolines);     // whatever fails from here on leaves no result
+  ExaHipRenderer::Isolines &res = r->isolines;
+  for (float &ms : res.stageMs) ms = 0.f;
+  if (!plane || !isos) { h->fail(std::string(fn) + ": null argument (the plane or the levels)"); return 1; }
+  for (int k = 0; k < 3; k++)
+    if (!(std::isfinite(plane->origin[k]) && std::isfinite(plane->du[k]) && std::isfinite(plane->dv[k]))) {
+      h->fail(std::string(fn) + ": the plane's origin, du and dv must be finite");
+      return 1;
+    }
+  if (plane->nu < 2 || plane->nv < 2) { h->fail(std::string(fn) + ": nu and nv must be >= 2 (a lattice of squares)"); return 1; }
+  const uint64_t n = uint64_t(plane->nu) * uint64_t(plane->nv);
+  if (n > uint64_t(INT32_MAX)) { h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points"); return 1; }
+  if (numIsos < 1 || numIsos > EXA_ISOLINES_MAX_LEVELS) { h->fail(std::string(fn) + ": 1..256 levels required (EXA_ISOLINES_MAX_LEVELS)"); return 1; }
+  for (int32_t l = 0; l < numIsos; l++)
+    if (!std::isfinite(isos[l])) { h->fail(std::string(fn) + ": every level must be finite"); return 1; }
+  hipStream_t s = (hipStream_t)hipStream;
+  const bool world = (flags & EXA_SAMPLE_WORLD_SPACE) != 0, grad = (flags & EXA_SAMPLE_GRADIENT) != 0;
+  const int32_t wf = world ? EXA_SAMPLE_WORLD_SPACE : 0;
+
+  IsoLineArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nu = uint32_t(plane->nu); a.nv = uint32_t(plane->nv);
+  for (int k = 0; k < 3; k++) { a.origin[k] = plane->origin[k]; a.du[k] = plane->du[k]; a.dv[k] = plane->dv[k]; }
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+
+  TimingEvents<5> t;
+  HIP_TRY(h, t.create());
+  float ms = 0.f;
+  // the values: the positions into a device buffer, then exa_hip_sample_points, or exa_hip_sample_derived, with a NaN fill
+  // on it (their checks of the kd tree and the frame state apply; synchronous, with the loop guard's check).  The positions
+  // are freed before the work space is allocated.
+  hipError_t e = res.values.alloc(n);
+  {
+    DevBuf<float> positions;
+    if (e == hipSuccess) e = positions.alloc(3 * size_t(n));
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and its positions (12 more)", e);
+    a.positions = positions.p;
+    HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    HIP_TRY(h, launchIsolinePositions(a, s));
+    if (int rc = quantity < 0 ? exa_hip_sample_points(h, positions.p, n, channels, 1, wf, NAN, res.values.p, nullptr, nullptr, 1, hipStream, 0)
+                              : exa_hip_sample_derived(h, positions.p, n, channels, quantity, wf, NAN, res.values.p, nullptr, 1, hipStream, 0)) {
+      h->fail(std::string(fn) + ": " + h->err);
+      return rc;
+    }
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, t.elapsed(0, 1, &res.stageMs[0]));
+    a.positions = nullptr;
+  }
+  a.values = res.values.p;
+  // the work space of one level, freed when the call returns: chunkBase, totals | blockCount, blockBase | rel | squareInfo,
+  // mask (every part aligned to its element)
+  DevBuf<char> work;
+  const size_t n64 = 2 * size_t(a.numChunks) + 2, n32 = 4 * size_t(a.numBlocks);
+  const size_t n16 = n + (n & 1), workBytes = n64 * 8 + n32 * 4 + n16 * 2 + 2 * n;
+  e = work.alloc(workBytes);
+  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the work space (4 bytes per lattice point)", e);
+  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
+  a.totals = a.chunkBase + 2 * size_t(a.numChunks);
+  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  a.blockBase = a.blockCount + 2 * size_t(a.numBlocks);
+  a.rel = reinterpret_cast<uint16_t *>(work.p + n64 * 8 + n32 * 4);
+  a.squareInfo = reinterpret_cast<uint8_t *>(work.p + n64 * 8 + n32 * 4 + n16 * 2);
+  a.mask = a.squareInfo + n;
+
+  // square pass, point pass and scans of the level a.iso, timed into stages 1..3; the level's totals {vertices, segments}
+  auto countLevel = [&](uint64_t totals[2]) -> int {
+    HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    HIP_TRY(h, launchIsolineSquarePass(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    HIP_TRY(h, launchIsolinePointPass(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[2], s));
+    HIP_TRY(h, launchIsolineScans(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[3], s));
+    HIP_TRY(h, hipMemcpyAsync(totals, a.totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 3; k++) { HIP_TRY(h, t.elapsed(k, k + 1, &ms)); res.stageMs[1 + k] += ms; }
+    return 0;
+  };
+  res.vertexOffsets.assign(size_t(numIsos) + 1, 0);
+  res.segmentOffsets.assign(size_t(numIsos) + 1, 0);
+  for (int32_t l = 0; l < numIsos; l++) {
+    uint64_t totals[2] = { 0, 0 };
+    a.iso = isos[l];
+    if (countLevel(totals)) return 1;
+    res.vertexOffsets[l + 1] = res.vertexOffsets[l] + totals[0];
+    res.segmentOffsets[l + 1] = res.segmentOffsets[l] + totals[1];
+    if (res.vertexOffsets[l + 1] > uint64_t(INT32_MAX) || res.segmentOffsets[l + 1] > uint64_t(INT32_MAX)) {
+      h->fail(std::string(fn) + ": more than INT32_MAX vertices or segments at level " + std::to_string(l) +
+              ", the indices are int32 (extract the levels in parts)");
+      return 1;
+    }
+  }
+  const uint64_t nv = res.vertexOffsets[numIsos], ns = res.segmentOffsets[numIsos];
+  if (nv && ns) {
+    e = res.vertices.alloc(3 * size_t(nv));
+    if (e == hipSuccess) e = res.uv.alloc(2 * size_t(nv));
+    if (e == hipSuccess) e = res.segments.alloc(2 * size_t(ns));
+    if (e == hipSuccess && grad) e = res.gradients.alloc(3 * size_t(nv));
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lines", e);
+    for (int32_t l = numIsos - 1; l >= 0; l--) {
+      if (res.vertexOffsets[l + 1] == res.vertexOffsets[l]) continue;          // no vertices: no segments either
+      a.iso = isos[l];
+      uint64_t totals[2] = { 0, 0 };
+      if (l != numIsos - 1 && countLevel(totals)) return 1;
+      a.vertexBase = uint32_t(res.vertexOffsets[l]);
+      a.vertices = res.vertices.p + 3 * size_t(res.vertexOffsets[l]);
+      a.uv = res.uv.p + 2 * size_t(res.vertexOffsets[l]);
+      a.segments = res.segments.p + 2 * size_t(res.segmentOffsets[l]);
+      HIP_TRY(h, hipEventRecord(t.ev[3], s));
+      HIP_TRY(h, launchIsolineEmit(a, s));
+      HIP_TRY(h, hipEventRecord(t.ev[4], s));
+      HIP_TRY(h, hipStreamSynchronize(s));
+      HIP_TRY(h, t.elapsed(3, 4, &ms));
+      res.stageMs[4] += ms;
+    }
+  }
+  if (grad && nv) {
+    // the existing points kernel on the device vertex buffer; its values go into the lattice buffer where that is done
+    // with and large enough (a lattice point owns up to three vertices per level)
+    DevBuf<float> scratch;
+    float *vals = res.values.p;
+    if (nv > n || (flags & EXA_ISOLINES_KEEP_VALUES)) {
+      e = scratch.alloc(size_t(nv));
+      if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the gradients", e);
+      vals = scratch.p;
+    }
+    HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    const int32_t pf = wf | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
+    if (int rc = exa_hip_sample_points(h, res.vertices.p, nv, channels, 1, pf, NAN, vals, res.gradients.p, nullptr, 1, hipStream, 0)) {
+      h->fail(std::string(fn) + ": " + h->err);
+      return rc;
+    }
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, t.elapsed(0, 1, &res.stageMs[5]));
+  }
+  res.keptValues = (flags & EXA_ISOLINES_KEEP_VALUES) != 0;
+  if (!res.keptValues) res.values.release();
+  res.withGradients = grad;
+  res.have = true;
+  lines.commit();
+  if (numVertices) *numVertices = nv;
+  if (numSegments) *numSegments = ns;
+  return 0;
+}
+
+int exa_hip_isolines(ExaHipRenderer *h, const ExaHipPlane *plane, int32_t channel, const float *isos, int32_t numIsos, int32_t flags,
+                     uint64_t *numVertices, uint64_t *numSegments, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isolines";
+  if (numVertices) *numVertices = 0;
+  if (numSegments) *numSegments = 0;
+  int rc = 1;
+  if (checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_SAMPLE_GRADIENT | EXA_ISOLINES_KEEP_VALUES,
+                 " (EXA_SAMPLE_WORLD_SPACE, EXA_SAMPLE_GRADIENT and EXA_ISOLINES_KEEP_VALUES apply)") &&
+      checkChannel(h, fn, channel))
+    rc = isolinesExtract(h, fn, plane, &channel, -1, isos, numIsos, flags, numVertices, numSegments, hipStream);
+  if (rc) (void)exa_hip_isolines_release(h);            // a failed extraction leaves no result, whichever check refused it
+  return rc;
+}
+
+int exa_hip_isolines_derived(ExaHipRenderer *h, const ExaHipPlane *plane, const int32_t channels[3], int32_t quantity,
+                             const float *isos, int32_t numIsos, int32_t flags, uint64_t *numVertices, uint64_t *numSegments,
+                             void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isolines_derived";
+  if (numVertices) *numVertices = 0;
+  if (numSegments) *numSegments = 0;
+  int rc = 1;
+  if (flags & EXA_SAMPLE_GRADIENT)
+    h->fail(std::string(fn) + ": EXA_SAMPLE_GRADIENT does not apply (a gradient of a derived quantity would need second derivatives)");
+  else if (checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_ISOLINES_KEEP_VALUES,
+                      " (EXA_SAMPLE_WORLD_SPACE and EXA_ISOLINES_KEEP_VALUES apply)")) {
+    const int comps = derivedComponents(h, fn, channels, quantity);
+    if (comps > 1) h->fail(std::string(fn) + ": contour lines need a one-component quantity (EXA_DERIVED_VORTICITY has three)");
+    else if (comps == 1)
+      rc = isolinesExtract(h, fn, plane, channels, quantity, isos, numIsos, flags, numVertices, numSegments, hipStream);
+  }
+  if (rc) (void)exa_hip_isolines_release(h);
+  return rc;
+}
+
+int exa_hip_isolines_read(ExaHipRenderer *h, float *vertices, float *uv, float *gradients, int32_t *segments, uint64_t *vertexOffsets,
+                          uint64_t *segmentOffsets, float *values, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_isolines_read";
+  ExaHipRenderer *r = firstChild(h);
+  const ExaHipRenderer::Isolines &res = r->isolines;
+  if (!res.have) { h->fail(std::string(fn) + ": no lines (exa_hip_isolines comes first; a release or a failed extraction drops them)"); return 1; }
+  if (gradients && !res.withGradients) { h->fail(std::string(fn) + ": the lines were extracted without EXA_SAMPLE_GRADIENT"); return 1; }
+  if (values && !res.keptValues) { h->fail(std::string(fn) + ": the lines were extracted without EXA_ISOLINES_KEEP_VALUES"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (vertices && res.vertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, res.vertices.p, res.vertices.n * sizeof(float), kind, s));
+  if (uv && res.uv.n) HIP_TRY(h, hipMemcpyAsync(uv, res.uv.p, res.uv.n * sizeof(float), kind, s));
+  if (gradients && res.gradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, res.gradients.p, res.gradients.n * sizeof(float), kind, s));
+  if (segments && res.segments.n) HIP_TRY(h, hipMemcpyAsync(segments, res.segments.p, res.segments.n * sizeof(int32_t), kind, s));
+  if (values && res.values.n) HIP_TRY(h, hipMemcpyAsync(values, res.values.p, res.values.n * sizeof(float), kind, s));
+  // the offsets live on the host
+  const size_t offBytes = res.vertexOffsets.size() * sizeof(uint64_t);
+  if (pointersAreDevice) {
+    if (vertexOffsets) HIP_TRY(h, hipMemcpyAsync(vertexOffsets, res.vertexOffsets.data(), offBytes, hipMemcpyHostToDevice, s));
+    if (segmentOffsets) HIP_TRY(h, hipMemcpyAsync(segmentOffsets, res.segmentOffsets.data(), offBytes, hipMemcpyHostToDevice, s));
+  } else {
+    if (vertexOffsets) std::memcpy(vertexOffsets, res.vertexOffsets.data(), offBytes);
+    if (segmentOffsets) std::memcpy(segmentOffsets, res.segmentOffsets.data(), offBytes);
+  }
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+int exa_hip_isolines_release(ExaHipRenderer *h)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isolines.release();
+  return 0;
+}
+
+int exa_hip_isolines_stage_ms(ExaHipRenderer *h, float ms[6])
+{
+  if (!h || !ms) return 1;
+  const ExaHipRenderer *r = firstChild(h);
+  for (int k = 0; k < 6; k++) ms[k] = r->isolines.stageMs[k];
   return 0;
 }
 

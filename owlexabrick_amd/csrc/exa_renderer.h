@@ -3,7 +3,7 @@
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes, the projections along rays and the
 // iso-surface extraction, exa_streamlines.cpp the streamline extraction, exa_stats.cpp the histogram and value range of
 // the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
-// one struct per call (ExaHipRenderer::probes, isoMesh, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
+// one struct per call (ExaHipRenderer::probes, isoMesh, isolines, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
 // argument checks below the renderer are what their host code shares.
 #pragma once
 #include "exa_device.h"
@@ -295,6 +295,23 @@ struct ExaHipRenderer {
     float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
     void release() { vertices.release(); gradients.release(); triangles.release(); have = false; }
   } isoMesh;
+  // the contour lines of the last exa_hip_isolines (in the renderer of devices[0] as well), independent of the mesh: the
+  // packed vertices with their plane coordinates, the segments, where each level's begin (numIsos + 1 entries each), the
+  // lattice values where EXA_ISOLINES_KEEP_VALUES kept them, and the time of the stages summed over the levels (positions
+  // and values, square pass, point pass, scans, emit, gradients)
+  struct Isolines {
+    DevBuf<float> vertices, uv, gradients, values;
+    DevBuf<int32_t> segments;
+    std::vector<uint64_t> vertexOffsets, segmentOffsets;
+    bool have = false, withGradients = false, keptValues = false;
+    float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
+    void release()
+    {
+      vertices.release(); uv.release(); gradients.release(); values.release(); segments.release();
+      vertexOffsets.clear(); segmentOffsets.clear();
+      have = withGradients = keptValues = false;
+    }
+  } isolines;
   // exa_hip_histogram (on a multi-device handle: in the renderer of devices[0]): the work list of the pass — segments
   // {brick, first cell} by level and the offsets of the runs, built by the first call (exa_stats.cpp) —, whether the scene's
   // volume-weighted cell count fits 64 bits, the device copy of a call's result and the device time of its kernel

@@ -28,6 +28,18 @@
 //                                            vorticity_magnitude, q or helicity, or its number 0..5.  vorticity has three
 //                                            components, written interleaved by --resample and refused by --isomesh.  With it
 //                                            --resample-channel / --isomesh-channel are an error
+//             [--isolines CHANNEL ox oy oz ux uy uz vx vy vz NU NV ISO[,ISO...] out.isolines] the contour lines field == ISO of
+//                                            CHANNEL, for every ISO of the list, on the plane lattice of NU x NV points whose
+//                                            point (i,j) lies at o + (i + .5) u + (j + .5) v in voxel space (exa_hip_isolines:
+//                                            marching triangles, indexed, the >= ISO side to the left of every segment).  With
+//                                            --derived the lines of that quantity (exa_hip_isolines_derived; CHANNEL is read and
+//                                            ignored, vorticity refused).  One text line `isolines NU NV levels N vertices V
+//                                            segments S`, then raw little-endian arrays: the levels (N float32), vertexOffsets
+//                                            and segmentOffsets (N + 1 uint64 each: level l owns the vertices / segments from
+//                                            offset l up to offset l + 1), vertices (V x 3 float32, in the plane's space), uv
+//                                            (V x 2 float32, lattice coordinates), segments (S x 2 int32, indices into the
+//                                            vertices); --frames 0 renders nothing; with
+//             [--isolines-world]             the plane is in world space
 //             [--histogram BINS file.txt]   the exact histogram of a channel's cell values (exa_hip_histogram), one line
 //                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
 //             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
@@ -167,6 +179,12 @@ int main(int argc, char **argv)
     int derived = -1;                                            // --derived: EXA_DERIVED_*
     vec3i derivedChannels(0, 1, 2);
     bool haveResampleChannel = false, haveIsoChannel = false;
+    std::string linesName;
+    int linesChannel = 0;
+    vec3f linesOrigin, linesDu, linesDv;
+    vec2i linesSize;
+    std::vector<float> linesIsos;
+    bool linesWorld = false;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -224,6 +242,21 @@ int main(int argc, char **argv)
       else if (a == "--isomesh-box") { isoBox.lower = { f(), f(), f() }; isoBox.upper = { f(), f(), f() }; haveIsoBox = true; }
       else if (a == "--isomesh-world") isoWorld = true;
       else if (a == "--isomesh-channel") { isoChannel = (int)f(); haveIsoChannel = true; }
+      else if (a == "--isolines") {
+        linesChannel = (int)f();
+        linesOrigin = { f(), f(), f() }; linesDu = { f(), f(), f() }; linesDv = { f(), f(), f() };
+        linesSize.x = (int)f(); linesSize.y = (int)f();
+        if (i + 2 >= argc) throw std::runtime_error("missing levels and file after --isolines CHANNEL o u v NU NV");
+        for (const char *p = argv[++i]; *p;) {
+          char *end = nullptr;
+          const float v = std::strtof(p, &end);
+          if (end == p || (*end != ',' && *end != 0)) throw std::runtime_error("--isolines wants a comma-separated list of levels");
+          linesIsos.push_back(v);
+          p = *end == ',' ? end + 1 : end;
+        }
+        linesName = argv[++i];
+      }
+      else if (a == "--isolines-world") linesWorld = true;
       else if (a == "--derived") {
         if (i + 1 >= argc) throw std::runtime_error("missing quantity after --derived");
         derived = derivedQuantity(argv[++i]);
@@ -402,6 +435,22 @@ int main(int argc, char **argv)
       else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
       std::printf("iso %.9g vertices %zu triangles %zu\n", isoValue, mesh->vertex.size(), mesh->index.size());
     }
+    if (!linesName.empty()) {
+      const Renderer::Isolines L = derived < 0 ? renderer.isolines(linesOrigin, linesDu, linesDv, linesSize, linesIsos, linesChannel, linesWorld)
+                                               : renderer.isolinesDerived(linesOrigin, linesDu, linesDv, linesSize, linesIsos, derivedChannels, derived, linesWorld);
+      FILE *f = std::fopen(linesName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + linesName);
+      const size_t n = linesIsos.size(), nv = L.vertex.size(), ns = L.segment.size() / 2;
+      std::fprintf(f, "isolines %d %d levels %zu vertices %zu segments %zu\n", linesSize.x, linesSize.y, n, nv, ns);
+      const bool ok = std::fwrite(linesIsos.data(), 4, n, f) == n && std::fwrite(L.vertexOffsets.data(), 8, n + 1, f) == n + 1
+                   && std::fwrite(L.segmentOffsets.data(), 8, n + 1, f) == n + 1 && std::fwrite(L.vertex.data(), 12, nv, f) == nv
+                   && std::fwrite(L.uv.data(), 8, nv, f) == nv && std::fwrite(L.segment.data(), 8, ns, f) == ns;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + linesName);
+      std::printf("isolines %d %d ", linesSize.x, linesSize.y);
+      if (derived < 0) std::printf("channel %d ", linesChannel);
+      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
+      std::printf("world %d levels %zu vertices %zu segments %zu\n", linesWorld ? 1 : 0, n, nv, ns);
+    }
     if (!surfaceName.empty()) {
       const bool fromIso = surfaceMesh == "iso";
       if (fromIso && isoName.empty()) throw std::runtime_error("--surface iso needs --isomesh in the same invocation");
@@ -518,7 +567,7 @@ int main(int argc, char **argv)
                   raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
-                        || !raycastName.empty() || !surfaceName.empty())) return 0;
+                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

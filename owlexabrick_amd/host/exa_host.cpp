@@ -616,6 +616,52 @@ TriangleMesh::SP Renderer::extractIsoSurfaceDerived(const box3f &box, vec3i dims
   return readIsoMesh(handle, nv, nt, nullptr, keep);
 }
 
+// the lines of the last extraction (exa_hip_isolines or exa_hip_isolines_derived) out of the module, which then drops them
+static Renderer::Isolines readIsolines(ExaHipRenderer *handle, uint64_t nv, uint64_t ns, size_t levels, bool gradients, size_t values)
+{
+  Renderer::Isolines L;
+  L.vertex.resize(nv);
+  L.uv.resize(2 * nv);
+  L.segment.resize(2 * ns);
+  L.vertexOffsets.resize(levels + 1);
+  L.segmentOffsets.resize(levels + 1);
+  if (gradients) L.gradient.resize(nv);
+  L.values.resize(values);
+  check(exa_hip_isolines_read(handle, reinterpret_cast<float *>(L.vertex.data()), L.uv.data(),
+                              gradients ? reinterpret_cast<float *>(L.gradient.data()) : nullptr, L.segment.data(),
+                              L.vertexOffsets.data(), L.segmentOffsets.data(), values ? L.values.data() : nullptr, 0, nullptr), handle);
+  check(exa_hip_isolines_release(handle), handle);
+  return L;
+}
+
+static ExaHipPlane planeOf(vec3f origin, vec3f du, vec3f dv, vec2i size)
+{
+  return ExaHipPlane{ { origin.x, origin.y, origin.z }, { du.x, du.y, du.z }, { dv.x, dv.y, dv.z }, size.x, size.y };
+}
+
+Renderer::Isolines Renderer::isolines(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos, int channel,
+                                      bool worldSpace, bool gradients, bool values)
+{
+  if (worldSpace) pushState();
+  const ExaHipPlane plane = planeOf(origin, du, dv, size);
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0) | (values ? EXA_ISOLINES_KEEP_VALUES : 0);
+  uint64_t nv = 0, ns = 0;
+  check(exa_hip_isolines(handle, &plane, channel, isos.data(), (int32_t)isos.size(), flags, &nv, &ns, nullptr), handle);
+  return readIsolines(handle, nv, ns, isos.size(), gradients, values ? size_t(size.x) * size_t(size.y) : 0);
+}
+
+Renderer::Isolines Renderer::isolinesDerived(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos,
+                                             vec3i channels, int quantity, bool worldSpace, bool values)
+{
+  if (worldSpace) pushState();
+  const ExaHipPlane plane = planeOf(origin, du, dv, size);
+  const int32_t ch[3] = { channels.x, channels.y, channels.z };
+  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (values ? EXA_ISOLINES_KEEP_VALUES : 0);
+  uint64_t nv = 0, ns = 0;
+  check(exa_hip_isolines_derived(handle, &plane, ch, quantity, isos.data(), (int32_t)isos.size(), flags, &nv, &ns, nullptr), handle);
+  return readIsolines(handle, nv, ns, isos.size(), false, values ? size_t(size.x) * size_t(size.y) : 0);
+}
+
 void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
                                 std::vector<uint64_t> *volume, ExaHipFieldStats *stats, const box3i *box)
 {

@@ -222,6 +222,25 @@ struct Renderer {
   TriangleMesh::SP extractIsoSurfaceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso,
                                             bool worldSpace = false, bool keep = false);
 
+  // the contour lines field == iso of `channel`, for every iso of `isos`, on the plane lattice of size.x x size.y points
+  // whose point (i,j) lies at origin + (i + 0.5) du + (j + 0.5) dv, by marching triangles (exa_hip_isolines; include/exa_hip.h
+  // states the contract): packed vertices without duplicates in the plane's space with their plane coordinates uv, segments
+  // of global vertex indices with the >= iso side to their left, level l in [vertexOffsets[l], vertexOffsets[l+1]) and
+  // [segmentOffsets[l], segmentOffsets[l+1]).  gradients: per vertex what samplePoints gives there with normalized = true;
+  // values: the lattice values, values[j*size.x + i] (the slice under the lines).  isolinesDerived: the same of a
+  // one-component quantity of the vector field `channels` (no gradients).
+  struct Isolines {
+    std::vector<vec3f> vertex, gradient;
+    std::vector<float> uv;                       // 2 per vertex
+    std::vector<int32_t> segment;                // 2 per segment
+    std::vector<uint64_t> vertexOffsets, segmentOffsets;
+    std::vector<float> values;
+  };
+  Isolines isolines(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos, int channel,
+                    bool worldSpace = false, bool gradients = false, bool values = false);
+  Isolines isolinesDerived(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos, vec3i channels,
+                           int quantity, bool worldSpace = false, bool values = false);
+
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
   // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
