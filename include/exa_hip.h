@@ -564,6 +564,85 @@ int exa_hip_isolines_read(ExaHipRenderer *, float *vertices /* V x 3 */, float *
 int exa_hip_isolines_release(ExaHipRenderer *);
 int exa_hip_isolines_stage_ms(ExaHipRenderer *, float ms[6]);
 
+/* ---- connected regions: the connected components of the set field >= iso (or < iso) on the lattice the other extractions
+ * use, numbered, with exact measurements per region — how many blobs (vortices of Q > threshold, clumps, voids) there are,
+ * how large each is, where it lies, where its extreme values sit and what the field sums to over it.  New relative to the
+ * reference.  Every output is an integer or a float bit pattern that depends on no schedule: two runs give the same bytes. ----
+ *
+ * Lattice and values.  lo, hi, dims and EXA_SAMPLE_WORLD_SPACE as for exa_hip_resample; dims >= 1 per axis (no cubes are
+ * needed: a line or a plane of points is a lattice), nx*ny*nz <= 2^31 - 1.  Linear index L = (k*ny + j)*nx + i.  V(L) is
+ * exactly what exa_hip_resample(lo, hi, dims, channel, the same flag, fill = NaN) returns in the handle's current basis_form,
+ * for exa_hip_regions_derived what exa_hip_resample_derived(channels, quantity, ...) returns (one-component quantities only).
+ *
+ * Inside.  inside(L) = V(L) is finite and V(L) >= iso; with EXA_REGIONS_BELOW: finite and V(L) < iso.  NaN, +-Inf and
+ * filled points are never inside.  iso must be finite.
+ *
+ * Edges.  Two inside points p and q are joined if q = p + d, d in {0,1}^3 \ {0}: the seven kinds of tetrahedron edge of the
+ * Kuhn split exa_hip_isosurface uses (three axis edges, three face diagonals, the cube diagonal), a neighbourhood of 14
+ * points, +-d.  With EXA_REGIONS_FACES only d in {e_x, e_y, e_z}, the 6 neighbours.  Kuhn is the default because it is the
+ * connectivity of the surface: where all cubes are valid, the regions are exactly the connected pieces of
+ * {interpolant >= iso} of the piecewise-linear interpolant whose level set exa_hip_isosurface emits (on a tetrahedron a
+ * linear function is >= iso on a convex set that holds the tetrahedron's inside vertices, so pieces meet exactly along
+ * tetrahedron edges with two inside ends) — regions and shells agree.  An edge needs no valid cube here, only two inside ends.
+ *
+ * Regions and labels.  A region is a connected component of that graph.  `first` is its smallest L; regions are numbered
+ * 0, 1, ... by ascending `first`.  labels[L] = the number of L's region, -1 outside.
+ *
+ * Sum.  M = max |V| over the inside points of the call.  sumExponent s = 0 if there is no inside point or M == 0, else
+ * s = 30 - e with M = f * 2^e, f in [0.5, 1) (frexpf).  q(v) = (double)v * 2^s rounded to the nearest integer, ties to even
+ * (the scaling is exact in double; |q| <= 2^30).  sumFixed = the sum of q over the region in 64-bit integers, which cannot
+ * overflow below 2^31 points.  The region's value sum is sumFixed * 2^-s, its integral that times the volume of a lattice
+ * cell.  Per point the quantisation is at most 2^-(s+1) < 2^-31 M.  Fixed point because integer adds commute: the sum is
+ * exact and the same in every reduction order, which no float atomic gives.
+ *
+ * min, max, argMin, argMax.  By the total order of exa_hip_histogram's value range (the ordered 32-bit key of the float
+ * bits: -0.0 < +0.0); argMin / argMax = the smallest L among the region's points that hold min / max.
+ * sumIndex = the sums of i, of j and of k: the centroid in lattice indices is sumIndex / points, exactly.  lo, hi: the
+ * inclusive bounding box in lattice indices.
+ *
+ * Independence.  As for the mesh: the result depends only on the scene, the lattice, the channel(s) and the quantity, iso,
+ * the flags, basis_form and (world space) the transform — on nothing a frame sets, nor on walk, accel, brick_order,
+ * interleave, sample_patch or sample_uniform.  A scene without a kd tree is refused.  A multi-device handle runs on
+ * devices[0].
+ *
+ * Calls.  Synchronous on hipStream.  The result lives in module-owned device memory until the next exa_hip_regions[_derived]
+ * (also a failed one), exa_hip_regions_release or exa_hip_destroy; it is independent of the mesh of exa_hip_isosurface and
+ * of the lines of exa_hip_isolines, none of the three calls drops another's result.  Zero regions is not an error.
+ * exa_hip_regions_read: labels numPoints, regions numRegions, values numPoints (only after EXA_REGIONS_KEEP_VALUES; without
+ * the flag a non-NULL `values` is an error); a NULL pointer skips that array; host arrays, or memory of the handle's first
+ * device with pointersAreDevice; an error before any extraction.  Errors carry a message that starts with the function's
+ * name and leave the handle usable: a NULL lo, hi, dims or channels, a non-finite iso or box float, dims < 1, too many
+ * points, a bad channel or quantity, a quantity of more than one component, unknown flag bits, world space before a frame
+ * state, a failed allocation.  A loop guard (the kd descent's, the union-find's) returns 3.
+ * exa_hip_regions_stage_ms: device ms of the last call's stages — values, init (inside test, count, M), merge (the unions),
+ * flatten (every point to its root, roots counted), rank (scans, numbering), stats (labels and measurements).
+ *
+ * Memory.  While the call runs: 4 bytes per lattice point for the values and 4 for the labels, which hold the union-find's
+ * parent links until the numbering replaces them in place (a root's number passes through the root's own slot, no second
+ * array), 8 bytes per block of 256 points for the scans, and 16 bytes per region for the min / max keys.  Afterwards: the
+ * labels, 88 bytes per region, and the values if kept. */
+#define EXA_REGIONS_KEEP_VALUES 16   /* flag: keep the lattice values for exa_hip_regions_read */
+#define EXA_REGIONS_BELOW       32   /* flag: inside(v) = v < iso instead of v >= iso */
+#define EXA_REGIONS_FACES       64   /* flag: join along the three axis edges only (6 neighbours) instead of the Kuhn edges (14) */
+typedef struct ExaHipRegion {
+  uint64_t points;            /* lattice points of the region */
+  int64_t  sumFixed;          /* sum of q(V) over the region, see Sum */
+  uint64_t sumIndex[3];       /* sum of i, of j, of k */
+  int32_t  lo[3], hi[3];      /* inclusive bounding box in lattice indices */
+  uint32_t first;             /* smallest linear index L of the region */
+  uint32_t argMin, argMax;    /* smallest L among the points that hold min / max */
+  float    min, max;
+} ExaHipRegion;               /* 88 bytes */
+int exa_hip_regions(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
+                    float iso, int32_t flags, uint64_t *numRegions, uint64_t *numInside, int32_t *sumExponent, void *hipStream);
+int exa_hip_regions_derived(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                            const int32_t channels[3], int32_t quantity, float iso, int32_t flags,
+                            uint64_t *numRegions, uint64_t *numInside, int32_t *sumExponent, void *hipStream);
+int exa_hip_regions_read(ExaHipRenderer *, int32_t *labels /* numPoints */, ExaHipRegion *regions /* numRegions */,
+                         float *values /* numPoints */, int32_t pointersAreDevice, void *hipStream);
+int exa_hip_regions_release(ExaHipRenderer *);
+int exa_hip_regions_stage_ms(ExaHipRenderer *, float ms[6]);
+
 /* ---- histogram and value range of one channel's cells: the exact histogram of the cell values by cell count and by
  * volume, the value range, the cell counts per level and the NaN / empty / out-of-range counts, optionally inside an integer
  * voxel box.  New relative to the reference, whose viewer left the hook unbuilt (exa/viewer.cpp:1274-1276, setValueRange /

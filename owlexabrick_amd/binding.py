@@ -131,6 +131,15 @@ SURFACE_MAX_CHANNELS = 4
 ISOLINES_KEEP_VALUES = 16
 ISOLINES_MAX_LEVELS = 256
 
+# exa_hip_regions (include/exa_hip.h)
+REGIONS_KEEP_VALUES = 16
+REGIONS_BELOW = 32
+REGIONS_FACES = 64
+# ExaHipRegion (a connected region of exa_hip_regions, not a region of the scene: REGION_DTYPE above): 84 bytes of fields, padded to 88
+LABELLED_REGION_DTYPE = np.dtype(dict(names=["points", "sumFixed", "sumIndex", "lo", "hi", "first", "argMin", "argMax", "min", "max"],
+                             formats=["<u8", "<i8", ("<u8", 3), ("<i4", 3), ("<i4", 3), "<u4", "<u4", "<u4", "<f4", "<f4"],
+                             offsets=[0, 8, 16, 40, 52, 64, 68, 72, 76, 80], itemsize=88))
+
 # exa_hip_raycast_iso (include/exa_hip.h)
 CROSS_MAX_REFINE = 32
 RAYCAST_KEYS = ("t", "position", "value", "gradient", "index", "side", "crossings")
@@ -247,6 +256,11 @@ _ABI = {
     "exa_hip_isolines_read": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_isolines_release": (None, [_vp]),
     "exa_hip_isolines_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_regions": (None, [_vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _P(_u64), _P(_i32), _vp]),
+    "exa_hip_regions_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _P(_u64), _P(_i32), _vp]),
+    "exa_hip_regions_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_regions_release": (None, [_vp]),
+    "exa_hip_regions_stage_ms": (None, [_vp, _vp]),
     "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
     "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),
@@ -793,6 +807,72 @@ class Renderer:
         finally:
             self.releaseIsolines()
 
+    # ---- connected regions of field >= iso on a lattice (exa_hip_regions*; include/exa_hip.h states the contract) ----
+    def extractRegions(self, lo, hi, dims, iso, channel=0, world=False, below=False, faces=False, keep_values=False,
+                       quantity=None, channels=(0, 1, 2), stream=None):
+        """label the connected regions of field >= iso (below: < iso) on the lattice of resample(lo, hi, dims), joined along
+        the Kuhn edges (faces: the axis edges only), into module-owned device memory; with a `quantity` the regions of that
+        derived quantity of `channels`.  Returns (numRegions, numInside, sum_exponent).  readRegions copies the result out,
+        releaseRegions frees it."""
+        flags = (self._probe_world(world) | (REGIONS_BELOW if below else 0) | (REGIONS_FACES if faces else 0)
+                 | (REGIONS_KEEP_VALUES if keep_values else 0))
+        nr, ni, se = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+        self._regions = None
+        if quantity is None:
+            rc = lib().exa_hip_regions(self.h, _f3(lo), _f3(hi), _i3(dims), int(channel), float(iso), flags, C.byref(nr),
+                                       C.byref(ni), C.byref(se), C.c_void_p(stream or 0))
+        else:
+            rc = lib().exa_hip_regions_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), derived_quantity(quantity),
+                                               float(iso), flags, C.byref(nr), C.byref(ni), C.byref(se), C.c_void_p(stream or 0))
+        self._check(rc)
+        self._regions = (int(nr.value), int(ni.value), int(se.value), tuple(int(d) for d in dims[::-1]), bool(keep_values))
+        return self._regions[:3]
+
+    def readRegions(self):
+        """the last extractRegions as a dict: labels int32 [nz, ny, nx] (the region's number, -1 outside), regions (a
+        structured array of LABELLED_REGION_DTYPE, numbered by ascending `first`), sum_exponent, num_inside, and values float32
+        [nz, ny, nx] where the extraction kept them"""
+        if not getattr(self, "_regions", None):
+            self._check(lib().exa_hip_regions_read(self.h, None, None, None, 0, None))      # refused
+            raise RuntimeError("readRegions: no extraction of this renderer to read")
+        nr, ni, se, shape, keep = self._regions
+        out = dict(labels=np.empty(shape, np.int32), regions=np.zeros(nr, LABELLED_REGION_DTYPE), sum_exponent=se, num_inside=ni)
+        if keep:
+            out["values"] = np.empty(shape, np.float32)
+        self._check(lib().exa_hip_regions_read(self.h, out["labels"].ctypes.data, out["regions"].ctypes.data if nr else None,
+                                               out["values"].ctypes.data if keep else None, 0, None))
+        return out
+
+    def releaseRegions(self):
+        self._check(lib().exa_hip_regions_release(self.h))
+        self._regions = None
+
+    def regionsStageMs(self):
+        """device ms of the last extractRegions' stages: values, init, merge, flatten, rank, stats"""
+        ms = (C.c_float * 6)()
+        self._check(lib().exa_hip_regions_stage_ms(self.h, ms))
+        return [float(v) for v in ms]
+
+    def regions(self, lo, hi, dims, iso, channel=0, world=False, below=False, faces=False, keep_values=False):
+        """the connected regions of field >= iso of `channel` on the lattice of resample(lo, hi, dims): the dict of
+        readRegions (region_measures turns its table into sums, means, volumes, integrals and centroids).  The device copy
+        is released before returning."""
+        self.extractRegions(lo, hi, dims, iso, channel=channel, world=world, below=below, faces=faces, keep_values=keep_values)
+        try:
+            return self.readRegions()
+        finally:
+            self.releaseRegions()
+
+    def regionsDerived(self, lo, hi, dims, iso, quantity, channels=(0, 1, 2), world=False, below=False, faces=False,
+                       keep_values=False):
+        """regions of a one-component derived quantity (a key of DERIVED, or its number) of the vector field `channels`"""
+        self.extractRegions(lo, hi, dims, iso, world=world, below=below, faces=faces, keep_values=keep_values,
+                            quantity=quantity, channels=channels)
+        try:
+            return self.readRegions()
+        finally:
+            self.releaseRegions()
+
     def derivedMs(self):
         """device ms of the kernels of the last sampleDerived / resampleDerived call, summed"""
         return self._ms(lib().exa_hip_derived_ms)
@@ -984,6 +1064,20 @@ def _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples):
     if shape[0] * shape[1] > 2 ** 31 - 1:
         shape = (0, 0)
     return rays, shape
+
+
+def region_measures(regions, sum_exponent, lo, hi, dims):
+    """what follows from the table of Renderer.regions over the lattice (lo, hi, dims), per region, in float64: `sum` of the
+    values (sumFixed * 2^-sum_exponent, exact up to the double's 53 bits), `mean`, `volume` (points times the volume of a
+    lattice cell), `integral` (sum times that volume), and `centroid` [n, 3], the mean position of the region's points in the
+    space of lo / hi (lattice point i on an axis lies at lo + (i + 0.5) * (hi - lo) / dims)"""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    step = (hi - lo) / np.asarray(dims, np.float64).reshape(3)
+    points = regions["points"].astype(np.float64)
+    total = np.ldexp(regions["sumFixed"].astype(np.float64), -int(sum_exponent))
+    cell = float(np.prod(step))
+    return dict(sum=total, mean=total / points, volume=points * cell, integral=total * cell,
+                centroid=lo + (regions["sumIndex"].astype(np.float64) / points[:, None] + 0.5) * step)
 
 
 def _f3(v):

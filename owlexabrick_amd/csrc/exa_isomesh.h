@@ -19,6 +19,8 @@
 
 #include <cstdint>
 
+#include "../../include/exa_hip.h"
+
 namespace exa {
 
 static const uint32_t kIsoBlock = 256;      // lattice points per block
@@ -86,5 +88,60 @@ hipError_t launchIsolineSquarePass(const IsoLineArgs &a, hipStream_t s);
 hipError_t launchIsolinePointPass(const IsoLineArgs &a, hipStream_t s);
 hipError_t launchIsolineScans(const IsoLineArgs &a, hipStream_t s);
 hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s);
+
+// ---- connected regions of the set inside(V) on the lattice (exa_hip_regions): a lock-free union-find over the lattice
+// points, one lane per point L = (k*ny + j)*nx + i, blocks of kIsoBlock consecutive L.  `parent` is the labels array of the
+// result: the forest while the call runs, the region numbers when it returns.
+//   init       parent[L] = L if inside, else kIsoRegionOutside; the number of inside points and the largest |V| among them
+//              (as float bits) into totals[1] and totals[2], one pair of atomics per block of kIsoRegionTiles tiles
+//   merge      for every inside L and every forward edge L -> L + d whose other end is inside: find both roots; while they
+//              differ, atomicMin the larger root's parent to the smaller.  A return value that is not the larger root says
+//              that it was no root any more: its link was `old`, which the atomicMin kept (old <= smaller) or replaced — in
+//              both cases `old` and the smaller root are what is left to unite.  Links only ever go from a larger to a
+//              smaller index, so every walk descends strictly and the root of a finished tree is its smallest L, `first`.
+//              No lane waits for another: a lost race is a retry with what the atomic returned.  The loads of the walks are
+//              agent-scope atomic loads (they bypass the L1, which other CUs' atomics never refresh); a stale value would
+//              only be an older ancestor.
+//   flatten    parent[L] = find(L); the block's number of roots (parent[L] == L) into blockCount
+//   scans      the iso-surface's, over that one count (launchIsoRegionScans); totals[0] = number of regions
+//   rank       a root's number = chunkBase + blockBase + its rank among the block's roots; it goes into the root's own slot
+//              as kIsoRegionRanked | number (L < 2^31 leaves the bit free) and starts the region's record
+//   stats      label = the number in the own slot (a root) or in the slot parent[L] names (masking the bit reads a root's
+//              slot rightly before and after that root's lane has stored its label), stored in place; the region's
+//              measurements, gathered by a lane over its kIsoRegionTiles tiles as long as the label stays, then reduced over
+//              the lanes of the wave that share the leading lane's label (twice: a wave mostly holds one or two labels)
+//              before one lane issues the atomics, what is left lane by lane: all waves of one large region add to one
+//              record, and atomics to one address go one after the other
+//   finish     min, max, argMin, argMax of every region out of its two 64-bit keys
+// Every walk is bounded by numPoints steps (it descends strictly, so it cannot take more) and refuses a link that ascends:
+// a bound that trips sets errorFlag, the module's loop guard.
+static const uint32_t kIsoRegionOutside = 0xffffffffu, kIsoRegionRanked = 0x80000000u;
+static const uint32_t kIsoRegionTiles = 16;     // blocks of the lattice per block of the init and the stats pass
+
+struct IsoRegionArgs {
+  const float *values;        // the lattice, numPoints floats
+  uint32_t numPoints;         // nx*ny*nz <= 2^31 - 1
+  uint32_t nx, ny, nz;
+  float iso;
+  int32_t below, faces;       // EXA_REGIONS_BELOW, EXA_REGIONS_FACES
+  uint32_t *parent;           // numPoints: the forest, then the labels
+  uint32_t numBlocks, numChunks;
+  uint32_t *blockCount;       // [numBlocks] roots
+  uint32_t *blockBase;        // [numBlocks]
+  uint64_t *chunkBase;        // [numChunks]
+  uint64_t *totals;           // [3]: regions (the scans), inside points, bits of max |V| (init; zeroed by the host)
+  int32_t *errorFlag;         // the module's loop guard
+  double scale;               // 2^sumExponent
+  uint32_t numRegions;
+  ExaHipRegion *regions;      // numRegions
+  uint64_t *keys;             // [numRegions][2]: (value key << 32) | L, by atomic min; (value key << 32) | ~L, by atomic max
+};
+
+hipError_t launchIsoRegionInit(const IsoRegionArgs &a, hipStream_t s);
+hipError_t launchIsoRegionMerge(const IsoRegionArgs &a, hipStream_t s);
+hipError_t launchIsoRegionFlatten(const IsoRegionArgs &a, hipStream_t s);
+hipError_t launchIsoRegionScans(const IsoRegionArgs &a, hipStream_t s);
+hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s);
+hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s);
 
 } // namespace exa

@@ -501,7 +501,335 @@ __global__ __launch_bounds__(kIsoBlock) void isolineEmitSegmentsKernel(const Iso
   emitTri<1>(inside, vb, mk, out);
 }
 
+// ---- connected regions of the inside set (exa_hip_regions): the union-find and the passes of exa_isomesh.h ----
+__device__ __forceinline__ bool regionInside(const IsoRegionArgs &a, float v)
+{
+  return __builtin_isfinite(v) && (a.below ? v < a.iso : v >= a.iso);
+}
+
+// the total order of exa_hip_histogram's value range on the float bits
+__device__ __forceinline__ uint32_t regionKey(float v)
+{
+  const uint32_t b = __float_as_uint(v);
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float regionValueOfKey(uint32_t key)
+{
+  return __uint_as_float(key ^ ((key >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
+// The root of x's tree as the loads show it.  Links descend strictly, so the walk ends within x steps; a link that ascends
+// (which no kernel here writes: the outside mark included) or more than numPoints steps trip the guard, and the walk stops
+// where it stands.  COHERENT: agent-scope loads for the merge, whose links other workgroups' atomics change meanwhile.
+template <bool COHERENT>
+__device__ __forceinline__ uint32_t regionFind(const IsoRegionArgs &a, uint32_t x, bool &tripped)
+{
+  for (uint32_t left = a.numPoints; left; left--) {
+    const uint32_t p = COHERENT ? __hip_atomic_load(a.parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.parent[x];
+    if (p == x) return x;
+    if (p > x) break;
+    x = p;
+  }
+  tripped = true;
+  return x;
+}
+
+// Unites the trees of x and y, both inside; returns the smaller root.  Every round either links a root (and ends) or goes on
+// with two indices below the larger one of the round before: at most numPoints rounds.
+__device__ __forceinline__ uint32_t regionUnite(const IsoRegionArgs &a, uint32_t x, uint32_t y, bool &tripped)
+{
+  uint32_t ra = regionFind<true>(a, x, tripped), rb = regionFind<true>(a, y, tripped);
+  for (uint32_t left = a.numPoints; ra != rb && !tripped; left--) {
+    const uint32_t hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+    const uint32_t old = atomicMin(a.parent + hi, lo);
+    if (old == hi) return lo;                         // hi was a root, and now hangs below lo
+    if (old > hi || left == 0u) { tripped = true; break; }
+    // hi had been linked to `old` in the meantime; the atomicMin kept that link or replaced it by lo, and in both cases
+    // what is left to unite is old with lo
+    ra = regionFind<true>(a, old, tripped);
+    rb = regionFind<true>(a, lo, tripped);
+  }
+  return ra < rb ? ra : rb;
+}
+
+// A block of the init and of the stats pass covers kIsoRegionTiles consecutive blocks of the lattice, tile after tile (a wave
+// still reads 64 consecutive L at a time): their atomics all go to a few addresses, one region's record or the two counts,
+// and what a lane has gathered over its tiles goes there once.
+__global__ __launch_bounds__(kIsoBlock) void isoRegionInitKernel(const IsoRegionArgs a)
+{
+  __shared__ uint32_t lds[2 * (kIsoBlock / 64)];
+  uint32_t count = 0, mag = 0;                        // mag: bits of |V|, ordered as unsigned integers for finite values
+  for (uint32_t t = 0; t < kIsoRegionTiles; t++) {
+    const uint64_t at = (uint64_t(blockIdx.x) * kIsoRegionTiles + t) * kIsoBlock + threadIdx.x;
+    if (at >= a.numPoints) break;
+    const uint32_t L = uint32_t(at);
+    const float v = a.values[L];
+    const bool in = regionInside(a, v);
+    if (in) {
+      const uint32_t m = __float_as_uint(v) & 0x7fffffffu;
+      mag = m > mag ? m : mag;
+      count++;
+    }
+    a.parent[L] = in ? L : kIsoRegionOutside;
+  }
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t m = uint32_t(__shfl_xor(int(mag), o));
+    mag = m > mag ? m : mag;
+    count += uint32_t(__shfl_xor(int(count), o));
+  }
+  if ((threadIdx.x & 63u) == 0u) { lds[threadIdx.x >> 6] = count; lds[kIsoBlock / 64 + (threadIdx.x >> 6)] = mag; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t sum = 0, top = 0;
+    for (uint32_t w = 0; w < kIsoBlock / 64; w++) {
+      sum += lds[w];
+      top = lds[kIsoBlock / 64 + w] > top ? lds[kIsoBlock / 64 + w] : top;
+    }
+    if (sum) {
+      atomicAdd(reinterpret_cast<unsigned long long *>(a.totals + 1), (unsigned long long)sum);
+      atomicMax(reinterpret_cast<uint32_t *>(a.totals + 2), top);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoRegionMergeKernel(const IsoRegionArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  if (a.parent[L] == kIsoRegionOutside) return;       // the mark is the init kernel's and never changes
+  const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+  bool tripped = false;
+  uint32_t root = L;
+#pragma unroll
+  for (int code = 1; code < 8; code++) {
+    if (a.faces && (code & (code - 1))) continue;
+    if (i + uint32_t(code & 1) >= a.nx || j + uint32_t((code >> 1) & 1) >= a.ny || k + uint32_t(code >> 2) >= a.nz) continue;
+    const uint32_t Q = L + uint32_t(size_t(code & 1) + size_t((code >> 1) & 1) * a.nx + size_t(code >> 2) * (size_t(a.nx) * a.ny));
+    if (a.parent[Q] == kIsoRegionOutside) continue;
+    root = regionUnite(a, root, Q, tripped);
+  }
+  // shorten the walks of those that come later: L straight below the root it has just seen (a monotone update as well)
+  if (root < L) atomicMin(a.parent + L, root);
+  if (tripped) atomicExch(a.errorFlag, 1);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoRegionFlattenKernel(const IsoRegionArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  uint32_t isRoot = 0;
+  bool tripped = false;
+  if (L < a.numPoints) {
+    const uint32_t p = a.parent[L];
+    if (p != kIsoRegionOutside) {
+      // other lanes store roots into their own slots meanwhile: a walk meets a link of the merge or the root itself
+      const uint32_t r = p <= L ? regionFind<false>(a, p, tripped) : L;
+      tripped = tripped || p > L;
+      if (r != p) a.parent[L] = r;
+      isRoot = r == L ? 1u : 0u;
+    }
+  }
+  uint32_t total;
+  (void)blockScan(isRoot, total, lds);
+  if (threadIdx.x == 0) a.blockCount[blockIdx.x] = total;
+  if (tripped) atomicExch(a.errorFlag, 1);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoRegionRankKernel(const IsoRegionArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  if (a.blockCount[blockIdx.x] == 0) return;          // the same for the whole block
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  const bool isRoot = L < a.numPoints && a.parent[L] == L;
+  uint32_t total;
+  const uint32_t before = blockScan(isRoot ? 1u : 0u, total, lds);
+  if (!isRoot) return;
+  const uint32_t number = uint32_t(a.chunkBase[blockIdx.x / kIsoChunk]) + a.blockBase[blockIdx.x] + before;   // < numPoints
+  a.parent[L] = kIsoRegionRanked | number;
+  ExaHipRegion &r = a.regions[number];
+  r.points = 0;
+  r.sumFixed = 0;
+  for (int c = 0; c < 3; c++) { r.sumIndex[c] = 0; r.lo[c] = INT32_MAX; r.hi[c] = INT32_MIN; }
+  r.first = L;
+  r.argMin = r.argMax = 0;
+  r.min = r.max = 0.f;
+  static_assert(sizeof(ExaHipRegion) == 88, "the table's record: 84 bytes of fields and 4 of padding");
+  reinterpret_cast<uint32_t *>(&r)[21] = 0u;          // the padding: every byte of the table is defined
+  a.keys[2 * size_t(number)] = ~0ull;
+  a.keys[2 * size_t(number) + 1] = 0ull;
+}
+
+// what a lane, or the lanes of a wave that share a label, add to a region
+struct RegionPart {
+  uint32_t points;
+  long long sum;
+  unsigned long long si, sj, sk;
+  int32_t lo[3], hi[3];
+  unsigned long long keyMin, keyMax;
+};
+
+__device__ __forceinline__ void regionReduce(RegionPart &p)
+{
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    p.points += uint32_t(__shfl_xor(int(p.points), o));
+    p.sum += __shfl_xor(p.sum, o);
+    p.si += __shfl_xor(p.si, o);
+    p.sj += __shfl_xor(p.sj, o);
+    p.sk += __shfl_xor(p.sk, o);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const int32_t l = __shfl_xor(p.lo[c], o), h = __shfl_xor(p.hi[c], o);
+      p.lo[c] = l < p.lo[c] ? l : p.lo[c];
+      p.hi[c] = h > p.hi[c] ? h : p.hi[c];
+    }
+    const unsigned long long kmin = __shfl_xor(p.keyMin, o), kmax = __shfl_xor(p.keyMax, o);
+    p.keyMin = kmin < p.keyMin ? kmin : p.keyMin;
+    p.keyMax = kmax > p.keyMax ? kmax : p.keyMax;
+  }
+}
+
+__device__ __forceinline__ void regionAdd(const IsoRegionArgs &a, uint32_t label, const RegionPart &p)
+{
+  ExaHipRegion &r = a.regions[label];
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.points), (unsigned long long)p.points);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumFixed), (unsigned long long)p.sum);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[0]), p.si);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[1]), p.sj);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[2]), p.sk);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    atomicMin(&r.lo[c], p.lo[c]);
+    atomicMax(&r.hi[c], p.hi[c]);
+  }
+  atomicMin(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label)), p.keyMin);
+  atomicMax(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label) + 1), p.keyMax);
+}
+
+__device__ __forceinline__ RegionPart regionNothing()
+{
+  return { 0u, 0ll, 0ull, 0ull, 0ull, { INT32_MAX, INT32_MAX, INT32_MAX }, { INT32_MIN, INT32_MIN, INT32_MIN }, ~0ull, 0ull };
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoRegionStatsKernel(const IsoRegionArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  // the lane's tiles, 256 points apart: in a region of some size they share its label, and the lane gathers them; where the
+  // label changes, what it holds goes to its region first
+  bool in = false;
+  uint32_t label = 0;
+  RegionPart own = regionNothing();
+#pragma unroll 1
+  for (uint32_t t = 0; t < kIsoRegionTiles; t++) {
+    const uint64_t at = (uint64_t(blockIdx.x) * kIsoRegionTiles + t) * kIsoBlock + threadIdx.x;
+    if (at >= a.numPoints) break;
+    const uint32_t L = uint32_t(at);
+    const uint32_t p = a.parent[L];
+    if (p == kIsoRegionOutside) continue;
+    // a root's slot holds kIsoRegionRanked | number until the root's lane stores the number itself: the mask reads both
+    const uint32_t mine = ((p & kIsoRegionRanked) ? p : a.parent[p < L ? p : L]) & ~kIsoRegionRanked;
+    if (mine >= a.numRegions) {                       // not what the passes before leave behind: nothing is added anywhere
+      atomicExch(a.errorFlag, 1);
+      continue;
+    }
+    a.parent[L] = mine;
+    if (in && mine != label) {
+      regionAdd(a, label, own);
+      own = regionNothing();
+    }
+    in = true;
+    label = mine;
+    const float v = a.values[L];
+    const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+    const unsigned long long key = (unsigned long long)regionKey(v) << 32;
+    own.points++;
+    own.sum += __double2ll_rn(double(v) * a.scale);
+    own.si += i; own.sj += j; own.sk += k;
+    own.lo[0] = min(own.lo[0], int32_t(i)); own.lo[1] = min(own.lo[1], int32_t(j)); own.lo[2] = min(own.lo[2], int32_t(k));
+    own.hi[0] = max(own.hi[0], int32_t(i)); own.hi[1] = max(own.hi[1], int32_t(j)); own.hi[2] = max(own.hi[2], int32_t(k));
+    own.keyMin = min(own.keyMin, key | L);
+    own.keyMax = max(own.keyMax, key | (~L));
+  }
+  // the lanes of a wave are consecutive L and mostly share one label or two: the label of the first pending lane is
+  // reduced over the wave and added by that lane, twice; what is left then goes lane by lane
+  unsigned long long pending = __ballot(in);
+#pragma unroll 1
+  for (int round = 0; round < 2; round++) {
+    if (!pending) return;                             // wave-uniform
+    const uint32_t leader = uint32_t(__ffsll(pending)) - 1u;
+    const uint32_t lb = uint32_t(__builtin_amdgcn_readlane(int(label), int(leader)));
+    const bool same = in && label == lb;
+    const unsigned long long m = __ballot(same);
+    RegionPart part = own;
+    if (!same) part = regionNothing();
+    if (__popcll(m) > 1) regionReduce(part);          // wave-uniform
+    if (lane == leader) regionAdd(a, lb, part);
+    in = in && !same;
+    pending &= ~m;
+  }
+  if (in) regionAdd(a, label, own);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoRegionFinishKernel(const IsoRegionArgs a)
+{
+  const uint32_t n = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (n >= a.numRegions) return;
+  const uint64_t kmin = a.keys[2 * size_t(n)], kmax = a.keys[2 * size_t(n) + 1];
+  ExaHipRegion &r = a.regions[n];
+  r.min = regionValueOfKey(uint32_t(kmin >> 32));
+  r.argMin = uint32_t(kmin);
+  r.max = regionValueOfKey(uint32_t(kmax >> 32));
+  r.argMax = ~uint32_t(kmax);
+}
+
 } // namespace
+
+hipError_t launchIsoRegionInit(const IsoRegionArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoRegionInitKernel, dim3((a.numBlocks + kIsoRegionTiles - 1) / kIsoRegionTiles), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoRegionMerge(const IsoRegionArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoRegionMergeKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoRegionFlatten(const IsoRegionArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoRegionFlattenKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the iso-surface's scans over the one count of the flatten pass (grid y = 1): they read nothing of their arguments but it
+hipError_t launchIsoRegionScans(const IsoRegionArgs &a, hipStream_t s)
+{
+  IsoMeshArgs m = {};
+  m.numBlocks = a.numBlocks; m.numChunks = a.numChunks;
+  m.blockCount = a.blockCount; m.blockBase = a.blockBase; m.chunkBase = a.chunkBase; m.totals = a.totals;
+  hipLaunchKernelGGL(isoScanChunksKernel, dim3(a.numChunks, 1), dim3(kIsoBlock), 0, s, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoScanTopKernel, dim3(1), dim3(kIsoBlock), 0, s, m);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoRegionRankKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the labels and the measurements, then min / max / argMin / argMax out of the keys
+hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoRegionStatsKernel, dim3((a.numBlocks + kIsoRegionTiles - 1) / kIsoRegionTiles), dim3(kIsoBlock), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoRegionFinishKernel, dim3((a.numRegions + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launchIsolinePositions(const IsoLineArgs &a, hipStream_t s)
 {

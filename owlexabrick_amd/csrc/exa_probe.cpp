@@ -3,7 +3,8 @@
 // (exa_hip_sample_derived, exa_hip_resample_derived), the projections along rays (exa_hip_project) and the iso-crossings along
 // the same rays (exa_hip_raycast_iso) in the same file, the field on the triangles of a mesh (exa_hip_sample_triangles), and
 // the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip) with the
-// contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit).
+// contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit) and the connected
+// regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -990,6 +991,199 @@ int exa_hip_isolines_stage_ms(ExaHipRenderer *h, float ms[6])
   if (!h || !ms) return 1;
   const ExaHipRenderer *r = firstChild(h);
   for (int k = 0; k < 6; k++) ms[k] = r->isolines.stageMs[k];
+  return 0;
+}
+
+// ---- connected regions of the inside set on a lattice (exa_isomesh.hip) ----
+const char *const kRegionGuard = ": the union-find's loop guard tripped (a parent link that does not descend)";
+
+// exa_hip_regions (quantity < 0: the lattice holds the one channel channels[0]) and exa_hip_regions_derived (it holds the
+// quantity of channels[0..2]).  The flags, the channels and the quantity are checked by the caller.  The labels array of the
+// result is the union-find's forest until the stats pass; two small read-backs: the counts (regions, inside points, max
+// |V|) behind the scans, which size the table and give the sum's exponent, and the loop guard at the end.
+static int regionsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                          const int32_t *channels, int32_t quantity, float iso, int32_t flags, uint64_t *numRegions,
+                          uint64_t *numInside, int32_t *sumExponent, void *hipStream)
+{
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isoRegions.release();
+  DropUnlessCommitted<ExaHipRenderer::IsoRegions> regions(r->isoRegions);     // whatever fails from here on leaves no result
+  ExaHipRenderer::IsoRegions &res = r->isoRegions;
+  for (float &ms : res.stageMs) ms = 0.f;
+  if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument (lo, hi or dims)"); return 1; }
+  if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
+  for (int k = 0; k < 3; k++) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) { h->fail(std::string(fn) + ": the box must be finite"); return 1; }
+    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
+  }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
+  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
+    return 1;
+  }
+  hipStream_t s = (hipStream_t)hipStream;
+  const int32_t wf = flags & EXA_SAMPLE_WORLD_SPACE;
+
+  IsoRegionArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.iso = iso;
+  a.below = (flags & EXA_REGIONS_BELOW) ? 1 : 0;
+  a.faces = (flags & EXA_REGIONS_FACES) ? 1 : 0;
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  a.errorFlag = r->errorFlag.p;
+  // the work space, freed when the call returns: chunkBase, totals | blockCount, blockBase; and the keys further down
+  DevBuf<char> work;
+  const size_t n64 = size_t(a.numChunks) + 3;
+  hipError_t e = res.values.alloc(n);
+  if (e == hipSuccess) e = res.labels.alloc(n);
+  if (e == hipSuccess) e = work.alloc(n64 * 8 + 2 * size_t(a.numBlocks) * 4);
+  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the labels (4 more)", e);
+  a.values = res.values.p;
+  a.parent = reinterpret_cast<uint32_t *>(res.labels.p);
+  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
+  a.totals = a.chunkBase + a.numChunks;
+  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  a.blockBase = a.blockCount + a.numBlocks;
+
+  TimingEvents<9> t;
+  HIP_TRY(h, t.create());
+  // the lattice: exa_hip_resample, or exa_hip_resample_derived, with a NaN fill into the device buffer (its checks of the
+  // box, the kd tree and the frame state apply; synchronous, with the descent's loop guard checked)
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  if (int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], wf, NAN, res.values.p, 1, hipStream, 0)
+                            : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, wf, NAN, res.values.p, 1, hipStream, 0)) {
+    h->fail(std::string(fn) + ": " + h->err);
+    return rc;
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  HIP_TRY(h, hipMemsetAsync(a.totals, 0, 3 * sizeof(uint64_t), s));
+  HIP_TRY(h, launchIsoRegionInit(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[2], s));
+  HIP_TRY(h, launchIsoRegionMerge(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[3], s));
+  HIP_TRY(h, launchIsoRegionFlatten(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[4], s));
+  HIP_TRY(h, launchIsoRegionScans(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[5], s));
+  uint64_t totals[3] = { 0, 0, 0 };              // regions, inside points, bits of max |V|
+  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  uint32_t maxBits = uint32_t(totals[2]);
+  float maxAbs;
+  std::memcpy(&maxAbs, &maxBits, sizeof(maxAbs));
+  int32_t exponent = 0;
+  if (totals[1] && maxAbs != 0.f) {
+    int ex = 0;
+    (void)std::frexp(maxAbs, &ex);
+    exponent = 30 - ex;
+  }
+  a.scale = std::ldexp(1.0, exponent);
+  a.numRegions = uint32_t(totals[0]);            // <= n
+  float rankMs = 0.f;
+  if (totals[0]) {
+    DevBuf<uint64_t> keys;
+    e = res.regions.alloc(size_t(totals[0]));
+    if (e == hipSuccess) e = keys.alloc(2 * size_t(totals[0]));
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the table of regions (88 bytes each, and 16 while the call runs)", e);
+    a.regions = res.regions.p;
+    a.keys = keys.p;
+    HIP_TRY(h, hipEventRecord(t.ev[6], s));
+    HIP_TRY(h, launchIsoRegionRank(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[7], s));
+    HIP_TRY(h, launchIsoRegionStats(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[8], s));
+    HIP_TRY(h, hipStreamSynchronize(s));         // the keys are freed behind it
+    HIP_TRY(h, t.elapsed(6, 7, &rankMs));
+    HIP_TRY(h, t.elapsed(7, 8, &res.stageMs[5]));
+  }                                              // no region: every label is the outside mark, which is -1
+  for (int k = 0; k < 5; k++) HIP_TRY(h, t.elapsed(k, k + 1, &res.stageMs[k]));
+  res.stageMs[4] += rankMs;
+  if (int rc = checkLoopGuard(h, r, fn, kRegionGuard)) return rc;
+  res.keptValues = (flags & EXA_REGIONS_KEEP_VALUES) != 0;
+  if (!res.keptValues) res.values.release();
+  res.have = true;
+  regions.commit();
+  if (numRegions) *numRegions = totals[0];
+  if (numInside) *numInside = totals[1];
+  if (sumExponent) *sumExponent = exponent;
+  return 0;
+}
+
+static const int32_t kRegionFlags = EXA_SAMPLE_WORLD_SPACE | EXA_REGIONS_KEEP_VALUES | EXA_REGIONS_BELOW | EXA_REGIONS_FACES;
+static const char *const kRegionFlagsHint = " (EXA_SAMPLE_WORLD_SPACE, EXA_REGIONS_KEEP_VALUES, EXA_REGIONS_BELOW and EXA_REGIONS_FACES apply)";
+
+int exa_hip_regions(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                    int32_t flags, uint64_t *numRegions, uint64_t *numInside, int32_t *sumExponent, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_regions";
+  if (numRegions) *numRegions = 0;
+  if (numInside) *numInside = 0;
+  if (sumExponent) *sumExponent = 0;
+  int rc = 1;
+  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint) && checkChannel(h, fn, channel))
+    rc = regionsExtract(h, fn, lo, hi, dims, &channel, -1, iso, flags, numRegions, numInside, sumExponent, hipStream);
+  if (rc) (void)exa_hip_regions_release(h);            // a failed call leaves no result, whichever check refused it
+  return rc;
+}
+
+int exa_hip_regions_derived(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                            int32_t quantity, float iso, int32_t flags, uint64_t *numRegions, uint64_t *numInside,
+                            int32_t *sumExponent, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_regions_derived";
+  if (numRegions) *numRegions = 0;
+  if (numInside) *numInside = 0;
+  if (sumExponent) *sumExponent = 0;
+  int rc = 1;
+  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint)) {
+    const int comps = derivedComponents(h, fn, channels, quantity);
+    if (comps > 1) h->fail(std::string(fn) + ": regions need a one-component quantity (EXA_DERIVED_VORTICITY has three)");
+    else if (comps == 1)
+      rc = regionsExtract(h, fn, lo, hi, dims, channels, quantity, iso, flags, numRegions, numInside, sumExponent, hipStream);
+  }
+  if (rc) (void)exa_hip_regions_release(h);
+  return rc;
+}
+
+int exa_hip_regions_read(ExaHipRenderer *h, int32_t *labels, ExaHipRegion *regions, float *values, int32_t pointersAreDevice,
+                         void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_regions_read";
+  ExaHipRenderer *r = firstChild(h);
+  const ExaHipRenderer::IsoRegions &res = r->isoRegions;
+  if (!res.have) { h->fail(std::string(fn) + ": no regions (exa_hip_regions comes first; a release or a failed call drops them)"); return 1; }
+  if (values && !res.keptValues) { h->fail(std::string(fn) + ": the regions were extracted without EXA_REGIONS_KEEP_VALUES"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (labels && res.labels.n) HIP_TRY(h, hipMemcpyAsync(labels, res.labels.p, res.labels.n * sizeof(int32_t), kind, s));
+  if (regions && res.regions.n) HIP_TRY(h, hipMemcpyAsync(regions, res.regions.p, res.regions.n * sizeof(ExaHipRegion), kind, s));
+  if (values && res.values.n) HIP_TRY(h, hipMemcpyAsync(values, res.values.p, res.values.n * sizeof(float), kind, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+int exa_hip_regions_release(ExaHipRenderer *h)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isoRegions.release();
+  return 0;
+}
+
+int exa_hip_regions_stage_ms(ExaHipRenderer *h, float ms[6])
+{
+  if (!h || !ms) return 1;
+  const ExaHipRenderer *r = firstChild(h);
+  for (int k = 0; k < 6; k++) ms[k] = r->isoRegions.stageMs[k];
   return 0;
 }
 

@@ -3,7 +3,7 @@
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes, the projections along rays and the
 // iso-surface extraction, exa_streamlines.cpp the streamline extraction, exa_stats.cpp the histogram and value range of
 // the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
-// one struct per call (ExaHipRenderer::probes, isoMesh, isolines, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
+// one struct per call (ExaHipRenderer::probes, isoMesh, isolines, isoRegions, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
 // argument checks below the renderer are what their host code shares.
 #pragma once
 #include "exa_device.h"
@@ -312,6 +312,18 @@ struct ExaHipRenderer {
       have = withGradients = keptValues = false;
     }
   } isolines;
+  // the regions of the last exa_hip_regions (in the renderer of devices[0] as well), independent of the mesh and of the
+  // lines: the labels (the union-find's parent links while the call runs), the table, the lattice values where
+  // EXA_REGIONS_KEEP_VALUES kept them, the counts the call returned, and the time of the stages (values, init, merge,
+  // flatten, rank, stats)
+  struct IsoRegions {
+    DevBuf<int32_t> labels;
+    DevBuf<ExaHipRegion> regions;
+    DevBuf<float> values;
+    bool have = false, keptValues = false;
+    float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
+    void release() { labels.release(); regions.release(); values.release(); have = keptValues = false; }
+  } isoRegions;
   // exa_hip_histogram (on a multi-device handle: in the renderer of devices[0]): the work list of the pass — segments
   // {brick, first cell} by level and the offsets of the runs, built by the first call (exa_stats.cpp) —, whether the scene's
   // volume-weighted cell count fits 64 bits, the device copy of a call's result and the device time of its kernel

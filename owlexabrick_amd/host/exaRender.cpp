@@ -40,6 +40,18 @@
 //                                            (V x 2 float32, lattice coordinates), segments (S x 2 int32, indices into the
 //                                            vertices); --frames 0 renders nothing; with
 //             [--isolines-world]             the plane is in world space
+//             [--regions CHANNEL ISO NX NY NZ out.regions] the connected regions of field >= ISO of CHANNEL on that lattice
+//                                            (exa_hip_regions: joined along the edges of --isomesh's tetrahedra, numbered by
+//                                            their smallest lattice index, exact measurements per region).  With --derived the
+//                                            regions of that quantity (exa_hip_regions_derived; CHANNEL is read and ignored,
+//                                            vorticity refused).  One text line `regions NX NY NZ count R inside I exponent S`,
+//                                            then raw little-endian arrays: the table (R records of 88 bytes, ExaHipRegion of
+//                                            include/exa_hip.h: a region's value sum is sumFixed * 2^-S) and the labels
+//                                            (NX*NY*NZ int32, x fastest: the region's number, -1 outside); --frames 0 renders
+//                                            nothing; with
+//             [--regions-box lx ly lz ux uy uz] [--regions-world] (box default as for --resample)
+//             [--regions-below]              field < ISO instead
+//             [--regions-faces]              joined along the three axes only (6 neighbours)
 //             [--histogram BINS file.txt]   the exact histogram of a channel's cell values (exa_hip_histogram), one line
 //                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
 //             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
@@ -179,6 +191,11 @@ int main(int argc, char **argv)
     int derived = -1;                                            // --derived: EXA_DERIVED_*
     vec3i derivedChannels(0, 1, 2);
     bool haveResampleChannel = false, haveIsoChannel = false;
+    std::string regionsName;
+    int regionsChannel = 0, regionsDims[3] = { 0, 0, 0 };
+    float regionsIso = 0.f;
+    bool regionsWorld = false, regionsBelow = false, regionsFaces = false, haveRegionsBox = false;
+    box3f regionsBox;
     std::string linesName;
     int linesChannel = 0;
     vec3f linesOrigin, linesDu, linesDv;
@@ -257,6 +274,17 @@ int main(int argc, char **argv)
         linesName = argv[++i];
       }
       else if (a == "--isolines-world") linesWorld = true;
+      else if (a == "--regions") {
+        regionsChannel = (int)f();
+        regionsIso = f();
+        for (int k = 0; k < 3; k++) regionsDims[k] = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --regions CHANNEL ISO NX NY NZ");
+        regionsName = argv[++i];
+      }
+      else if (a == "--regions-box") { regionsBox.lower = { f(), f(), f() }; regionsBox.upper = { f(), f(), f() }; haveRegionsBox = true; }
+      else if (a == "--regions-world") regionsWorld = true;
+      else if (a == "--regions-below") regionsBelow = true;
+      else if (a == "--regions-faces") regionsFaces = true;
       else if (a == "--derived") {
         if (i + 1 >= argc) throw std::runtime_error("missing quantity after --derived");
         derived = derivedQuantity(argv[++i]);
@@ -451,6 +479,24 @@ int main(int argc, char **argv)
       else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
       std::printf("world %d levels %zu vertices %zu segments %zu\n", linesWorld ? 1 : 0, n, nv, ns);
     }
+    if (!regionsName.empty()) {
+      const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
+      const vec3i dims(regionsDims[0], regionsDims[1], regionsDims[2]);
+      const Renderer::Regions R = derived < 0 ? renderer.regions(box, dims, regionsChannel, regionsIso, regionsWorld, regionsBelow, regionsFaces)
+                                              : renderer.regionsDerived(box, dims, derivedChannels, derived, regionsIso, regionsWorld, regionsBelow, regionsFaces);
+      FILE *f = std::fopen(regionsName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + regionsName);
+      const size_t nr = R.regions.size(), n = R.labels.size();
+      std::fprintf(f, "regions %d %d %d count %zu inside %llu exponent %d\n", dims.x, dims.y, dims.z, nr,
+                   (unsigned long long)R.numInside, R.sumExponent);
+      const bool ok = std::fwrite(R.regions.data(), sizeof(ExaHipRegion), nr, f) == nr && std::fwrite(R.labels.data(), 4, n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + regionsName);
+      std::printf("regions %d %d %d ", dims.x, dims.y, dims.z);
+      if (derived < 0) std::printf("channel %d ", regionsChannel);
+      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
+      std::printf("iso %.9g world %d below %d faces %d count %zu inside %llu exponent %d\n", regionsIso, regionsWorld ? 1 : 0,
+                  regionsBelow ? 1 : 0, regionsFaces ? 1 : 0, nr, (unsigned long long)R.numInside, R.sumExponent);
+    }
     if (!surfaceName.empty()) {
       const bool fromIso = surfaceMesh == "iso";
       if (fromIso && isoName.empty()) throw std::runtime_error("--surface iso needs --isomesh in the same invocation");
@@ -567,7 +613,7 @@ int main(int argc, char **argv)
                   raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
-                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty())) return 0;
+                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

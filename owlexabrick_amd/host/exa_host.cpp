@@ -616,6 +616,54 @@ TriangleMesh::SP Renderer::extractIsoSurfaceDerived(const box3f &box, vec3i dims
   return readIsoMesh(handle, nv, nt, nullptr, keep);
 }
 
+// the regions of the last exa_hip_regions or exa_hip_regions_derived out of the module, which then drops them
+static Renderer::Regions readRegions(ExaHipRenderer *handle, vec3i dims, uint64_t numRegions, uint64_t numInside, int32_t sumExponent,
+                                     bool values)
+{
+  Renderer::Regions R;
+  const size_t n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
+  R.dims = dims;
+  R.numInside = numInside;
+  R.sumExponent = sumExponent;
+  R.labels.resize(n);
+  R.regions.resize(numRegions);
+  if (values) R.values.resize(n);
+  check(exa_hip_regions_read(handle, R.labels.data(), R.regions.data(), values ? R.values.data() : nullptr, 0, nullptr), handle);
+  check(exa_hip_regions_release(handle), handle);
+  return R;
+}
+
+static int regionFlags(bool worldSpace, bool below, bool faces, bool values)
+{
+  return (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (below ? EXA_REGIONS_BELOW : 0) | (faces ? EXA_REGIONS_FACES : 0) |
+         (values ? EXA_REGIONS_KEEP_VALUES : 0);
+}
+
+Renderer::Regions Renderer::regions(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace, bool below, bool faces,
+                                    bool values)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z };
+  uint64_t nr = 0, ni = 0;
+  int32_t se = 0;
+  check(exa_hip_regions(handle, lo, hi, d, channel, iso, regionFlags(worldSpace, below, faces, values), &nr, &ni, &se, nullptr), handle);
+  return readRegions(handle, dims, nr, ni, se, values);
+}
+
+Renderer::Regions Renderer::regionsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, bool worldSpace,
+                                           bool below, bool faces, bool values)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  uint64_t nr = 0, ni = 0;
+  int32_t se = 0;
+  check(exa_hip_regions_derived(handle, lo, hi, d, ch, quantity, iso, regionFlags(worldSpace, below, faces, values), &nr, &ni, &se,
+                                nullptr), handle);
+  return readRegions(handle, dims, nr, ni, se, values);
+}
+
 // the lines of the last extraction (exa_hip_isolines or exa_hip_isolines_derived) out of the module, which then drops them
 static Renderer::Isolines readIsolines(ExaHipRenderer *handle, uint64_t nv, uint64_t ns, size_t levels, bool gradients, size_t values)
 {

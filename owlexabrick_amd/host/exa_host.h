@@ -241,6 +241,24 @@ struct Renderer {
   Isolines isolinesDerived(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos, vec3i channels,
                            int quantity, bool worldSpace = false, bool values = false);
 
+  // the connected regions of field >= iso (below: < iso) of `channel` on the lattice of resample(box, dims), joined along
+  // the Kuhn edges of extractIsoSurface's split (faces: along the axes only), numbered by their smallest lattice index, each
+  // with its exact measurements (exa_hip_regions; include/exa_hip.h states the contract): labels[(k*dims.y + j)*dims.x + i] =
+  // the region's number or -1; a region's value sum is sumFixed * 2^-sumExponent.  values: the lattice as well.
+  // regionsDerived: the same of a one-component quantity of the vector field `channels`.
+  struct Regions {
+    vec3i dims;
+    std::vector<int32_t> labels;
+    std::vector<ExaHipRegion> regions;
+    std::vector<float> values;
+    uint64_t numInside = 0;
+    int32_t sumExponent = 0;
+  };
+  Regions regions(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace = false, bool below = false,
+                  bool faces = false, bool values = false);
+  Regions regionsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, bool worldSpace = false,
+                         bool below = false, bool faces = false, bool values = false);
+
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
   // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
