@@ -197,6 +197,13 @@ const char *exa_prep_last_error(void);
  * planes are in the range of the walk's short exact division. */
 int exa_prep_ropes(const ExaPrep *, uint64_t *numLeaves, uint64_t *numNodes, float *leafBoxes, int32_t *leafLinks,
                    int32_t *leafRegion, ExaKdNode *nodes, int32_t *flags);
+/* diagnostic: the 16-byte cube records exa_hip_create builds beside the march headers (option "cube_records") for a scene
+ * whose bricks are all cubes of one edge 2^k, 1 <= k <= 7, with every `begin` a multiple of the cube's cell count, begin /
+ * 8^k < 2^23 and levels 0..30 (owlexabrick_amd/csrc/exa_cube.h).  *log2Edge = k, or 0 when the scene is no cube scene (then
+ * nothing is built).  beginAlt (may be NULL): numBricks `begin` values of the other brick order, held to the same conditions.
+ * records (may be NULL): leafListSize x 4 words {float(lower.xyz) as float bits, ((begin >> 3k) << 9) | (127 - level)}. */
+int exa_prep_cube_records(const ExaBrick *bricks, uint64_t numBricks, const int32_t *leafList, uint64_t leafListSize,
+                          const uint32_t *beginAlt, int32_t *log2Edge, int32_t *records);
 /* diagnostic: replaces the prep's region kd-tree by a caller's own (what a caller may hand exa_hip_create in
  * ExaHipScene.kdNodes); exa_prep_scene and exa_prep_ropes then see that tree.  Checked as exa_hip_create checks it: axis 0..2,
  * references in range, children after their parent. */
@@ -967,7 +974,10 @@ int exa_hip_sample_triangles_ms(ExaHipRenderer *, float *ms);
  * as uploaded; "addr64" 1 = the march forms 64-bit cell / header / node addresses even where a scene is small enough for
  * 32-bit offsets from a uniform base (default 0: chosen per scene; "pack_records" 0 = the march takes region ids from the walk and loads the region
  * records, as it does in scenes whose records {first brick, brick count, level} do not fit the 32 bits of a leaf reference (default 1:
- * packed where they fit; tests); tests); "brick_order" 0 = the bricks' cells lie in
+ * packed where they fit; tests); tests); "cube_records" 1 (default) = in a scene whose bricks are all cubes of one power-of-two
+ * edge (exa_prep_cube_records says which) the one-channel 32-bit rope march reads 16-byte brick records with the edge as a
+ * kernel argument instead of the 32-byte march headers (16 bytes of device memory per leaf-list entry, built by exa_hip_create;
+ * bit-identical frames), 0 = the march headers, as in every other scene. "brick_order" 0 = the bricks' cells lie in
  * memory in the order of the brick list (the running `begin` of OptixRenderer.cpp:71-93), 1 = along a Morton curve of the
  * brick centres (re-laid on the device at the next frame; cells are only found through their brick's `begin`, so pixels
  * cannot change; environment EXA_BRICK_ORDER sets the initial value); "tile_feedback" 1 (default) = after a

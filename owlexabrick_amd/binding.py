@@ -215,6 +215,7 @@ _ABI = {
     "exa_prep_create_ex": (None, [_vp, _u64, _vp, _u64, _P(_vp), _P(_u64), _i32, _i32, _i32, _i32, _P(_vp)]),
     "exa_prep_destroy": (None, [_vp]),
     "exa_prep_ropes": (None, [_vp, _P(_u64), _P(_u64), _vp, _vp, _vp, _vp, _P(_i32)]),
+    "exa_prep_cube_records": (None, [_vp, _u64, _vp, _u64, _vp, _P(_i32), _vp]),
     "exa_prep_scene": (None, [_vp, _P(ExaHipScene)]),
     "exa_prep_set_kd_tree": (None, [_vp, _vp, _u64, _i32]),
     "exa_prep_last_error": (C.c_char_p, None),
@@ -300,6 +301,23 @@ def lib():
                 fn.argtypes = argtypes
         _lib = L
     return _lib
+
+
+def cube_records(bricks, leaflist, begin_alt=None):
+    """the cube records the module builds for a scene whose bricks are all cubes of one power-of-two edge
+    (exa_prep_cube_records, a diagnostic): (k, records [n,4] uint32) with k = log2 of the edge, or (0, None) when the scene
+    is no cube scene.  bricks: BRICK_DTYPE array; leaflist: int32 brick indices; begin_alt: the `begin` values of the other
+    brick order, held to the same conditions."""
+    bricks = np.ascontiguousarray(bricks, dtype=BRICK_DTYPE)
+    leaflist = np.ascontiguousarray(leaflist, dtype=np.int32)
+    alt = None if begin_alt is None else np.ascontiguousarray(begin_alt, dtype=np.uint32)
+    assert alt is None or alt.size == bricks.size
+    k = C.c_int32(-1)
+    rec = np.zeros((leaflist.size, 4), dtype=np.uint32)
+    if lib().exa_prep_cube_records(bricks.ctypes.data, bricks.size, leaflist.ctypes.data if leaflist.size else None, leaflist.size,
+                                   None if alt is None else alt.ctypes.data, C.byref(k), rec.ctypes.data if rec.size else None):
+        raise RuntimeError(lib().exa_prep_last_error().decode())
+    return (int(k.value), rec) if k.value else (0, None)
 
 
 class Prep:

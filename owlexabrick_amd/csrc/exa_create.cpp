@@ -4,6 +4,7 @@
 #include "exa_renderer.h"
 #include "exa_hostbvh.h"
 #include "exa_coords.h"
+#include "exa_cube.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -234,6 +235,19 @@ int exa_hip_create(const ExaHipScene *scene, int32_t device, ExaHipRenderer **ou
   }
   chooseAddressForms(h, scene);
   CREATE_TRY(h->scalars.upload(scene->scalars, size_t(scene->numFields) * scene->totalCells));
+  // cube records beside the march headers, where the scene has only cubes of one power-of-two edge: 16 B per leaf-list
+  // entry (half the headers' size, so below 4 GiB wherever the 32-bit march runs).  They are an optimisation: without the
+  // memory for them the scene renders from the march headers.
+  h->cubeLog2 = exa::cubeSceneLog2(scene->bricks, scene->numBricks, h->beginMorton.data());
+  if (h->cubeLog2) {
+    std::vector<int32_t> rec(scene->leafListSize * 4);
+    exa::buildCubeRecords(scene->bricks, scene->leafList, scene->leafListSize, h->cubeLog2, rec.data());
+    if (h->leafHdrCube.upload(reinterpret_cast<const int4 *>(rec.data()), scene->leafListSize) != hipSuccess) {
+      (void)hipGetLastError();
+      h->leafHdrCube.release();
+      h->cubeLog2 = 0;
+    }
+  }
   std::vector<RegionInfo> ri(scene->numRegions);
   std::vector<float2> vr(scene->numRegions);
   std::vector<float> dom(scene->numRegions * 6);

@@ -225,6 +225,10 @@ struct RenderArgs {
   uint32_t           aoBins;
   uint32_t          *tileCostPre;   // != null: per tile id, steps of the longest iso march of the surfaces pre-pass
   uint32_t          *tileCost;      // != null: per tile id, brick visits of the tile's longest ray (launch-order feedback)
+  // (new members go behind the ones above: the kernels address their arguments by offset, and the shipped march variants are
+  // held to their machine code)
+  const int4        *leafHdrCube;   // != null: cube records along the leaf list, one int4 per entry (exa_cube.h) — every brick a
+  int32_t            cubeLog2;      // cube of edge 2^cubeLog2; the launch takes the cube instantiation of the rope march
 };
 
 // The point probes (exa_hip_sample_points / exa_hip_resample, exa_sample_kernels.h): the region is found by descending the
@@ -399,6 +403,9 @@ hipError_t launchRopeActivity(RopeLeaf *leaves, uint32_t numRegions, const uint8
 hipError_t launchPermuteBricks(const float *src, float *dst, const uint32_t *srcBegin, const uint32_t *dstBegin, int4 *bricks,
                                unsigned long long numBricks, int4 *leafHdr, const int32_t *leafList, unsigned long long leafListSize,
                                unsigned long long totalCells, int numFields, hipStream_t s);
+// ... and of every cube record (exa_cube.h), which keeps its level bits: w = ((dstBegin[brick] >> 3 cubeLog2) << 9) | (w & 511)
+hipError_t launchPatchCubeRecords(int4 *leafHdrCube, const int32_t *leafList, unsigned long long leafListSize,
+                                  const uint32_t *dstBegin, int cubeLog2, hipStream_t s);
 // out[cell * nch + c] = scalars[channelOffset[c] + cell] for c < nch
 hipError_t launchInterleave(const DeviceScene &sc, unsigned long long totalCells, int nch, float *out, hipStream_t s);
 hipError_t launchUntile(const uint32_t *gathered, unsigned long long shardStride, int world,

@@ -34,6 +34,7 @@ int ExaHipRenderer::applyBrickOrder(hipStream_t s)
   HIP_TRY(this, moved.alloc(scalars.n));
   HIP_TRY(this, launchPermuteBricks(scalars.p, moved.p, dFrom.p, dTo.p, bricks.p, numBricks, leafHdr.p, leafList.p, leafListSize,
                                     totalCells, numFields, s));
+  if (leafHdrCube.p) HIP_TRY(this, launchPatchCubeRecords(leafHdrCube.p, leafList.p, leafListSize, dTo.p, cubeLog2, s));
   HIP_TRY(this, hipStreamSynchronize(s));
   std::swap(scalars.p, moved.p);                         // `moved` now owns the old array and frees it
   sc.scalars = scalars.p;
@@ -531,6 +532,9 @@ int ExaHipRenderer::fillRenderArgs(RenderArgs &a, uint32_t *dstDevice, bool stat
   a.leafBeginBits = packed ? leafBeginBits : 0;
   a.leafSizeBits = packed ? leafSizeBits : 0;
   a.regionRec = regionRec.p;
+  // cube scene: the one-channel 32-bit rope march may read the cube records (launchRenderKdT decides)
+  a.leafHdrCube = (cubeRecords && cubeLog2) ? leafHdrCube.p : nullptr;
+  a.cubeLog2 = cubeLog2;
   a.ropeLeaves = (ropeThisFrame && ropeBuilt) ? ropeLeaves.p : nullptr;
   a.ropeNodes = ropeNodes.p;
   a.ropeRoot = ropeRoot;

@@ -409,14 +409,21 @@ __device__ __forceinline__ Pair loadPair(const float *__restrict__ p) { return *
 // other caller) takes -+1, the derivative with respect to the brick's own cell coordinate (INV_CELL_WIDTH == 1.f,
 // exabrick.cu:640-641).  2^-level is a power of two: every product with it is exact, so a brick's terms are the
 // reference's times 2^-level bit for bit.  sumW and sumWV do not depend on it.
-template <bool DERIV, int STATS, bool SMALL, bool VOXEL = false>
+//
+// CUBE (the cube instantiations of the one-channel rope march only, SMALL): every brick of the scene is a cube of edge
+// 2^cubeLog2, a wave-uniform kernel argument, and b0 is the brick's cube record (exa_cube.h; b1 is not looked at): the sizes
+// are scalar operands of the compares and clamps, the row offsets shifts instead of multiplies, 2^-level is b0.w << 23.  The
+// same integers and floats enter every address and every float operation as from the brick's march header.
+template <bool DERIV, int STATS, bool SMALL, bool VOXEL = false, bool CUBE = false>
 __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4 b0, const int4 b1,
-                                             const float *__restrict__ field, V3 pos)
+                                             const float *__restrict__ field, V3 pos, const int cubeLog2 = 0)
 {
+  static_assert(!CUBE || SMALL, "cube records: the 32-bit address form only");
   // march header (exa_module: leafHdr): b0 = (float(lower.xyz), 2^-level) as float bits, b1 = (size.xyz, begin)
-  const int sx = b1.x, sy = b1.y, sz = b1.z;
-  const uint32_t begin = (uint32_t)b1.w;
-  const float invCw = __int_as_float(b0.w);                 // exact 2^-level: (p/cw) == p*invCw
+  // cube record: b0 = (float(lower.xyz), ((begin >> 3k) << 9) | (127 - level))
+  const int sx = CUBE ? (1 << cubeLog2) : b1.x, sy = CUBE ? sx : b1.y, sz = CUBE ? sx : b1.z;
+  const uint32_t begin = CUBE ? ((uint32_t)b0.w >> 9) << (3 * cubeLog2) : (uint32_t)b1.w;
+  const float invCw = __int_as_float(CUBE ? (int)((uint32_t)b0.w << 23) : b0.w);   // exact 2^-level: (p/cw) == p*invCw
   const float lpx = EXA_F1 ? __builtin_fmaf(pos.x - __int_as_float(b0.x), invCw, -0.5f) : (pos.x - __int_as_float(b0.x)) * invCw - 0.5f;
   const float lpy = EXA_F1 ? __builtin_fmaf(pos.y - __int_as_float(b0.y), invCw, -0.5f) : (pos.y - __int_as_float(b0.y)) * invCw - 0.5f;
   const float lpz = EXA_F1 ? __builtin_fmaf(pos.z - __int_as_float(b0.z), invCw, -0.5f) : (pos.z - __int_as_float(b0.z)) * invCw - 0.5f;
@@ -433,17 +440,29 @@ __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4
   // clamp(l, 0, size-1) as one v_med3_i32 (sizes >= 1, so 0 <= size-1 and the median IS the clamp); the compiler
   // cannot prove the bound order and emits v_max + v_min (the 0 is the instruction's inline constant: as a "v" operand
   // it occupied a register across the whole march)
-  auto med3 = [](int a, int c) { int r; asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(c)); return r; };   // clamp(a, 0, c)
+  // (CUBE: the bound is wave-uniform, a scalar operand; the edge is >= 2, so size-2 needs no max)
+  auto med3 = [](int a, int c) {                                                                                     // clamp(a, 0, c)
+    int r;
+    if (CUBE) asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(a), "s"(c));
+    else asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(c));
+    return r;
+  };
   const int cxl = med3(lx, sx - 1), cxh = min(hx, sx - 1);
   const int cyl = med3(ly, sy - 1), cyh = min(hy, sy - 1);
   const int czl = med3(lz, sz - 1), czh = min(hz, sz - 1);
-  const int bx = med3(lx, max(sx - 2, 0));
+  const int bx = med3(lx, CUBE ? sx - 2 : max(sx - 2, 0));
   float s000, s100, s010, s110, s001, s101, s011, s111;
   {
     // (eight 4-byte loads instead of four 8-byte pair loads would save the pair base, two compares and eight
     // selects, ~10 VALU per visit — measured on C4: 26.1 instead of 22.5 ms, the L1 request rate matters too)
     uint32_t rowLL, rowHL, rowLH, rowHH;                      // cell index of the pair's first cell, per (y,z) row
-    if (SMALL) {
+    if (CUBE) {
+      // x + (y << k) + (z << 2k) + begin: six v_lshl_add_u32 with scalar shifts and one add, no multiply
+      const uint32_t at = begin + (uint32_t)bx;
+      const uint32_t zl = ((uint32_t)czl << (2 * cubeLog2)) + at, zh = ((uint32_t)czh << (2 * cubeLog2)) + at;
+      rowLL = ((uint32_t)cyl << cubeLog2) + zl; rowHL = ((uint32_t)cyh << cubeLog2) + zl;
+      rowLH = ((uint32_t)cyl << cubeLog2) + zh; rowHH = ((uint32_t)cyh << cubeLog2) + zh;
+    } else if (SMALL) {
       // SMALL: every factor below 2^24 and every product below 2^32 (checked per scene on the host)
       // (the compiler turns this one __umul24 into the quarter-rate v_mul_lo_u32; forcing v_mul_u32_u24 with inline asm
       // measured 22.25 against 22.19 ms — the asm pins the schedule — so it stays)
@@ -2342,7 +2361,11 @@ __global__ __launch_bounds__(kKdBlock, (ISO_ONLY ? EXA_AO_ISO_WAVES : EXA_PREPAS
 
 // MULTI: 0 = one primary channel; 1 = several, at most two TF tables in LDS (the 6-workgroup layout below); 2 = several, more tables
 // NCH: 0 = cell values field by field (the ABI's layout; one channel, or the channels one after the other);
-//      2..4 = that many primary channels from the channel-interleaved copy, all of them per brick visit (addBasisFastIl)
+//      2..4 = that many primary channels from the channel-interleaved copy, all of them per brick visit (addBasisFastIl);
+//      1 = one primary channel field by field as with 0, in a cube scene: the brick records are the 16-byte cube records
+//          (a.leafHdrCube, exa_cube.h; addBasisFast<.., CUBE>) and a lane keeps one int4 of the current record instead of two.
+//          MULTI == 0, ROPE, SMALL, not instrumented, form 1.  (A value of this parameter and not a parameter of its own: the
+//          variants are known to the profiling tools and the resource tests by this parameter list.)
 // ROPE: the walk is the rope walk (ropeStep) instead of the stack walk (kdStep); everything behind the segment queue is the same
 // waves per SIMD a variant of the march is compiled for.  Seven for the one-channel rope march (72 registers, no scratch; a
 // queue of five entries lets seven workgroups share a CU's LDS): C4 17.28 -> 17.08 ms, inside camera 22.60 -> 22.01, C5 1075 ->
@@ -2351,7 +2374,7 @@ __global__ __launch_bounds__(kKdBlock, (ISO_ONLY ? EXA_AO_ISO_WAVES : EXA_PREPAS
 // frame is heavy on HBM traffic already and a seventh wave costs it 2 %: 26.47 -> 27.04 ms).
 constexpr int marchWaves(int MULTI, int STATS, bool SMALL, int NCH, bool ROPE)
 {
-  return NCH ? (NCH == 2 ? EXA_IL2_WAVES : EXA_IL34_WAVES)
+  return NCH > 1 ? (NCH == 2 ? EXA_IL2_WAVES : EXA_IL34_WAVES)
              : (MULTI == 1 ? EXA_MULTI_WAVES
                            : (MULTI ? 5 : ((ROPE && !STATS && SMALL && EXA_BASIS_FORM == 1) ? EXA_ROPE_WAVES : EXA_MARCH_WAVES)));
 }
@@ -2359,14 +2382,25 @@ constexpr int marchWaves(int MULTI, int STATS, bool SMALL, int NCH, bool ROPE)
 template <bool GRAD, bool FAST, int MULTI, bool SURF, int STATS, bool SMALL, int NCH = 0, bool ROPE = false>
 __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE)) void renderFrameKdKernel(const RenderArgs a)
 {
-  constexpr bool LEAN = marchWaves(MULTI, STATS, SMALL, NCH, ROPE) >= 7;
+  // the template's NCH: 1 = the cube records, one channel; IL = the channels of the interleaved march (0: field by field)
+  constexpr bool CUBE = NCH == 1;
+  constexpr int IL = CUBE ? 0 : NCH;
+  static_assert(!CUBE || (MULTI == 0 && ROPE && SMALL && STATS == 0 && EXA_BASIS_FORM == 1 && !EXA_EMPTY_CELLS),
+                "the cube records are a variant of the shipped one-channel 32-bit rope march");
+  // The cube variants hold one int4 of the record instead of two, so they have the registers to keep |dir|^2 and the refined
+  // reciprocals across the march instead of forming them again (LEAN, which the other seven-wave variants need to stay within
+  // 72): C4 15.83 against 16.02 ms with LEAN (profiles/cube_records_bench.txt).  -DEXA_CUBE_LEAN=1 builds them with it.
+#ifndef EXA_CUBE_LEAN
+#define EXA_CUBE_LEAN 0
+#endif
+  constexpr bool LEAN = marchWaves(MULTI, STATS, SMALL, NCH, ROPE) >= 7 && (!CUBE || EXA_CUBE_LEAN);
   // Does the queue hand over the region's packed record (the march tree's leaf reference) or its id?  The 32-bit variants of the
   // rope march are launched only for scenes whose records pack (launchRenderKdT: `small`), its counting variant takes ids: known
   // when the kernel is compiled (no test of a kernel argument in the pop and at the leaf: C4 17.11 -> 17.03 ms).  Everything else
   // finds out from its arguments.
   constexpr int PACKED_CT = !ROPE ? -1 : (STATS == 1 ? 0 : (SMALL ? 1 : -1));
   const bool packedRec = PACKED_CT < 0 ? a.leafBeginBits != 0 : PACKED_CT != 0;
-  static_assert(NCH == 0 || (MULTI == 2 && STATS == 0), "the interleaved march is a multi-channel variant of the shipped kernel");
+  static_assert(IL == 0 || (MULTI == 2 && STATS == 0), "the interleaved march is a multi-channel variant of the shipped kernel");
   // Entries of the lane's short stack.  The two-table multi-channel march runs with one fewer: a workgroup then needs
   // 25 KB instead of 28 KB of LDS and a sixth workgroup fits a CU (C3: 30.8 -> 29.4 ms; a shorter stack alone costs ~1 %:
   // a dropped entry is re-found by a restart from the root).  With three tables the sixth workgroup does not fit either
@@ -2377,7 +2411,7 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
   // the occupancy a variant is compiled for is only reached if that many workgroups' LDS fit a CU (160 KB): the fewest TF
   // tables the variant is launched with (launchRenderKdT: one per primary channel; MULTI == 1: exactly two) + the lane's
   // queue, and for the stack walk its stack
-  static_assert(ldsFits(marchLds(MULTI == 1, ROPE, NCH ? NCH : (MULTI ? 2 : 1)), marchWaves(MULTI, STATS, SMALL, NCH, ROPE)),
+  static_assert(ldsFits(marchLds(MULTI == 1, ROPE, IL ? IL : (MULTI ? 2 : 1)), marchWaves(MULTI, STATS, SMALL, NCH, ROPE)),
                 "LDS per workgroup x waves per SIMD exceeds the CU's 160 KB: shorten the queue or lower the occupancy");
   const LdsPtrs lds = carveLds(marchLds(MULTI == 1, ROPE, a.numXfChannels));
   float4 *queue4 = lds.queue4;                                        // rope walk: 16-byte entries, one LDS access each
@@ -2461,11 +2495,11 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
     int4 hb0 = make_int4(0, 0, 0, 1), hb1 = make_int4(1, 1, 1, 0);
     Basis B;
     B.sumWV = 0.f; B.sumW = 0.f; B.sumD = mk(0.f, 0.f, 0.f); B.sumDC = mk(0.f, 0.f, 0.f);
-    // interleaved march: value-weighted sums of channels 1..NCH-1 (channel 0 and the shared sumW / sumDC live in B)
-    float xWV[NCH > 1 ? NCH - 1 : 1];
-    V3 xD[NCH > 1 ? NCH - 1 : 1];
+    // interleaved march: value-weighted sums of channels 1..IL-1 (channel 0 and the shared sumW / sumDC live in B)
+    float xWV[IL > 1 ? IL - 1 : 1];
+    V3 xD[IL > 1 ? IL - 1 : 1];
 #pragma unroll
-    for (int c = 0; c < (NCH > 1 ? NCH - 1 : 1); c++) { xWV[c] = 0.f; xD[c] = mk(0.f, 0.f, 0.f); }
+    for (int c = 0; c < (IL > 1 ? IL - 1 : 1); c++) { xWV[c] = 0.f; xD[c] = mk(0.f, 0.f, 0.f); }
     const float *field0 = a.sc.scalars + a.sc.channelOffset[0];   // wave-uniform
     const float *field = field0;
     // fast_math, one channel: the reciprocal of the TF range is the same for every sample of the frame; it is
@@ -2478,11 +2512,11 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       xfRcpRange0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__builtin_amdgcn_rcpf(xfRange0))));
     }
     // ... and with the interleaved march one per channel (a transcendental per channel and sample otherwise)
-    float xfRcpRangeN[NCH ? NCH : 1], xfRangeN[NCH ? NCH : 1];
+    float xfRcpRangeN[IL ? IL : 1], xfRangeN[IL ? IL : 1];
 #pragma unroll
-    for (int c = 0; c < (NCH ? NCH : 1); c++) {
-      xfRangeN[c] = (FAST && NCH) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((fs.xfDomain[c][1] - fs.xfDomain[c][0]) + 1e-20f))) : 0.f;
-      xfRcpRangeN[c] = (FAST && NCH) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__builtin_amdgcn_rcpf(xfRangeN[c])))) : 0.f;
+    for (int c = 0; c < (IL ? IL : 1); c++) {
+      xfRangeN[c] = (FAST && IL) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((fs.xfDomain[c][1] - fs.xfDomain[c][0]) + 1e-20f))) : 0.f;
+      xfRcpRangeN[c] = (FAST && IL) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__builtin_amdgcn_rcpf(xfRangeN[c])))) : 0.f;
     }
 
     unsigned iter = 0;
@@ -2560,7 +2594,9 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       // (requesting the NEXT visit's record here, behind this visit's cell loads — so that a visit in a region of several
       // bricks does not wait for two loads one after the other — was measured: C4 17.35 -> 18.92 ms; profiles/r05_experiments.txt)
       if (listSize > 1 || w.pk.get(PK_NEEDHDR)) {
-        if (SMALL) {                                       // the header array is below 4 GiB
+        if (CUBE) {                                        // the brick's cube record: one 16-byte load, one int4 kept (hb1 is never set)
+          hb0 = *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(a.leafHdrCube) + ((uint32_t)(listBegin + child) << 4));
+        } else if (SMALL) {                                // the header array is below 4 GiB
           const char *hp = reinterpret_cast<const char *>(a.sc.leafHdr) + ((uint32_t)(listBegin + child) << 5);
           hb0 = *reinterpret_cast<const int4 *>(hp); hb1 = *reinterpret_cast<const int4 *>(hp + 16);
         } else {
@@ -2571,7 +2607,8 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       }
       // (two consecutive samples of a one-brick segment per iteration, so that both samples' cell loads are in flight together, was
       // built and measured at 5 and 4 waves per SIMD: C4 17.34 -> 25.05 ms; profiles/r05_experiments.txt 9)
-      if (NCH) addBasisFastIl<GRAD, SMALL, (NCH ? NCH : 2)>(B, xWV, xD, hb0, hb1, a.cellsIl, rayAt(ray.org, t_sample, ray.dir));
+      if (IL) addBasisFastIl<GRAD, SMALL, (IL ? IL : 2)>(B, xWV, xD, hb0, hb1, a.cellsIl, rayAt(ray.org, t_sample, ray.dir));
+      else if (CUBE) addBasisFast<GRAD, STATS, SMALL, false, CUBE>(C, B, hb0, hb1, field0, rayAt(ray.org, t_sample, ray.dir), a.cubeLog2);
       else addBasisFast<GRAD, STATS, SMALL>(C, B, hb0, hb1, MULTI ? field : field0, rayAt(ray.org, t_sample, ray.dir));   // :1166
       child++;
       if (child < listSize) continue;
@@ -2579,12 +2616,12 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       // ---- all bricks of the region seen: finish this channel's sample (:800-806, :910-927) ----
       C.lap(ST_T_FINAL);
       C.phase(ST_W_FINAL);
-      if (NCH) {
+      if (IL) {
         // every primary channel's sample of this step, in channel order (:1163-1178); valid or not is the same for all
         // of them (sumW does not depend on the cell values)
         if (B.sumW > 1e-20f) {
 #pragma unroll
-          for (int c = 0; c < NCH; c++) {
+          for (int c = 0; c < IL; c++) {
             const float wv = c == 0 ? B.sumWV : xWV[c == 0 ? 0 : c - 1];
             const V3 sd = c == 0 ? B.sumD : xD[c == 0 ? 0 : c - 1];
             const float cellValue = fdivExact<FAST>(wv, B.sumW);
@@ -2594,7 +2631,7 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
           }
         }
 #pragma unroll
-        for (int c = 0; c < (NCH > 1 ? NCH - 1 : 1); c++) { xWV[c] = 0.f; xD[c] = mk(0.f, 0.f, 0.f); }
+        for (int c = 0; c < (IL > 1 ? IL - 1 : 1); c++) { xWV[c] = 0.f; xD[c] = mk(0.f, 0.f, 0.f); }
       } else if (B.sumW > 1e-20f) {
         C.count(ST_SAMPLES);
         const float cellValue = fdivExact<FAST>(B.sumWV, B.sumW);
@@ -2604,7 +2641,7 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       }
       B.sumWV = 0.f; B.sumW = 0.f; B.sumD = mk(0.f, 0.f, 0.f); B.sumDC = mk(0.f, 0.f, 0.f);
       child = 0;
-      if (MULTI && !NCH) {
+      if (MULTI && !IL) {
         chan++;
         if (chan < numChannels) {
           field = a.sc.scalars + a.sc.channelOffset[chan];
@@ -3150,6 +3187,17 @@ static hipError_t launchRenderKdT(const RenderArgs &a, int numBlocks, bool grad,
     return hipGetLastError();
   }
 #endif
+#if EXA_TU_ROPE && EXA_BASIS_FORM == 1 && !EXA_EMPTY_CELLS
+  // cube scene (a.leafHdrCube: exa_frame.cpp, option cube_records): the shipped one-channel 32-bit rope march on the cube records
+  if (ROPE && mode == 0 && !stats && small && fast && a.leafHdrCube) {
+#define EXA_CUBE(G, I) hipLaunchKernelGGL((renderFrameKdKernel<G, true, 0, I, 0, true, 1, ROPE>), grid, block, \
+                                          marchLds(false, ROPE, a.numXfChannels, EXA_LDS_PAD).total, s, a)
+    if (grad) { if (surf) EXA_CUBE(true, true); else EXA_CUBE(true, false); }
+    else      { if (surf) EXA_CUBE(false, true); else EXA_CUBE(false, false); }
+#undef EXA_CUBE
+    return hipGetLastError();
+  }
+#endif
   if (grad) { if (fast) EXA_PICKM(true, true); else EXA_PICKM(true, false); }
   else      { if (fast) EXA_PICKM(false, true); else EXA_PICKM(false, false); }
 #undef EXA_PICKM
@@ -3430,6 +3478,21 @@ hipError_t launchPermuteBricks(const float *src, float *dst, const uint32_t *src
   hipLaunchKernelGGL(permuteBricksKernel, dim3((unsigned)numBricks), dim3(256), 0, s, src, dst, srcBegin, dstBegin, bricks, totalCells, numFields);
   const unsigned long long n = numBricks > leafListSize ? numBricks : leafListSize;
   hipLaunchKernelGGL(patchBeginKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bricks, numBricks, leafHdr, leafList, leafListSize, dstBegin);
+  return hipGetLastError();
+}
+// the same for the cube records (exa_cube.h): the brick's index begin / S^3 above the nine level bits
+__global__ __launch_bounds__(256) void patchCubeRecordsKernel(int4 *leafHdrCube, const int32_t *leafList, unsigned long long leafListSize,
+                                                              const uint32_t *dstBegin, int cubeLog2)
+{
+  const unsigned long long i = blockIdx.x * 256ull + threadIdx.x;
+  if (i < leafListSize) leafHdrCube[i].w = (int)(((dstBegin[leafList[i]] >> (3 * cubeLog2)) << 9) | ((uint32_t)leafHdrCube[i].w & 0x1ffu));
+}
+hipError_t launchPatchCubeRecords(int4 *leafHdrCube, const int32_t *leafList, unsigned long long leafListSize,
+                                  const uint32_t *dstBegin, int cubeLog2, hipStream_t s)
+{
+  if (leafListSize == 0) return hipSuccess;
+  hipLaunchKernelGGL(patchCubeRecordsKernel, dim3((unsigned)((leafListSize + 255) / 256)), dim3(256), 0, s, leafHdrCube, leafList,
+                     leafListSize, dstBegin, cubeLog2);
   return hipGetLastError();
 }
 

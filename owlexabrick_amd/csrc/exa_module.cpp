@@ -243,6 +243,7 @@ int exa_hip_set_option(ExaHipRenderer *h, const char *key, int32_t value)
   if (!std::strcmp(key, "interleave")) { h->interleave = value != 0; return 0; }
   if (!std::strcmp(key, "addr64")) { h->addr64 = value != 0; return 0; }
   if (!std::strcmp(key, "pack_records")) { h->packRecords = value != 0; return 0; }
+  if (!std::strcmp(key, "cube_records")) { h->cubeRecords = value != 0; return 0; }
   if (!std::strcmp(key, "brick_order")) {
     if (value && !h->brickOrderPossible) {
       h->fail("exa_hip_set_option: brick_order 1 needs channel offsets f * totalCells and brick begins that partition [0, totalCells)");

@@ -10,6 +10,7 @@
 #include "../../include/exa_hip.h"
 #include "exa_ropes.h"
 #include "exa_coords.h"
+#include "exa_cube.h"
 
 #include <algorithm>
 #include <atomic>
@@ -435,6 +436,21 @@ int exa_prep_ropes(const ExaPrep *P, uint64_t *numLeaves, uint64_t *numNodes, fl
   }
   if (nodes) std::copy(rb.nodes.begin(), rb.nodes.end(), nodes);
   if (flags) *flags = (rb.boxesMatch ? 1 : 0) | (rb.planesOnGrid ? 2 : 0);
+  return 0;
+}
+
+// Diagnostic (tests/test_cube_records.py): the cube records exa_hip_create builds for the one-channel rope march (exa_cube.h),
+// on the host.  *log2Edge = k of the cube edge 2^k, or 0: the scene is no cube scene and nothing is built.  beginAlt (may be
+// NULL): the bricks' `begin` in the other brick order, held to the same conditions.  records (may be NULL): leafListSize x 4
+// words, filled when the scene is a cube scene.
+int exa_prep_cube_records(const ExaBrick *bricks, uint64_t numBricks, const int32_t *leafList, uint64_t leafListSize,
+                          const uint32_t *beginAlt, int32_t *log2Edge, int32_t *records)
+{
+  if (!bricks || !log2Edge || (leafListSize && !leafList)) { g_prepError = "exa_prep_cube_records: null argument"; return 1; }
+  for (uint64_t i = 0; i < leafListSize; i++)
+    if (leafList[i] < 0 || uint64_t(leafList[i]) >= numBricks) { g_prepError = "exa_prep_cube_records: leaf list entry out of range"; return 1; }
+  *log2Edge = exa::cubeSceneLog2(bricks, numBricks, beginAlt);
+  if (*log2Edge && records) exa::buildCubeRecords(bricks, leafList, leafListSize, *log2Edge, records);
   return 0;
 }
 

@@ -124,6 +124,11 @@ struct ExaHipRenderer {
   DevBuf<int4> bricks;
   DevBuf<int32_t> leafList;
   DevBuf<int4> leafHdr;
+  // Cube records (exa_cube.h): one int4 per leaf-list entry beside leafHdr, built when every brick is a cube of one edge
+  // 2^cubeLog2 (0: no cube scene, nothing built); the one-channel 32-bit rope march reads them instead of the march headers
+  DevBuf<int4> leafHdrCube;
+  int cubeLog2 = 0;
+  int cubeRecords = 1;               // option "cube_records": 0 = the march headers also in a cube scene
   DevBuf<float> scalars;
   // channel-interleaved copy of the primary channels, float[cell][ilChannels], for the multi-channel march (built on the
   // device by the first frame that marches 2..4 channels; the field-major arrays of the ABI stay for everything else)

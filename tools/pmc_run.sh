@@ -1,6 +1,7 @@
 #!/bin/bash
 # Collects rocprofv3 PMC counters for bench.py in separate passes (one rocprofv3 run per
 # counter group; never combined with trace options) and prints a per-kernel summary.
+# Ends at the first pass that fails, with that pass' exit status.
 # usage (on the GPU box): tools/pmc_run.sh <outdir> [bench args...]
 set -u
 OUT=$1; shift
@@ -18,7 +19,12 @@ PASSES=(
 )
 i=0
 for p in "${PASSES[@]}"; do
-  timeout -k 10 400 rocprofv3 --pmc $p --output-format csv -d "$OUT/pass$i" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --cpu-baseline off "$@" > "$OUT/pass$i.json" 2> "$OUT/pass$i.log" || { echo "pass $i failed"; tail -3 "$OUT/pass$i.log"; }
+  timeout -k 10 400 rocprofv3 --pmc $p --output-format csv -d "$OUT/pass$i" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --cpu-baseline off "$@" > "$OUT/pass$i.json" 2> "$OUT/pass$i.log"
+  status=$?
+  if [ $status -ne 0 ]; then        # nothing more is started on a GPU that a pass has failed or hung on
+    echo "pass $i failed (exit status $status)"; tail -3 "$OUT/pass$i.log"
+    exit $status
+  fi
   i=$((i+1))
 done
 python3 "$ROOT/tools/pmc_summary.py" "$OUT" | tee "$OUT/summary.txt"
