@@ -776,6 +776,68 @@ int exa_hip_streamlines_read(ExaHipRenderer *, float *vertices /* numVertices x 
 int exa_hip_streamlines_release(ExaHipRenderer *);
 int exa_hip_streamlines_ms(ExaHipRenderer *, float *ms);   /* device time of the last extraction's kernels, summed */
 
+/* ---- line integral convolution (LIC): the dense picture of where a vector field goes on a cut plane.  Per pixel of the
+ * plane lattice of exa_hip_isolines the field line of the in-plane part of three channels is followed backward and forward
+ * from the pixel's centre, and the noise of the pixels it passes is averaged (box filter).  The dense sibling of
+ * exa_hip_streamlines: one launch integrates and reduces in registers, nothing of size pixels x steps is stored. ----
+ *
+ * Space.  Voxel space only, for the reason exa_hip_streamlines states.  All float arithmetic is float32, every operation
+ * rounded separately, nothing contracted; sqrtf and `/` are correctly rounded.
+ *
+ * Lattice coordinates.  A position is c = (a, b) in pixel units; pixel (i, j) has its centre at (float(i) + 0.5f,
+ * float(j) + 0.5f); p(c) = (origin + a*du) + b*dv per component, the association of exa_hip_isolines' lattice points, so a
+ * centre is that lattice's point.  Output index j*nu + i; nu, nv >= 1, nu*nv <= 2^31 - 1.
+ *
+ * Plane metric, formed once: G11 = (du.x*du.x + du.y*du.y) + du.z*du.z, G12 (du.dv) and G22 (dv.dv) likewise,
+ * det = G11*G22 - G12*G12.  A plane with a non-finite float, or with det not finite or !(det > 0), is refused.
+ *
+ * Evaluation E2(c).  E(p(c)) is the E(q) of exa_hip_streamlines without EXA_STREAM_NORMALIZE: LEFT, NOVALUE, or v.  Then
+ * r1 = (v0*du.x + v1*du.y) + v2*du.z, r2 the same with dv; va = (G22*r1 - G12*r2) / det, vb = (G11*r2 - G12*r1) / det;
+ * s = sqrtf(va*va + vb*vb).  If !(s > 0) or s is not finite the outcome is STAGNANT (a field normal to the plane
+ * stagnates); otherwise d = (va/s, vb/s).  The lines are the field lines of the in-plane component; `step` is an arc length
+ * in pixels.
+ *
+ * One direction from the centre c0.  hs = +step forward, -step backward.  If E2(c0) fails, both directions end with that
+ * reason.  Otherwise, up to halfLength times:
+ *     k1 = hs*d(c)   k2 = hs*d(c + .5f*k1)   k3 = hs*d(c + .5f*k2)   k4 = hs*d(c + k3)
+ *     cn = c + (1/6.f) * (((k1 + 2.f*k2) + 2.f*k3) + k4)
+ * per component (the streamlines' step); a failing stage ends the direction with its reason.  cn bit-equal to c ends it
+ * STAGNANT.  !(cn.a >= 0.f && cn.a < float(nu) && cn.b >= 0.f && cn.b < float(nv)) ends it EXA_LIC_END_IMAGE.  Then E2(cn):
+ * a failure ends the direction with that reason and cn is not counted; otherwise the sample N((int)cn.a, (int)cn.b) is
+ * added, the direction's count goes up by one and d(cn) is the next k1.  After halfLength samples the reason is MAXSTEPS.
+ *
+ * Noise.  N(ix, iy) = noise[iy*nu + ix], or with noise == NULL the built-in hash, in uint32 arithmetic:
+ *     h = ix*0x9E3779B1 + iy*0x85EBCA77 + seed*0xC2B2AE3D
+ *     h ^= h>>16; h *= 0x7FEB352D; h ^= h>>15; h *= 0x846CA68B; h ^= h>>16; N = h>>24
+ * ((ix, iy, seed) = (1,0,0) -> 109, (0,1,0) -> 196, (3,5,7) -> 178, (66,44,1) -> 71).
+ *
+ * Outputs per pixel (a NULL pointer skips that array).  The centre's E fails (LEFT / NOVALUE): sum 0, count 0, lic = speed =
+ * fill, both reasons that reason.  The centre stagnates: sum = N(i, j), count 1, both reasons STAGNANT.  Otherwise sum =
+ * N(i, j) + the forward samples + the backward samples, count = 1 + both directions' counts, one reason per direction
+ * (reasons[2*k] backward, reasons[2*k+1] forward).  In the last two cases lic = float(sum) / float(count), one true division,
+ * and speed = sqrtf((v0*v0 + v1*v1) + v2*v2) at the centre.  The sums are integers of at most 8193 * 255: exact in uint32 and
+ * in float32 whatever the order they are added in.
+ *
+ * Independence.  The bytes depend only on the scene, the plane, channels, step, halfLength, the noise or the seed, fill and
+ * basis_form — not on anything a frame sets, nor on walk, accel, brick_order, interleave, lic_lanes, lic_patch or the other
+ * options, nor on whether the arrays are host or device memory.
+ *
+ * Calls.  Synchronous on hipStream; a pending brick_order change is applied first; a scene without a kd tree is refused; a
+ * multi-device handle runs on devices[0].  The arrays, the noise included, are host memory, or memory of the handle's first
+ * device with pointersAreDevice; host arrays pass through one device buffer of the call (up to 25 bytes per pixel).  Errors
+ * with a message that starts with "exa_hip_lic: ", after which the handle stays usable: a NULL plane or NULL channels; a
+ * non-finite plane float, the det rule, nu or nv < 1, more than 2^31 - 1 points; a channel outside [0, numFields); step not
+ * finite or <= 0; halfLength outside 1 .. EXA_LIC_MAX_STEPS; any flag bit (a non-finite fill is allowed); a failed
+ * allocation; the descent's loop guard (return code 3, as the probes).  exa_hip_lic_ms: the device time of the last call's
+ * kernels, summed; 0 before any call and after a refused one. */
+#define EXA_LIC_MAX_STEPS 4096     /* the cap of halfLength (per direction) */
+#define EXA_LIC_END_IMAGE 5        /* a direction ended because the line left the image; the other reasons are EXA_STREAM_END_* */
+int exa_hip_lic(ExaHipRenderer *, const ExaHipPlane *, const int32_t channels[3], float step, int32_t halfLength,
+                const uint8_t *noise /* nu*nv, or NULL: the built-in hash */, uint32_t seed, int32_t flags /* 0 */, float fill,
+                float *lic /* nu*nv */, uint32_t *sum, uint32_t *count, float *speed, int32_t *reasons /* nu*nv x 2: backward, forward */,
+                int32_t pointersAreDevice, void *hipStream);
+int exa_hip_lic_ms(ExaHipRenderer *, float *ms);
+
 /* ---- projections: the field itself reduced along lines of sight — per pixel the sum, the number, the maximum and the
  * minimum of the samples of one channel along a ray, as plain arrays: column density (sum*dt), the mean along the ray
  * (sum/count), maximum- and minimum-intensity images.  New relative to the reference, whose only images are RGBA8 pictures
@@ -1004,6 +1066,9 @@ int exa_hip_sample_triangles_ms(ExaHipRenderer *, float *ms);
  * (1, default) or lane by lane (0): same values bit for bit either way;
  * "surface_pack" 1 (default) = exa_hip_sample_triangles packs triangles of at most 16 samples into shared waves (groups of
  * 1, 4 or 16 lanes per triangle), 0 = every triangle gets a wave of its own: same bytes either way;
+ * "lic_lanes" 1 (default) = exa_hip_lic gives a pixel one lane, which integrates backward, then forward, 2 = a lane per pixel
+ * and direction, the pair's integer sums added by a lane exchange; "lic_patch" 1 (default) = a wave's pixels form a patch 8
+ * pixels wide (8 x 8, or 8 x 4 with two lanes per pixel), 0 = a row (64 x 1 / 32 x 1): same bytes in every layout;
  * "profile_marker" N = launch an empty kernel (profileMarkerKernel) on the null stream now: a bracket in a profiler's
  * dispatch list, no effect on any frame.
  * "walk" selects how the DVR march of the kd path finds its segments: 1 = the ordered walk of the region kd-tree with a

@@ -117,6 +117,9 @@ STREAM_NORMALIZE = 4
 STREAM_VELOCITIES = 8
 STREAM_MAX_STEPS = 1 << 20
 STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREAM_END_STAGNANT = range(5)
+# exa_hip_lic (include/exa_hip.h): the cap of half_length, and the end reason it adds to the STREAM_END_* ones
+LIC_MAX_STEPS = 4096
+LIC_END_IMAGE = 5
 
 # exa_hip_project (include/exa_hip.h)
 PROJECT_NORMALIZE = 4
@@ -268,6 +271,8 @@ _ABI = {
     "exa_hip_streamlines_read": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_streamlines_release": (None, [_vp]),
     "exa_hip_streamlines_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_lic": (None, [_vp, _P(ExaHipPlane), _vp, _f32, _i32, _vp, C.c_uint32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_lic_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_project": (None, [_vp, _P(ExaHipRays), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_project_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_raycast_iso": (None, [_vp, _P(ExaHipRays), _i32, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
@@ -970,6 +975,33 @@ class Renderer:
             return self.readStreamlines()
         finally:
             self.releaseStreamlines()
+
+    # ---- line integral convolution on a cut plane (exa_hip_lic; include/exa_hip.h states the contract) ----
+    def lic(self, plane, channels=(0, 1, 2), step=0.5, half_length=20, noise=None, seed=0, fill=float("nan"), stream=None):
+        """the dense picture of the in-plane direction of the vector field `channels` on plane = (origin, du, dv, (nu, nv)),
+        the lattice of isolines: per pixel the noise along its field line, `half_length` steps of `step` pixels backward and
+        forward, averaged.  noise: uint8 [nv, nu], or None for the built-in hash of (ix, iy, seed).  Returns a dict of arrays
+        [nv, nu]: lic (float32: sum / count; `fill` where the centre has no value), sum and count (uint32), speed (float32:
+        |v| at the centre) and reasons (int32 [nv, nu, 2]: STREAM_END_* or LIC_END_IMAGE, backward and forward)."""
+        origin, du, dv, size = plane
+        nu, nv = int(size[0]), int(size[1])
+        s = ExaHipPlane(_f3(origin), _f3(du), _f3(dv), nu, nv)
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, dtype=np.uint8)
+            if noise.size != nu * nv:
+                raise ValueError("lic: the noise must hold nu * nv bytes")
+        shape = (max(nv, 0), max(nu, 0))
+        out = dict(lic=np.empty(shape, np.float32), sum=np.empty(shape, np.uint32), count=np.empty(shape, np.uint32),
+                   speed=np.empty(shape, np.float32), reasons=np.empty(shape + (2,), np.int32))
+        self._check(lib().exa_hip_lic(self.h, C.byref(s), _i3(channels), float(step), int(half_length),
+                                      noise.ctypes.data if noise is not None else None, int(seed) & 0xFFFFFFFF, 0, float(fill),
+                                      out["lic"].ctypes.data, out["sum"].ctypes.data, out["count"].ctypes.data,
+                                      out["speed"].ctypes.data, out["reasons"].ctypes.data, 0, C.c_void_p(stream or 0)))
+        return out
+
+    def licMs(self):
+        """device ms of the last lic call's kernels, summed"""
+        return self._ms(lib().exa_hip_lic_ms)
 
     # ---- projections along rays (exa_hip_project; include/exa_hip.h states the contract) ----
     def project(self, org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples, channel=0, world=False,

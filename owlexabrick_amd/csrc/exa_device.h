@@ -340,6 +340,29 @@ struct StreamArgs {
   float             *velocities;    // numVertices x 3, or NULL
 };
 
+// Line integral convolution on a plane lattice (exa_hip_lic, exa_lic_kernels.h): RK4 in lattice coordinates along the in-plane
+// part of three channels, on the evaluation of the streamlines; the noise samples of a pixel's two directions are added up in
+// registers.  A wave holds the lanes of one patch of 64 / lanesPerPixel pixels, 2^patchShift of them along u.
+struct LicArgs {
+  SampleArgs         s;             // the lookup and the field (probeSetup); fieldOffset[0..2] = the three channels
+  float              origin[3], du[3], dv[3];
+  uint32_t           nu, nv;
+  float              g11, g12, g22, det;     // the plane's metric, formed on the host as the contract words it
+  float              step;
+  int32_t            halfLength;
+  const uint8_t     *noise;         // nu*nv, device; NULL: the built-in hash of (ix, iy, seed)
+  uint32_t           seed;
+  float              fill;
+  int32_t            lanesPerPixel; // 1: a lane integrates backward, then forward; 2: neighbouring lanes take one direction each
+  int32_t            patchShift;    // log2 of the patch's extent along u
+  uint32_t           patchesX;      // patches of the image along u
+  unsigned long long waveBase, numWaves;     // first patch of this launch; patches in all
+  // outputs (each may be NULL), index j*nu + i; reasons: two per pixel (backward, forward)
+  float             *lic, *speed;
+  uint32_t          *sum, *count;
+  int32_t           *reasons;
+};
+
 // ---- exa_lbvh.hip: LBVH topology over numPrims boxes (6 floats each, device), built on the device ----
 hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNode *nodes, int32_t *levelIds,
                                    std::vector<uint32_t> &internalNodesPerDepth, hipStream_t s);
@@ -379,7 +402,9 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
   hipError_t launchSampleTriangles(const TriArgs &a, bool uniform, hipStream_t s);                                   \
   /* the streamline integrator (exa_stream_f*.o): lanes [a.laneBase, a.numLanes) of at most 2^24 per launch; emit = the  \
      second launch, which stores the vertices */                                                                        \
-  hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);
+  hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);                                         \
+  /* line integral convolution (exa_stream_f*.o): the patches [a.waveBase, a.numWaves) of at most 2^18 per launch */    \
+  hipError_t launchLic(const LicArgs &a, hipStream_t s);
 namespace form0 { EXA_FORM_LAUNCHERS }
 namespace form1 { EXA_FORM_LAUNCHERS }
 // ... and once more in the source order with the reference's ALLOW_EMPTY_CELLS semantics (-DEXA_EMPTY_CELLS=1: a corner whose

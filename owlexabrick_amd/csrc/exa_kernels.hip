@@ -792,6 +792,8 @@ __device__ __forceinline__ bool samplePoint(Ctx<STATS> &C, float &value, V3 &der
 #elif EXA_TU_STREAM
 // the streamline integrator (exa_hip_streamlines) in translation units of its own (-DEXA_TU_STREAM=1: exa_stream_f*.o)
 #include "exa_stream_kernels.h"
+// ... and the line integral convolution on its evaluation (exa_hip_lic)
+#include "exa_lic_kernels.h"
 } // namespace EXA_FORM_NS
 #else
 

@@ -240,6 +240,11 @@ int exa_hip_set_option(ExaHipRenderer *h, const char *key, int32_t value)
   }
   if (!std::strcmp(key, "sample_uniform")) { h->probes.uniform = value != 0; return 0; }
   if (!std::strcmp(key, "surface_pack")) { h->surface.pack = value != 0; return 0; }
+  if (!std::strcmp(key, "lic_lanes")) {
+    if (value != 1 && value != 2) { h->fail("exa_hip_set_option: lic_lanes is 1 (a lane per pixel) or 2 (a lane per pixel and direction)"); return 1; }
+    h->lic.lanes = value; return 0;
+  }
+  if (!std::strcmp(key, "lic_patch")) { h->lic.patch = value != 0; return 0; }
   if (!std::strcmp(key, "interleave")) { h->interleave = value != 0; return 0; }
   if (!std::strcmp(key, "addr64")) { h->addr64 = value != 0; return 0; }
   if (!std::strcmp(key, "pack_records")) { h->packRecords = value != 0; return 0; }

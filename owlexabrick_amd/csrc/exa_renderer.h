@@ -1,7 +1,8 @@
 // exa_renderer.h — internal to the exa_hip_* module (not installed): the renderer behind the opaque ExaHipRenderer handle
 // of include/exa_hip.h and the helpers its translation units share.  exa_create.cpp builds and destroys a renderer,
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes, the projections along rays and the
-// iso-surface extraction, exa_streamlines.cpp the streamline extraction, exa_stats.cpp the histogram and value range of
+// iso-surface extraction, exa_streamlines.cpp the streamline extraction and the line integral convolution on its
+// evaluation, exa_stats.cpp the histogram and value range of
 // the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
 // one struct per call (ExaHipRenderer::probes, isoMesh, isolines, isoRegions, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
 // argument checks below the renderer are what their host code shares.
@@ -357,6 +358,13 @@ struct ExaHipRenderer {
       have = false;
     }
   } lines;
+  // exa_hip_lic (in the renderer of devices[0] as well): the device time of the last call's kernels, summed, and how the
+  // lanes are laid out — options "lic_lanes" (lanes per pixel, 1 or 2) and "lic_patch" (0 = a wave's pixels in a row,
+  // 1 = in a patch 8 pixels wide); the bytes are the same in every layout
+  struct Lic {
+    float kernelMs = 0.f;
+    int lanes = 1, patch = 1;
+  } lic;
   // the device time of the last exa_hip_project's kernel launches, summed (in the renderer of devices[0])
   struct Projection {
     float kernelMs = 0.f;

@@ -18,8 +18,9 @@
 // Brick loop outside, channels inside: the three addBasisFast calls of a brick share its two header loads, its cell
 // coordinates, predicates and masked per-axis weights (the same pure expressions of h0, h1 and q: formed once), and each
 // channel's sums see the additions of sampleSums on that channel in the same order.
-template <bool NORM>
-__device__ __forceinline__ int streamEval(const StreamArgs &a, V3 q, V3 &v, V3 &d, bool &tripped)
+// Args: StreamArgs, or the LicArgs of exa_lic_kernels.h (a.s is all that is read).
+template <bool NORM, typename Args>
+__device__ __forceinline__ int streamEval(const Args &a, V3 q, V3 &v, V3 &d, bool &tripped)
 {
   const int region = sampleInRoot(a.s, q) ? sampleKdLeaf(a.s, a.s.kdRoot, q, tripped) : -1;
   if (region < 0) return EXA_STREAM_END_LEFT;

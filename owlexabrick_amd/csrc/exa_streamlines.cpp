@@ -2,6 +2,8 @@
 // packed polylines (kernels in exa_stream_kernels.h; include/exa_hip.h states the contract).  Count, then emit: the
 // integration runs twice, the first time storing only how many vertices every direction appends and why it ended; the
 // counts are scanned on the host (the call is synchronous), and the second run stores every vertex at its packed position.
+// Behind it exa_hip_lic, the dense sibling on a plane lattice (kernel in exa_lic_kernels.h, in the same units): one launch,
+// nothing counted first and nothing emitted but the image.
 #include "exa_renderer.h"
 
 #include <cmath>
@@ -168,6 +170,106 @@ int exa_hip_streamlines_ms(ExaHipRenderer *h, float *ms)
 {
   if (!h || !ms) return 1;
   *ms = firstChild(h)->lines.kernelMs;
+  return 0;
+}
+
+// ---- line integral convolution on a plane lattice (streamlinesKernelLic, exa_lic_kernels.h) ----
+// One launch per 2^18 patches (2^24 lanes).  Host arrays pass through one device buffer of the call, {lic | sum | count |
+// speed | reasons | noise}: every part a multiple of 4 bytes in front of the noise, so each is aligned to its element; a
+// line crosses the whole image, so the image is not cut into tiles.
+int exa_hip_lic(ExaHipRenderer *h, const ExaHipPlane *plane, const int32_t channels[3], float step, int32_t halfLength,
+                const uint8_t *noise, uint32_t seed, int32_t flags, float fill, float *lic, uint32_t *sum, uint32_t *count,
+                float *speed, int32_t *reasons, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_lic";
+  ExaHipRenderer *r = firstChild(h);
+  r->lic.kernelMs = 0.f;
+  if (!plane || !channels) { h->fail(std::string(fn) + ": null argument (the plane or the channels)"); return 1; }
+  for (int k = 0; k < 3; k++)
+    if (!(std::isfinite(plane->origin[k]) && std::isfinite(plane->du[k]) && std::isfinite(plane->dv[k]))) {
+      h->fail(std::string(fn) + ": the plane's origin, du and dv must be finite");
+      return 1;
+    }
+  if (plane->nu < 1 || plane->nv < 1) { h->fail(std::string(fn) + ": nu and nv must be >= 1"); return 1; }
+  const uint64_t n = uint64_t(plane->nu) * uint64_t(plane->nv);
+  if (n > uint64_t(INT32_MAX)) { h->fail(std::string(fn) + ": an image of more than 2^31 - 1 points"); return 1; }
+  // the plane's metric, every operation rounded separately
+  const float *du = plane->du, *dv = plane->dv;
+  const float g11 = (du[0] * du[0] + du[1] * du[1]) + du[2] * du[2];
+  const float g12 = (du[0] * dv[0] + du[1] * dv[1]) + du[2] * dv[2];
+  const float g22 = (dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2];
+  const float p1 = g11 * g22, p2 = g12 * g12, det = p1 - p2;
+  if (!std::isfinite(det) || !(det > 0.f)) {
+    h->fail(std::string(fn) + ": du and dv do not span a plane (G11*G22 - G12*G12 must be finite and > 0 in float32)");
+    return 1;
+  }
+  for (int c = 0; c < 3; c++)
+    if (!checkChannel(h, fn, channels[c])) return 1;
+  if (!(std::isfinite(step) && step > 0.f)) { h->fail(std::string(fn) + ": step must be finite and > 0"); return 1; }
+  if (halfLength < 1 || halfLength > EXA_LIC_MAX_STEPS) { h->fail(std::string(fn) + ": halfLength must be in 1.." + std::to_string(EXA_LIC_MAX_STEPS)); return 1; }
+  if (!checkFlags(h, fn, flags, 0, " (none is defined)")) return 1;
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  LicArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (probeSetup(h, r, fn, false, s, a.s)) return 1;
+  a.s.numChannels = 3;
+  for (int c = 0; c < 3; c++) a.s.fieldOffset[c] = r->sc.channelOffset[channels[c]];
+  for (int k = 0; k < 3; k++) { a.origin[k] = plane->origin[k]; a.du[k] = du[k]; a.dv[k] = dv[k]; }
+  a.nu = uint32_t(plane->nu); a.nv = uint32_t(plane->nv);
+  a.g11 = g11; a.g12 = g12; a.g22 = g22; a.det = det;
+  a.step = step;
+  a.halfLength = halfLength;
+  a.seed = seed;
+  a.fill = fill;
+  a.lanesPerPixel = r->lic.lanes;
+  const uint32_t perWave = 64u / uint32_t(a.lanesPerPixel);
+  a.patchShift = r->lic.patch ? 3 : (a.lanesPerPixel == 2 ? 5 : 6);
+  const uint64_t pw = 1ull << a.patchShift, ph = perWave >> a.patchShift;
+  a.patchesX = uint32_t((a.nu + pw - 1) / pw);
+  a.numWaves = uint64_t(a.patchesX) * ((a.nv + ph - 1) / ph);
+
+  const bool staged = !pointersAreDevice;
+  DevBuf<char> stage;
+  if (staged) {
+    const size_t bytes = (lic ? 4 * n : 0) + (sum ? 4 * n : 0) + (count ? 4 * n : 0) + (speed ? 4 * n : 0) + (reasons ? 8 * n : 0) + (noise ? n : 0);
+    const hipError_t e = stage.alloc(bytes);
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the image's arrays (up to 25 bytes per pixel with host pointers)", e);
+    char *cut = stage.p;
+    auto carve = [&](const void *user, size_t size) { char *part = user ? cut : nullptr; if (user) cut += size; return part; };
+    a.lic = reinterpret_cast<float *>(carve(lic, 4 * n));
+    a.sum = reinterpret_cast<uint32_t *>(carve(sum, 4 * n));
+    a.count = reinterpret_cast<uint32_t *>(carve(count, 4 * n));
+    a.speed = reinterpret_cast<float *>(carve(speed, 4 * n));
+    a.reasons = reinterpret_cast<int32_t *>(carve(reasons, 8 * n));
+    a.noise = reinterpret_cast<const uint8_t *>(carve(noise, n));
+    if (noise) HIP_TRY(h, hipMemcpyAsync(const_cast<uint8_t *>(a.noise), noise, n, hipMemcpyHostToDevice, s));
+  } else {
+    a.lic = lic; a.sum = sum; a.count = count; a.speed = speed; a.reasons = reasons; a.noise = noise;
+  }
+  TimingEvents<2> t;
+  HIP_TRY(h, t.create());
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  for (a.waveBase = 0; a.waveBase < a.numWaves; a.waveBase += 1ull << 18) HIP_TRY(h, EXA_FORM(r, launchLic)(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  if (staged) {
+    if (lic) HIP_TRY(h, hipMemcpyAsync(lic, a.lic, 4 * n, hipMemcpyDeviceToHost, s));
+    if (sum) HIP_TRY(h, hipMemcpyAsync(sum, a.sum, 4 * n, hipMemcpyDeviceToHost, s));
+    if (count) HIP_TRY(h, hipMemcpyAsync(count, a.count, 4 * n, hipMemcpyDeviceToHost, s));
+    if (speed) HIP_TRY(h, hipMemcpyAsync(speed, a.speed, 4 * n, hipMemcpyDeviceToHost, s));
+    if (reasons) HIP_TRY(h, hipMemcpyAsync(reasons, a.reasons, 8 * n, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(h, hipStreamSynchronize(s));
+  if (int rc = checkLoopGuard(h, r, fn, kDescentGuard)) return rc;
+  HIP_TRY(h, t.elapsed(0, 1, &r->lic.kernelMs));
+  return 0;
+}
+
+int exa_hip_lic_ms(ExaHipRenderer *h, float *ms)
+{
+  if (!h || !ms) return 1;
+  *ms = firstChild(h)->lic.kernelMs;
   return 0;
 }
 

@@ -40,6 +40,14 @@
 //                                            (V x 2 float32, lattice coordinates), segments (S x 2 int32, indices into the
 //                                            vertices); --frames 0 renders nothing; with
 //             [--isolines-world]             the plane is in world space
+//             [--lic C0,C1,C2 ox oy oz ux uy uz vx vy vz NU NV STEP HALFLENGTH out.lic] line integral convolution of the vector
+//                                            field of channels C0 C1 C2 on the plane lattice of --isolines, voxel space
+//                                            (exa_hip_lic: per pixel the built-in noise along the field line of the in-plane
+//                                            part, HALFLENGTH steps of STEP pixels backward and forward, averaged).  One text
+//                                            line `lic NU NV channels C0 C1 C2 step STEP halfLength L seed N`, then the image:
+//                                            NU*NV raw little-endian float32, row j = 0 first (NaN where the pixel's centre has
+//                                            no value); --frames 0 renders nothing; with
+//             [--lic-seed N]                 the seed of the built-in noise (default 0)
 //             [--regions CHANNEL ISO NX NY NZ out.regions] the connected regions of field >= ISO of CHANNEL on that lattice
 //                                            (exa_hip_regions: joined along the edges of --isomesh's tetrahedra, numbered by
 //                                            their smallest lattice index, exact measurements per region).  With --derived the
@@ -202,6 +210,13 @@ int main(int argc, char **argv)
     vec2i linesSize;
     std::vector<float> linesIsos;
     bool linesWorld = false;
+    std::string licName;
+    vec3i licChannels(0, 1, 2);
+    vec3f licOrigin, licDu, licDv;
+    vec2i licSize;
+    float licStep = 0.5f;
+    int licHalfLength = 20;
+    uint32_t licSeed = 0;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -274,6 +289,19 @@ int main(int argc, char **argv)
         linesName = argv[++i];
       }
       else if (a == "--isolines-world") linesWorld = true;
+      else if (a == "--lic") {
+        if (i + 1 >= argc) throw std::runtime_error("missing channels after --lic");
+        char tail = 0;
+        if (std::sscanf(argv[++i], "%d,%d,%d%c", &licChannels.x, &licChannels.y, &licChannels.z, &tail) != 3)
+          throw std::runtime_error("--lic wants three comma-separated channels C0,C1,C2");
+        licOrigin = { f(), f(), f() }; licDu = { f(), f(), f() }; licDv = { f(), f(), f() };
+        licSize.x = (int)f(); licSize.y = (int)f();
+        licStep = f();
+        licHalfLength = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --lic C0,C1,C2 o u v NU NV STEP HALFLENGTH");
+        licName = argv[++i];
+      }
+      else if (a == "--lic-seed") { if (i + 1 >= argc) throw std::runtime_error("missing value after --lic-seed"); licSeed = (uint32_t)std::strtoul(argv[++i], nullptr, 10); }
       else if (a == "--regions") {
         regionsChannel = (int)f();
         regionsIso = f();
@@ -479,6 +507,21 @@ int main(int argc, char **argv)
       else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
       std::printf("world %d levels %zu vertices %zu segments %zu\n", linesWorld ? 1 : 0, n, nv, ns);
     }
+    if (!licName.empty()) {
+      const Renderer::Lic L = renderer.lic(licOrigin, licDu, licDv, licSize, licChannels, licStep, licHalfLength, nullptr, licSeed);
+      FILE *f = std::fopen(licName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + licName);
+      const size_t n = L.lic.size();
+      std::fprintf(f, "lic %d %d channels %d %d %d step %.9g halfLength %d seed %u\n", licSize.x, licSize.y, licChannels.x, licChannels.y,
+                   licChannels.z, licStep, licHalfLength, licSeed);
+      const bool ok = std::fwrite(L.lic.data(), 4, n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + licName);
+      size_t covered = 0;
+      unsigned long long samples = 0;
+      for (uint32_t c : L.count) { covered += c > 0; samples += c; }
+      std::printf("lic %d %d channels %d %d %d step %.9g halfLength %d seed %u pixels_covered %zu samples %llu\n", licSize.x, licSize.y,
+                  licChannels.x, licChannels.y, licChannels.z, licStep, licHalfLength, licSeed, covered, samples);
+    }
     if (!regionsName.empty()) {
       const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
       const vec3i dims(regionsDims[0], regionsDims[1], regionsDims[2]);
@@ -613,7 +656,8 @@ int main(int argc, char **argv)
                   raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
-                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty())) return 0;
+                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty()
+                        || !licName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

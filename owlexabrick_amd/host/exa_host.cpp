@@ -753,6 +753,20 @@ Renderer::Streamlines Renderer::streamlines(const vec3f *seeds, size_t n, vec3i 
   return L;
 }
 
+Renderer::Lic Renderer::lic(vec3f origin, vec3f du, vec3f dv, vec2i size, vec3i channels, float step, int halfLength,
+                            const uint8_t *noise, uint32_t seed, float fill)
+{
+  const ExaHipPlane plane = planeOf(origin, du, dv, size);
+  const int32_t ch[3] = { channels.x, channels.y, channels.z };
+  // 0 pixels for a size the module refuses (it checks the size)
+  const size_t n = size.x > 0 && size.y > 0 && uint64_t(size.x) * uint64_t(size.y) <= uint64_t(INT32_MAX) ? size_t(size.x) * size_t(size.y) : 0;
+  Lic L;
+  L.lic.resize(n); L.speed.resize(n); L.sum.resize(n); L.count.resize(n); L.reason.resize(2 * n);
+  check(exa_hip_lic(handle, &plane, ch, step, halfLength, noise, seed, 0, fill, L.lic.data(), L.sum.data(), L.count.data(),
+                    L.speed.data(), L.reason.data(), 0, nullptr), handle);
+  return L;
+}
+
 // the pixels of the rays' image, 0 for a size the module refuses (it checks the size)
 static size_t rayPixels(const ExaHipRays &rays)
 {

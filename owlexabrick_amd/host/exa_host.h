@@ -283,6 +283,18 @@ struct Renderer {
   Streamlines streamlines(const vec3f *seeds, size_t n, vec3i channels, float step, int maxSteps, bool forward = true,
                           bool backward = false, bool normalize = false, bool velocities = false);
 
+  // line integral convolution of the vector field (channels.x, .y, .z) on the plane lattice of isolines, in VOXEL space
+  // (exa_hip_lic; include/exa_hip.h states the contract): per pixel the noise — `noise` (size.x * size.y bytes) or, for NULL,
+  // the built-in hash of (ix, iy, seed) — along the field line of the in-plane part, halfLength steps of `step` pixels
+  // backward and forward, averaged.  Row-major, index j*size.x + i; a pixel whose centre has no value gets `fill`.
+  struct Lic {
+    std::vector<float> lic, speed;       // sum / count; |v| at the centre
+    std::vector<uint32_t> sum, count;
+    std::vector<int32_t> reason;         // 2 per pixel: EXA_STREAM_END_* or EXA_LIC_END_IMAGE, backward and forward
+  };
+  Lic lic(vec3f origin, vec3f du, vec3f dv, vec2i size, vec3i channels, float step, int halfLength,
+          const uint8_t *noise = nullptr, uint32_t seed = 0, float fill = NAN);
+
   // the field of `channel` reduced along one ray per pixel (exa_hip_project; include/exa_hip.h states the contract): pixel
   // (x, y) of the rays.width x rays.height image starts at org + (x+.5)*orgDu + (y+.5)*orgDv, runs along
   // dir + (x+.5)*dirDu + (y+.5)*dirDv (normalize: divided by its length) and is sampled at tmin + (i+.5)*dt, i < numSamples,
