@@ -838,6 +838,74 @@ int exa_hip_lic(ExaHipRenderer *, const ExaHipPlane *, const int32_t channels[3]
                 int32_t pointersAreDevice, void *hipStream);
 int exa_hip_lic_ms(ExaHipRenderer *, float *ms);
 
+/* ---- flow map and stretch: the Lagrangian view of a vector field.  From every point of a lattice a particle is carried along
+ * the field of three channels for the time T = numSteps * step; the flow map is where it ends, and the stretch is the largest
+ * eigenvalue of the Cauchy-Green tensor of the map's differences, from which the finite-time Lyapunov exponent (FTLE) follows:
+ * the ridges of that field are the separatrices, the separation (forward) and attachment (backward) lines and the edges of
+ * vortices.  One launch integrates with only the end state kept in registers, a second one runs the stencil; nothing of size
+ * points x numSteps is stored. ----
+ *
+ * Space.  Voxel space only, for the reason exa_hip_streamlines states.  All float arithmetic is float32, every operation
+ * rounded separately, nothing contracted; `/` and sqrtf are correctly rounded; no transcendental function runs on the device.
+ *
+ * Lattice.  lo, hi, dims as for exa_hip_resample, dims >= 1 per axis, nx*ny*nz <= 2^31 - 1: point (i,j,k) lies at
+ * P = lo + (float(i) + 0.5f) * ((hi - lo) / float(n)) per axis.  Linear index L = (k*ny + j)*nx + i, n = nx*ny*nz points.
+ *
+ * Flow map.  end(L), steps(L), reasons(L) are taken from the line that exa_hip_streamlines(seeds = {P(L)}, channels, step,
+ * maxSteps = numSteps, flags = the one direction) returns — its "One direction" paragraph, without EXA_STREAM_NORMALIZE, so
+ * `step` is a time: end(L) is the last vertex of that line bit for bit, steps(L) its vertex count minus one, reasons(L) that
+ * direction's reason.  A seed whose own evaluation fails gives end = P(L), steps = 0 and its reason.
+ *
+ * Validity.  valid(L) = reasons(L) is EXA_STREAM_END_MAXSTEPS or EXA_STREAM_END_STAGNANT: a particle that stagnates stays where
+ * it is for the rest of the time.
+ *
+ * Stencil.  Per axis a with n_a >= 2, m_a is the neighbour of L at index max(i_a - 1, 0) and p_a the one at min(i_a + 1, n_a - 1):
+ * central differences inside, one-sided ones on the lattice's faces.  Column a of the deformation gradient is
+ *     F[c][a] = (end_c(p_a) - end_c(m_a)) / (P_a(p_a) - P_a(m_a))          c = 0, 1, 2
+ * and the column of an axis with n_a == 1 is zero: a plane or a line of points gives the 2-D / 1-D stretch of the 3-D
+ * displacement.  stretch(L) = fill unless L and every stencil point of L are valid.
+ *
+ * Tensor.  C_ab = (F[0][a]*F[0][b] + F[1][a]*F[1][b]) + F[2][a]*F[2][b] for the six entries ab = 00, 11, 22, 01, 02, 12.
+ *
+ * Largest eigenvalue.  Five sweeps of cyclic Jacobi on the symmetric a = C, each sweep the rotations (p,q) = (0,1), (0,2),
+ * (1,2), r the third index.  A rotation is skipped if and only if a_pq == 0.0f; otherwise, in this order,
+ *     theta = (a_qq - a_pp) / (2.f*a_pq)
+ *     t = copysignf(1.f, theta) / (fabsf(theta) + sqrtf(theta*theta + 1.f))
+ *     c = 1.f / sqrtf(t*t + 1.f)        s = t*c
+ *     a_pp' = a_pp - t*a_pq             a_qq' = a_qq + t*a_pq
+ *     a_rp' = c*a_rp - s*a_rq           a_rq' = s*a_rp + c*a_rq          a_pq' = 0
+ * (t*a_pq is one product, used twice).  Then m = a_00; if (a_11 > m) m = a_11; if (a_22 > m) m = a_22; stretch(L) = m.  NaN and
+ * infinities propagate by these formulas, nothing is special-cased.
+ *
+ * FTLE.  Never formed on the device (logf is not correctly rounded, and the outputs here are byte-exact).
+ * FTLE = log(stretch) / (2 * |T|), T = numSteps * step, formed in double and rounded to float; fill where stretch is fill.  The
+ * binding, the host library and exaRender form it so.
+ *
+ * Independence.  As the streamlines: the bytes depend only on the scene, the lattice, channels, step, numSteps, the direction,
+ * fill and basis_form — not on anything a frame sets, nor on walk, accel, brick_order, interleave, flowmap_patch or the other
+ * options, nor on whether the arrays are host or device memory; end, steps and reasons of point L equal the one-point call.
+ *
+ * Calls.  Synchronous on hipStream; a pending brick_order change is applied first; a scene without a kd tree is refused; a
+ * multi-device handle runs on devices[0]; a NULL output pointer skips that array.  The arrays are host memory, or memory of the
+ * handle's first device with pointersAreDevice.  Errors with a message that starts with "exa_hip_flowmap: ", after which the
+ * handle stays usable: NULL lo, hi, dims or channels; the box and dims errors of exa_hip_resample, more than 2^31 - 1 points; a
+ * channel outside [0, numFields); step not finite or <= 0; numSteps outside 1 .. EXA_STREAM_MAX_STEPS; neither or both
+ * direction flags, unknown flag bits (a non-finite fill is allowed); a failed allocation; the descent's loop guard (return
+ * code 3, as the probes).
+ *
+ * Memory.  One device buffer of the call: with host pointers every array asked for, and end and reasons also when only the
+ * stretch is asked for (at most 24 bytes per point); with device pointers only what the stretch reads and the caller did not
+ * ask for (end 12, reasons 4: at most 16 bytes per point, nothing when end and reasons are given or stretch is NULL).
+ * exa_hip_flowmap_ms: the device time of the last call's two stages, integrate and stretch; both 0 before any call and after a
+ * refused one. */
+#define EXA_FLOWMAP_FORWARD  1      /* exactly one of the two */
+#define EXA_FLOWMAP_BACKWARD 2
+int exa_hip_flowmap(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                    const int32_t channels[3], float step, int32_t numSteps, int32_t flags, float fill,
+                    float *end /* n x 3 */, uint32_t *steps /* n */, int32_t *reasons /* n */, float *stretch /* n */,
+                    int32_t pointersAreDevice, void *hipStream);
+int exa_hip_flowmap_ms(ExaHipRenderer *, float ms[2]);   /* integrate, stretch */
+
 /* ---- projections: the field itself reduced along lines of sight — per pixel the sum, the number, the maximum and the
  * minimum of the samples of one channel along a ray, as plain arrays: column density (sum*dt), the mean along the ray
  * (sum/count), maximum- and minimum-intensity images.  New relative to the reference, whose only images are RGBA8 pictures
@@ -1069,6 +1137,8 @@ int exa_hip_sample_triangles_ms(ExaHipRenderer *, float *ms);
  * "lic_lanes" 1 (default) = exa_hip_lic gives a pixel one lane, which integrates backward, then forward, 2 = a lane per pixel
  * and direction, the pair's integer sums added by a lane exchange; "lic_patch" 1 (default) = a wave's pixels form a patch 8
  * pixels wide (8 x 8, or 8 x 4 with two lanes per pixel), 0 = a row (64 x 1 / 32 x 1): same bytes in every layout;
+ * "flowmap_patch" 1 (default) = a wave of exa_hip_flowmap takes a 4 x 4 x 4 patch of lattice points (an axis shorter than 4
+ * gives its share to the others: 8 x 8 x 1 on a plane), 0 = 64 points along x: same bytes either way;
  * "profile_marker" N = launch an empty kernel (profileMarkerKernel) on the null stream now: a bracket in a profiler's
  * dispatch list, no effect on any frame.
  * "walk" selects how the DVR march of the kd path finds its segments: 1 = the ordered walk of the region kd-tree with a

@@ -120,6 +120,9 @@ STREAM_END_NONE, STREAM_END_MAXSTEPS, STREAM_END_LEFT, STREAM_END_NOVALUE, STREA
 # exa_hip_lic (include/exa_hip.h): the cap of half_length, and the end reason it adds to the STREAM_END_* ones
 LIC_MAX_STEPS = 4096
 LIC_END_IMAGE = 5
+# exa_hip_flowmap (include/exa_hip.h): exactly one of the two directions
+FLOWMAP_FORWARD = 1
+FLOWMAP_BACKWARD = 2
 
 # exa_hip_project (include/exa_hip.h)
 PROJECT_NORMALIZE = 4
@@ -273,6 +276,8 @@ _ABI = {
     "exa_hip_streamlines_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_lic": (None, [_vp, _P(ExaHipPlane), _vp, _f32, _i32, _vp, C.c_uint32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_lic_ms": (None, [_vp, _P(_f32)]),
+    "exa_hip_flowmap": (None, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_flowmap_ms": (None, [_vp, _vp]),
     "exa_hip_project": (None, [_vp, _P(ExaHipRays), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_project_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_raycast_iso": (None, [_vp, _P(ExaHipRays), _i32, _f32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
@@ -1003,6 +1008,30 @@ class Renderer:
         """device ms of the last lic call's kernels, summed"""
         return self._ms(lib().exa_hip_lic_ms)
 
+    # ---- flow map and FTLE stretch on a lattice (exa_hip_flowmap; include/exa_hip.h states the contract) ----
+    def flowmap(self, lo, hi, dims, channels=(0, 1, 2), step=0.5, num_steps=20, backward=False, fill=float("nan"), stream=None):
+        """where a particle released at every point of the lattice of resample (lo, hi, dims; voxel space) is after num_steps
+        RK4 steps of the time `step` through the vector field `channels`, forward or backward, and how much the map stretches.
+        Returns a dict of arrays [nz, ny, nx]: end (float32 [nz, ny, nx, 3]), steps (uint32), reasons (int32, STREAM_END_*),
+        stretch (float32: the largest eigenvalue of the Cauchy-Green tensor; `fill` where the point or a stencil neighbour did
+        not last the time) and ftle (float32: log(stretch) / (2 |T|), T = num_steps * step, formed in float64; `fill` where
+        stretch is)."""
+        shape = tuple(max(int(d), 0) for d in tuple(dims)[::-1])                # the module checks the dims
+        out = dict(end=np.empty(shape + (3,), np.float32), steps=np.empty(shape, np.uint32), reasons=np.empty(shape, np.int32),
+                   stretch=np.empty(shape, np.float32))
+        self._check(lib().exa_hip_flowmap(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), float(step), int(num_steps),
+                                          FLOWMAP_BACKWARD if backward else FLOWMAP_FORWARD, float(fill), out["end"].ctypes.data,
+                                          out["steps"].ctypes.data, out["reasons"].ctypes.data, out["stretch"].ctypes.data, 0,
+                                          C.c_void_p(stream or 0)))
+        out["ftle"] = ftle_of_stretch(out["stretch"], step, num_steps, fill)
+        return out
+
+    def flowmapMs(self):
+        """device ms of the last flowmap call's two stages: (integrate, stretch)"""
+        ms = (C.c_float * 2)(0, 0)
+        self._check(lib().exa_hip_flowmap_ms(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
     # ---- projections along rays (exa_hip_project; include/exa_hip.h states the contract) ----
     def project(self, org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples, channel=0, world=False,
                 normalize=False, stream=None):
@@ -1128,6 +1157,16 @@ def region_measures(regions, sum_exponent, lo, hi, dims):
     cell = float(np.prod(step))
     return dict(sum=total, mean=total / points, volume=points * cell, integral=total * cell,
                 centroid=lo + (regions["sumIndex"].astype(np.float64) / points[:, None] + 0.5) * step)
+
+
+def ftle_of_stretch(stretch, step, num_steps, fill=float("nan")):
+    """FTLE = log(stretch) / (2 |T|), T = num_steps * float32(step), formed in float64 and rounded to float32; `fill` where
+    stretch holds the bits of float32(fill) (include/exa_hip.h, exa_hip_flowmap)"""
+    stretch = np.ascontiguousarray(stretch, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        ftle = (np.log(stretch.astype(np.float64)) / (2.0 * num_steps * np.float64(np.float32(step)))).astype(np.float32)
+    filled = stretch.view(np.uint32) == np.float32(fill).view(np.uint32)
+    return np.where(filled, np.float32(fill), ftle).astype(np.float32)
 
 
 def _f3(v):

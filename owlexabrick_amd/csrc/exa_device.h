@@ -363,6 +363,23 @@ struct LicArgs {
   int32_t           *reasons;
 };
 
+// The flow map of a lattice (exa_hip_flowmap, exa_flowmap_kernels.h): the streamlines' RK4 from every lattice point, one
+// direction, only the end state kept.  A wave holds the lanes of one patch of 64 points, 2^shift[a] of them along axis a.
+struct FlowmapArgs {
+  SampleArgs         s;             // the lookup and the field (probeSetup); fieldOffset[0..2] = the three channels
+  float              lo[3], cell[3];         // lattice point i on axis a: lo[a] + (float(i) + 0.5f) * cell[a]
+  uint32_t           nx, ny, nz;
+  float              hs;            // +step forward, -step backward
+  int32_t            numSteps;
+  uint32_t           shift[3];      // log2 of the patch's extents; they add up to 6
+  uint32_t           patchesX, patchesY;     // patches of the lattice along x and y
+  unsigned long long waveBase, numWaves;     // first patch of this launch; patches in all
+  // outputs (each may be NULL), index L = (k*ny + j)*nx + i
+  float             *end;           // 3 floats per point
+  uint32_t          *steps;
+  int32_t           *reasons;
+};
+
 // ---- exa_lbvh.hip: LBVH topology over numPrims boxes (6 floats each, device), built on the device ----
 hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNode *nodes, int32_t *levelIds,
                                    std::vector<uint32_t> &internalNodesPerDepth, hipStream_t s);
@@ -404,7 +421,9 @@ hipError_t buildLbvhTopologyDevice(const float *boxes, uint32_t numPrims, BvhNod
      second launch, which stores the vertices */                                                                        \
   hipError_t launchStreamlines(const StreamArgs &a, bool emit, hipStream_t s);                                         \
   /* line integral convolution (exa_stream_f*.o): the patches [a.waveBase, a.numWaves) of at most 2^18 per launch */    \
-  hipError_t launchLic(const LicArgs &a, hipStream_t s);
+  hipError_t launchLic(const LicArgs &a, hipStream_t s);                                                               \
+  /* the flow map of a lattice (exa_stream_f*.o): the patches [a.waveBase, a.numWaves) of at most 2^18 per launch */      \
+  hipError_t launchFlowmap(const FlowmapArgs &a, hipStream_t s);
 namespace form0 { EXA_FORM_LAUNCHERS }
 namespace form1 { EXA_FORM_LAUNCHERS }
 // ... and once more in the source order with the reference's ALLOW_EMPTY_CELLS semantics (-DEXA_EMPTY_CELLS=1: a corner whose

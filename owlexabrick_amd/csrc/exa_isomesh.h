@@ -144,4 +144,19 @@ hipError_t launchIsoRegionScans(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s);
 
+// ---- the stretch of a flow map (exa_hip_flowmap): one lane per lattice point L = (k*ny + j)*nx + i reads the map's end
+// points and reasons at its stencil (per axis the neighbours at max(i-1, 0) and min(i+1, n-1)), forms the deformation
+// gradient, the Cauchy-Green tensor and its largest eigenvalue by five sweeps of cyclic Jacobi, as the contract words them.
+struct IsoStretchArgs {
+  const float *end;           // the flow map: 3 floats per lattice point
+  const int32_t *reasons;     // EXA_STREAM_END_* per lattice point
+  uint32_t numPoints;         // nx*ny*nz <= 2^31 - 1
+  uint32_t nx, ny, nz;
+  float lo[3], cell[3];       // lattice point i on axis a: lo[a] + (float(i) + 0.5f) * cell[a]
+  float fill;
+  float *stretch;             // numPoints
+};
+
+hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s);
+
 } // namespace exa

@@ -2,7 +2,9 @@
 // include/exa_hip.h the contract).  A translation unit of its own: nothing of the renderer or of the probes is compiled
 // here, the lattice values arrive in a device buffer.  Compiled with -ffp-contract=off: a vertex position is
 // P(p) + t * (P(q) - P(p)) with every operation rounded separately.  Behind them the kernels of exa_hip_isolines, the same
-// pipeline on the squares of a plane lattice (isoline...Kernel), which shares the block scan and the scans.
+// pipeline on the squares of a plane lattice (isoline...Kernel), which shares the block scan and the scans; the union-find of
+// exa_hip_regions; and the stretch stencil of exa_hip_flowmap (isoLatticeStretchKernel), another pass over a lattice that does not
+// depend on the basis form.
 #include "exa_isomesh.h"
 
 namespace exa {
@@ -782,7 +784,78 @@ __global__ __launch_bounds__(kIsoBlock) void isoRegionFinishKernel(const IsoRegi
   r.argMax = ~uint32_t(kmax);
 }
 
+// ---- the stretch of a flow map on a lattice (exa_hip_flowmap): the largest eigenvalue of the Cauchy-Green tensor of the
+// map's differences, one lane per lattice point.  The matrix lives in named registers and the three rotations of a sweep are
+// written out: no indexed local array, so no scratch. ----
+__device__ __forceinline__ bool stretchValid(int32_t reason)
+{
+  return reason == EXA_STREAM_END_MAXSTEPS || reason == EXA_STREAM_END_STAGNANT;
+}
+
+// column a of the deformation gradient at point L, index idx of n along the axis, `stride` points apart: central inside,
+// one-sided on the faces, zero for an axis of one point; false if a stencil point is not valid
+__device__ __forceinline__ bool stretchColumn(const IsoStretchArgs &a, uint32_t L, uint32_t idx, uint32_t n, size_t stride, float lo,
+                                              float cell, float &f0, float &f1, float &f2)
+{
+  f0 = f1 = f2 = 0.f;
+  if (n < 2) return true;
+  const uint32_t im = idx > 0 ? idx - 1 : 0, ip = idx + 1 < n ? idx + 1 : n - 1;
+  const size_t m = size_t(L) - size_t(idx - im) * stride, p = size_t(L) + size_t(ip - idx) * stride;
+  const float dx = (lo + (float(ip) + .5f) * cell) - (lo + (float(im) + .5f) * cell);
+  f0 = (a.end[3 * p] - a.end[3 * m]) / dx;
+  f1 = (a.end[3 * p + 1] - a.end[3 * m + 1]) / dx;
+  f2 = (a.end[3 * p + 2] - a.end[3 * m + 2]) / dx;
+  return stretchValid(a.reasons[m]) && stretchValid(a.reasons[p]);
+}
+
+// one rotation (p, q) of cyclic Jacobi, r the third index
+__device__ __forceinline__ void stretchRotate(float &app, float &aqq, float &apq, float &arp, float &arq)
+{
+  if (apq == 0.0f) return;
+  const float theta = (aqq - app) / (2.f * apq);
+  const float t = copysignf(1.f, theta) / (fabsf(theta) + sqrtf(theta * theta + 1.f));
+  const float c = 1.f / sqrtf(t * t + 1.f);
+  const float s = t * c;
+  const float tp = t * apq;
+  const float rp = c * arp - s * arq, rq = s * arp + c * arq;
+  app = app - tp;
+  aqq = aqq + tp;
+  arp = rp;
+  arq = rq;
+  apq = 0.f;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoLatticeStretchKernel(const IsoStretchArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  const uint32_t i = L % a.nx, j = (L / a.nx) % a.ny, k = L / (a.nx * a.ny);
+  float f00, f10, f20, f01, f11, f21, f02, f12, f22;               // F[c][a]
+  bool ok = stretchValid(a.reasons[L]);
+  ok = stretchColumn(a, L, i, a.nx, 1, a.lo[0], a.cell[0], f00, f10, f20) && ok;
+  ok = stretchColumn(a, L, j, a.ny, a.nx, a.lo[1], a.cell[1], f01, f11, f21) && ok;
+  ok = stretchColumn(a, L, k, a.nz, size_t(a.nx) * a.ny, a.lo[2], a.cell[2], f02, f12, f22) && ok;
+  if (!ok) { a.stretch[L] = a.fill; return; }
+  float a00 = (f00 * f00 + f10 * f10) + f20 * f20, a11 = (f01 * f01 + f11 * f11) + f21 * f21, a22 = (f02 * f02 + f12 * f12) + f22 * f22;
+  float a01 = (f00 * f01 + f10 * f11) + f20 * f21, a02 = (f00 * f02 + f10 * f12) + f20 * f22, a12 = (f01 * f02 + f11 * f12) + f21 * f22;
+  for (int sweep = 0; sweep < 5; sweep++) {
+    stretchRotate(a00, a11, a01, a02, a12);
+    stretchRotate(a00, a22, a02, a01, a12);
+    stretchRotate(a11, a22, a12, a01, a02);
+  }
+  float m = a00;
+  if (a11 > m) m = a11;
+  if (a22 > m) m = a22;
+  a.stretch[L] = m;
+}
+
 } // namespace
+
+hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoLatticeStretchKernel, dim3((a.numPoints + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launchIsoRegionInit(const IsoRegionArgs &a, hipStream_t s)
 {

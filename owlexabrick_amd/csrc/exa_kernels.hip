@@ -794,6 +794,8 @@ __device__ __forceinline__ bool samplePoint(Ctx<STATS> &C, float &value, V3 &der
 #include "exa_stream_kernels.h"
 // ... and the line integral convolution on its evaluation (exa_hip_lic)
 #include "exa_lic_kernels.h"
+// ... and the flow map of a lattice (exa_hip_flowmap)
+#include "exa_flowmap_kernels.h"
 } // namespace EXA_FORM_NS
 #else
 

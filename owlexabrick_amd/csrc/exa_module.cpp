@@ -245,6 +245,7 @@ int exa_hip_set_option(ExaHipRenderer *h, const char *key, int32_t value)
     h->lic.lanes = value; return 0;
   }
   if (!std::strcmp(key, "lic_patch")) { h->lic.patch = value != 0; return 0; }
+  if (!std::strcmp(key, "flowmap_patch")) { h->flowmap.patch = value != 0; return 0; }
   if (!std::strcmp(key, "interleave")) { h->interleave = value != 0; return 0; }
   if (!std::strcmp(key, "addr64")) { h->addr64 = value != 0; return 0; }
   if (!std::strcmp(key, "pack_records")) { h->packRecords = value != 0; return 0; }

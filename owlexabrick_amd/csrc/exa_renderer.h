@@ -1,8 +1,8 @@
 // exa_renderer.h — internal to the exa_hip_* module (not installed): the renderer behind the opaque ExaHipRenderer handle
 // of include/exa_hip.h and the helpers its translation units share.  exa_create.cpp builds and destroys a renderer,
 // exa_frame.cpp prepares and launches a frame, exa_probe.cpp holds the point probes, the projections along rays and the
-// iso-surface extraction, exa_streamlines.cpp the streamline extraction and the line integral convolution on its
-// evaluation, exa_stats.cpp the histogram and value range of
+// iso-surface extraction, exa_streamlines.cpp the streamline extraction and, on its evaluation, the line integral
+// convolution and the flow map, exa_stats.cpp the histogram and value range of
 // the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
 // one struct per call (ExaHipRenderer::probes, isoMesh, isolines, isoRegions, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
 // argument checks below the renderer are what their host code shares.
@@ -365,6 +365,13 @@ struct ExaHipRenderer {
     float kernelMs = 0.f;
     int lanes = 1, patch = 1;
   } lic;
+  // exa_hip_flowmap (in the renderer of devices[0] as well): the device time of the last call's two stages (integrate,
+  // stretch), and which 64 lattice points a wave takes — option "flowmap_patch" (0 = 64 along x, 1 = a 4 x 4 x 4 patch); the
+  // bytes are the same either way
+  struct Flowmap {
+    float ms[2] = { 0.f, 0.f };
+    int patch = 1;
+  } flowmap;
   // the device time of the last exa_hip_project's kernel launches, summed (in the renderer of devices[0])
   struct Projection {
     float kernelMs = 0.f;

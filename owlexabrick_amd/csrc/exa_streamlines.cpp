@@ -3,8 +3,10 @@
 // integration runs twice, the first time storing only how many vertices every direction appends and why it ended; the
 // counts are scanned on the host (the call is synchronous), and the second run stores every vertex at its packed position.
 // Behind it exa_hip_lic, the dense sibling on a plane lattice (kernel in exa_lic_kernels.h, in the same units): one launch,
-// nothing counted first and nothing emitted but the image.
+// nothing counted first and nothing emitted but the image; and exa_hip_flowmap, the same integration from every point of a
+// lattice with only the end state kept (kernel in exa_flowmap_kernels.h), and the stretch stencil over it.
 #include "exa_renderer.h"
+#include "exa_isomesh.h"
 
 #include <cmath>
 #include <cstring>
@@ -270,6 +272,130 @@ int exa_hip_lic_ms(ExaHipRenderer *h, float *ms)
 {
   if (!h || !ms) return 1;
   *ms = firstChild(h)->lic.kernelMs;
+  return 0;
+}
+
+// ---- the flow map of a lattice and its stretch (streamlinesKernelFlowmap, exa_flowmap_kernels.h; isoLatticeStretchKernel,
+// exa_isomesh.hip) ----
+// The extents 2^shift[a] of a wave's patch of 64 lattice points.  patch 0: 64 along x.  patch 1: 4 x 4 x 4; an axis shorter
+// than 4 gets the largest power of two it holds, and what it frees goes to x, y and z in turn, wherever the lattice is longer
+// than the patch (to x when it is nowhere).
+static void flowmapPatch(int patch, const int32_t dims[3], uint32_t shift[3])
+{
+  shift[0] = 6; shift[1] = shift[2] = 0;
+  if (!patch) return;
+  int spare = 0;
+  for (int k = 0; k < 3; k++) {
+    shift[k] = dims[k] >= 4 ? 2 : (dims[k] >= 2 ? 1 : 0);
+    spare += 2 - int(shift[k]);
+  }
+  for (int turn = 0; spare > 0 && turn < 18; turn++) {
+    const int k = turn % 3;
+    if (int64_t(dims[k]) > (int64_t(1) << shift[k])) { shift[k]++; spare--; }
+  }
+  shift[0] += uint32_t(spare);
+}
+
+int exa_hip_flowmap(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                    float step, int32_t numSteps, int32_t flags, float fill, float *end, uint32_t *steps, int32_t *reasons,
+                    float *stretch, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_flowmap";
+  ExaHipRenderer *r = firstChild(h);
+  r->flowmap.ms[0] = r->flowmap.ms[1] = 0.f;
+  if (!lo || !hi || !dims || !channels) { h->fail(std::string(fn) + ": null argument (lo, hi, dims or channels)"); return 1; }
+  for (int k = 0; k < 3; k++) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
+    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
+  }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);       // each < 2^31: the product of two fits
+  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
+    return 1;
+  }
+  for (int c = 0; c < 3; c++)
+    if (!checkChannel(h, fn, channels[c])) return 1;
+  if (!(std::isfinite(step) && step > 0.f)) { h->fail(std::string(fn) + ": step must be finite and > 0"); return 1; }
+  if (numSteps < 1 || numSteps > EXA_STREAM_MAX_STEPS) { h->fail(std::string(fn) + ": numSteps must be in 1.." + std::to_string(EXA_STREAM_MAX_STEPS)); return 1; }
+  if (!checkFlags(h, fn, flags, EXA_FLOWMAP_FORWARD | EXA_FLOWMAP_BACKWARD, "")) return 1;
+  if (flags != EXA_FLOWMAP_FORWARD && flags != EXA_FLOWMAP_BACKWARD) {
+    h->fail(std::string(fn) + ": exactly one direction (EXA_FLOWMAP_FORWARD or EXA_FLOWMAP_BACKWARD)");
+    return 1;
+  }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  FlowmapArgs a;
+  std::memset(&a, 0, sizeof(a));
+  if (probeSetup(h, r, fn, false, s, a.s)) return 1;
+  a.s.numChannels = 3;
+  for (int c = 0; c < 3; c++) a.s.fieldOffset[c] = r->sc.channelOffset[channels[c]];
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.cell[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.hs = flags == EXA_FLOWMAP_FORWARD ? step : -step;
+  a.numSteps = numSteps;
+  flowmapPatch(r->flowmap.patch, dims, a.shift);
+  auto patches = [&](int k) { return (uint64_t(dims[k]) + (1ull << a.shift[k]) - 1) >> a.shift[k]; };
+  a.patchesX = uint32_t(patches(0));
+  a.patchesY = uint32_t(patches(1));
+  a.numWaves = patches(0) * patches(1) * patches(2);
+
+  // One device buffer of the call, {end | steps | reasons | stretch}: with host pointers every array the caller asks for,
+  // with device pointers none of them; in both cases the flow map the stretch reads (end, reasons) where the caller does
+  // not ask for it.
+  const bool staged = !pointersAreDevice;
+  auto own = [&](const void *user, bool needed) { return user ? staged : needed; };
+  const bool ownEnd = own(end, stretch != nullptr), ownSteps = own(steps, false), ownReasons = own(reasons, stretch != nullptr),
+             ownStretch = own(stretch, false);
+  DevBuf<char> work;
+  const size_t bytes = (ownEnd ? 12 * n : 0) + (ownSteps ? 4 * n : 0) + (ownReasons ? 4 * n : 0) + (ownStretch ? 4 * n : 0);
+  if (bytes) {
+    const hipError_t e = work.alloc(bytes);
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the flow map (up to 24 bytes per point with host pointers, up to 16 with device pointers)", e);
+  }
+  char *cut = work.p;
+  auto carve = [&](bool mine, void *user, size_t size) { char *part = mine ? cut : static_cast<char *>(user); if (mine) cut += size; return part; };
+  a.end = reinterpret_cast<float *>(carve(ownEnd, end, 12 * n));
+  a.steps = reinterpret_cast<uint32_t *>(carve(ownSteps, steps, 4 * n));
+  a.reasons = reinterpret_cast<int32_t *>(carve(ownReasons, reasons, 4 * n));
+  IsoStretchArgs st;
+  std::memset(&st, 0, sizeof(st));
+  st.stretch = reinterpret_cast<float *>(carve(ownStretch, stretch, 4 * n));
+  st.end = a.end; st.reasons = a.reasons;
+  st.numPoints = uint32_t(n);
+  st.nx = a.nx; st.ny = a.ny; st.nz = a.nz;
+  for (int k = 0; k < 3; k++) { st.lo[k] = a.lo[k]; st.cell[k] = a.cell[k]; }
+  st.fill = fill;
+
+  TimingEvents<3> t;
+  HIP_TRY(h, t.create());
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  if (a.end || a.steps || a.reasons)
+    for (a.waveBase = 0; a.waveBase < a.numWaves; a.waveBase += 1ull << 18) HIP_TRY(h, EXA_FORM(r, launchFlowmap)(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  if (st.stretch) HIP_TRY(h, launchIsoLatticeStretch(st, s));
+  HIP_TRY(h, hipEventRecord(t.ev[2], s));
+  if (staged) {
+    if (end) HIP_TRY(h, hipMemcpyAsync(end, a.end, 12 * n, hipMemcpyDeviceToHost, s));
+    if (steps) HIP_TRY(h, hipMemcpyAsync(steps, a.steps, 4 * n, hipMemcpyDeviceToHost, s));
+    if (reasons) HIP_TRY(h, hipMemcpyAsync(reasons, a.reasons, 4 * n, hipMemcpyDeviceToHost, s));
+    if (stretch) HIP_TRY(h, hipMemcpyAsync(stretch, st.stretch, 4 * n, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(h, hipStreamSynchronize(s));
+  if (int rc = checkLoopGuard(h, r, fn, kDescentGuard)) return rc;
+  float ms0 = 0.f, ms1 = 0.f;
+  HIP_TRY(h, t.elapsed(0, 1, &ms0));
+  HIP_TRY(h, t.elapsed(1, 2, &ms1));
+  r->flowmap.ms[0] = ms0;
+  r->flowmap.ms[1] = ms1;
+  return 0;
+}
+
+int exa_hip_flowmap_ms(ExaHipRenderer *h, float ms[2])
+{
+  if (!h || !ms) return 1;
+  ms[0] = firstChild(h)->flowmap.ms[0];
+  ms[1] = firstChild(h)->flowmap.ms[1];
   return 0;
 }
 

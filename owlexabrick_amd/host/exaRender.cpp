@@ -48,6 +48,14 @@
 //                                            NU*NV raw little-endian float32, row j = 0 first (NaN where the pixel's centre has
 //                                            no value); --frames 0 renders nothing; with
 //             [--lic-seed N]                 the seed of the built-in noise (default 0)
+//             [--ftle C0,C1,C2 lx ly lz ux uy uz NX NY NZ STEP NUMSTEPS fwd|bwd out.ftle] flow map and FTLE of the vector field of
+//                                            channels C0 C1 C2 on the lattice of --resample over the box [l, u], voxel space
+//                                            (exa_hip_flowmap: NUMSTEPS RK4 steps of the time STEP from every lattice point,
+//                                            forward or backward in time).  One text line `ftle NX NY NZ channels C0 C1 C2 step
+//                                            STEP numSteps N direction fwd|bwd`, then five raw little-endian arrays, each in the
+//                                            order (k*NY + j)*NX + i: end (3 float32 per point), steps (uint32), reasons (int32),
+//                                            stretch (float32), ftle (float32; NaN where the point or a stencil neighbour did
+//                                            not last the time); --frames 0 renders nothing
 //             [--regions CHANNEL ISO NX NY NZ out.regions] the connected regions of field >= ISO of CHANNEL on that lattice
 //                                            (exa_hip_regions: joined along the edges of --isomesh's tetrahedra, numbered by
 //                                            their smallest lattice index, exact measurements per region).  With --derived the
@@ -217,6 +225,12 @@ int main(int argc, char **argv)
     float licStep = 0.5f;
     int licHalfLength = 20;
     uint32_t licSeed = 0;
+    std::string ftleName;
+    vec3i ftleChannels(0, 1, 2), ftleDims(1, 1, 1);
+    vec3f ftleLo, ftleHi;
+    float ftleStep = 0.5f;
+    int ftleNumSteps = 20;
+    bool ftleBackward = false;
     for (int i = 1; i < argc; i++) {
       const std::string a = argv[i];
       auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
@@ -300,6 +314,21 @@ int main(int argc, char **argv)
         licHalfLength = (int)f();
         if (i + 1 >= argc) throw std::runtime_error("missing file after --lic C0,C1,C2 o u v NU NV STEP HALFLENGTH");
         licName = argv[++i];
+      }
+      else if (a == "--ftle") {
+        if (i + 1 >= argc) throw std::runtime_error("missing channels after --ftle");
+        char tail = 0;
+        if (std::sscanf(argv[++i], "%d,%d,%d%c", &ftleChannels.x, &ftleChannels.y, &ftleChannels.z, &tail) != 3)
+          throw std::runtime_error("--ftle wants three comma-separated channels C0,C1,C2");
+        ftleLo = { f(), f(), f() }; ftleHi = { f(), f(), f() };
+        ftleDims.x = (int)f(); ftleDims.y = (int)f(); ftleDims.z = (int)f();
+        ftleStep = f();
+        ftleNumSteps = (int)f();
+        if (i + 2 >= argc) throw std::runtime_error("missing direction and file after --ftle C0,C1,C2 l u NX NY NZ STEP NUMSTEPS");
+        const std::string dir = argv[++i];
+        if (dir != "fwd" && dir != "bwd") throw std::runtime_error("--ftle wants the direction fwd or bwd");
+        ftleBackward = dir == "bwd";
+        ftleName = argv[++i];
       }
       else if (a == "--lic-seed") { if (i + 1 >= argc) throw std::runtime_error("missing value after --lic-seed"); licSeed = (uint32_t)std::strtoul(argv[++i], nullptr, 10); }
       else if (a == "--regions") {
@@ -522,6 +551,22 @@ int main(int argc, char **argv)
       std::printf("lic %d %d channels %d %d %d step %.9g halfLength %d seed %u pixels_covered %zu samples %llu\n", licSize.x, licSize.y,
                   licChannels.x, licChannels.y, licChannels.z, licStep, licHalfLength, licSeed, covered, samples);
     }
+    if (!ftleName.empty()) {
+      const Renderer::Flowmap M = renderer.flowmap(ftleLo, ftleHi, ftleDims, ftleChannels, ftleStep, ftleNumSteps, ftleBackward);
+      FILE *f = std::fopen(ftleName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + ftleName);
+      const size_t n = M.stretch.size();
+      std::fprintf(f, "ftle %d %d %d channels %d %d %d step %.9g numSteps %d direction %s\n", ftleDims.x, ftleDims.y, ftleDims.z,
+                   ftleChannels.x, ftleChannels.y, ftleChannels.z, ftleStep, ftleNumSteps, ftleBackward ? "bwd" : "fwd");
+      const bool ok = std::fwrite(M.end.data(), 12, n, f) == n && std::fwrite(M.steps.data(), 4, n, f) == n
+                      && std::fwrite(M.reason.data(), 4, n, f) == n && std::fwrite(M.stretch.data(), 4, n, f) == n
+                      && std::fwrite(M.ftle.data(), 4, n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + ftleName);
+      size_t valid = 0;
+      for (float v : M.ftle) valid += !std::isnan(v);
+      std::printf("ftle %d %d %d channels %d %d %d step %.9g numSteps %d direction %s points_with_ftle %zu\n", ftleDims.x, ftleDims.y,
+                  ftleDims.z, ftleChannels.x, ftleChannels.y, ftleChannels.z, ftleStep, ftleNumSteps, ftleBackward ? "bwd" : "fwd", valid);
+    }
     if (!regionsName.empty()) {
       const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
       const vec3i dims(regionsDims[0], regionsDims[1], regionsDims[2]);
@@ -657,7 +702,7 @@ int main(int argc, char **argv)
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
                         || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty()
-                        || !licName.empty())) return 0;
+                        || !licName.empty() || !ftleName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

@@ -767,6 +767,30 @@ Renderer::Lic Renderer::lic(vec3f origin, vec3f du, vec3f dv, vec2i size, vec3i 
   return L;
 }
 
+Renderer::Flowmap Renderer::flowmap(vec3f lo, vec3f hi, vec3i dims, vec3i channels, float step, int numSteps, bool backward, float fill)
+{
+  const float l[3] = { lo.x, lo.y, lo.z }, u[3] = { hi.x, hi.y, hi.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  // 0 points for dims the module refuses (it checks them)
+  size_t n = 0;
+  if (dims.x > 0 && dims.y > 0 && dims.z > 0 && uint64_t(dims.x) * uint64_t(dims.y) <= uint64_t(INT32_MAX)
+      && uint64_t(dims.x) * uint64_t(dims.y) * uint64_t(dims.z) <= uint64_t(INT32_MAX))
+    n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
+  Flowmap M;
+  M.end.resize(n); M.steps.resize(n); M.reason.resize(n); M.stretch.resize(n); M.ftle.resize(n);
+  check(exa_hip_flowmap(handle, l, u, d, ch, step, numSteps, backward ? EXA_FLOWMAP_BACKWARD : EXA_FLOWMAP_FORWARD, fill,
+                        reinterpret_cast<float *>(M.end.data()), M.steps.data(), M.reason.data(), M.stretch.data(), 0, nullptr), handle);
+  // FTLE = log(stretch) / (2 |T|) in double, rounded once; fill where the stretch holds the bits of fill
+  const double twoT = 2.0 * double(numSteps) * double(step);
+  uint32_t fillBits, bits;
+  std::memcpy(&fillBits, &fill, 4);
+  for (size_t i = 0; i < n; i++) {
+    std::memcpy(&bits, &M.stretch[i], 4);
+    M.ftle[i] = bits == fillBits ? fill : float(std::log(double(M.stretch[i])) / twoT);
+  }
+  return M;
+}
+
 // the pixels of the rays' image, 0 for a size the module refuses (it checks the size)
 static size_t rayPixels(const ExaHipRays &rays)
 {

@@ -295,6 +295,19 @@ struct Renderer {
   Lic lic(vec3f origin, vec3f du, vec3f dv, vec2i size, vec3i channels, float step, int halfLength,
           const uint8_t *noise = nullptr, uint32_t seed = 0, float fill = NAN);
 
+  // flow map and stretch of the vector field (channels.x, .y, .z) on the lattice of resample, in VOXEL space (exa_hip_flowmap;
+  // include/exa_hip.h states the contract): per lattice point where a particle released there is after numSteps RK4 steps of
+  // the time `step`, forward or backward; the largest eigenvalue of the Cauchy-Green tensor of the map's differences; and the
+  // FTLE = log(stretch) / (2 |T|), T = numSteps * step, formed in double.  Index (k*dims.y + j)*dims.x + i; stretch and ftle are
+  // `fill` where the point or one of its stencil neighbours did not last the time.
+  struct Flowmap {
+    std::vector<vec3f> end;
+    std::vector<uint32_t> steps;
+    std::vector<int32_t> reason;         // EXA_STREAM_END_*
+    std::vector<float> stretch, ftle;
+  };
+  Flowmap flowmap(vec3f lo, vec3f hi, vec3i dims, vec3i channels, float step, int numSteps, bool backward = false, float fill = NAN);
+
   // the field of `channel` reduced along one ray per pixel (exa_hip_project; include/exa_hip.h states the contract): pixel
   // (x, y) of the rays.width x rays.height image starts at org + (x+.5)*orgDu + (y+.5)*orgDv, runs along
   // dir + (x+.5)*dirDu + (y+.5)*dirDv (normalize: divided by its length) and is sampled at tmin + (i+.5)*dt, i < numSamples,

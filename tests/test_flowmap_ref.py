@@ -1,0 +1,232 @@
+"""The numpy restatement of exa_hip_flowmap's contract (tests/flowmap_ref.py), held on the CPU: the Jacobi sweeps against numpy's
+float64 eigenvalues on a seeded set of tensors; hand cases; a rigid rotation, whose stretch is 1 up to what float64 RK4 through
+the same stencil gives; a saddle against the closed form of RK4 on a linear field; the two feeds of the flow map against each
+other; ftle() against math.log; and the inputs the GPU test uses reach every reason, failed seeds, points invalid only through
+a neighbour and one-sided stencils on every axis, so that test cannot pass on empty ground."""
+import math
+
+import numpy as np
+import pytest
+
+import flowmap_ref as fr
+import lic_ref as lr
+import streamline_ref as sr
+from common import Case
+
+F = np.float32
+U = np.uint32
+
+# Jacobi against float64 (test_jacobi_against_float64_eigenvalues): seed 20261020, 40 000 random tensors F^T F with column
+# scales e^[-6, 6], 4 000 with near-multiple eigenvalues, the identity, a zero column.  Largest relative error of the float32
+# result against numpy.linalg.eigvalsh in float64 of the same float32 tensor, measured on the restatement alone 2026-10-20:
+JACOBI_SEED = 20261020
+JACOBI_MEASURED = 2.14e-7
+# Rigid rotation (test_rigid_rotation_has_stretch_one): largest |stretch32 - stretch64| over the lattice, forward and backward,
+# stretch64 = float64 RK4 of the analytic field through the same stencil with float64 eigenvalues; measured 2026-10-20:
+ROTATION_MEASURED = 3.7e-6
+# Saddle (test_saddle_equals_the_closed_form_of_rk4): largest relative error of stretch against g(step)^(2 numSteps); measured
+# 2026-10-20:
+SADDLE_MEASURED = 1.82e-6
+
+
+def _tensor_set():
+    """the six entries (float32 arrays) of the seeded set"""
+    rng = np.random.default_rng(JACOBI_SEED)
+    Fm = rng.standard_normal((40000, 3, 3)) * np.exp(rng.uniform(-6.0, 6.0, (40000, 1, 3)))           # [.., c, a]: column scales
+    Fm[-1] = np.eye(3)                                                                                # the exact identity
+    Fm[-2, :, 1] = 0.0                                                                                # a zero column
+    Fm[-3, :, 0] = 0.0
+    Fm = Fm.astype(F)
+    entries = list(fr.tensor(Fm[:, :, 0], Fm[:, :, 1], Fm[:, :, 2]))
+    # near-multiple eigenvalues: Q diag(1, 1 + d, 1 + k d) Q^T, d = 10^[-7, -2], k in {0, 1, 2}
+    Q = np.linalg.qr(rng.standard_normal((4000, 3, 3)))[0]
+    d = 10.0 ** rng.uniform(-7.0, -2.0, 4000)
+    lam = np.stack([np.ones(4000), 1.0 + d, 1.0 + rng.integers(0, 3, 4000) * d], axis=1)
+    C = np.einsum("nij,nj,nkj->nik", Q, lam, Q)
+    near = [C[:, 0, 0], C[:, 1, 1], C[:, 2, 2], C[:, 0, 1], C[:, 0, 2], C[:, 1, 2]]
+    return [np.concatenate([a, b.astype(F)]) for a, b in zip(entries, near)]
+
+
+def _eigvalsh64(entries):
+    a00, a11, a22, a01, a02, a12 = (np.asarray(x, np.float64) for x in entries)
+    M = np.stack([np.stack([a00, a01, a02], -1), np.stack([a01, a11, a12], -1), np.stack([a02, a12, a22], -1)], -2)
+    return np.linalg.eigvalsh(M)[:, -1]
+
+
+def test_jacobi_against_float64_eigenvalues():
+    """measured 2.138e-7 (seed 20261020, 44 000 tensors); asserted: twice 2.14e-7, because the set is a sample"""
+    entries = _tensor_set()
+    assert all(e.dtype == F for e in entries)
+    got = fr.jacobi_max(*entries)
+    want = _eigvalsh64(entries)
+    assert np.all(np.isfinite(got)) and np.all(want > 0)
+    err = np.abs(got.astype(np.float64) - want) / want
+    print(f"jacobi: largest relative error {err.max():.3e} at {int(err.argmax())} of {len(err)}")
+    assert err.max() <= 2 * JACOBI_MEASURED
+    # the sweep count has margin: four sweeps give the bytes of five
+    four = fr.jacobi_max(*entries, sweeps=4)
+    assert np.array_equal(four.view(U), got.view(U))
+
+
+def test_hand_cases():
+    one = lambda *v: fr.jacobi_max(*[np.array([x], F) for x in v])[0]                 # noqa: E731
+    # a diagonal tensor and the zero tensor come back untouched
+    assert one(0.25, 7.5, 3.0, 0, 0, 0) == F(7.5) and one(9, 1, 2, 0, 0, 0) == F(9) and one(1, 2, 11, 0, 0, 0) == F(11)
+    z = one(0, 0, 0, 0, 0, 0)
+    assert z == 0 and not np.signbit(z)
+    # [[2,1,0],[1,2,0],[0,0,1]] has the eigenvalues 1, 1, 3
+    assert abs(float(one(2, 2, 1, 1, 0, 0)) - 3.0) <= 3.0 * 2 * JACOBI_MEASURED
+    # NaN propagates by the formulas
+    assert np.isnan(one(np.nan, 2, 1, 1, 0.5, 0.25)) and np.isnan(one(2, 2, 1, np.nan, 0, 0)) and np.isnan(one(2, 2, 1, 1, 0.5, np.nan))
+    # a_qq == a_pp: theta = 0, t = copysign(1, +0) = 1: [[1, 0.5], [0.5, 1]] -> 1.5
+    assert abs(float(one(1, 1, 0, 0.5, 0, 0)) - 1.5) <= 1.5 * 2 * JACOBI_MEASURED
+
+
+def test_stencil_of_a_linear_map():
+    # end = A P + b on a lattice with an axis of one point: that axis' column is zero, the others are A's columns
+    A = np.array([[2.0, 0.5, 9.0], [0.0, 1.0, 9.0], [0.25, 0.0, 9.0]])
+    lo, hi, dims = (1.0, 2.0, 3.0), (5.0, 4.0, 4.0), (4, 2, 1)
+    P = fr.positions(lo, hi, dims)
+    end = (P.astype(np.float64) @ A.T + 1.0).astype(F)
+    reasons = np.full(len(P), fr.END_MAXSTEPS, np.int32)
+    got = fr.stretch(end, reasons, lo, hi, dims)
+    want = np.linalg.eigvalsh(A[:, :2].T @ A[:, :2])[-1]
+    assert got.shape == (1, 2, 4) and np.allclose(got, want, rtol=1e-5)
+    # an invalid point takes its stencil neighbours along, and only them
+    reasons[1] = fr.END_LEFT                                            # (i, j, k) = (1, 0, 0)
+    got = fr.stretch(end, reasons, lo, hi, dims, fill=-1.0)
+    assert (got == -1.0).tolist() == [[[True, True, True, False], [False, True, False, False]]]
+    # a stagnant point is valid
+    reasons[1] = fr.END_STAGNANT
+    assert not (fr.stretch(end, reasons, lo, hi, dims, fill=-1.0) == -1.0).any()
+
+
+_rotation = {}
+
+
+def _rotation_oracle():
+    if not _rotation:
+        _rotation["S"] = Case(sr.rotation_scene(), basis_form=1).oracle_scene()
+    return _rotation["S"]
+
+
+@pytest.mark.parametrize("backward", [False, True])
+def test_rigid_rotation_has_stretch_one(backward):
+    """measured |stretch32 - stretch64| <= 3.695e-6 forward, 2.742e-6 backward, and stretch64 = 1 to 1e-12; asserted: twice 3.7e-6"""
+    lo, hi, dims, step, n = (3.5, 3.5, 2.0), (8.5, 8.5, 5.0), (5, 5, 3), 0.125, 12
+    res = fr.flowmap(fr.oracle_feed(_rotation_oracle(), (1, 2, 3)), lo, hi, dims, step, n, backward)
+    assert np.all(res["reasons"] == fr.END_MAXSTEPS) and np.all(res["steps"] == n)
+    P = fr.positions(lo, hi, dims)
+    end64 = sr.rotation_rk4_64(P, -step if backward else step, n)[:, -1].reshape(3, 5, 5, 3)
+    s64 = fr.stretch64(end64, fr.axis_coords(lo, hi, dims))
+    # RK4 of a rotation by the angle h multiplies the radius by |1 + ih + (ih)^2/2 + (ih)^3/6 + (ih)^4/24| < 1 per step; along
+    # z the map is a translation, so the largest eigenvalue is that axis' 1
+    h = step
+    radius = math.hypot(1 - h * h / 2 + h ** 4 / 24, h - h ** 3 / 6)
+    assert radius < 1 and np.allclose(s64, 1.0, rtol=1e-12)
+    d = np.abs(res["stretch"].astype(np.float64) - s64).max()
+    print(f"rotation: |stretch32 - stretch64| <= {d:.3e}; |stretch64 - 1| <= {np.abs(s64 - 1).max():.3e}")
+    assert d <= 2 * ROTATION_MEASURED
+    interior = res["stretch"][1:-1, 1:-1, 1:-1]
+    assert np.abs(interior.astype(np.float64) - 1.0).max() <= np.abs(s64 - 1).max() + 2 * ROTATION_MEASURED
+
+
+@pytest.mark.parametrize("backward", [False, True])
+def test_saddle_equals_the_closed_form_of_rk4(backward):
+    """measured relative error 1.810e-6 forward, 3.743e-7 backward (stretch 20.0854); asserted: twice 1.82e-6"""
+    S = Case(fr.saddle_scene(), basis_form=1).oracle_scene()
+    lo, hi, dims, step, n = (5.2, 5.3, 3.0), (6.8, 6.7, 5.0), (4, 3, 2), 0.125, 12
+    res = fr.flowmap(fr.oracle_feed(S, (1, 2, 3)), lo, hi, dims, step, n, backward)
+    assert np.all(res["reasons"] == fr.END_MAXSTEPS)
+    # the lines stay where the reconstruction is linear: they are monotone in |x - 6| and |y - 6|, so the ends bound them
+    both = np.concatenate([res["end"].reshape(-1, 3), fr.positions(lo, hi, dims)])
+    assert np.all(both >= (0.5, 0.5, 0.5)) and np.all(both <= (11.5, 11.5, 7.5))
+    g = fr.rk4_growth(step)
+    want = g ** (2 * n)
+    err = np.abs(res["stretch"].astype(np.float64) - want).max() / want
+    print(f"saddle: relative error of stretch {err:.3e}; stretch {want:.6f}")
+    assert err <= 2 * SADDLE_MEASURED
+    # FTLE = log g(step) / step, a little below the field's exponent 1
+    f = fr.ftle(res["stretch"], step, n).astype(np.float64)
+    assert np.abs(f - math.log(g) / step).max() <= 2 * SADDLE_MEASURED / (2 * n * step) + 2.0 ** -24
+    assert 0.999 < math.log(g) / step < 1.0
+
+
+def test_the_two_feeds_give_the_same_bytes():
+    name, make, channels, _, empty, box, step = fr.CASES[0]
+    lo, hi = box((5, 4, 3))
+    for backward in (False, True):
+        a = fr.case_result(0, 1, (5, 4, 3), 12, backward)
+        S = fr._results[("S", 0, 1)]
+        b = fr.flowmap(fr.stepper_feed(lr.oracle_evaluator(S, channels)), lo, hi, (5, 4, 3), step, 12, backward)
+        fr.same(a, b, backward)
+        assert np.array_equal(a["seed_ok"], b["seed_ok"])
+
+
+@pytest.mark.parametrize("step,num_steps", [(0.125, 12), (0.5, 1), (0.3, 4096), (1e-3, 7)])
+def test_ftle_against_math_log(step, num_steps):
+    values = [1e-30, 0.5, 1.0, 1.0 + 2.0 ** -23, 2.0, 7.389056, 1234.5, 1e6, 3e38, 0.0, np.inf]
+    got = fr.ftle(np.array(values, F), step, num_steps)
+    assert got.dtype == F
+    for s, g in zip(np.array(values, F), got):
+        if s == 0 or np.isinf(s):
+            assert g == (-np.inf if s == 0 else np.inf)
+            continue
+        want = F(math.log(float(s)) / (2.0 * num_steps * float(F(step))))
+        # one double log, one division, one rounding: at most one float32 ulp apart
+        assert abs(int(np.array(g).view(np.int32)) - int(np.array(want).view(np.int32))) <= 1, (s, g, want)
+    # fill where stretch is fill, by its bits
+    assert np.isnan(fr.ftle(np.array([np.nan], F), step, num_steps)[0])
+    assert fr.ftle(np.array([-7.5, 2.0], F), step, num_steps, fill=-7.5)[0] == F(-7.5)
+
+
+# what each input of the GPU test must reach at 12 steps, forward and backward: {(name, lattice): {what: at least this many}}
+WANT = {
+    ("rotation", (5, 4, 3)): {fr.END_MAXSTEPS: 20, fr.END_LEFT: 8, "failed_seed": 6, "through_neighbour": 8, "stretch": 12,
+                              "one_sided_x": 3, "one_sided_y": 4, "one_sided_z": 8},
+    ("rotation", (9, 7, 5)): {fr.END_MAXSTEPS: 100, fr.END_LEFT: 50, "failed_seed": 16, "through_neighbour": 30, "stretch": 70,
+                              "one_sided_x": 5, "one_sided_y": 7, "one_sided_z": 28},
+    ("amr3", (5, 4, 3)): {fr.END_MAXSTEPS: 24, fr.END_LEFT: 6, "failed_seed": 6, "through_neighbour": 6, "stretch": 18,
+                          "one_sided_x": 6, "one_sided_y": 9, "one_sided_z": 12},
+    ("amr3", (9, 7, 5)): {fr.END_MAXSTEPS: 120, fr.END_LEFT: 25, "failed_seed": 16, "through_neighbour": 16, "stretch": 80,
+                          "one_sided_x": 16, "one_sided_y": 20, "one_sided_z": 28},
+    ("amr3_holes", (5, 4, 3)): {fr.END_NOVALUE: 4, "failed_seed": 4, "through_neighbour": 10, "stretch": 15},
+    ("amr3_holes", (9, 7, 5)): {fr.END_NOVALUE: 20, "failed_seed": 20, "through_neighbour": 60, "stretch": 70},
+    ("zero", (5, 4, 3)): {fr.END_STAGNANT: 19, fr.END_LEFT: 11, "failed_seed": 11, "through_neighbour": 12, "stretch": 7,
+                          "one_sided_x": 3, "one_sided_y": 4, "one_sided_z": 5},
+    ("zero", (9, 7, 5)): {fr.END_STAGNANT: 90, fr.END_LEFT: 60, "failed_seed": 60, "through_neighbour": 40, "stretch": 50,
+                          "one_sided_x": 7, "one_sided_y": 10, "one_sided_z": 17},
+}
+
+
+def reaches(name, dims, res):
+    n = fr.coverage(res)
+    for k, least in WANT[(name, tuple(dims))].items():
+        assert n[k] >= least, (name, dims, k, n)
+    return n
+
+
+@pytest.mark.parametrize("dims", fr.LATTICES, ids=lambda d: "x".join(map(str, d)))
+@pytest.mark.parametrize("idx", range(len(fr.CASES)), ids=[c[0] for c in fr.CASES])
+def test_inputs_of_the_gpu_test_reach_every_reason(idx, dims):
+    name, forms = fr.CASES[idx][0], fr.CASES[idx][3]
+    for backward in (False, True):
+        res = fr.case_result(idx, forms[-1], dims, 12, backward)
+        print(name, dims, backward, reaches(name, dims, res))
+        # a failed seed stays where it is with no step; a stretch is there exactly where the point and its stencil are valid
+        failed = ~res["seed_ok"]
+        assert np.all(res["steps"][failed] == 0) and not fr.valid(res["reasons"][failed]).any()
+        assert np.array_equal(res["end"][failed].view(U), fr.positions(*fr.CASES[idx][5](dims), dims).reshape(res["end"].shape)[failed].view(U))
+        assert np.all(np.isnan(res["stretch"]) == ~(fr.valid(res["reasons"]) & fr.stencil_valid(res["reasons"])))
+        assert np.all(res["steps"] <= 12) and np.all(res["steps"][res["reasons"] == fr.END_MAXSTEPS] == 12)
+
+
+def test_every_kind_of_point_occurs_somewhere():
+    seen = set()
+    for want in WANT.values():
+        seen |= set(want)
+    assert {fr.END_MAXSTEPS, fr.END_LEFT, fr.END_NOVALUE, fr.END_STAGNANT, "failed_seed", "through_neighbour", "one_sided_x",
+            "one_sided_y", "one_sided_z"} <= seen
+    # an axis of one point, on every axis, among the shapes of the GPU test
+    for axis in range(3):
+        assert any(s[axis] == 1 and max(s) > 1 for s in fr.SHAPES)
