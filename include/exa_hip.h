@@ -906,6 +906,127 @@ int exa_hip_flowmap(ExaHipRenderer *, const float lo[3], const float hi[3], cons
                     int32_t pointersAreDevice, void *hipStream);
 int exa_hip_flowmap_ms(ExaHipRenderer *, float ms[2]);   /* integrate, stretch */
 
+/* ---- critical points: the topology of a vector field.  Where the flow of three channels, sampled on the lattice the other
+ * extractions use, stagnates, and what kind of point each zero is: source, sink, one of the two saddles, each plain or
+ * spiralling.  The points seed separatrices (exa_hip_streamlines), explain a LIC image and find stagnation and attachment
+ * points.  New relative to the reference.  Every output is an integer or a float / double bit pattern that depends on no
+ * schedule: placement is by prefix sums, the counters are integer sums, two runs give the same bytes. ----
+ *
+ * Arithmetic.  All arithmetic float32 unless stated, every operation rounded separately, nothing contracted; `/` is correctly
+ * rounded; every expression below is written in the association the kernels use; sums written "x = x + y" over the corners
+ * m = 0..7 run in ascending m from x = 0.0f.  NaN and infinities propagate by the formulas, nothing is special-cased or clamped.
+ *
+ * Lattice and values.  lo, hi, dims and EXA_SAMPLE_WORLD_SPACE as for exa_hip_resample; dims >= 2 per axis (cells are
+ * needed), nx*ny*nz <= 2^31 - 1.  step[a] = (hi[a] - lo[a]) / float(dims[a]).  Linear index L = (k*ny + j)*nx + i.
+ * V_c(L), c = 0, 1, 2, is exactly what exa_hip_resample(lo, hi, dims, channels[c], the same flag, fill = NaN) returns in the
+ * handle's current basis_form.  Channels may repeat.
+ *
+ * Cells.  Cell (i,j,k) exists for i < nx-1, j < ny-1, k < nz-1; its number is the linear index L of its origin (i,j,k).  Its
+ * corner m = dx + 2 dy + 4 dz is the lattice point (i+dx, j+dy, k+dz), with values V_c(m).  A cell is valid if all 24 corner
+ * floats are finite.  stats.cells = (nx-1)(ny-1)(nz-1), stats.invalidCells = the cells that are not valid.
+ *
+ * Candidates.  A valid cell is a candidate if for each component c the minimum lo_c and the maximum hi_c of V_c over the 8
+ * corners satisfy  lo_c <= 0 && 0 <= hi_c && lo_c < hi_c.  A cell in which a component is constant is never a candidate (the
+ * all-zero interior of a body).  stats.candidates counts them.
+ *
+ * Trilinear interpolant.  For s = (s0, s1, s2):  u_a[0] = 1.f - s_a, u_a[1] = s_a.  Per corner m = (dx,dy,dz):
+ *     wxy = u_0[dx] * u_1[dy]        wxz = u_0[dx] * u_2[dz]        wyz = u_1[dy] * u_2[dz]        w = wxy * u_2[dz]
+ * and per component c, over the corners in ascending m,
+ *     F_c    = F_c    + w * V_c(m)
+ *     J_c0   = J_c0   + (dx ? wyz * V_c(m) : -(wyz * V_c(m)))
+ *     J_c1   = J_c1   + (dy ? wxz * V_c(m) : -(wxz * V_c(m)))
+ *     J_c2   = J_c2   + (dz ? wxy * V_c(m) : -(wxy * V_c(m)))
+ * F = T(s) and J = dT/ds (J_ca = dT_c/ds_a), accumulated corner by corner.
+ *
+ * Newton iteration.  s = (0.5, 0.5, 0.5); exactly `iterations` steps (1 .. EXA_CRITICAL_MAX_ITERATIONS), no early exit.  A
+ * step forms F and J at s, then solves J delta = -F by Cramer's rule with the cofactors
+ *     A00 = J11*J22 - J12*J21      A01 = J02*J21 - J01*J22      A02 = J01*J12 - J02*J11
+ *     A10 = J12*J20 - J10*J22      A11 = J00*J22 - J02*J20      A12 = J02*J10 - J00*J12
+ *     A20 = J10*J21 - J11*J20      A21 = J01*J20 - J00*J21      A22 = J00*J11 - J01*J10
+ *     det = (A00*J00 + A01*J10) + A02*J20
+ *     delta_a = -(((Aa0*F0 + Aa1*F1) + Aa2*F2) / det)              s_a = s_a + delta_a
+ * A singular matrix divides by zero and gives infinities or NaN.  det is the first row of the cofactors times the first column
+ * of J, the expansion the numerator of delta_0 has: in a cell whose corners with dx = 0 are all zero (the layer around a body
+ * of zeros below x0) the first step has F_c = 0.5 * J_c0 exactly, so delta_0 = -0.5 and s_0 = 0 exactly, where the second step
+ * finds F = 0 and det = 0: 0/0, nonFinite.
+ *
+ * Acceptance.  With the final s and the delta of the last step, tested in this order:
+ *     nonFinite     some s_a or delta_a is not finite
+ *     leftCell      not (0 <= s_a < 1) on some axis a; in the last cell of an axis (i_a == n_a - 2) s_a <= 1 is allowed.  A
+ *                   root on a face between two cells so belongs to one of them by rule
+ *     notConverged  lastStep = max(max(|delta_0|, |delta_1|), |delta_2|) > tolerance (tolerance finite, in (0, 1])
+ * A rejected candidate is counted in exactly one of stats.nonFinite, leftCell, notConverged; the others are found.  At most
+ * one point per cell is found: a cell that holds several zeros gives the one the iteration runs to, or none.  Duplicates
+ * are not merged: the interpolants of two cells differ outside their shared face, so both may accept a root close to it.
+ *
+ * Output.  One ExaHipCriticalPoint per found candidate, in ascending cell number:
+ *     local = s                  position[a] = lo[a] + ((float(i_a) + 0.5f) + s_a) * step[a]   (the lattice's space)
+ *     lastStep as above          jacobian[c*3 + a] = J_ca / step[a], J formed once more at the final s
+ * Classification in double from the float32 `jacobian`, j = (double)jacobian:
+ *     P = -((j[0] + j[4]) + j[8])
+ *     Q = ((j[0]*j[4] - j[1]*j[3]) + (j[0]*j[8] - j[2]*j[6])) + (j[4]*j[8] - j[5]*j[7])
+ *     R = -((j[0]*(j[4]*j[8] - j[5]*j[7]) - j[1]*(j[3]*j[8] - j[5]*j[6])) + j[2]*(j[3]*j[7] - j[4]*j[6]))
+ *     D = (27.0*(R*R) + (4.0*((P*P)*P) - 18.0*(P*Q))*R) + (4.0*((Q*Q)*Q) - (P*P)*(Q*Q))
+ * invariants = (P, Q, R) of the characteristic polynomial lambda^3 + P lambda^2 + Q lambda + R; discriminant = D, the negative
+ * of the cubic's discriminant.  The Routh column is e = (1, P, (P*Q - R)/P, R); an entry counts as positive iff it is > 0 (a NaN
+ * is not); n+ = the number of k in 0..2 at which e_k and e_k+1 differ in that.  type = n+ (bits 0-1: the eigenvalues with a
+ * positive real part: 0 sink, 3 source, 1 and 2 the two saddles) | EXA_CRITICAL_SPIRAL if D > 0 (a complex pair) |
+ * EXA_CRITICAL_DEGENERATE if P == 0, P*Q - R == 0, R == 0 or one of P, (P*Q - R)/P, R is not finite; n+ is then still what the
+ * rule gives.
+ *
+ * Probe (EXA_CRITICAL_PROBE).  The point probe runs on the positions while they are on the device: probe[(p*3 + c)*4 + 0] is
+ * the value, [.. + 1..3] the gradient and probeStatus[p*3 + c] the status of channel channels[c] at position(p), bit for bit
+ * what exa_hip_sample_points(positions, channels, 3, the world flag | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED,
+ * fill = NaN) returns: the residual of the real field at the lattice's root and the real field's voxel-space Jacobian.
+ *
+ * Independence.  As for the regions: the result depends only on the scene, the lattice, the channels, iterations,
+ * tolerance, the flags, basis_form and (world space) the transform — on nothing a frame sets, nor on walk, accel,
+ * brick_order, interleave, sample_patch or sample_uniform.  A scene without a kd tree is refused.  A multi-device handle runs
+ * on devices[0].
+ *
+ * Calls.  Synchronous on hipStream.  The result lives in module-owned device memory until the next exa_hip_critical_points
+ * (also a failed one), exa_hip_critical_points_release or exa_hip_destroy; it is independent of the mesh, the lines and the
+ * regions: none of the four calls drops another's result.  Zero points is not an error.  numPoints and stats (or NULL) are
+ * written by a call that succeeds, and zeroed by one that fails.  exa_hip_critical_points_read: points numPoints records,
+ * probe numPoints x 12 floats, probeStatus numPoints x 3 (both only after EXA_CRITICAL_PROBE; without the flag a non-NULL
+ * pointer is an error); a NULL pointer skips that array; host arrays, or memory of the handle's first device with
+ * pointersAreDevice; an error before any extraction.  Errors carry a message that starts with the function's name and leave
+ * the handle usable: a NULL lo, hi, dims or channels, the box and dims errors of exa_hip_resample, dims < 2, too many points,
+ * a bad channel, iterations outside 1 .. EXA_CRITICAL_MAX_ITERATIONS, a tolerance that is not finite or outside (0, 1],
+ * unknown flag bits, world space before a frame state, a failed allocation.  The kd descent's loop guard returns 3.
+ * exa_hip_critical_points_stage_ms: device ms of the last call's stages — values (three lattices), cells (validity,
+ * candidates, counts), scans (both rounds, with the compaction of the candidate list), refine (the iteration), emit (records
+ * and classification), probe.
+ *
+ * Memory.  While the call runs: 12 bytes per lattice point for the three lattices, 1 bit per lattice point for the candidate
+ * marks and 8 bytes per block of 256 points for the scans; 24 bytes per candidate (its cell 4, s and lastStep 16, its class 4)
+ * and 8 bytes per block of 256 candidates.  Afterwards: 104 bytes per found point, and with the probe 60 more (48 + 12), and
+ * another 60 while the probe runs (the positions 12, the probe's own values 12 and gradients 36). */
+#define EXA_CRITICAL_MAX_ITERATIONS 32
+#define EXA_CRITICAL_SPIRAL         4    /* type: a complex pair of eigenvalues (D > 0) */
+#define EXA_CRITICAL_DEGENERATE     8    /* type: an entry of the Routh column is zero or not finite */
+#define EXA_CRITICAL_PROBE          16   /* flag: probe the real field at the found positions */
+typedef struct ExaHipCriticalPoint {
+  uint32_t cell;              /* linear index L of the cell's origin */
+  int32_t  type;              /* n+ | EXA_CRITICAL_SPIRAL | EXA_CRITICAL_DEGENERATE */
+  float    local[3];          /* s */
+  float    position[3];       /* lo[a] + ((float(i_a) + 0.5f) + s[a]) * step[a], the lattice's space */
+  float    lastStep;          /* max |delta| of the last iteration */
+  float    jacobian[9];       /* [c*3 + a] = (dT_c/ds_a) / step[a]: per unit of the lattice's space */
+  double   invariants[3];     /* P, Q, R of lambda^3 + P lambda^2 + Q lambda + R */
+  double   discriminant;      /* D */
+} ExaHipCriticalPoint;        /* 104 bytes */
+typedef struct ExaHipCriticalStats {
+  uint64_t cells, invalidCells, candidates, found, nonFinite, leftCell, notConverged;
+} ExaHipCriticalStats;
+int exa_hip_critical_points(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                            const int32_t channels[3], int32_t iterations, float tolerance, int32_t flags,
+                            uint64_t *numPoints, ExaHipCriticalStats *stats /* or NULL */, void *hipStream);
+int exa_hip_critical_points_read(ExaHipRenderer *, ExaHipCriticalPoint *points, float *probe /* n x 12, or NULL */,
+                                 int32_t *probeStatus /* n x 3, or NULL */, int32_t pointersAreDevice, void *hipStream);
+int exa_hip_critical_points_release(ExaHipRenderer *);
+int exa_hip_critical_points_stage_ms(ExaHipRenderer *, float ms[6]);   /* values, cells, scans, refine, emit, probe */
+
 /* ---- projections: the field itself reduced along lines of sight — per pixel the sum, the number, the maximum and the
  * minimum of the samples of one channel along a ray, as plain arrays: column density (sum*dt), the mean along the ray
  * (sum/count), maximum- and minimum-intensity images.  New relative to the reference, whose only images are RGBA8 pictures

@@ -146,6 +146,16 @@ LABELLED_REGION_DTYPE = np.dtype(dict(names=["points", "sumFixed", "sumIndex", "
                              formats=["<u8", "<i8", ("<u8", 3), ("<i4", 3), ("<i4", 3), "<u4", "<u4", "<u4", "<f4", "<f4"],
                              offsets=[0, 8, 16, 40, 52, 64, 68, 72, 76, 80], itemsize=88))
 
+# exa_hip_critical_points (include/exa_hip.h): the flag, the bits of a point's type beside n+ (bits 0-1), ExaHipCriticalPoint
+# (104 bytes, no padding) and the fields of ExaHipCriticalStats
+CRITICAL_PROBE = 16
+CRITICAL_MAX_ITERATIONS = 32
+CRITICAL = {"n_plus_mask": 3, "sink": 0, "saddle_1": 1, "saddle_2": 2, "source": 3, "spiral": 4, "degenerate": 8}
+CRITICAL_POINT_DTYPE = np.dtype(dict(names=["cell", "type", "local", "position", "lastStep", "jacobian", "invariants", "discriminant"],
+                                     formats=["<u4", "<i4", ("<f4", 3), ("<f4", 3), "<f4", ("<f4", 9), ("<f8", 3), "<f8"],
+                                     offsets=[0, 4, 8, 20, 32, 36, 72, 96], itemsize=104))
+CRITICAL_STATS = ("cells", "invalidCells", "candidates", "found", "nonFinite", "leftCell", "notConverged")
+
 # exa_hip_raycast_iso (include/exa_hip.h)
 CROSS_MAX_REFINE = 32
 RAYCAST_KEYS = ("t", "position", "value", "gradient", "index", "side", "crossings")
@@ -268,6 +278,10 @@ _ABI = {
     "exa_hip_regions_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_regions_release": (None, [_vp]),
     "exa_hip_regions_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_critical_points": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _vp, _vp]),
+    "exa_hip_critical_points_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_critical_points_release": (None, [_vp]),
+    "exa_hip_critical_points_stage_ms": (None, [_vp, _vp]),
     "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
     "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),
@@ -900,6 +914,57 @@ class Renderer:
             return self.readRegions()
         finally:
             self.releaseRegions()
+
+    # ---- critical points of a flow on a lattice (exa_hip_critical_points*; include/exa_hip.h states the contract) ----
+    def extractCriticalPoints(self, lo, hi, dims, channels=(0, 1, 2), iterations=8, tolerance=2.0 ** -10, world=False, probe=False,
+                              stream=None):
+        """find and classify the zeros of the vector field `channels` on the lattice of resample(lo, hi, dims), one per cell at
+        the most, into module-owned device memory.  Returns (numPoints, stats dict of CRITICAL_STATS).  readCriticalPoints
+        copies the result out, releaseCriticalPoints frees it."""
+        flags = self._probe_world(world) | (CRITICAL_PROBE if probe else 0)
+        n, st = C.c_uint64(0), (C.c_uint64 * len(CRITICAL_STATS))()
+        self._critical = None
+        self._check(lib().exa_hip_critical_points(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), int(iterations), float(tolerance),
+                                                  flags, C.byref(n), st, C.c_void_p(stream or 0)))
+        self._critical = (int(n.value), bool(probe))
+        return int(n.value), dict(zip(CRITICAL_STATS, (int(v) for v in st)))
+
+    def readCriticalPoints(self):
+        """the last extractCriticalPoints: (points, a structured array of CRITICAL_POINT_DTYPE in ascending cell number; probe
+        float32 [n, 3, 4] = value and voxel-space gradient of each channel at each position, or None; probe_status int32 [n, 3]
+        or None)"""
+        if not getattr(self, "_critical", None):
+            self._check(lib().exa_hip_critical_points_read(self.h, None, None, None, 0, None))      # refused
+            raise RuntimeError("readCriticalPoints: no extraction of this renderer to read")
+        n, probed = self._critical
+        points = np.zeros(n, CRITICAL_POINT_DTYPE)
+        probe = np.empty((n, 3, 4), np.float32) if probed else None
+        status = np.empty((n, 3), np.int32) if probed else None
+        self._check(lib().exa_hip_critical_points_read(self.h, points.ctypes.data if n else None, probe.ctypes.data if probed and n else None,
+                                                       status.ctypes.data if probed and n else None, 0, None))
+        return points, probe, status
+
+    def releaseCriticalPoints(self):
+        self._check(lib().exa_hip_critical_points_release(self.h))
+        self._critical = None
+
+    def criticalPointsStageMs(self):
+        """device ms of the last extractCriticalPoints' stages: values, cells, scans, refine, emit, probe"""
+        ms = (C.c_float * 6)()
+        self._check(lib().exa_hip_critical_points_stage_ms(self.h, ms))
+        return [float(v) for v in ms]
+
+    def criticalPoints(self, lo, hi, dims, channels=(0, 1, 2), iterations=8, tolerance=2.0 ** -10, world=False, probe=False):
+        """the critical points of the vector field `channels` on the lattice of resample(lo, hi, dims): (points, stats), with
+        probe=True (points, stats, probe, probe_status) as readCriticalPoints gives them.  type & 3 is n+, the eigenvalues with
+        a positive real part; CRITICAL names the other bits.  The device copy is released before returning."""
+        _, stats = self.extractCriticalPoints(lo, hi, dims, channels=channels, iterations=iterations, tolerance=tolerance,
+                                              world=world, probe=probe)
+        try:
+            points, values, status = self.readCriticalPoints()
+        finally:
+            self.releaseCriticalPoints()
+        return (points, stats, values, status) if probe else (points, stats)
 
     def derivedMs(self):
         """device ms of the kernels of the last sampleDerived / resampleDerived call, summed"""

@@ -159,4 +159,60 @@ struct IsoStretchArgs {
 
 hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s);
 
+// ---- critical points of a vector field on a lattice (exa_hip_critical_points): the zeros of the trilinear interpolant of
+// three lattices, cell by cell.  `values` holds the three lattices one behind the other (component c at values + c*numPoints).
+//   cells      one lane per L, blocks of kIsoBlock consecutive L, a block of the launch taking kIsoCriticalTiles of them one
+//              after the other: the 8 x 3 corner loads, validity and the candidate test; the wave's ballot of candidates into
+//              marks (one 64-bit word per wave: a bit per lattice point), the block's count into blockCount; what the lanes
+//              have counted of cells and invalid cells over their tiles goes to the counters once per block of the launch
+//   scans      the iso-surface's over blockCount (launchIsoCriticalScans), then the compaction: candidate number
+//              chunkBase + blockBase + the marks below the lane's bit -> candidates[], ascending L
+//   refine     one lane per candidate, dense waves, the iteration count wave-uniform: s, lastStep and the class
+//              (kIsoCriticalFound or the reject's counter) into state / result, the block's found count into candCount, the
+//              rejects to the counters by one integer atomic per wave and class
+//   scans      the same over candCount
+//   emit       one record per found candidate at candChunkBase + candBase + its rank in the block; J once more at s, the
+//              classification in double; the position also into `positions` where the probe follows
+//   pack       the probe's values and gradients interleaved into the n x 3 x 4 array of the contract
+static const uint32_t kIsoCriticalTiles = 8;    // blocks of the lattice per block of the cell pass
+static const int32_t kIsoCriticalFound = 0;     // result[]: found, else the index of the reject's counter in ExaHipCriticalStats
+static const int32_t kIsoCriticalNonFinite = 4, kIsoCriticalLeftCell = 5, kIsoCriticalNotConverged = 6;
+
+struct IsoCriticalArgs {
+  const float *values;        // 3 * numPoints floats
+  uint32_t numPoints;         // nx*ny*nz <= 2^31 - 1
+  uint32_t nx, ny, nz;
+  float lo[3], step[3];       // lattice point i on axis a: lo[a] + (float(i) + 0.5f) * step[a]
+  int32_t iterations;
+  float tolerance;
+  unsigned long long *marks;  // [numBlocks][kIsoBlock / 64]
+  uint32_t numBlocks, numChunks;
+  uint32_t *blockCount;       // [numBlocks] candidates
+  uint32_t *blockBase;        // [numBlocks]
+  uint64_t *chunkBase;        // [numChunks]
+  uint64_t *totals;           // [2]: candidates, found (the two rounds of scans)
+  unsigned long long *counters;   // an ExaHipCriticalStats, zeroed by the host: the kernels add to cells, invalidCells and the rejects
+  uint32_t numCandidates;
+  uint32_t *candidates;       // [numCandidates] cell numbers, ascending
+  float *state;               // [numCandidates][4]: s, lastStep
+  int32_t *result;            // [numCandidates]
+  uint32_t numCandBlocks, numCandChunks;
+  uint32_t *candCount;        // [numCandBlocks] found
+  uint32_t *candBase;         // [numCandBlocks]
+  uint64_t *candChunkBase;    // [numCandChunks]
+  uint32_t numFound;
+  ExaHipCriticalPoint *points;    // [numFound]
+  float *positions;           // [numFound][3], or nullptr
+  const float *probeValues;   // pack: [numFound][3], [numFound][3][3] -> probe [numFound][3][4]
+  const float *probeGradients;
+  float *probe;
+};
+
+hipError_t launchIsoCriticalCells(const IsoCriticalArgs &a, hipStream_t s);
+hipError_t launchIsoCriticalScans(const IsoCriticalArgs &a, bool found, hipStream_t s);     // found: the second round
+hipError_t launchIsoCriticalCompact(const IsoCriticalArgs &a, hipStream_t s);
+hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s);
+hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s);
+hipError_t launchIsoCriticalPack(const IsoCriticalArgs &a, hipStream_t s);
+
 } // namespace exa

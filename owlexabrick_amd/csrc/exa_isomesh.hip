@@ -3,8 +3,9 @@
 // here, the lattice values arrive in a device buffer.  Compiled with -ffp-contract=off: a vertex position is
 // P(p) + t * (P(q) - P(p)) with every operation rounded separately.  Behind them the kernels of exa_hip_isolines, the same
 // pipeline on the squares of a plane lattice (isoline...Kernel), which shares the block scan and the scans; the union-find of
-// exa_hip_regions; and the stretch stencil of exa_hip_flowmap (isoLatticeStretchKernel), another pass over a lattice that does not
-// depend on the basis form.
+// exa_hip_regions; the stretch stencil of exa_hip_flowmap (isoLatticeStretchKernel), another pass over a lattice that does not
+// depend on the basis form; and the critical points of a flow on a lattice (exa_hip_critical_points, isoCritical...Kernel),
+// which place their output with the same scans.
 #include "exa_isomesh.h"
 
 namespace exa {
@@ -849,7 +850,317 @@ __global__ __launch_bounds__(kIsoBlock) void isoLatticeStretchKernel(const IsoSt
   a.stretch[L] = m;
 }
 
+// ---- critical points of a vector field on a lattice (exa_hip_critical_points): the passes of exa_isomesh.h ----
+__device__ __forceinline__ size_t criticalOffset(const IsoCriticalArgs &a, int m)
+{
+  return size_t(m & 1) + size_t((m >> 1) & 1) * a.nx + size_t(m >> 2) * (size_t(a.nx) * a.ny);
+}
+
+// The cell pass: a streaming stencil over the three lattices.  Plain loads (EXA_CRITICAL_LDS 0): the eight corners of a wave's
+// 64 cells are four rows of 65 consecutive floats per component, so the corner loads of neighbouring lanes and of the next
+// y / z row hit the lines the L1 and L2 already hold.  EXA_CRITICAL_LDS 1 stages those rows of a block, 4 x 257 floats per
+// component, in LDS first (12 loads per lane instead of 24, and 24 LDS reads); tools/ab_variants.sh builds the two.  Plain
+// loads are the default: on a 256^3 lattice the slab takes 2.3 x their time (profiles/critical_cells_ab.txt).  The bytes are
+// the same either way.
+#ifndef EXA_CRITICAL_LDS
+#define EXA_CRITICAL_LDS 0
+#endif
+
+__global__ __launch_bounds__(kIsoBlock) void isoCriticalCellKernel(const IsoCriticalArgs a)
+{
+  __shared__ uint32_t lds[3 * (kIsoBlock / 64)];
+#if EXA_CRITICAL_LDS
+  __shared__ float slab[3][4][kIsoBlock + 1];           // [component][dy + 2 dz][x]
+#endif
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t cells = 0, invalid = 0;
+#pragma unroll 1
+  for (uint32_t t = 0; t < kIsoCriticalTiles; t++) {
+    const uint32_t tile = blockIdx.x * kIsoCriticalTiles + t;
+    if (tile >= a.numBlocks) break;                     // the same for the whole block
+    const uint64_t at = uint64_t(tile) * kIsoBlock + threadIdx.x;
+#if EXA_CRITICAL_LDS
+    // a valid cell's corners are lattice points; what lies behind the lattice's end is never read
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const float *v = a.values + size_t(c) * a.numPoints;
+        const uint64_t row = uint64_t(tile) * kIsoBlock + criticalOffset(a, 2 * r);
+        slab[c][r][threadIdx.x] = row + threadIdx.x < a.numPoints ? v[row + threadIdx.x] : 0.f;
+        if (threadIdx.x == 0) slab[c][r][kIsoBlock] = row + kIsoBlock < a.numPoints ? v[row + kIsoBlock] : 0.f;
+      }
+    __syncthreads();
+#endif
+    bool cand = false;
+    if (at < a.numPoints) {
+      const uint32_t L = uint32_t(at);
+      const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+      if (i + 1 < a.nx && j + 1 < a.ny && k + 1 < a.nz) {
+        cells++;
+        bool finite = true;
+        cand = true;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+#if EXA_CRITICAL_LDS
+          float mn = slab[c][0][threadIdx.x], mx = mn;
+#else
+          const float *v = a.values + size_t(c) * a.numPoints + L;
+          float mn = v[0], mx = mn;
+#endif
+          finite = finite && __builtin_isfinite(mn);
+#pragma unroll
+          for (int m = 1; m < 8; m++) {
+#if EXA_CRITICAL_LDS
+            const float x = slab[c][m >> 1][threadIdx.x + (m & 1)];
+#else
+            const float x = v[criticalOffset(a, m)];
+#endif
+            finite = finite && __builtin_isfinite(x);
+            mn = fminf(mn, x);
+            mx = fmaxf(mx, x);
+          }
+          cand = cand && mn <= 0.f && 0.f <= mx && mn < mx;
+        }
+        cand = cand && finite;
+        invalid += finite ? 0u : 1u;
+      }
+    }
+    const unsigned long long marks = __ballot(cand);
+    if (lane == 0u) {
+      a.marks[size_t(tile) * (kIsoBlock / 64) + wave] = marks;
+      lds[wave] = uint32_t(__popcll(marks));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.blockCount[tile] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+    __syncthreads();
+  }
+  static_assert(kIsoBlock / 64 == 4, "the block's count is written out for four waves");
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    cells += uint32_t(__shfl_xor(int(cells), o));
+    invalid += uint32_t(__shfl_xor(int(invalid), o));
+  }
+  if (lane == 0u) { lds[4 + wave] = cells; lds[8 + wave] = invalid; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t c = (lds[4] + lds[5]) + (lds[6] + lds[7]), n = (lds[8] + lds[9]) + (lds[10] + lds[11]);
+    if (c) atomicAdd(a.counters + 0, (unsigned long long)c);
+    if (n) atomicAdd(a.counters + 1, (unsigned long long)n);
+  }
+}
+
+// candidate number = the candidates in front of the block (the scans) + those of the block's earlier waves + the marks below
+// the lane's own bit: the list is in ascending L
+__global__ __launch_bounds__(kIsoBlock) void isoCriticalCompactKernel(const IsoCriticalArgs a)
+{
+  if (a.blockCount[blockIdx.x] == 0) return;          // the same for the whole block
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned long long *marks = a.marks + size_t(blockIdx.x) * (kIsoBlock / 64);
+  const unsigned long long mine = marks[wave];
+  if (!((mine >> lane) & 1ull)) return;
+  uint32_t before = uint32_t(__popcll(mine & ((1ull << lane) - 1ull)));
+  for (unsigned w = 0; w < wave; w++) before += uint32_t(__popcll(marks[w]));
+  const uint64_t first = a.chunkBase[blockIdx.x / kIsoChunk] + a.blockBase[blockIdx.x];      // < numPoints
+  a.candidates[first + before] = blockIdx.x * kIsoBlock + threadIdx.x;
+}
+
+// F = T(s) and J = dT/ds of the cell with origin L, accumulated corner by corner in the contract's association: twelve sums
+// in registers instead of 24 corner values
+struct CriticalJet { float f[3]; float j[3][3]; };
+
+template <int M>
+__device__ __forceinline__ void criticalCorner(const IsoCriticalArgs &a, const float *v, const float (&u)[3][2], CriticalJet &t)
+{
+  constexpr int dx = M & 1, dy = (M >> 1) & 1, dz = M >> 2;
+  const float wxy = u[0][dx] * u[1][dy], wxz = u[0][dx] * u[2][dz], wyz = u[1][dy] * u[2][dz];
+  const float w = wxy * u[2][dz];
+  const size_t off = criticalOffset(a, M);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const float x = v[size_t(c) * a.numPoints + off];
+    t.f[c] = t.f[c] + w * x;
+    const float px = wyz * x, py = wxz * x, pz = wxy * x;
+    t.j[c][0] = t.j[c][0] + (dx ? px : -px);
+    t.j[c][1] = t.j[c][1] + (dy ? py : -py);
+    t.j[c][2] = t.j[c][2] + (dz ? pz : -pz);
+  }
+}
+
+__device__ __forceinline__ void criticalJet(const IsoCriticalArgs &a, uint32_t L, float s0, float s1, float s2, CriticalJet &t)
+{
+  const float u[3][2] = { { 1.f - s0, s0 }, { 1.f - s1, s1 }, { 1.f - s2, s2 } };
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    t.f[c] = 0.f;
+    t.j[c][0] = t.j[c][1] = t.j[c][2] = 0.f;
+  }
+  const float *v = a.values + L;
+  criticalCorner<0>(a, v, u, t);
+  criticalCorner<1>(a, v, u, t);
+  criticalCorner<2>(a, v, u, t);
+  criticalCorner<3>(a, v, u, t);
+  criticalCorner<4>(a, v, u, t);
+  criticalCorner<5>(a, v, u, t);
+  criticalCorner<6>(a, v, u, t);
+  criticalCorner<7>(a, v, u, t);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoCriticalRefineKernel(const IsoCriticalArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t n = blockIdx.x * kIsoBlock + threadIdx.x;
+  int32_t result = -1;                                  // no candidate
+  if (n < a.numCandidates) {
+    const uint32_t L = a.candidates[n];
+    const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+    float s0 = 0.5f, s1 = 0.5f, s2 = 0.5f, d0 = 0.f, d1 = 0.f, d2 = 0.f;
+#pragma unroll 1
+    for (int32_t it = 0; it < a.iterations; it++) {
+      CriticalJet t;
+      criticalJet(a, L, s0, s1, s2, t);
+      const float a00 = t.j[1][1] * t.j[2][2] - t.j[1][2] * t.j[2][1], a01 = t.j[0][2] * t.j[2][1] - t.j[0][1] * t.j[2][2],
+                  a02 = t.j[0][1] * t.j[1][2] - t.j[0][2] * t.j[1][1];
+      const float a10 = t.j[1][2] * t.j[2][0] - t.j[1][0] * t.j[2][2], a11 = t.j[0][0] * t.j[2][2] - t.j[0][2] * t.j[2][0],
+                  a12 = t.j[0][2] * t.j[1][0] - t.j[0][0] * t.j[1][2];
+      const float a20 = t.j[1][0] * t.j[2][1] - t.j[1][1] * t.j[2][0], a21 = t.j[0][1] * t.j[2][0] - t.j[0][0] * t.j[2][1],
+                  a22 = t.j[0][0] * t.j[1][1] - t.j[0][1] * t.j[1][0];
+      const float det = (a00 * t.j[0][0] + a01 * t.j[1][0]) + a02 * t.j[2][0];
+      d0 = -(((a00 * t.f[0] + a01 * t.f[1]) + a02 * t.f[2]) / det);
+      d1 = -(((a10 * t.f[0] + a11 * t.f[1]) + a12 * t.f[2]) / det);
+      d2 = -(((a20 * t.f[0] + a21 * t.f[1]) + a22 * t.f[2]) / det);
+      s0 = s0 + d0;
+      s1 = s1 + d1;
+      s2 = s2 + d2;
+    }
+    const bool finite = __builtin_isfinite(s0) && __builtin_isfinite(s1) && __builtin_isfinite(s2) && __builtin_isfinite(d0) &&
+                        __builtin_isfinite(d1) && __builtin_isfinite(d2);
+    const bool inside = s0 >= 0.f && (s0 < 1.f || (i + 2 == a.nx && s0 <= 1.f)) && s1 >= 0.f && (s1 < 1.f || (j + 2 == a.ny && s1 <= 1.f)) &&
+                        s2 >= 0.f && (s2 < 1.f || (k + 2 == a.nz && s2 <= 1.f));
+    const float lastStep = fmaxf(fmaxf(fabsf(d0), fabsf(d1)), fabsf(d2));
+    result = !finite ? kIsoCriticalNonFinite : (!inside ? kIsoCriticalLeftCell : (!(lastStep <= a.tolerance) ? kIsoCriticalNotConverged : kIsoCriticalFound));
+    float *state = a.state + 4 * size_t(n);
+    state[0] = s0; state[1] = s1; state[2] = s2; state[3] = lastStep;
+    a.result[n] = result;
+  }
+  const unsigned long long found = __ballot(result == kIsoCriticalFound);
+#pragma unroll
+  for (int32_t r = kIsoCriticalNonFinite; r <= kIsoCriticalNotConverged; r++) {
+    const unsigned long long m = __ballot(result == r);
+    if (m && lane == 0u) atomicAdd(a.counters + r, (unsigned long long)__popcll(m));
+  }
+  if (lane == 0u) lds[wave] = uint32_t(__popcll(found));
+  __syncthreads();
+  if (threadIdx.x == 0) a.candCount[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoCriticalEmitKernel(const IsoCriticalArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  if (a.candCount[blockIdx.x] == 0) return;           // the same for the whole block
+  const uint32_t n = blockIdx.x * kIsoBlock + threadIdx.x;
+  const bool found = n < a.numCandidates && a.result[n] == kIsoCriticalFound;
+  uint32_t total;
+  const uint32_t before = blockScan(found ? 1u : 0u, total, lds);
+  if (!found) return;
+  const uint64_t index = a.candChunkBase[blockIdx.x / kIsoChunk] + a.candBase[blockIdx.x] + before;     // < numFound
+  const uint32_t L = a.candidates[n];
+  const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+  const float *state = a.state + 4 * size_t(n);
+  const float s0 = state[0], s1 = state[1], s2 = state[2];
+  CriticalJet t;
+  criticalJet(a, L, s0, s1, s2, t);
+  ExaHipCriticalPoint &p = a.points[index];
+  static_assert(sizeof(ExaHipCriticalPoint) == 104, "the record: 72 bytes of integers and floats, four doubles, no padding");
+  p.cell = L;
+  p.local[0] = s0; p.local[1] = s1; p.local[2] = s2;
+  const float px = a.lo[0] + ((float(i) + 0.5f) + s0) * a.step[0], py = a.lo[1] + ((float(j) + 0.5f) + s1) * a.step[1],
+              pz = a.lo[2] + ((float(k) + 0.5f) + s2) * a.step[2];
+  p.position[0] = px; p.position[1] = py; p.position[2] = pz;
+  if (a.positions) {
+    float *out = a.positions + 3 * index;
+    out[0] = px; out[1] = py; out[2] = pz;
+  }
+  p.lastStep = state[3];
+  const float j0 = t.j[0][0] / a.step[0], j1 = t.j[0][1] / a.step[1], j2 = t.j[0][2] / a.step[2];
+  const float j3 = t.j[1][0] / a.step[0], j4 = t.j[1][1] / a.step[1], j5 = t.j[1][2] / a.step[2];
+  const float j6 = t.j[2][0] / a.step[0], j7 = t.j[2][1] / a.step[1], j8 = t.j[2][2] / a.step[2];
+  p.jacobian[0] = j0; p.jacobian[1] = j1; p.jacobian[2] = j2;
+  p.jacobian[3] = j3; p.jacobian[4] = j4; p.jacobian[5] = j5;
+  p.jacobian[6] = j6; p.jacobian[7] = j7; p.jacobian[8] = j8;
+  // the classification, in double from the float32 jacobian
+  const double e0 = j0, e1 = j1, e2 = j2, e3 = j3, e4 = j4, e5 = j5, e6 = j6, e7 = j7, e8 = j8;
+  const double P = -((e0 + e4) + e8);
+  const double Q = ((e0 * e4 - e1 * e3) + (e0 * e8 - e2 * e6)) + (e4 * e8 - e5 * e7);
+  const double R = -((e0 * (e4 * e8 - e5 * e7) - e1 * (e3 * e8 - e5 * e6)) + e2 * (e3 * e7 - e4 * e6));
+  const double D = (27.0 * (R * R) + (4.0 * ((P * P) * P) - 18.0 * (P * Q)) * R) + (4.0 * ((Q * Q) * Q) - (P * P) * (Q * Q));
+  const double num = P * Q - R, third = num / P;
+  const bool p1 = P > 0.0, p2 = third > 0.0, p3 = R > 0.0;
+  const int32_t nplus = (p1 ? 0 : 1) + (p1 != p2 ? 1 : 0) + (p2 != p3 ? 1 : 0);
+  const bool degenerate = P == 0.0 || num == 0.0 || R == 0.0 || !(__builtin_isfinite(P) && __builtin_isfinite(third) && __builtin_isfinite(R));
+  p.type = nplus | (D > 0.0 ? EXA_CRITICAL_SPIRAL : 0) | (degenerate ? EXA_CRITICAL_DEGENERATE : 0);
+  p.invariants[0] = P; p.invariants[1] = Q; p.invariants[2] = R;
+  p.discriminant = D;
+}
+
+// the probe's values [n][3] and gradients [n][3][3] into probe [n][3][4]: one lane per point and channel
+__global__ __launch_bounds__(kIsoBlock) void isoCriticalPackKernel(const IsoCriticalArgs a)
+{
+  const uint64_t q = uint64_t(blockIdx.x) * kIsoBlock + threadIdx.x;
+  if (q >= 3ull * a.numFound) return;
+  const float *g = a.probeGradients + 3 * q;
+  float *out = a.probe + 4 * q;
+  out[0] = a.probeValues[q];
+  out[1] = g[0]; out[2] = g[1]; out[3] = g[2];
+}
+
 } // namespace
+
+hipError_t launchIsoCriticalCells(const IsoCriticalArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoCriticalCellKernel, dim3((a.numBlocks + kIsoCriticalTiles - 1) / kIsoCriticalTiles), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the iso-surface's scans over one count (grid y = 1): the candidates per block of the lattice, or (found) the found points
+// per block of candidates; the total goes to totals[0] or totals[1]
+hipError_t launchIsoCriticalScans(const IsoCriticalArgs &a, bool found, hipStream_t s)
+{
+  IsoMeshArgs m = {};
+  m.numBlocks = found ? a.numCandBlocks : a.numBlocks; m.numChunks = found ? a.numCandChunks : a.numChunks;
+  m.blockCount = found ? a.candCount : a.blockCount; m.blockBase = found ? a.candBase : a.blockBase;
+  m.chunkBase = found ? a.candChunkBase : a.chunkBase; m.totals = a.totals + (found ? 1 : 0);
+  hipLaunchKernelGGL(isoScanChunksKernel, dim3(m.numChunks, 1), dim3(kIsoBlock), 0, s, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoScanTopKernel, dim3(1), dim3(kIsoBlock), 0, s, m);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoCriticalCompact(const IsoCriticalArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoCriticalCompactKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoCriticalRefineKernel, dim3(a.numCandBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoCriticalEmitKernel, dim3(a.numCandBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoCriticalPack(const IsoCriticalArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoCriticalPackKernel, dim3(uint32_t((3ull * a.numFound + kIsoBlock - 1) / kIsoBlock)), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s)
 {

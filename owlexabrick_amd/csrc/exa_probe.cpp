@@ -4,7 +4,8 @@
 // the same rays (exa_hip_raycast_iso) in the same file, the field on the triangles of a mesh (exa_hip_sample_triangles), and
 // the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip) with the
 // contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit) and the connected
-// regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit).
+// regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit) and the critical points of
+// a flow on it (exa_hip_critical_points; the same unit).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -1184,6 +1185,197 @@ int exa_hip_regions_stage_ms(ExaHipRenderer *h, float ms[6])
   if (!h || !ms) return 1;
   const ExaHipRenderer *r = firstChild(h);
   for (int k = 0; k < 6; k++) ms[k] = r->isoRegions.stageMs[k];
+  return 0;
+}
+
+// ---- critical points of a vector field on a lattice (exa_isomesh.hip) ----
+// The three lattices are three exa_hip_resample calls into one device buffer.  Two small read-backs size what follows: the
+// number of candidates behind the first scans (the candidate list and the iteration's state), the number of found points
+// behind the second (the records).  The timing events are recorded stage by stage also where a stage has nothing to do.
+int exa_hip_critical_points(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                            int32_t iterations, float tolerance, int32_t flags, uint64_t *numPoints, ExaHipCriticalStats *stats,
+                            void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_critical_points";
+  if (numPoints) *numPoints = 0;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isoCritical.release();
+  DropUnlessCommitted<ExaHipRenderer::IsoCritical> result(r->isoCritical);     // whatever fails from here on leaves no result
+  ExaHipRenderer::IsoCritical &res = r->isoCritical;
+  for (float &ms : res.stageMs) ms = 0.f;
+  if (!lo || !hi || !dims || !channels) { h->fail(std::string(fn) + ": null argument (lo, hi, dims or channels)"); return 1; }
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_CRITICAL_PROBE, " (EXA_SAMPLE_WORLD_SPACE and EXA_CRITICAL_PROBE apply)")) return 1;
+  for (int c = 0; c < 3; c++)
+    if (!checkChannel(h, fn, channels[c])) return 1;
+  if (iterations < 1 || iterations > EXA_CRITICAL_MAX_ITERATIONS) { h->fail(std::string(fn) + ": iterations must be 1 .. EXA_CRITICAL_MAX_ITERATIONS (32)"); return 1; }
+  if (!(std::isfinite(tolerance) && tolerance > 0.f && tolerance <= 1.f)) { h->fail(std::string(fn) + ": the tolerance must be finite and in (0, 1]"); return 1; }
+  for (int k = 0; k < 3; k++) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
+    if (dims[k] < 2) { h->fail(std::string(fn) + ": dims must be >= 2 on every axis (a lattice of cells)"); return 1; }
+  }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
+  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
+    return 1;
+  }
+  hipStream_t s = (hipStream_t)hipStream;
+  const int32_t wf = flags & EXA_SAMPLE_WORLD_SPACE;
+  const bool probe = (flags & EXA_CRITICAL_PROBE) != 0;
+
+  IsoCriticalArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  a.iterations = iterations;
+  a.tolerance = tolerance;
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  // the work space of the lattice, freed when the call returns: marks | chunkBase | totals, counters | blockCount, blockBase
+  DevBuf<float> values;
+  DevBuf<char> work;
+  const size_t waves = size_t(a.numBlocks) * (kIsoBlock / 64), n64 = waves + a.numChunks + 2 + 7;
+  hipError_t e = values.alloc(3 * size_t(n));
+  if (e == hipSuccess) e = work.alloc(n64 * 8 + 2 * size_t(a.numBlocks) * 4);
+  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the three lattices (12 bytes per point) and the work space", e);
+  a.values = values.p;
+  a.marks = reinterpret_cast<unsigned long long *>(work.p);
+  a.chunkBase = reinterpret_cast<uint64_t *>(work.p) + waves;
+  a.totals = a.chunkBase + a.numChunks;
+  a.counters = reinterpret_cast<unsigned long long *>(a.totals + 2);
+  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  a.blockBase = a.blockCount + a.numBlocks;
+
+  TimingEvents<8> t;
+  HIP_TRY(h, t.create());
+  // the lattices: exa_hip_resample with a NaN fill into the device buffer (its checks of the kd tree and the frame state
+  // apply; synchronous, with the descent's loop guard checked)
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  for (int c = 0; c < 3; c++)
+    if (int rc = exa_hip_resample(h, lo, hi, dims, channels[c], wf, NAN, values.p + size_t(c) * n, 1, hipStream, 0)) {
+      h->fail(std::string(fn) + ": " + h->err);
+      return rc;
+    }
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  HIP_TRY(h, hipMemsetAsync(a.totals, 0, 9 * sizeof(uint64_t), s));
+  HIP_TRY(h, launchIsoCriticalCells(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[2], s));
+  HIP_TRY(h, launchIsoCriticalScans(a, false, s));
+  uint64_t totals[2] = { 0, 0 };                 // candidates, found
+  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  a.numCandidates = uint32_t(totals[0]);         // <= n
+  a.numCandBlocks = uint32_t((totals[0] + kIsoBlock - 1) / kIsoBlock);
+  a.numCandChunks = (a.numCandBlocks + kIsoChunk - 1) / kIsoChunk;
+  // the work space of the candidates: candChunkBase | candidates, result, candCount, candBase | state
+  DevBuf<char> candWork;
+  DevBuf<float> positions, probeValues, probeGradients;
+  if (a.numCandidates) {
+    const size_t nc = a.numCandidates, c32 = 2 * nc + 2 * size_t(a.numCandBlocks);
+    e = candWork.alloc(size_t(a.numCandChunks) * 8 + c32 * 4 + 4 * nc * 4);
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the candidates (24 bytes each)", e);
+    a.candChunkBase = reinterpret_cast<uint64_t *>(candWork.p);
+    a.candidates = reinterpret_cast<uint32_t *>(candWork.p + size_t(a.numCandChunks) * 8);
+    a.result = reinterpret_cast<int32_t *>(a.candidates + nc);
+    a.candCount = reinterpret_cast<uint32_t *>(a.result + nc);
+    a.candBase = a.candCount + a.numCandBlocks;
+    a.state = reinterpret_cast<float *>(a.candBase + a.numCandBlocks);
+    HIP_TRY(h, launchIsoCriticalCompact(a, s));
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[3], s));
+  if (a.numCandidates) HIP_TRY(h, launchIsoCriticalRefine(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[4], s));
+  if (a.numCandidates) {
+    HIP_TRY(h, launchIsoCriticalScans(a, true, s));
+    HIP_TRY(h, hipMemcpyAsync(totals + 1, a.totals + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[5], s));
+  a.numFound = uint32_t(totals[1]);              // <= the candidates
+  if (a.numFound) {
+    const size_t nf = a.numFound;
+    e = res.points.alloc(nf);
+    if (e == hipSuccess && probe) e = positions.alloc(3 * nf);
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the points (104 bytes each)", e);
+    a.points = res.points.p;
+    a.positions = positions.p;
+    HIP_TRY(h, launchIsoCriticalEmit(a, s));
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[6], s));
+  if (probe && a.numFound) {
+    // the existing points kernel on the device positions, then its two arrays interleaved into the contract's one
+    const size_t nf = a.numFound;
+    e = probeValues.alloc(3 * nf);
+    if (e == hipSuccess) e = probeGradients.alloc(9 * nf);
+    if (e == hipSuccess) e = res.probe.alloc(12 * nf);
+    if (e == hipSuccess) e = res.probeStatus.alloc(3 * nf);
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the probe (120 bytes per point)", e);
+    const int32_t pf = wf | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
+    if (int rc = exa_hip_sample_points(h, positions.p, nf, channels, 3, pf, NAN, probeValues.p, probeGradients.p, res.probeStatus.p, 1, hipStream, 0)) {
+      h->fail(std::string(fn) + ": " + h->err);
+      return rc;
+    }
+    a.probeValues = probeValues.p;
+    a.probeGradients = probeGradients.p;
+    a.probe = res.probe.p;
+    HIP_TRY(h, launchIsoCriticalPack(a, s));
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[7], s));
+  uint64_t counters[7] = { 0, 0, 0, 0, 0, 0, 0 };
+  HIP_TRY(h, hipMemcpyAsync(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));             // the work spaces are freed behind it
+  float ms[7];
+  for (int k = 0; k < 7; k++) HIP_TRY(h, t.elapsed(k, k + 1, &ms[k]));
+  res.stageMs[0] = ms[0]; res.stageMs[1] = ms[1]; res.stageMs[2] = ms[2] + ms[4];
+  res.stageMs[3] = ms[3]; res.stageMs[4] = ms[5]; res.stageMs[5] = probe && a.numFound ? ms[6] : 0.f;
+  res.probed = probe;
+  res.have = true;
+  result.commit();
+  if (numPoints) *numPoints = totals[1];
+  if (stats) {
+    stats->cells = counters[0]; stats->invalidCells = counters[1];
+    stats->candidates = totals[0]; stats->found = totals[1];
+    stats->nonFinite = counters[4]; stats->leftCell = counters[5]; stats->notConverged = counters[6];
+  }
+  return 0;
+}
+
+int exa_hip_critical_points_read(ExaHipRenderer *h, ExaHipCriticalPoint *points, float *probe, int32_t *probeStatus,
+                                 int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_critical_points_read";
+  ExaHipRenderer *r = firstChild(h);
+  const ExaHipRenderer::IsoCritical &res = r->isoCritical;
+  if (!res.have) { h->fail(std::string(fn) + ": no points (exa_hip_critical_points comes first; a release or a failed call drops them)"); return 1; }
+  if ((probe || probeStatus) && !res.probed) { h->fail(std::string(fn) + ": the points were extracted without EXA_CRITICAL_PROBE"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (points && res.points.n) HIP_TRY(h, hipMemcpyAsync(points, res.points.p, res.points.n * sizeof(ExaHipCriticalPoint), kind, s));
+  if (probe && res.probe.n) HIP_TRY(h, hipMemcpyAsync(probe, res.probe.p, res.probe.n * sizeof(float), kind, s));
+  if (probeStatus && res.probeStatus.n) HIP_TRY(h, hipMemcpyAsync(probeStatus, res.probeStatus.p, res.probeStatus.n * sizeof(int32_t), kind, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+int exa_hip_critical_points_release(ExaHipRenderer *h)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isoCritical.release();
+  return 0;
+}
+
+int exa_hip_critical_points_stage_ms(ExaHipRenderer *h, float ms[6])
+{
+  if (!h || !ms) return 1;
+  const ExaHipRenderer *r = firstChild(h);
+  for (int k = 0; k < 6; k++) ms[k] = r->isoCritical.stageMs[k];
   return 0;
 }
 

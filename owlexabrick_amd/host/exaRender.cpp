@@ -56,6 +56,15 @@
 //                                            order (k*NY + j)*NX + i: end (3 float32 per point), steps (uint32), reasons (int32),
 //                                            stretch (float32), ftle (float32; NaN where the point or a stencil neighbour did
 //                                            not last the time); --frames 0 renders nothing
+//             [--critical C0,C1,C2 lx ly lz ux uy uz NX NY NZ ITERATIONS TOLERANCE out.crit] the critical points of the vector
+//                                            field of channels C0 C1 C2 on the lattice of --resample over the box [l, u], voxel
+//                                            space (exa_hip_critical_points: the zeros of the trilinear interpolant, one per
+//                                            cell at the most, by ITERATIONS Newton steps, accepted within TOLERANCE, classified
+//                                            by the Jacobian).  One text line `critical NX NY NZ box lx ly lz ux uy uz channels
+//                                            C0 C1 C2 iterations N tolerance T cells .. invalidCells .. candidates .. found ..
+//                                            nonFinite .. leftCell .. notConverged ..`, then `found` raw little-endian records of
+//                                            104 bytes (ExaHipCriticalPoint of include/exa_hip.h), in ascending cell number;
+//                                            --frames 0 renders nothing
 //             [--regions CHANNEL ISO NX NY NZ out.regions] the connected regions of field >= ISO of CHANNEL on that lattice
 //                                            (exa_hip_regions: joined along the edges of --isomesh's tetrahedra, numbered by
 //                                            their smallest lattice index, exact measurements per region).  With --derived the
@@ -225,6 +234,11 @@ int main(int argc, char **argv)
     float licStep = 0.5f;
     int licHalfLength = 20;
     uint32_t licSeed = 0;
+    std::string criticalName;
+    vec3i criticalChannels(0, 1, 2), criticalDims(2, 2, 2);
+    vec3f criticalLo, criticalHi;
+    int criticalIterations = 8;
+    float criticalTolerance = 0.0009765625f;
     std::string ftleName;
     vec3i ftleChannels(0, 1, 2), ftleDims(1, 1, 1);
     vec3f ftleLo, ftleHi;
@@ -314,6 +328,18 @@ int main(int argc, char **argv)
         licHalfLength = (int)f();
         if (i + 1 >= argc) throw std::runtime_error("missing file after --lic C0,C1,C2 o u v NU NV STEP HALFLENGTH");
         licName = argv[++i];
+      }
+      else if (a == "--critical") {
+        if (i + 1 >= argc) throw std::runtime_error("missing channels after --critical");
+        char tail = 0;
+        if (std::sscanf(argv[++i], "%d,%d,%d%c", &criticalChannels.x, &criticalChannels.y, &criticalChannels.z, &tail) != 3)
+          throw std::runtime_error("--critical wants three comma-separated channels C0,C1,C2");
+        criticalLo = { f(), f(), f() }; criticalHi = { f(), f(), f() };
+        criticalDims.x = (int)f(); criticalDims.y = (int)f(); criticalDims.z = (int)f();
+        criticalIterations = (int)f();
+        criticalTolerance = f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --critical C0,C1,C2 l u NX NY NZ ITERATIONS TOLERANCE");
+        criticalName = argv[++i];
       }
       else if (a == "--ftle") {
         if (i + 1 >= argc) throw std::runtime_error("missing channels after --ftle");
@@ -567,6 +593,34 @@ int main(int argc, char **argv)
       std::printf("ftle %d %d %d channels %d %d %d step %.9g numSteps %d direction %s points_with_ftle %zu\n", ftleDims.x, ftleDims.y,
                   ftleDims.z, ftleChannels.x, ftleChannels.y, ftleChannels.z, ftleStep, ftleNumSteps, ftleBackward ? "bwd" : "fwd", valid);
     }
+    if (!criticalName.empty()) {
+      const Renderer::CriticalPoints P = renderer.criticalPoints(box3f(criticalLo, criticalHi), criticalDims, criticalChannels,
+                                                                 criticalIterations, criticalTolerance);
+      FILE *f = std::fopen(criticalName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + criticalName);
+      const ExaHipCriticalStats &st = P.stats;
+      char line[512];
+      std::snprintf(line, sizeof(line), "critical %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channels %d %d %d iterations %d tolerance %.9g "
+                    "cells %llu invalidCells %llu candidates %llu found %llu nonFinite %llu leftCell %llu notConverged %llu",
+                    criticalDims.x, criticalDims.y, criticalDims.z, criticalLo.x, criticalLo.y, criticalLo.z, criticalHi.x, criticalHi.y,
+                    criticalHi.z, criticalChannels.x, criticalChannels.y, criticalChannels.z, criticalIterations, criticalTolerance,
+                    (unsigned long long)st.cells, (unsigned long long)st.invalidCells, (unsigned long long)st.candidates,
+                    (unsigned long long)st.found, (unsigned long long)st.nonFinite, (unsigned long long)st.leftCell,
+                    (unsigned long long)st.notConverged);
+      std::fprintf(f, "%s\n", line);
+      const size_t n = P.points.size();
+      const bool ok = std::fwrite(P.points.data(), sizeof(ExaHipCriticalPoint), n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + criticalName);
+      // the found points by n+ (sink, the two saddles, source) and, of each, the spiralling ones
+      size_t kind[4] = { 0, 0, 0, 0 }, spiral[4] = { 0, 0, 0, 0 }, degenerate = 0;
+      for (const ExaHipCriticalPoint &p : P.points) {
+        kind[p.type & 3]++;
+        spiral[p.type & 3] += (p.type & EXA_CRITICAL_SPIRAL) ? 1 : 0;
+        degenerate += (p.type & EXA_CRITICAL_DEGENERATE) ? 1 : 0;
+      }
+      std::printf("%s sinks %zu spiral %zu saddles1 %zu spiral %zu saddles2 %zu spiral %zu sources %zu spiral %zu degenerate %zu\n", line,
+                  kind[0], spiral[0], kind[1], spiral[1], kind[2], spiral[2], kind[3], spiral[3], degenerate);
+    }
     if (!regionsName.empty()) {
       const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
       const vec3i dims(regionsDims[0], regionsDims[1], regionsDims[2]);
@@ -702,7 +756,7 @@ int main(int argc, char **argv)
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
                         || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty()
-                        || !licName.empty() || !ftleName.empty())) return 0;
+                        || !licName.empty() || !ftleName.empty() || !criticalName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);
       renderer.updateFrameID(0);

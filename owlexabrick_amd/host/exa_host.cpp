@@ -664,6 +664,24 @@ Renderer::Regions Renderer::regionsDerived(const box3f &box, vec3i dims, vec3i c
   return readRegions(handle, dims, nr, ni, se, values);
 }
 
+Renderer::CriticalPoints Renderer::criticalPoints(const box3f &box, vec3i dims, vec3i channels, int iterations, float tolerance,
+                                                  bool worldSpace, bool probe)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  CriticalPoints P;
+  uint64_t n = 0;
+  check(exa_hip_critical_points(handle, lo, hi, d, ch, iterations, tolerance,
+                                (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (probe ? EXA_CRITICAL_PROBE : 0), &n, &P.stats, nullptr), handle);
+  P.points.resize(n);
+  if (probe) { P.probe.resize(12 * n); P.probeStatus.resize(3 * n); }
+  check(exa_hip_critical_points_read(handle, P.points.data(), probe ? P.probe.data() : nullptr, probe ? P.probeStatus.data() : nullptr, 0,
+                                     nullptr), handle);
+  check(exa_hip_critical_points_release(handle), handle);
+  return P;
+}
+
 // the lines of the last extraction (exa_hip_isolines or exa_hip_isolines_derived) out of the module, which then drops them
 static Renderer::Isolines readIsolines(ExaHipRenderer *handle, uint64_t nv, uint64_t ns, size_t levels, bool gradients, size_t values)
 {

@@ -259,6 +259,20 @@ struct Renderer {
   Regions regionsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, bool worldSpace = false,
                          bool below = false, bool faces = false, bool values = false);
 
+  // the critical points of the vector field (channels.x, .y, .z) on the lattice of resample(box, dims): the zeros of the
+  // trilinear interpolant, at most one per cell, found by `iterations` Newton steps and accepted within `tolerance`, each
+  // classified by its Jacobian (exa_hip_critical_points; include/exa_hip.h states the contract): type & 3 = the eigenvalues
+  // with a positive real part, EXA_CRITICAL_SPIRAL, EXA_CRITICAL_DEGENERATE.  probe: per point and channel the value and the
+  // voxel-space gradient of the real field at the position (4 floats), and the probe's status.
+  struct CriticalPoints {
+    std::vector<ExaHipCriticalPoint> points;     // in ascending cell number
+    ExaHipCriticalStats stats;
+    std::vector<float> probe;                    // points x 3 x 4, empty unless asked for
+    std::vector<int32_t> probeStatus;            // points x 3
+  };
+  CriticalPoints criticalPoints(const box3f &box, vec3i dims, vec3i channels, int iterations = 8, float tolerance = 0.0009765625f,
+                                bool worldSpace = false, bool probe = false);
+
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
   // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
