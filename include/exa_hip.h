@@ -650,6 +650,81 @@ int exa_hip_regions_read(ExaHipRenderer *, int32_t *labels /* numPoints */, ExaH
 int exa_hip_regions_release(ExaHipRenderer *);
 int exa_hip_regions_stage_ms(ExaHipRenderer *, float ms[6]);
 
+/* ---- basins: one feature per local maximum of the set field >= iso (or per minimum of field < iso), shallow ones merged
+ * away — a watershed segmentation with prominence merging.  Where one threshold leaves every vortex (clump, halo) in one
+ * connected region, the basins split that region peak by peak; minDepth says how far a peak must stand out of the highest
+ * pass to a neighbour to count as a feature of its own.  New relative to the reference.  Every output is an integer or a
+ * float bit pattern that depends on no schedule: two runs give the same bytes. ----
+ *
+ * Lattice, values, inside, edges.  Exactly as for exa_hip_regions, with its flags (EXA_SAMPLE_WORLD_SPACE,
+ * EXA_REGIONS_KEEP_VALUES, EXA_REGIONS_BELOW, EXA_REGIONS_FACES): L = (k*ny + j)*nx + i, V(L) what exa_hip_resample (or
+ * exa_hip_resample_derived for a one-component quantity) returns with fill = NaN, inside(L) = V finite and V >= iso (BELOW:
+ * V < iso), iso finite; edges join inside points p and p +- d, d in {0,1}^3 \ {0} (FACES: the 6 axis neighbours).
+ *
+ * Height and order.  h(L) = the ordered 32-bit key of V(L): bits ^ (sign ? 0xffffffff : 0x80000000); with EXA_REGIONS_BELOW
+ * its complement, so that the call finds basins of minima and everything below reads the same.  p > q ("p is greater") iff
+ * h(p) > h(q), or h(p) == h(q) and L(p) < L(q): a strict total order on the points.
+ *
+ * Ascent.  up(p) = the greatest among p and its inside neighbours.  A point with up(p) == p is a peak; peak(p) is the fixed
+ * point of up from p (links rise strictly: no cycles).  A raw basin is the set of inside points with one peak.  On a plateau
+ * the tie-break makes several raw basins of depth 0, which any minDepth > 0 merges.
+ *
+ * Merging, in rounds.  minDepth >= 0, not NaN; +INFINITY is allowed.  Components start as the raw basins; peak(C) is the
+ * greatest point of C.  In a round, every edge (p, q) whose ends lie in different components has the height
+ * hs = min(h(p), h(q)); each component A with such an edge takes the neighbour component B with the greatest 64-bit word
+ * hs << 32 | (0xffffffff - L(peak(B))) — the highest pass, ties to the smaller peak index.  saddle(A) = the float whose key
+ * is that hs; depth(A) = float32(V(peak A) - saddle), with BELOW float32(saddle - V(peak A)): one float32 subtraction,
+ * always >= 0.  A links to B iff depth(A) < minDepth and peak(B) > peak(A).  All links of a round are made at once and
+ * chains are followed to their end (links rise strictly: no cycles); the components of the next round are the unions.
+ * Rounds repeat until one makes no link; `rounds` counts those that made one.  With minDepth == 0 none does.  At the end
+ * every component that still has a neighbour has depth >= minDepth.  With minDepth = +INFINITY the components are exactly
+ * the regions of exa_hip_regions with the same flags (unless a depth overflows to +Inf, which is not < +INFINITY).
+ *
+ * Numbering and table.  Basins are numbered 0, 1, ... by ascending L of their peak; labels[L] = the number, -1 outside.
+ * points, sumFixed (with the sumExponent rule of the regions: M over all inside points of the call), sumIndex, lo, hi, argMin,
+ * argMax, min, max as in ExaHipRegion; the peak is argMax, with BELOW argMin.  first = the smallest L of the basin.
+ * neighbour = the number of the basin across the highest pass after the last round, -1 if there is none; saddle = that
+ * pass, NaN without a neighbour; depth = the depth at that pass, +INFINITY without a neighbour.
+ * numRawBasins = the number of peaks, numBasins = the number of components at the end.
+ *
+ * Calls, independence, errors.  As for the regions (synchronous; the result lives until the next exa_hip_basins[_derived],
+ * also a failed one, exa_hip_basins_release or exa_hip_destroy; a multi-device handle runs on devices[0]; a scene without a
+ * kd tree is refused): the mesh, the lines, the regions, the critical points and the basins never drop one another's
+ * result.  Zero basins is not an error.  Errors carry a message that starts with the function's name and leave the handle
+ * usable: those of the regions, and a NaN or negative minDepth.  A loop guard returns 3: the kd descent's, a chain of links
+ * longer than numPoints, more rounds than numRawBasins (every round but the last removes a component).
+ * exa_hip_basins_stage_ms: device ms of the last call's stages — values, ascent (inside test, up links and their
+ * resolution), passes (all rounds' pass kernels), links (all rounds' link, jump and merge kernels), rank (the scans and
+ * numberings of the peaks and of the basins), stats (labels and measurements).
+ *
+ * Memory.  While the call runs: 4 bytes per lattice point for the values and 4 for the labels, which hold the up links,
+ * then the peak, then the component of every point until the numbering replaces it in place; 8 bytes per block of 256
+ * points for the scans; 20 bytes per raw basin (its peak, its link, its final number, the 64-bit word of its pass) and 16
+ * bytes per basin for the min / max keys.  Afterwards: the labels, 96 bytes per basin, and the values if kept. */
+typedef struct ExaHipBasin {
+  uint64_t points;            /* lattice points of the basin */
+  int64_t  sumFixed;          /* sum of q(V) over the basin, see Sum of the regions */
+  uint64_t sumIndex[3];       /* sum of i, of j, of k */
+  int32_t  lo[3], hi[3];      /* inclusive bounding box in lattice indices */
+  uint32_t first;             /* smallest linear index L of the basin */
+  uint32_t argMin, argMax;    /* smallest L among the points that hold min / max */
+  float    min, max;
+  int32_t  neighbour;         /* the basin across the highest pass, -1 if none */
+  float    saddle;            /* the value of that pass, NaN if none */
+  float    depth;             /* |V(peak) - saddle|, +INFINITY if none */
+} ExaHipBasin;                /* 96 bytes, no padding */
+int exa_hip_basins(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                   float minDepth, int32_t flags, uint64_t *numBasins, uint64_t *numRawBasins, uint64_t *numInside,
+                   int32_t *sumExponent, int32_t *rounds, void *hipStream);
+int exa_hip_basins_derived(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                           const int32_t channels[3], int32_t quantity, float iso, float minDepth, int32_t flags,
+                           uint64_t *numBasins, uint64_t *numRawBasins, uint64_t *numInside, int32_t *sumExponent,
+                           int32_t *rounds, void *hipStream);
+int exa_hip_basins_read(ExaHipRenderer *, int32_t *labels /* numPoints */, ExaHipBasin *basins /* numBasins */,
+                        float *values /* numPoints */, int32_t pointersAreDevice, void *hipStream);
+int exa_hip_basins_release(ExaHipRenderer *);
+int exa_hip_basins_stage_ms(ExaHipRenderer *, float ms[6]);
+
 /* ---- histogram and value range of one channel's cells: the exact histogram of the cell values by cell count and by
  * volume, the value range, the cell counts per level and the NaN / empty / out-of-range counts, optionally inside an integer
  * voxel box.  New relative to the reference, whose viewer left the hook unbuilt (exa/viewer.cpp:1274-1276, setValueRange /

@@ -145,6 +145,11 @@ REGIONS_FACES = 64
 LABELLED_REGION_DTYPE = np.dtype(dict(names=["points", "sumFixed", "sumIndex", "lo", "hi", "first", "argMin", "argMax", "min", "max"],
                              formats=["<u8", "<i8", ("<u8", 3), ("<i4", 3), ("<i4", 3), "<u4", "<u4", "<u4", "<f4", "<f4"],
                              offsets=[0, 8, 16, 40, 52, 64, 68, 72, 76, 80], itemsize=88))
+# ExaHipBasin (a basin of exa_hip_basins): the fields of ExaHipRegion, then the highest pass; 96 bytes, no padding
+BASIN_DTYPE = np.dtype([("points", "<u8"), ("sumFixed", "<i8"), ("sumIndex", "<u8", 3), ("lo", "<i4", 3), ("hi", "<i4", 3),
+                        ("first", "<u4"), ("argMin", "<u4"), ("argMax", "<u4"), ("min", "<f4"), ("max", "<f4"),
+                        ("neighbour", "<i4"), ("saddle", "<f4"), ("depth", "<f4")])
+assert BASIN_DTYPE.itemsize == 96
 
 # exa_hip_critical_points (include/exa_hip.h): the flag, the bits of a point's type beside n+ (bits 0-1), ExaHipCriticalPoint
 # (104 bytes, no padding) and the fields of ExaHipCriticalStats
@@ -278,6 +283,12 @@ _ABI = {
     "exa_hip_regions_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_regions_release": (None, [_vp]),
     "exa_hip_regions_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_basins": (None, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _P(_u64), _P(_u64), _P(_u64), _P(_i32), _P(_i32), _vp]),
+    "exa_hip_basins_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _P(_u64), _P(_u64), _P(_u64), _P(_i32),
+                                      _P(_i32), _vp]),
+    "exa_hip_basins_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_basins_release": (None, [_vp]),
+    "exa_hip_basins_stage_ms": (None, [_vp, _vp]),
     "exa_hip_critical_points": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _P(_u64), _vp, _vp]),
     "exa_hip_critical_points_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_critical_points_release": (None, [_vp]),
@@ -914,6 +925,77 @@ class Renderer:
             return self.readRegions()
         finally:
             self.releaseRegions()
+
+    # ---- basins: one per peak of field >= iso, merged by depth (exa_hip_basins*; include/exa_hip.h states the contract) ----
+    def extractBasins(self, lo, hi, dims, iso, min_depth, channel=0, world=False, below=False, faces=False, keep_values=False,
+                      quantity=None, channels=(0, 1, 2), stream=None):
+        """the basins of field >= iso (below: of the minima of < iso) on the lattice of resample(lo, hi, dims): every inside
+        point goes to the peak it climbs to, peaks that stand out of their highest pass by less than min_depth are merged
+        across it; into module-owned device memory.  With a `quantity` the basins of that derived quantity of `channels`.
+        Returns (numBasins, numRawBasins, numInside, sum_exponent, rounds).  readBasins copies the result out, releaseBasins
+        frees it."""
+        flags = (self._probe_world(world) | (REGIONS_BELOW if below else 0) | (REGIONS_FACES if faces else 0)
+                 | (REGIONS_KEEP_VALUES if keep_values else 0))
+        nb, nr, ni, se, rounds = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_int32(0)
+        self._basins = None
+        if quantity is None:
+            rc = lib().exa_hip_basins(self.h, _f3(lo), _f3(hi), _i3(dims), int(channel), float(iso), float(min_depth), flags,
+                                      C.byref(nb), C.byref(nr), C.byref(ni), C.byref(se), C.byref(rounds), C.c_void_p(stream or 0))
+        else:
+            rc = lib().exa_hip_basins_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), derived_quantity(quantity),
+                                              float(iso), float(min_depth), flags, C.byref(nb), C.byref(nr), C.byref(ni),
+                                              C.byref(se), C.byref(rounds), C.c_void_p(stream or 0))
+        self._check(rc)
+        self._basins = (int(nb.value), int(nr.value), int(ni.value), int(se.value), int(rounds.value),
+                        tuple(int(d) for d in dims[::-1]), bool(keep_values))
+        return self._basins[:5]
+
+    def readBasins(self):
+        """the last extractBasins as a dict: the keys of readRegions (labels int32 [nz, ny, nx], the basin's number or -1;
+        sum_exponent; num_inside; values where kept) with the table under `regions` and under `basins` (a structured array of
+        BASIN_DTYPE, numbered by ascending lattice index of the peak), num_raw and rounds"""
+        if not getattr(self, "_basins", None):
+            self._check(lib().exa_hip_basins_read(self.h, None, None, None, 0, None))       # refused
+            raise RuntimeError("readBasins: no extraction of this renderer to read")
+        nb, nr, ni, se, rounds, shape, keep = self._basins
+        table = np.zeros(nb, BASIN_DTYPE)
+        out = dict(labels=np.empty(shape, np.int32), regions=table, basins=table, sum_exponent=se, num_inside=ni, num_raw=nr,
+                   rounds=rounds)
+        if keep:
+            out["values"] = np.empty(shape, np.float32)
+        self._check(lib().exa_hip_basins_read(self.h, out["labels"].ctypes.data, table.ctypes.data if nb else None,
+                                              out["values"].ctypes.data if keep else None, 0, None))
+        return out
+
+    def releaseBasins(self):
+        self._check(lib().exa_hip_basins_release(self.h))
+        self._basins = None
+
+    def basinsStageMs(self):
+        """device ms of the last extractBasins' stages: values, ascent, passes, links, rank, stats"""
+        ms = (C.c_float * 6)()
+        self._check(lib().exa_hip_basins_stage_ms(self.h, ms))
+        return [float(v) for v in ms]
+
+    def basins(self, lo, hi, dims, iso, min_depth, channel=0, world=False, below=False, faces=False, keep_values=False):
+        """the basins of field >= iso of `channel` on the lattice of resample(lo, hi, dims): the dict of readBasins
+        (region_measures reads its table as it reads that of regions).  The device copy is released before returning."""
+        self.extractBasins(lo, hi, dims, iso, min_depth, channel=channel, world=world, below=below, faces=faces,
+                           keep_values=keep_values)
+        try:
+            return self.readBasins()
+        finally:
+            self.releaseBasins()
+
+    def basinsDerived(self, lo, hi, dims, iso, min_depth, quantity, channels=(0, 1, 2), world=False, below=False, faces=False,
+                      keep_values=False):
+        """basins of a one-component derived quantity (a key of DERIVED, or its number) of the vector field `channels`"""
+        self.extractBasins(lo, hi, dims, iso, min_depth, world=world, below=below, faces=faces, keep_values=keep_values,
+                           quantity=quantity, channels=channels)
+        try:
+            return self.readBasins()
+        finally:
+            self.releaseBasins()
 
     # ---- critical points of a flow on a lattice (exa_hip_critical_points*; include/exa_hip.h states the contract) ----
     def extractCriticalPoints(self, lo, hi, dims, channels=(0, 1, 2), iterations=8, tolerance=2.0 ** -10, world=False, probe=False,

@@ -144,6 +144,73 @@ hipError_t launchIsoRegionScans(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s);
 
+// ---- basins of the inside set on the lattice (exa_hip_basins): one basin per peak, shallow ones merged in rounds.  `comp` is
+// the labels array of the result and holds, one after the other: the up link of every point (an index L), its peak (the up
+// links resolved), its raw basin (the peak's number among the peaks, ascending L), its component (the raw number of the
+// component's peak, round by round) and at last the basin's number.  Outside points hold kIsoRegionOutside throughout.
+//   init       isoRegionInitKernel as it is: comp[L] = L or the outside mark, the inside count and max |V|
+//   up         one lane per point, the 14 or 6 neighbours by plain loads: comp[L] = the greatest of L and its inside neighbours
+//   jump       pointer doubling in place, for the points' links and later for the components': a lane follows kIsoBasinHops
+//              links from where its own points and stores where it got; a lane that did not reach a fixed point counts into
+//              *jumpCount, which the host reads to end the loop.  Every slot only ever moves along its own chain, so a
+//              racing read sees an ancestor, older or newer.  A chain shrinks to a fifth per pass.
+//   count      the block's number of fixed points (slot i holds i) into blockCount; the scans are the iso-surface's
+//   rank       a peak's raw number goes into its own slot as kIsoRegionRanked | number; peakOf[number] = L, link[number] = number
+//   label      comp[L] = the raw number, through the peak's slot (the mask reads it before and after the peak's own lane)
+//   pass       one lane per inside point: over its edges into other components the greatest word
+//              min(h, h') << 32 | ~component, which orders as the contract's word does since raw numbers ascend with the
+//              peak's L; reduced over the lanes of the wave that share the leading lane's component (twice), then one
+//              64-bit atomicMax on pass[component] — skipped where a plain load already shows as much
+//   link       one lane per raw number that still is a component: saddle and depth from its word; it links to the neighbour
+//              if depth < minDepth and the neighbour's peak is greater, and counts the link into *jumpCount
+//   merge      comp[L] = link[comp[L]], the links resolved by the jump passes before
+//   final      a component's number among the components (count and scans over the raw numbers) into finalOf; its record
+//              started, with the raw number parked in `neighbour` for the finish
+//   stats      isoRegionStatsKernel's scheme on the 96-byte record
+//   first      one lane per point over the final labels: `first` by an atomic min from the lanes that begin a run of a label
+//              within their wave, skipped where a load already shows a smaller one
+//   finish     min / max / argMin / argMax out of the keys; neighbour, saddle and depth out of the last round's word
+static const uint32_t kIsoBasinHops = 4;
+
+struct IsoBasinArgs {
+  const float *values;        // the lattice, numPoints floats
+  uint32_t numPoints;         // nx*ny*nz <= 2^31 - 1
+  uint32_t nx, ny, nz;
+  float iso;
+  int32_t below, faces;       // EXA_REGIONS_BELOW, EXA_REGIONS_FACES
+  uint32_t *comp;             // numPoints, see above
+  uint32_t numBlocks, numChunks;   // of the lattice; the count pass and the scans also run over the raw numbers, which are fewer
+  uint32_t *blockCount;       // [numBlocks]
+  uint32_t *blockBase;        // [numBlocks]
+  uint64_t *chunkBase;        // [numChunks]
+  uint64_t *totals;           // [3]: the scans' total, inside points, bits of max |V| (init; zeroed by the host)
+  int32_t *errorFlag;         // the module's loop guard
+  double scale;               // 2^sumExponent
+  float minDepth;
+  uint32_t *jumpArray;        // jump and count: comp (jumpSize = numPoints) or link (numRaw)
+  uint32_t jumpSize;
+  uint32_t *jumpCount;        // jump: lanes not yet at a fixed point; link: links made
+  uint32_t numRaw;
+  uint32_t *peakOf;           // [numRaw] L of the raw basin's peak
+  uint32_t *link;             // [numRaw] the component a raw basin belongs to (itself: it is one)
+  uint32_t *finalOf;          // [numRaw] a component's number in the table
+  uint64_t *pass;             // [numRaw] the round's word, zeroed by the host before the pass kernel
+  uint32_t numBasins;
+  ExaHipBasin *basins;        // numBasins
+  uint64_t *keys;             // [numBasins][2], as for the regions
+};
+
+hipError_t launchIsoBasinInit(const IsoBasinArgs &a, hipStream_t s);
+hipError_t launchIsoBasinUp(const IsoBasinArgs &a, hipStream_t s);
+hipError_t launchIsoBasinJump(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s);
+hipError_t launchIsoBasinCount(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s);    // and the scans
+hipError_t launchIsoBasinRank(const IsoBasinArgs &a, hipStream_t s);                                     // rank and label
+hipError_t launchIsoBasinPass(const IsoBasinArgs &a, hipStream_t s);
+hipError_t launchIsoBasinLink(const IsoBasinArgs &a, hipStream_t s);
+hipError_t launchIsoBasinMerge(const IsoBasinArgs &a, hipStream_t s);
+hipError_t launchIsoBasinFinal(const IsoBasinArgs &a, hipStream_t s);
+hipError_t launchIsoBasinStats(const IsoBasinArgs &a, hipStream_t s);                                    // stats, first and finish
+
 // ---- the stretch of a flow map (exa_hip_flowmap): one lane per lattice point L = (k*ny + j)*nx + i reads the map's end
 // points and reasons at its stencil (per axis the neighbours at max(i-1, 0) and min(i+1, n-1)), forms the deformation
 // gradient, the Cauchy-Green tensor and its largest eigenvalue by five sweeps of cyclic Jacobi, as the contract words them.

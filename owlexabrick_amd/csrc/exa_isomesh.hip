@@ -3,7 +3,7 @@
 // here, the lattice values arrive in a device buffer.  Compiled with -ffp-contract=off: a vertex position is
 // P(p) + t * (P(q) - P(p)) with every operation rounded separately.  Behind them the kernels of exa_hip_isolines, the same
 // pipeline on the squares of a plane lattice (isoline...Kernel), which shares the block scan and the scans; the union-find of
-// exa_hip_regions; the stretch stencil of exa_hip_flowmap (isoLatticeStretchKernel), another pass over a lattice that does not
+// exa_hip_regions and, behind it, the ascent, the rounds and the table of exa_hip_basins (isoBasin...Kernel); the stretch stencil of exa_hip_flowmap (isoLatticeStretchKernel), another pass over a lattice that does not
 // depend on the basis form; and the critical points of a flow on a lattice (exa_hip_critical_points, isoCritical...Kernel),
 // which place their output with the same scans.
 #include "exa_isomesh.h"
@@ -785,6 +785,347 @@ __global__ __launch_bounds__(kIsoBlock) void isoRegionFinishKernel(const IsoRegi
   r.argMax = ~uint32_t(kmax);
 }
 
+// ---- basins of the inside set (exa_hip_basins): the ascent, the rounds and the table of exa_isomesh.h ----
+__device__ __forceinline__ bool basinInside(const IsoBasinArgs &a, float v)
+{
+  return __builtin_isfinite(v) && (a.below ? v < a.iso : v >= a.iso);
+}
+
+// the height of the contract: the ordered key, complemented for basins of minima
+__device__ __forceinline__ uint32_t basinHeight(const IsoBasinArgs &a, float v)
+{
+  const uint32_t key = regionKey(v);
+  return a.below ? ~key : key;
+}
+
+// f(Q) for every lattice neighbour Q of L: p +- d over the seven (three with faces) kinds of edge
+template <typename F>
+__device__ __forceinline__ void basinNeighbours(const IsoBasinArgs &a, uint32_t L, F f)
+{
+  const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+#pragma unroll
+  for (int code = 1; code < 8; code++) {
+    if (a.faces && (code & (code - 1))) continue;
+    const uint32_t dx = uint32_t(code & 1), dy = uint32_t((code >> 1) & 1), dz = uint32_t(code >> 2);
+    const uint32_t off = uint32_t(size_t(dx) + size_t(dy) * a.nx + size_t(dz) * (size_t(a.nx) * a.ny));
+    if (i + dx < a.nx && j + dy < a.ny && k + dz < a.nz) f(L + off);
+    if (i >= dx && j >= dy && k >= dz) f(L - off);
+  }
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinUpKernel(const IsoBasinArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  const float v = a.values[L];
+  if (!basinInside(a, v)) return;                     // the init kernel's outside mark stays
+  // the order of the contract as one word: the height, then the smaller L
+  unsigned long long best = (unsigned long long)basinHeight(a, v) << 32 | (~L);
+  basinNeighbours(a, L, [&](uint32_t Q) {
+    const float w = a.values[Q];
+    if (!basinInside(a, w)) return;
+    const unsigned long long r = (unsigned long long)basinHeight(a, w) << 32 | (~Q);
+    best = r > best ? r : best;
+  });
+  a.comp[L] = ~uint32_t(best);
+}
+
+// Pointer doubling in place.  Other lanes move their own slots along their own chains meanwhile, so whatever a load shows
+// is an ancestor.  A slot that names nothing of the array (the outside mark inside a chain included) trips the guard.
+__global__ __launch_bounds__(kIsoBlock) void isoBasinJumpKernel(const IsoBasinArgs a)
+{
+  const uint32_t x = blockIdx.x * kIsoBlock + threadIdx.x;
+  bool more = false, tripped = false;
+  if (x < a.jumpSize) {
+    const uint32_t own = a.jumpArray[x];
+    if (own != kIsoRegionOutside) {
+      uint32_t p = own;
+      bool fixed = false;
+      for (uint32_t hop = 0; hop <= kIsoBasinHops && !fixed && !tripped; hop++) {
+        if (p >= a.jumpSize) { tripped = true; break; }
+        const uint32_t q = a.jumpArray[p];
+        if (q == p) fixed = true;
+        else if (hop < kIsoBasinHops) p = q;            // the last round only looks whether p is a fixed point
+      }
+      if (!tripped) {
+        if (p != own) a.jumpArray[x] = p;
+        more = !fixed;
+      }
+    }
+  }
+  const unsigned long long m = __ballot(more);
+  if (m && (threadIdx.x & 63u) == uint32_t(__ffsll(m)) - 1u) atomicAdd(a.jumpCount, 1u);
+  if (tripped) atomicExch(a.errorFlag, 1);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinCountKernel(const IsoBasinArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  const uint32_t x = blockIdx.x * kIsoBlock + threadIdx.x;
+  const uint32_t isRoot = x < a.jumpSize && a.jumpArray[x] == x ? 1u : 0u;
+  uint32_t total;
+  (void)blockScan(isRoot, total, lds);
+  if (threadIdx.x == 0) a.blockCount[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinRankKernel(const IsoBasinArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  if (a.blockCount[blockIdx.x] == 0) return;          // the same for the whole block
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  const bool isPeak = L < a.numPoints && a.comp[L] == L;
+  uint32_t total;
+  const uint32_t before = blockScan(isPeak ? 1u : 0u, total, lds);
+  if (!isPeak) return;
+  const uint32_t number = uint32_t(a.chunkBase[blockIdx.x / kIsoChunk]) + a.blockBase[blockIdx.x] + before;   // < numRaw
+  a.comp[L] = kIsoRegionRanked | number;
+  a.peakOf[number] = L;
+  a.link[number] = number;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinLabelKernel(const IsoBasinArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  const uint32_t p = a.comp[L];
+  if (p == kIsoRegionOutside) return;
+  // a peak's slot holds kIsoRegionRanked | number until the peak's lane stores the number itself: the mask reads both
+  uint32_t mine = kIsoRegionOutside;
+  if (p & kIsoRegionRanked) mine = p & ~kIsoRegionRanked;
+  else if (p < a.numPoints) mine = a.comp[p] & ~kIsoRegionRanked;
+  if (mine >= a.numRaw) {                             // not what the passes before leave behind
+    atomicExch(a.errorFlag, 1);
+    return;
+  }
+  a.comp[L] = mine;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinPassKernel(const IsoBasinArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t mine = kIsoRegionOutside;
+  unsigned long long word = 0ull;
+  if (L < a.numPoints) mine = a.comp[L];
+  if (mine >= a.numRaw) mine = kIsoRegionOutside;     // the outside mark, or what only a tripped guard leaves behind
+  if (mine != kIsoRegionOutside) {
+    uint32_t height = 0u;
+    bool haveHeight = false;
+    basinNeighbours(a, L, [&](uint32_t Q) {
+      const uint32_t other = a.comp[Q];
+      if (other >= a.numRaw || other == mine) return;               // outside, or, most edges, inside: nothing more is read
+      if (!haveHeight) { height = basinHeight(a, a.values[L]); haveHeight = true; }
+      const uint32_t hq = basinHeight(a, a.values[Q]);
+      const unsigned long long w = (unsigned long long)(hq < height ? hq : height) << 32 | (~other);
+      word = w > word ? w : word;
+    });
+  }
+  // the lanes of a wave are consecutive L and mostly share one component or two: as in the regions' stats pass
+  bool in = word != 0ull;
+  unsigned long long pending = __ballot(in);
+#pragma unroll 1
+  for (int round = 0; round < 2; round++) {
+    if (!pending) return;                             // wave-uniform
+    const uint32_t leader = uint32_t(__ffsll(pending)) - 1u;
+    const uint32_t lb = uint32_t(__builtin_amdgcn_readlane(int(mine), int(leader)));
+    const bool same = in && mine == lb;
+    const unsigned long long m = __ballot(same);
+    unsigned long long top = same ? word : 0ull;
+    if (__popcll(m) > 1) {                            // wave-uniform
+#pragma unroll
+      for (int o = 32; o; o >>= 1) {
+        const unsigned long long t = __shfl_xor(top, o);
+        top = t > top ? t : top;
+      }
+    }
+    if (lane == leader && top > a.pass[lb]) atomicMax(reinterpret_cast<unsigned long long *>(a.pass + lb), top);
+    in = in && !same;
+    pending &= ~m;
+  }
+  if (in && word > a.pass[mine]) atomicMax(reinterpret_cast<unsigned long long *>(a.pass + mine), word);
+}
+
+// saddle and depth of the component n out of its word w != 0: one float32 subtraction
+__device__ __forceinline__ float basinDepth(const IsoBasinArgs &a, uint32_t n, unsigned long long w, float &saddle)
+{
+  const uint32_t hs = uint32_t(w >> 32);
+  saddle = regionValueOfKey(a.below ? ~hs : hs);
+  const float top = a.values[a.peakOf[n]];
+  return a.below ? saddle - top : top - saddle;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinLinkKernel(const IsoBasinArgs a)
+{
+  const uint32_t n = blockIdx.x * kIsoBlock + threadIdx.x;
+  bool linked = false;
+  if (n < a.numRaw && a.link[n] == n) {
+    const unsigned long long w = a.pass[n];
+    const uint32_t B = ~uint32_t(w);
+    if (w != 0ull && B < a.numRaw) {
+      float saddle;
+      const float depth = basinDepth(a, n, w, saddle);
+      const uint32_t hn = basinHeight(a, a.values[a.peakOf[n]]), hb = basinHeight(a, a.values[a.peakOf[B]]);
+      // raw numbers ascend with the peak's L
+      if (depth < a.minDepth && (hb > hn || (hb == hn && B < n))) {
+        a.link[n] = B;
+        linked = true;
+      }
+    } else if (w != 0ull) atomicExch(a.errorFlag, 1);
+  }
+  const unsigned long long m = __ballot(linked);
+  if (m && (threadIdx.x & 63u) == uint32_t(__ffsll(m)) - 1u) atomicAdd(a.jumpCount, uint32_t(__popcll(m)));
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinMergeKernel(const IsoBasinArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (L >= a.numPoints) return;
+  const uint32_t c = a.comp[L];
+  if (c == kIsoRegionOutside) return;
+  if (c >= a.numRaw) { atomicExch(a.errorFlag, 1); return; }
+  const uint32_t to = a.link[c];
+  if (to != c) a.comp[L] = to;
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinFinalKernel(const IsoBasinArgs a)
+{
+  __shared__ uint32_t lds[kIsoBlock / 64];
+  if (a.blockCount[blockIdx.x] == 0) return;          // the same for the whole block
+  const uint32_t n = blockIdx.x * kIsoBlock + threadIdx.x;
+  const bool isRoot = n < a.numRaw && a.link[n] == n;
+  uint32_t total;
+  const uint32_t before = blockScan(isRoot ? 1u : 0u, total, lds);
+  if (!isRoot) return;
+  const uint32_t number = uint32_t(a.chunkBase[blockIdx.x / kIsoChunk]) + a.blockBase[blockIdx.x] + before;   // < numBasins
+  a.finalOf[n] = number;
+  ExaHipBasin &r = a.basins[number];
+  r.points = 0;
+  r.sumFixed = 0;
+  for (int c = 0; c < 3; c++) { r.sumIndex[c] = 0; r.lo[c] = INT32_MAX; r.hi[c] = INT32_MIN; }
+  r.first = kIsoRegionOutside;
+  r.argMin = r.argMax = 0;
+  r.min = r.max = 0.f;
+  static_assert(sizeof(ExaHipBasin) == 96, "the table's record: no padding");
+  r.neighbour = int32_t(n);                           // parked for the finish kernel, which needs the component's word
+  r.saddle = r.depth = 0.f;
+  a.keys[2 * size_t(number)] = ~0ull;
+  a.keys[2 * size_t(number) + 1] = 0ull;
+}
+
+// what a lane, or the lanes of a wave that share a label, add to a basin: the regions' part on the basins' record
+__device__ __forceinline__ void basinAdd(const IsoBasinArgs &a, uint32_t label, const RegionPart &p)
+{
+  ExaHipBasin &r = a.basins[label];
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.points), (unsigned long long)p.points);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumFixed), (unsigned long long)p.sum);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[0]), p.si);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[1]), p.sj);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[2]), p.sk);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    atomicMin(&r.lo[c], p.lo[c]);
+    atomicMax(&r.hi[c], p.hi[c]);
+  }
+  atomicMin(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label)), p.keyMin);
+  atomicMax(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label) + 1), p.keyMax);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinStatsKernel(const IsoBasinArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  // isoRegionStatsKernel's scheme: a lane gathers its tiles as long as the label stays, the wave reduces the leading
+  // lane's label twice, what is left goes lane by lane
+  bool in = false;
+  uint32_t label = 0;
+  RegionPart own = regionNothing();
+#pragma unroll 1
+  for (uint32_t t = 0; t < kIsoRegionTiles; t++) {
+    const uint64_t at = (uint64_t(blockIdx.x) * kIsoRegionTiles + t) * kIsoBlock + threadIdx.x;
+    if (at >= a.numPoints) break;
+    const uint32_t L = uint32_t(at);
+    const uint32_t c = a.comp[L];
+    if (c == kIsoRegionOutside) continue;
+    const uint32_t mine = c < a.numRaw ? a.finalOf[c] : kIsoRegionOutside;
+    if (mine >= a.numBasins) {                        // not what the passes before leave behind: nothing is added anywhere
+      atomicExch(a.errorFlag, 1);
+      continue;
+    }
+    a.comp[L] = mine;
+    if (in && mine != label) {
+      basinAdd(a, label, own);
+      own = regionNothing();
+    }
+    in = true;
+    label = mine;
+    const float v = a.values[L];
+    const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+    const unsigned long long key = (unsigned long long)regionKey(v) << 32;
+    own.points++;
+    own.sum += __double2ll_rn(double(v) * a.scale);
+    own.si += i; own.sj += j; own.sk += k;
+    own.lo[0] = min(own.lo[0], int32_t(i)); own.lo[1] = min(own.lo[1], int32_t(j)); own.lo[2] = min(own.lo[2], int32_t(k));
+    own.hi[0] = max(own.hi[0], int32_t(i)); own.hi[1] = max(own.hi[1], int32_t(j)); own.hi[2] = max(own.hi[2], int32_t(k));
+    own.keyMin = min(own.keyMin, key | L);
+    own.keyMax = max(own.keyMax, key | (~L));
+  }
+  unsigned long long pending = __ballot(in);
+#pragma unroll 1
+  for (int round = 0; round < 2; round++) {
+    if (!pending) return;                             // wave-uniform
+    const uint32_t leader = uint32_t(__ffsll(pending)) - 1u;
+    const uint32_t lb = uint32_t(__builtin_amdgcn_readlane(int(label), int(leader)));
+    const bool same = in && label == lb;
+    const unsigned long long m = __ballot(same);
+    RegionPart part = own;
+    if (!same) part = regionNothing();
+    if (__popcll(m) > 1) regionReduce(part);          // wave-uniform
+    if (lane == leader) basinAdd(a, lb, part);
+    in = in && !same;
+    pending &= ~m;
+  }
+  if (in) basinAdd(a, label, own);
+}
+
+// `first` of every basin, behind the stats pass: the labels are final, and a thirteenth value per lane would take the stats
+// kernel past its 64 registers.  A wave holds 64 consecutive L; only a lane whose left neighbour holds another label (or the
+// wave's first lane) can be its basin's smallest L, and it goes to the record unless an agent-scope load (past the L1, which
+// other CUs' atomics never refresh) already shows a smaller one — in a basin of some size nearly every wave finds one.
+__global__ __launch_bounds__(kIsoBlock) void isoBasinFirstKernel(const IsoBasinArgs a)
+{
+  const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
+  const uint32_t label = L < a.numPoints ? a.comp[L] : kIsoRegionOutside;
+  const uint32_t left = uint32_t(__shfl_up(int(label), 1));
+  if (label >= a.numBasins) return;                   // outside
+  if ((threadIdx.x & 63u) != 0u && left == label) return;
+  uint32_t *first = &a.basins[label].first;
+  if (L < __hip_atomic_load(first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(first, L);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoBasinFinishKernel(const IsoBasinArgs a)
+{
+  const uint32_t b = blockIdx.x * kIsoBlock + threadIdx.x;
+  if (b >= a.numBasins) return;
+  const uint64_t kmin = a.keys[2 * size_t(b)], kmax = a.keys[2 * size_t(b) + 1];
+  ExaHipBasin &r = a.basins[b];
+  r.min = regionValueOfKey(uint32_t(kmin >> 32));
+  r.argMin = uint32_t(kmin);
+  r.max = regionValueOfKey(uint32_t(kmax >> 32));
+  r.argMax = ~uint32_t(kmax);
+  const uint32_t n = uint32_t(r.neighbour);           // the component's raw number, parked by the final kernel
+  const unsigned long long w = n < a.numRaw ? a.pass[n] : 0ull;
+  const uint32_t B = ~uint32_t(w);
+  if (w != 0ull && B < a.numRaw) {
+    float saddle;
+    r.depth = basinDepth(a, n, w, saddle);
+    r.saddle = saddle;
+    r.neighbour = int32_t(a.finalOf[B]);
+  } else {
+    r.neighbour = -1;
+    r.saddle = __uint_as_float(0x7fc00000u);
+    r.depth = __uint_as_float(0x7f800000u);
+  }
+}
+
 // ---- the stretch of a flow map on a lattice (exa_hip_flowmap): the largest eigenvalue of the Cauchy-Green tensor of the
 // map's differences, one lane per lattice point.  The matrix lives in named registers and the three rotations of a sweep are
 // written out: no indexed local array, so no scratch. ----
@@ -1212,6 +1553,96 @@ hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s)
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(isoRegionFinishKernel, dim3((a.numRegions + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the regions' init pass as it is: comp[L] = L or the outside mark, the inside count and max |V| into totals[1], totals[2]
+hipError_t launchIsoBasinInit(const IsoBasinArgs &a, hipStream_t s)
+{
+  IsoRegionArgs r = {};
+  r.values = a.values; r.numPoints = a.numPoints; r.nx = a.nx; r.ny = a.ny; r.nz = a.nz;
+  r.iso = a.iso; r.below = a.below; r.faces = a.faces;
+  r.parent = a.comp; r.numBlocks = a.numBlocks; r.numChunks = a.numChunks; r.totals = a.totals; r.errorFlag = a.errorFlag;
+  return launchIsoRegionInit(r, s);
+}
+
+hipError_t launchIsoBasinUp(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinUpKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// one pass of pointer doubling over array[0, size); *jumpCount, zeroed by the caller, counts the waves that are not done
+hipError_t launchIsoBasinJump(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s)
+{
+  IsoBasinArgs j = a;
+  j.jumpArray = array; j.jumpSize = size;
+  hipLaunchKernelGGL(isoBasinJumpKernel, dim3((size + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, j);
+  return hipGetLastError();
+}
+
+// the fixed points of array[0, size) per block, and the iso-surface's scans over that one count: totals[0] = their number
+hipError_t launchIsoBasinCount(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s)
+{
+  IsoBasinArgs j = a;
+  j.jumpArray = array; j.jumpSize = size;
+  IsoMeshArgs m = {};
+  m.numBlocks = (size + kIsoBlock - 1) / kIsoBlock; m.numChunks = (m.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  m.blockCount = a.blockCount; m.blockBase = a.blockBase; m.chunkBase = a.chunkBase; m.totals = a.totals;
+  hipLaunchKernelGGL(isoBasinCountKernel, dim3(m.numBlocks), dim3(kIsoBlock), 0, s, j);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoScanChunksKernel, dim3(m.numChunks, 1), dim3(kIsoBlock), 0, s, m);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoScanTopKernel, dim3(1), dim3(kIsoBlock), 0, s, m);
+  return hipGetLastError();
+}
+
+// the peaks' raw numbers, then every point's
+hipError_t launchIsoBasinRank(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinRankKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoBasinLabelKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoBasinPass(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinPassKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoBasinLink(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinLinkKernel, dim3((a.numRaw + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoBasinMerge(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinMergeKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launchIsoBasinFinal(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinFinalKernel, dim3((a.numRaw + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the labels and the measurements, then what the keys and the last round's words hold
+hipError_t launchIsoBasinStats(const IsoBasinArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(isoBasinStatsKernel, dim3((a.numBlocks + kIsoRegionTiles - 1) / kIsoRegionTiles), dim3(kIsoBlock), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoBasinFirstKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(isoBasinFinishKernel, dim3((a.numBasins + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
   return hipGetLastError();
 }
 

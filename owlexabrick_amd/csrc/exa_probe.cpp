@@ -4,8 +4,9 @@
 // the same rays (exa_hip_raycast_iso) in the same file, the field on the triangles of a mesh (exa_hip_sample_triangles), and
 // the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip) with the
 // contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit) and the connected
-// regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit) and the critical points of
-// a flow on it (exa_hip_critical_points; the same unit).
+// regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit), its basins, one per peak
+// (exa_hip_basins, exa_hip_basins_derived; the same unit), and the critical points of a flow on it (exa_hip_critical_points;
+// the same unit).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -1185,6 +1186,285 @@ int exa_hip_regions_stage_ms(ExaHipRenderer *h, float ms[6])
   if (!h || !ms) return 1;
   const ExaHipRenderer *r = firstChild(h);
   for (int k = 0; k < 6; k++) ms[k] = r->isoRegions.stageMs[k];
+  return 0;
+}
+
+// ---- basins of the inside set on a lattice: one per peak, shallow ones merged in rounds (exa_isomesh.hip) ----
+const char *const kBasinGuard = ": a loop guard of the basins tripped (a chain of links longer than the lattice, or more rounds than raw basins)";
+
+// exa_hip_basins (quantity < 0: the lattice holds the one channel channels[0]) and exa_hip_basins_derived.  The flags, the
+// channels and the quantity are checked by the caller.  The labels array of the result holds the up links, then the
+// components, until the stats pass.  Small read-backs steer the call: 4 bytes per pass of pointer doubling and per round
+// (the links it made), the counts behind the two numberings (peaks, then components), the loop guard at the end.
+static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                         const int32_t *channels, int32_t quantity, float iso, float minDepth, int32_t flags, uint64_t *numBasins,
+                         uint64_t *numRawBasins, uint64_t *numInside, int32_t *sumExponent, int32_t *rounds, void *hipStream)
+{
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isoBasins.release();
+  DropUnlessCommitted<ExaHipRenderer::IsoBasins> basins(r->isoBasins);       // whatever fails from here on leaves no result
+  ExaHipRenderer::IsoBasins &res = r->isoBasins;
+  for (float &ms : res.stageMs) ms = 0.f;
+  if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument (lo, hi or dims)"); return 1; }
+  if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
+  if (!(minDepth >= 0.f)) { h->fail(std::string(fn) + ": minDepth must be >= 0 (+INFINITY is allowed, NaN is not)"); return 1; }
+  for (int k = 0; k < 3; k++) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) { h->fail(std::string(fn) + ": the box must be finite"); return 1; }
+    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
+  }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
+  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
+    return 1;
+  }
+  hipStream_t s = (hipStream_t)hipStream;
+  const int32_t wf = flags & EXA_SAMPLE_WORLD_SPACE;
+
+  IsoBasinArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.iso = iso;
+  a.minDepth = minDepth;
+  a.below = (flags & EXA_REGIONS_BELOW) ? 1 : 0;
+  a.faces = (flags & EXA_REGIONS_FACES) ? 1 : 0;
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  a.errorFlag = r->errorFlag.p;
+  // the work space, freed when the call returns: chunkBase, totals, the jump count | blockCount, blockBase; the raw basins'
+  // arrays and the keys further down
+  DevBuf<char> work;
+  const size_t n64 = size_t(a.numChunks) + 4;
+  hipError_t e = res.values.alloc(n);
+  if (e == hipSuccess) e = res.labels.alloc(n);
+  if (e == hipSuccess) e = work.alloc(n64 * 8 + 2 * size_t(a.numBlocks) * 4);
+  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the labels (4 more)", e);
+  a.values = res.values.p;
+  a.comp = reinterpret_cast<uint32_t *>(res.labels.p);
+  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
+  a.totals = a.chunkBase + a.numChunks;
+  a.jumpCount = reinterpret_cast<uint32_t *>(a.totals + 3);
+  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  a.blockBase = a.blockCount + a.numBlocks;
+
+  TimingEvents<3> t;
+  HIP_TRY(h, t.create());
+  // what lies between two events, added to a stage; the stream is idle behind it
+  auto lap = [&](int from, int stage) -> int {
+    float ms = 0.f;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, t.elapsed(from, from + 1, &ms));
+    res.stageMs[stage] += ms;
+    return 0;
+  };
+  // pointer doubling over array[0, size) to its end: a chain shrinks to a fifth per pass, so 2^31 links need 14 passes
+  auto resolve = [&](uint32_t *array, uint32_t size) -> int {
+    for (int pass = 0;; pass++) {
+      uint32_t left = 0;
+      HIP_TRY(h, hipMemsetAsync(a.jumpCount, 0, sizeof(uint32_t), s));
+      HIP_TRY(h, launchIsoBasinJump(a, array, size, s));
+      HIP_TRY(h, hipMemcpyAsync(&left, a.jumpCount, sizeof(left), hipMemcpyDeviceToHost, s));
+      HIP_TRY(h, hipStreamSynchronize(s));
+      if (!left) return 0;
+      if (pass >= 32) {
+        if (int rc = checkLoopGuard(h, r, fn, kBasinGuard)) return rc;
+        h->fail(std::string(fn) + kBasinGuard);
+        return 3;
+      }
+    }
+  };
+
+  // the lattice: exa_hip_resample, or exa_hip_resample_derived, with a NaN fill into the device buffer (its checks of the
+  // box, the kd tree and the frame state apply; synchronous, with the descent's loop guard checked)
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  if (int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], wf, NAN, res.values.p, 1, hipStream, 0)
+                            : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, wf, NAN, res.values.p, 1, hipStream, 0)) {
+    h->fail(std::string(fn) + ": " + h->err);
+    return rc;
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  if (int rc = lap(0, 0)) return rc;
+
+  // the ascent: inside test and counts, the up links, their resolution
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  HIP_TRY(h, hipMemsetAsync(a.totals, 0, 3 * sizeof(uint64_t), s));
+  HIP_TRY(h, launchIsoBasinInit(a, s));
+  HIP_TRY(h, launchIsoBasinUp(a, s));
+  if (int rc = resolve(a.comp, a.numPoints)) return rc;
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  if (int rc = lap(0, 1)) return rc;
+
+  // the peaks, counted and numbered
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  HIP_TRY(h, launchIsoBasinCount(a, a.comp, a.numPoints, s));
+  uint64_t totals[3] = { 0, 0, 0 };              // raw basins, inside points, bits of max |V|
+  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  uint32_t maxBits = uint32_t(totals[2]);
+  float maxAbs;
+  std::memcpy(&maxAbs, &maxBits, sizeof(maxAbs));
+  int32_t exponent = 0;
+  if (totals[1] && maxAbs != 0.f) {
+    int ex = 0;
+    (void)std::frexp(maxAbs, &ex);
+    exponent = 30 - ex;
+  }
+  a.scale = std::ldexp(1.0, exponent);
+  a.numRaw = uint32_t(totals[0]);                // <= n
+  uint64_t numFinal = 0;
+  int32_t numRounds = 0;
+  if (a.numRaw) {
+    // per raw basin: the word of its pass | its peak, its link, its final number
+    DevBuf<char> raw;
+    DevBuf<uint64_t> keys;
+    e = raw.alloc(size_t(a.numRaw) * 20);
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the raw basins (20 bytes each)", e);
+    a.pass = reinterpret_cast<uint64_t *>(raw.p);
+    a.peakOf = reinterpret_cast<uint32_t *>(raw.p + size_t(a.numRaw) * 8);
+    a.link = a.peakOf + a.numRaw;
+    a.finalOf = a.link + a.numRaw;
+    HIP_TRY(h, launchIsoBasinRank(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    if (int rc = lap(0, 4)) return rc;
+
+    // the rounds; the last one makes no link and leaves every component's word for the table
+    for (;;) {
+      uint32_t links = 0;
+      HIP_TRY(h, hipEventRecord(t.ev[0], s));
+      HIP_TRY(h, hipMemsetAsync(a.pass, 0, size_t(a.numRaw) * 8, s));
+      HIP_TRY(h, launchIsoBasinPass(a, s));
+      HIP_TRY(h, hipEventRecord(t.ev[1], s));
+      HIP_TRY(h, hipMemsetAsync(a.jumpCount, 0, sizeof(uint32_t), s));
+      HIP_TRY(h, launchIsoBasinLink(a, s));
+      HIP_TRY(h, hipMemcpyAsync(&links, a.jumpCount, sizeof(links), hipMemcpyDeviceToHost, s));
+      HIP_TRY(h, hipStreamSynchronize(s));
+      if (links) {
+        if (uint32_t(numRounds) >= a.numRaw) {   // every round but the last removes a component
+          if (int rc = checkLoopGuard(h, r, fn, kBasinGuard)) return rc;
+          h->fail(std::string(fn) + kBasinGuard);
+          return 3;
+        }
+        numRounds++;
+        if (int rc = resolve(a.link, a.numRaw)) return rc;
+        HIP_TRY(h, launchIsoBasinMerge(a, s));
+      }
+      HIP_TRY(h, hipEventRecord(t.ev[2], s));
+      if (int rc = lap(0, 2)) return rc;
+      if (int rc = lap(1, 3)) return rc;
+      if (!links) break;
+    }
+
+    // the components, counted and numbered; the table
+    HIP_TRY(h, hipEventRecord(t.ev[0], s));
+    HIP_TRY(h, launchIsoBasinCount(a, a.link, a.numRaw, s));
+    HIP_TRY(h, hipMemcpyAsync(&numFinal, a.totals, sizeof(numFinal), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    a.numBasins = uint32_t(numFinal);            // 1 <= numBasins <= numRaw
+    e = res.basins.alloc(size_t(numFinal));
+    if (e == hipSuccess) e = keys.alloc(2 * size_t(numFinal));
+    if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the table of basins (96 bytes each, and 16 while the call runs)", e);
+    a.basins = res.basins.p;
+    a.keys = keys.p;
+    HIP_TRY(h, launchIsoBasinFinal(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    HIP_TRY(h, launchIsoBasinStats(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[2], s));
+    if (int rc = lap(0, 4)) return rc;           // the raw basins' arrays and the keys are freed behind it
+    if (int rc = lap(1, 5)) return rc;
+  } else {                                       // no basin: every label is the outside mark, which is -1
+    HIP_TRY(h, hipEventRecord(t.ev[1], s));
+    if (int rc = lap(0, 4)) return rc;
+  }
+  if (int rc = checkLoopGuard(h, r, fn, kBasinGuard)) return rc;
+  res.keptValues = (flags & EXA_REGIONS_KEEP_VALUES) != 0;
+  if (!res.keptValues) res.values.release();
+  res.have = true;
+  basins.commit();
+  if (numBasins) *numBasins = numFinal;
+  if (numRawBasins) *numRawBasins = totals[0];
+  if (numInside) *numInside = totals[1];
+  if (sumExponent) *sumExponent = exponent;
+  if (rounds) *rounds = numRounds;
+  return 0;
+}
+
+static void basinsZero(uint64_t *numBasins, uint64_t *numRawBasins, uint64_t *numInside, int32_t *sumExponent, int32_t *rounds)
+{
+  if (numBasins) *numBasins = 0;
+  if (numRawBasins) *numRawBasins = 0;
+  if (numInside) *numInside = 0;
+  if (sumExponent) *sumExponent = 0;
+  if (rounds) *rounds = 0;
+}
+
+int exa_hip_basins(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                   float minDepth, int32_t flags, uint64_t *numBasins, uint64_t *numRawBasins, uint64_t *numInside,
+                   int32_t *sumExponent, int32_t *rounds, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_basins";
+  basinsZero(numBasins, numRawBasins, numInside, sumExponent, rounds);
+  int rc = 1;
+  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint) && checkChannel(h, fn, channel))
+    rc = basinsExtract(h, fn, lo, hi, dims, &channel, -1, iso, minDepth, flags, numBasins, numRawBasins, numInside, sumExponent, rounds,
+                       hipStream);
+  if (rc) (void)exa_hip_basins_release(h);             // a failed call leaves no result, whichever check refused it
+  return rc;
+}
+
+int exa_hip_basins_derived(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                           int32_t quantity, float iso, float minDepth, int32_t flags, uint64_t *numBasins, uint64_t *numRawBasins,
+                           uint64_t *numInside, int32_t *sumExponent, int32_t *rounds, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_basins_derived";
+  basinsZero(numBasins, numRawBasins, numInside, sumExponent, rounds);
+  int rc = 1;
+  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint)) {
+    const int comps = derivedComponents(h, fn, channels, quantity);
+    if (comps > 1) h->fail(std::string(fn) + ": basins need a one-component quantity (EXA_DERIVED_VORTICITY has three)");
+    else if (comps == 1)
+      rc = basinsExtract(h, fn, lo, hi, dims, channels, quantity, iso, minDepth, flags, numBasins, numRawBasins, numInside, sumExponent,
+                         rounds, hipStream);
+  }
+  if (rc) (void)exa_hip_basins_release(h);
+  return rc;
+}
+
+int exa_hip_basins_read(ExaHipRenderer *h, int32_t *labels, ExaHipBasin *basins, float *values, int32_t pointersAreDevice,
+                        void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_basins_read";
+  ExaHipRenderer *r = firstChild(h);
+  const ExaHipRenderer::IsoBasins &res = r->isoBasins;
+  if (!res.have) { h->fail(std::string(fn) + ": no basins (exa_hip_basins comes first; a release or a failed call drops them)"); return 1; }
+  if (values && !res.keptValues) { h->fail(std::string(fn) + ": the basins were extracted without EXA_REGIONS_KEEP_VALUES"); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (labels && res.labels.n) HIP_TRY(h, hipMemcpyAsync(labels, res.labels.p, res.labels.n * sizeof(int32_t), kind, s));
+  if (basins && res.basins.n) HIP_TRY(h, hipMemcpyAsync(basins, res.basins.p, res.basins.n * sizeof(ExaHipBasin), kind, s));
+  if (values && res.values.n) HIP_TRY(h, hipMemcpyAsync(values, res.values.p, res.values.n * sizeof(float), kind, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+int exa_hip_basins_release(ExaHipRenderer *h)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  r->isoBasins.release();
+  return 0;
+}
+
+int exa_hip_basins_stage_ms(ExaHipRenderer *h, float ms[6])
+{
+  if (!h || !ms) return 1;
+  const ExaHipRenderer *r = firstChild(h);
+  for (int k = 0; k < 6; k++) ms[k] = r->isoBasins.stageMs[k];
   return 0;
 }
 

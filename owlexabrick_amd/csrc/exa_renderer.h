@@ -4,7 +4,7 @@
 // iso-surface extraction, exa_streamlines.cpp the streamline extraction and, on its evaluation, the line integral
 // convolution and the flow map, exa_stats.cpp the histogram and value range of
 // the cells, exa_module.cpp the setters, options and read-backs.  What the calls outside a frame keep on the handle is
-// one struct per call (ExaHipRenderer::probes, isoMesh, isolines, isoRegions, isoCritical, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
+// one struct per call (ExaHipRenderer::probes, isoMesh, isolines, isoRegions, isoCritical, isoBasins, hist, lines, project, surface); TimingEvents, DropUnlessCommitted and the
 // argument checks below the renderer are what their host code shares.
 #pragma once
 #include "exa_device.h"
@@ -341,6 +341,18 @@ struct ExaHipRenderer {
     float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
     void release() { points.release(); probe.release(); probeStatus.release(); have = probed = false; }
   } isoCritical;
+  // the basins of the last exa_hip_basins (in the renderer of devices[0] as well), independent of the mesh, the lines, the
+  // regions and the critical points: the labels (the up links, then the components while the call runs), the table, the
+  // lattice values where EXA_REGIONS_KEEP_VALUES kept them, and the time of the stages (values, ascent, passes, links, rank,
+  // stats)
+  struct IsoBasins {
+    DevBuf<int32_t> labels;
+    DevBuf<ExaHipBasin> basins;
+    DevBuf<float> values;
+    bool have = false, keptValues = false;
+    float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
+    void release() { labels.release(); basins.release(); values.release(); have = keptValues = false; }
+  } isoBasins;
   // exa_hip_histogram (on a multi-device handle: in the renderer of devices[0]): the work list of the pass — segments
   // {brick, first cell} by level and the offsets of the runs, built by the first call (exa_stats.cpp) —, whether the scene's
   // volume-weighted cell count fits 64 bits, the device copy of a call's result and the device time of its kernel

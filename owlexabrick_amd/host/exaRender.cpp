@@ -77,6 +77,15 @@
 //             [--regions-box lx ly lz ux uy uz] [--regions-world] (box default as for --resample)
 //             [--regions-below]              field < ISO instead
 //             [--regions-faces]              joined along the three axes only (6 neighbours)
+//             [--basins CHANNEL ISO MINDEPTH NX NY NZ out.basins] the basins of field >= ISO of CHANNEL on that lattice: one per
+//                                            local maximum, those shallower than MINDEPTH (`inf` is allowed) merged across their
+//                                            highest pass (exa_hip_basins).  With --derived the basins of that quantity
+//                                            (exa_hip_basins_derived; CHANNEL is read and ignored, vorticity refused).  One text
+//                                            line `basins NX NY NZ count B raw P rounds N inside I exponent S`, then raw
+//                                            little-endian arrays: the table (B records of 96 bytes, ExaHipBasin of
+//                                            include/exa_hip.h) and the labels (NX*NY*NZ int32, x fastest: the basin's number, -1
+//                                            outside); --frames 0 renders nothing; --regions-box, --regions-world,
+//                                            --regions-below and --regions-faces apply to it as well
 //             [--histogram BINS file.txt]   the exact histogram of a channel's cell values (exa_hip_histogram), one line
 //                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
 //             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
@@ -221,6 +230,9 @@ int main(int argc, char **argv)
     float regionsIso = 0.f;
     bool regionsWorld = false, regionsBelow = false, regionsFaces = false, haveRegionsBox = false;
     box3f regionsBox;
+    std::string basinsName;
+    int basinsChannel = 0, basinsDims[3] = { 0, 0, 0 };
+    float basinsIso = 0.f, basinsMinDepth = 0.f;
     std::string linesName;
     int linesChannel = 0;
     vec3f linesOrigin, linesDu, linesDv;
@@ -363,6 +375,14 @@ int main(int argc, char **argv)
         for (int k = 0; k < 3; k++) regionsDims[k] = (int)f();
         if (i + 1 >= argc) throw std::runtime_error("missing file after --regions CHANNEL ISO NX NY NZ");
         regionsName = argv[++i];
+      }
+      else if (a == "--basins") {
+        basinsChannel = (int)f();
+        basinsIso = f();
+        basinsMinDepth = f();
+        for (int k = 0; k < 3; k++) basinsDims[k] = (int)f();
+        if (i + 1 >= argc) throw std::runtime_error("missing file after --basins CHANNEL ISO MINDEPTH NX NY NZ");
+        basinsName = argv[++i];
       }
       else if (a == "--regions-box") { regionsBox.lower = { f(), f(), f() }; regionsBox.upper = { f(), f(), f() }; haveRegionsBox = true; }
       else if (a == "--regions-world") regionsWorld = true;
@@ -639,6 +659,25 @@ int main(int argc, char **argv)
       std::printf("iso %.9g world %d below %d faces %d count %zu inside %llu exponent %d\n", regionsIso, regionsWorld ? 1 : 0,
                   regionsBelow ? 1 : 0, regionsFaces ? 1 : 0, nr, (unsigned long long)R.numInside, R.sumExponent);
     }
+    if (!basinsName.empty()) {
+      const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
+      const vec3i dims(basinsDims[0], basinsDims[1], basinsDims[2]);
+      const Renderer::Basins B = derived < 0 ? renderer.basins(box, dims, basinsChannel, basinsIso, basinsMinDepth, regionsWorld, regionsBelow, regionsFaces)
+                                             : renderer.basinsDerived(box, dims, derivedChannels, derived, basinsIso, basinsMinDepth, regionsWorld, regionsBelow, regionsFaces);
+      FILE *f = std::fopen(basinsName.c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + basinsName);
+      const size_t nb = B.basins.size(), n = B.labels.size();
+      std::fprintf(f, "basins %d %d %d count %zu raw %llu rounds %d inside %llu exponent %d\n", dims.x, dims.y, dims.z, nb,
+                   (unsigned long long)B.numRaw, B.rounds, (unsigned long long)B.numInside, B.sumExponent);
+      const bool ok = std::fwrite(B.basins.data(), sizeof(ExaHipBasin), nb, f) == nb && std::fwrite(B.labels.data(), 4, n, f) == n;
+      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + basinsName);
+      std::printf("basins %d %d %d ", dims.x, dims.y, dims.z);
+      if (derived < 0) std::printf("channel %d ", basinsChannel);
+      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
+      std::printf("iso %.9g minDepth %.9g world %d below %d faces %d count %zu raw %llu rounds %d inside %llu exponent %d\n", basinsIso,
+                  basinsMinDepth, regionsWorld ? 1 : 0, regionsBelow ? 1 : 0, regionsFaces ? 1 : 0, nb, (unsigned long long)B.numRaw, B.rounds,
+                  (unsigned long long)B.numInside, B.sumExponent);
+    }
     if (!surfaceName.empty()) {
       const bool fromIso = surfaceMesh == "iso";
       if (fromIso && isoName.empty()) throw std::runtime_error("--surface iso needs --isomesh in the same invocation");
@@ -755,7 +794,7 @@ int main(int argc, char **argv)
                   raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
     }
     if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
-                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty()
+                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty() || !basinsName.empty()
                         || !licName.empty() || !ftleName.empty() || !criticalName.empty())) return 0;
     if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
       renderer.updateDt(dt);

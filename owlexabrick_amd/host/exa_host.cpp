@@ -664,6 +664,51 @@ Renderer::Regions Renderer::regionsDerived(const box3f &box, vec3i dims, vec3i c
   return readRegions(handle, dims, nr, ni, se, values);
 }
 
+// the basins of the last exa_hip_basins or exa_hip_basins_derived out of the module, which then drops them
+static Renderer::Basins readBasins(ExaHipRenderer *handle, vec3i dims, uint64_t numBasins, uint64_t numRaw, uint64_t numInside,
+                                   int32_t sumExponent, int32_t rounds, bool values)
+{
+  Renderer::Basins B;
+  const size_t n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
+  B.dims = dims;
+  B.numInside = numInside;
+  B.numRaw = numRaw;
+  B.sumExponent = sumExponent;
+  B.rounds = rounds;
+  B.labels.resize(n);
+  B.basins.resize(numBasins);
+  if (values) B.values.resize(n);
+  check(exa_hip_basins_read(handle, B.labels.data(), B.basins.data(), values ? B.values.data() : nullptr, 0, nullptr), handle);
+  check(exa_hip_basins_release(handle), handle);
+  return B;
+}
+
+Renderer::Basins Renderer::basins(const box3f &box, vec3i dims, int channel, float iso, float minDepth, bool worldSpace, bool below,
+                                  bool faces, bool values)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z };
+  uint64_t nb = 0, nr = 0, ni = 0;
+  int32_t se = 0, rounds = 0;
+  check(exa_hip_basins(handle, lo, hi, d, channel, iso, minDepth, regionFlags(worldSpace, below, faces, values), &nb, &nr, &ni, &se,
+                       &rounds, nullptr), handle);
+  return readBasins(handle, dims, nb, nr, ni, se, rounds, values);
+}
+
+Renderer::Basins Renderer::basinsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, float minDepth,
+                                         bool worldSpace, bool below, bool faces, bool values)
+{
+  if (worldSpace) pushState();
+  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
+  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  uint64_t nb = 0, nr = 0, ni = 0;
+  int32_t se = 0, rounds = 0;
+  check(exa_hip_basins_derived(handle, lo, hi, d, ch, quantity, iso, minDepth, regionFlags(worldSpace, below, faces, values), &nb, &nr,
+                               &ni, &se, &rounds, nullptr), handle);
+  return readBasins(handle, dims, nb, nr, ni, se, rounds, values);
+}
+
 Renderer::CriticalPoints Renderer::criticalPoints(const box3f &box, vec3i dims, vec3i channels, int iterations, float tolerance,
                                                   bool worldSpace, bool probe)
 {

@@ -259,6 +259,24 @@ struct Renderer {
   Regions regionsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, bool worldSpace = false,
                          bool below = false, bool faces = false, bool values = false);
 
+  // the basins of field >= iso (below: of minima of < iso) on the same lattice: one per local maximum, those that stand
+  // out of their highest pass by less than minDepth merged into the neighbour across it, round by round (exa_hip_basins;
+  // include/exa_hip.h states the contract).  Numbered by the lattice index of their peak; labels, values, numInside and
+  // sumExponent as for the regions; numRaw = the number of peaks, rounds = the rounds that merged something.
+  // basinsDerived: the same of a one-component quantity of the vector field `channels`.
+  struct Basins {
+    vec3i dims;
+    std::vector<int32_t> labels;
+    std::vector<ExaHipBasin> basins;
+    std::vector<float> values;
+    uint64_t numInside = 0, numRaw = 0;
+    int32_t sumExponent = 0, rounds = 0;
+  };
+  Basins basins(const box3f &box, vec3i dims, int channel, float iso, float minDepth, bool worldSpace = false, bool below = false,
+                bool faces = false, bool values = false);
+  Basins basinsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, float minDepth,
+                       bool worldSpace = false, bool below = false, bool faces = false, bool values = false);
+
   // the critical points of the vector field (channels.x, .y, .z) on the lattice of resample(box, dims): the zeros of the
   // trilinear interpolant, at most one per cell, found by `iterations` Newton steps and accepted within `tolerance`, each
   // classified by its Jacobian (exa_hip_critical_points; include/exa_hip.h states the contract): type & 3 = the eigenvalues
