@@ -46,8 +46,19 @@ struct IsoMeshArgs {
 
 hipError_t launchIsoCubePass(const IsoMeshArgs &a, hipStream_t s);
 hipError_t launchIsoPointPass(const IsoMeshArgs &a, hipStream_t s);
-hipError_t launchIsoScans(const IsoMeshArgs &a, hipStream_t s);
 hipError_t launchIsoEmit(const IsoMeshArgs &a, hipStream_t s);
+
+// the scans of every extraction here: `counts` (1 or 2) arrays of block counts, one behind the other in each of the four
+// buffers.  blockBase = the exclusive sums within the chunks, chunkBase = those over the chunk sums, totals = the sums.
+struct IsoScanArgs {
+  uint32_t numBlocks, numChunks;
+  uint32_t *blockCount;       // [counts][numBlocks]
+  uint32_t *blockBase;        // [counts][numBlocks]
+  uint64_t *chunkBase;        // [counts][numChunks]
+  uint64_t *totals;           // [counts]
+};
+
+hipError_t launchIsoScans(const IsoScanArgs &a, int counts, hipStream_t s);
 
 // ---- contour lines on a plane lattice (exa_hip_isolines): the 2D sibling, marching triangles on the split of every lattice
 // square along the diagonal (0,0)-(1,1).  One lane per lattice point L = j*nu + i, blocks of kIsoBlock consecutive L, one
@@ -58,7 +69,7 @@ hipError_t launchIsoEmit(const IsoMeshArgs &a, hipStream_t s);
 //                 is not finite), and the block's segment count
 //   point pass    mask[L] = bit (code-1) for every crossing triangle edge L -> L + (dx,dy), code = dx + 2 dy, that lies in a
 //                 valid square; rel[L] and the block's count as above
-//   scans         the iso-surface's (launchIsolineScans hands them the counts)
+//   scans         the iso-surface's
 //   emit          vertices and uv at vertexBase + chunkBase + blockBase + rel + popcount(mask below the edge's bit); segment
 //                 indices through the owning point's base and mask.  vertices, uv and segments point at the level's first
 //                 entry, vertexBase is the global index of its first vertex
@@ -86,7 +97,6 @@ struct IsoLineArgs {
 hipError_t launchIsolinePositions(const IsoLineArgs &a, hipStream_t s);
 hipError_t launchIsolineSquarePass(const IsoLineArgs &a, hipStream_t s);
 hipError_t launchIsolinePointPass(const IsoLineArgs &a, hipStream_t s);
-hipError_t launchIsolineScans(const IsoLineArgs &a, hipStream_t s);
 hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s);
 
 // ---- connected regions of the set inside(V) on the lattice (exa_hip_regions): a lock-free union-find over the lattice
@@ -103,7 +113,7 @@ hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s);
 //              agent-scope atomic loads (they bypass the L1, which other CUs' atomics never refresh); a stale value would
 //              only be an older ancestor.
 //   flatten    parent[L] = find(L); the block's number of roots (parent[L] == L) into blockCount
-//   scans      the iso-surface's, over that one count (launchIsoRegionScans); totals[0] = number of regions
+//   scans      the iso-surface's, over that one count; totals[0] = number of regions
 //   rank       a root's number = chunkBase + blockBase + its rank among the block's roots; it goes into the root's own slot
 //              as kIsoRegionRanked | number (L < 2^31 leaves the bit free) and starts the region's record
 //   stats      label = the number in the own slot (a root) or in the slot parent[L] names (masking the bit reads a root's
@@ -140,7 +150,6 @@ struct IsoRegionArgs {
 hipError_t launchIsoRegionInit(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionMerge(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionFlatten(const IsoRegionArgs &a, hipStream_t s);
-hipError_t launchIsoRegionScans(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s);
 hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s);
 
@@ -203,7 +212,7 @@ struct IsoBasinArgs {
 hipError_t launchIsoBasinInit(const IsoBasinArgs &a, hipStream_t s);
 hipError_t launchIsoBasinUp(const IsoBasinArgs &a, hipStream_t s);
 hipError_t launchIsoBasinJump(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s);
-hipError_t launchIsoBasinCount(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s);    // and the scans
+hipError_t launchIsoBasinCount(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s);
 hipError_t launchIsoBasinRank(const IsoBasinArgs &a, hipStream_t s);                                     // rank and label
 hipError_t launchIsoBasinPass(const IsoBasinArgs &a, hipStream_t s);
 hipError_t launchIsoBasinLink(const IsoBasinArgs &a, hipStream_t s);
@@ -232,7 +241,7 @@ hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s);
 //              after the other: the 8 x 3 corner loads, validity and the candidate test; the wave's ballot of candidates into
 //              marks (one 64-bit word per wave: a bit per lattice point), the block's count into blockCount; what the lanes
 //              have counted of cells and invalid cells over their tiles goes to the counters once per block of the launch
-//   scans      the iso-surface's over blockCount (launchIsoCriticalScans), then the compaction: candidate number
+//   scans      the iso-surface's over blockCount, then the compaction: candidate number
 //              chunkBase + blockBase + the marks below the lane's bit -> candidates[], ascending L
 //   refine     one lane per candidate, dense waves, the iteration count wave-uniform: s, lastStep and the class
 //              (kIsoCriticalFound or the reject's counter) into state / result, the block's found count into candCount, the
@@ -252,7 +261,7 @@ struct IsoCriticalArgs {
   float lo[3], step[3];       // lattice point i on axis a: lo[a] + (float(i) + 0.5f) * step[a]
   int32_t iterations;
   float tolerance;
-  unsigned long long *marks;  // [numBlocks][kIsoBlock / 64]
+  unsigned long long *marks;  // [numBlocks][kIsoBlock / 64], read and written word by word: behind the counters, 8-byte aligned
   uint32_t numBlocks, numChunks;
   uint32_t *blockCount;       // [numBlocks] candidates
   uint32_t *blockBase;        // [numBlocks]
@@ -276,7 +285,6 @@ struct IsoCriticalArgs {
 };
 
 hipError_t launchIsoCriticalCells(const IsoCriticalArgs &a, hipStream_t s);
-hipError_t launchIsoCriticalScans(const IsoCriticalArgs &a, bool found, hipStream_t s);     // found: the second round
 hipError_t launchIsoCriticalCompact(const IsoCriticalArgs &a, hipStream_t s);
 hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s);
 hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s);

@@ -172,8 +172,8 @@ __global__ __launch_bounds__(kIsoBlock) void isoPointKernel(const IsoMeshArgs a)
   if (threadIdx.x == 0) a.blockCount[blockIdx.x] = total;
 }
 
-// ---- scans: blockIdx.y = 0 vertices, 1 triangles ----
-__global__ __launch_bounds__(kIsoBlock) void isoScanChunksKernel(const IsoMeshArgs a)
+// ---- scans: one row of the grid per count (the iso-surface's: blockIdx.y = 0 vertices, 1 triangles) ----
+__global__ __launch_bounds__(kIsoBlock) void isoScanChunksKernel(const IsoScanArgs a)
 {
   __shared__ uint32_t lds[kIsoBlock / 64];
   constexpr uint32_t per = kIsoChunk / kIsoBlock;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(kIsoBlock) void isoScanChunksKernel(const IsoMeshAr
   if (threadIdx.x == 0) a.chunkBase[size_t(blockIdx.y) * a.numChunks + blockIdx.x] = total;     // the sum; scanned in place next
 }
 
-__global__ __launch_bounds__(kIsoBlock) void isoScanTopKernel(const IsoMeshArgs a)
+__global__ __launch_bounds__(kIsoBlock) void isoScanTopKernel(const IsoScanArgs a)
 {
   __shared__ uint64_t sums[kIsoBlock];
   uint64_t *chunk = a.chunkBase + size_t(blockIdx.x) * a.numChunks;
@@ -505,7 +505,8 @@ __global__ __launch_bounds__(kIsoBlock) void isolineEmitSegmentsKernel(const Iso
 }
 
 // ---- connected regions of the inside set (exa_hip_regions): the union-find and the passes of exa_isomesh.h ----
-__device__ __forceinline__ bool regionInside(const IsoRegionArgs &a, float v)
+template <typename A>      // IsoRegionArgs or IsoBasinArgs
+__device__ __forceinline__ bool regionInside(const A &a, float v)
 {
   return __builtin_isfinite(v) && (a.below ? v < a.iso : v >= a.iso);
 }
@@ -638,6 +639,34 @@ __global__ __launch_bounds__(kIsoBlock) void isoRegionFlattenKernel(const IsoReg
   if (tripped) atomicExch(a.errorFlag, 1);
 }
 
+// A record of the table (ExaHipRegion, or ExaHipBasin with the same leading fields) before the stats pass adds to it, and
+// its two keys.  rest(): the record's words behind `max`, stored before the keys: the compiler merges them with the stores
+// in front, which it cannot do across the stores to the keys.
+template <typename R, typename F>
+__device__ __forceinline__ void recordStart(R &r, uint64_t *keys, uint32_t number, uint32_t first, F rest)
+{
+  r.points = 0;
+  r.sumFixed = 0;
+  for (int c = 0; c < 3; c++) { r.sumIndex[c] = 0; r.lo[c] = INT32_MAX; r.hi[c] = INT32_MIN; }
+  r.first = first;
+  r.argMin = r.argMax = 0;
+  r.min = r.max = 0.f;
+  rest();
+  keys[2 * size_t(number)] = ~0ull;
+  keys[2 * size_t(number) + 1] = 0ull;
+}
+
+// min, max, argMin, argMax of record n out of its two keys
+template <typename R>
+__device__ __forceinline__ void recordRange(R &r, const uint64_t *keys, uint32_t n)
+{
+  const uint64_t kmin = keys[2 * size_t(n)], kmax = keys[2 * size_t(n) + 1];
+  r.min = regionValueOfKey(uint32_t(kmin >> 32));
+  r.argMin = uint32_t(kmin);
+  r.max = regionValueOfKey(uint32_t(kmax >> 32));
+  r.argMax = ~uint32_t(kmax);
+}
+
 __global__ __launch_bounds__(kIsoBlock) void isoRegionRankKernel(const IsoRegionArgs a)
 {
   __shared__ uint32_t lds[kIsoBlock / 64];
@@ -650,16 +679,8 @@ __global__ __launch_bounds__(kIsoBlock) void isoRegionRankKernel(const IsoRegion
   const uint32_t number = uint32_t(a.chunkBase[blockIdx.x / kIsoChunk]) + a.blockBase[blockIdx.x] + before;   // < numPoints
   a.parent[L] = kIsoRegionRanked | number;
   ExaHipRegion &r = a.regions[number];
-  r.points = 0;
-  r.sumFixed = 0;
-  for (int c = 0; c < 3; c++) { r.sumIndex[c] = 0; r.lo[c] = INT32_MAX; r.hi[c] = INT32_MIN; }
-  r.first = L;
-  r.argMin = r.argMax = 0;
-  r.min = r.max = 0.f;
   static_assert(sizeof(ExaHipRegion) == 88, "the table's record: 84 bytes of fields and 4 of padding");
-  reinterpret_cast<uint32_t *>(&r)[21] = 0u;          // the padding: every byte of the table is defined
-  a.keys[2 * size_t(number)] = ~0ull;
-  a.keys[2 * size_t(number) + 1] = 0ull;
+  recordStart(r, a.keys, number, L, [&] { reinterpret_cast<uint32_t *>(&r)[21] = 0u; });     // the padding: every byte of the table is defined
 }
 
 // what a lane, or the lanes of a wave that share a label, add to a region
@@ -692,9 +713,10 @@ __device__ __forceinline__ void regionReduce(RegionPart &p)
   }
 }
 
-__device__ __forceinline__ void regionAdd(const IsoRegionArgs &a, uint32_t label, const RegionPart &p)
+template <typename R>
+__device__ __forceinline__ void recordAdd(R *table, uint64_t *keys, uint32_t label, const RegionPart &p)
 {
-  ExaHipRegion &r = a.regions[label];
+  R &r = table[label];
   atomicAdd(reinterpret_cast<unsigned long long *>(&r.points), (unsigned long long)p.points);
   atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumFixed), (unsigned long long)p.sum);
   atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[0]), p.si);
@@ -705,8 +727,8 @@ __device__ __forceinline__ void regionAdd(const IsoRegionArgs &a, uint32_t label
     atomicMin(&r.lo[c], p.lo[c]);
     atomicMax(&r.hi[c], p.hi[c]);
   }
-  atomicMin(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label)), p.keyMin);
-  atomicMax(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label) + 1), p.keyMax);
+  atomicMin(reinterpret_cast<unsigned long long *>(keys + 2 * size_t(label)), p.keyMin);
+  atomicMax(reinterpret_cast<unsigned long long *>(keys + 2 * size_t(label) + 1), p.keyMax);
 }
 
 __device__ __forceinline__ RegionPart regionNothing()
@@ -714,7 +736,11 @@ __device__ __forceinline__ RegionPart regionNothing()
   return { 0u, 0ll, 0ull, 0ull, 0ull, { INT32_MAX, INT32_MAX, INT32_MAX }, { INT32_MIN, INT32_MIN, INT32_MIN }, ~0ull, 0ull };
 }
 
-__global__ __launch_bounds__(kIsoBlock) void isoRegionStatsKernel(const IsoRegionArgs a)
+// The stats pass of the regions and of the basins (a: IsoRegionArgs or IsoBasinArgs).  labelOf(L, slot): the number of the
+// record of the inside point L, whose slot of `labels` holds `slot`; a number that is none of the table's `count` records is
+// not what the passes before leave behind and trips the guard.
+template <typename A, typename R, typename F>
+__device__ __forceinline__ void recordStats(const A &a, uint32_t *labels, R *table, uint32_t count, F labelOf)
 {
   const uint32_t lane = threadIdx.x & 63u;
   // the lane's tiles, 256 points apart: in a region of some size they share its label, and the lane gathers them; where the
@@ -727,17 +753,16 @@ __global__ __launch_bounds__(kIsoBlock) void isoRegionStatsKernel(const IsoRegio
     const uint64_t at = (uint64_t(blockIdx.x) * kIsoRegionTiles + t) * kIsoBlock + threadIdx.x;
     if (at >= a.numPoints) break;
     const uint32_t L = uint32_t(at);
-    const uint32_t p = a.parent[L];
+    const uint32_t p = labels[L];
     if (p == kIsoRegionOutside) continue;
-    // a root's slot holds kIsoRegionRanked | number until the root's lane stores the number itself: the mask reads both
-    const uint32_t mine = ((p & kIsoRegionRanked) ? p : a.parent[p < L ? p : L]) & ~kIsoRegionRanked;
-    if (mine >= a.numRegions) {                       // not what the passes before leave behind: nothing is added anywhere
+    const uint32_t mine = labelOf(L, p);
+    if (mine >= count) {                              // nothing is added anywhere
       atomicExch(a.errorFlag, 1);
       continue;
     }
-    a.parent[L] = mine;
+    labels[L] = mine;
     if (in && mine != label) {
-      regionAdd(a, label, own);
+      recordAdd(table, a.keys, label, own);
       own = regionNothing();
     }
     in = true;
@@ -766,31 +791,29 @@ __global__ __launch_bounds__(kIsoBlock) void isoRegionStatsKernel(const IsoRegio
     RegionPart part = own;
     if (!same) part = regionNothing();
     if (__popcll(m) > 1) regionReduce(part);          // wave-uniform
-    if (lane == leader) regionAdd(a, lb, part);
+    if (lane == leader) recordAdd(table, a.keys, lb, part);
     in = in && !same;
     pending &= ~m;
   }
-  if (in) regionAdd(a, label, own);
+  if (in) recordAdd(table, a.keys, label, own);
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoRegionStatsKernel(const IsoRegionArgs a)
+{
+  // a root's slot holds kIsoRegionRanked | number until the root's lane stores the number itself: the mask reads both
+  recordStats(a, a.parent, a.regions, a.numRegions, [&](uint32_t L, uint32_t p) {
+    return ((p & kIsoRegionRanked) ? p : a.parent[p < L ? p : L]) & ~kIsoRegionRanked;
+  });
 }
 
 __global__ __launch_bounds__(kIsoBlock) void isoRegionFinishKernel(const IsoRegionArgs a)
 {
   const uint32_t n = blockIdx.x * kIsoBlock + threadIdx.x;
   if (n >= a.numRegions) return;
-  const uint64_t kmin = a.keys[2 * size_t(n)], kmax = a.keys[2 * size_t(n) + 1];
-  ExaHipRegion &r = a.regions[n];
-  r.min = regionValueOfKey(uint32_t(kmin >> 32));
-  r.argMin = uint32_t(kmin);
-  r.max = regionValueOfKey(uint32_t(kmax >> 32));
-  r.argMax = ~uint32_t(kmax);
+  recordRange(a.regions[n], a.keys, n);
 }
 
 // ---- basins of the inside set (exa_hip_basins): the ascent, the rounds and the table of exa_isomesh.h ----
-__device__ __forceinline__ bool basinInside(const IsoBasinArgs &a, float v)
-{
-  return __builtin_isfinite(v) && (a.below ? v < a.iso : v >= a.iso);
-}
-
 // the height of the contract: the ordered key, complemented for basins of minima
 __device__ __forceinline__ uint32_t basinHeight(const IsoBasinArgs &a, float v)
 {
@@ -818,12 +841,12 @@ __global__ __launch_bounds__(kIsoBlock) void isoBasinUpKernel(const IsoBasinArgs
   const uint32_t L = blockIdx.x * kIsoBlock + threadIdx.x;
   if (L >= a.numPoints) return;
   const float v = a.values[L];
-  if (!basinInside(a, v)) return;                     // the init kernel's outside mark stays
+  if (!regionInside(a, v)) return;                     // the init kernel's outside mark stays
   // the order of the contract as one word: the height, then the smaller L
   unsigned long long best = (unsigned long long)basinHeight(a, v) << 32 | (~L);
   basinNeighbours(a, L, [&](uint32_t Q) {
     const float w = a.values[Q];
-    if (!basinInside(a, w)) return;
+    if (!regionInside(a, w)) return;
     const unsigned long long r = (unsigned long long)basinHeight(a, w) << 32 | (~Q);
     best = r > best ? r : best;
   });
@@ -999,91 +1022,16 @@ __global__ __launch_bounds__(kIsoBlock) void isoBasinFinalKernel(const IsoBasinA
   const uint32_t number = uint32_t(a.chunkBase[blockIdx.x / kIsoChunk]) + a.blockBase[blockIdx.x] + before;   // < numBasins
   a.finalOf[n] = number;
   ExaHipBasin &r = a.basins[number];
-  r.points = 0;
-  r.sumFixed = 0;
-  for (int c = 0; c < 3; c++) { r.sumIndex[c] = 0; r.lo[c] = INT32_MAX; r.hi[c] = INT32_MIN; }
-  r.first = kIsoRegionOutside;
-  r.argMin = r.argMax = 0;
-  r.min = r.max = 0.f;
   static_assert(sizeof(ExaHipBasin) == 96, "the table's record: no padding");
-  r.neighbour = int32_t(n);                           // parked for the finish kernel, which needs the component's word
-  r.saddle = r.depth = 0.f;
-  a.keys[2 * size_t(number)] = ~0ull;
-  a.keys[2 * size_t(number) + 1] = 0ull;
-}
-
-// what a lane, or the lanes of a wave that share a label, add to a basin: the regions' part on the basins' record
-__device__ __forceinline__ void basinAdd(const IsoBasinArgs &a, uint32_t label, const RegionPart &p)
-{
-  ExaHipBasin &r = a.basins[label];
-  atomicAdd(reinterpret_cast<unsigned long long *>(&r.points), (unsigned long long)p.points);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumFixed), (unsigned long long)p.sum);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[0]), p.si);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[1]), p.sj);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&r.sumIndex[2]), p.sk);
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    atomicMin(&r.lo[c], p.lo[c]);
-    atomicMax(&r.hi[c], p.hi[c]);
-  }
-  atomicMin(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label)), p.keyMin);
-  atomicMax(reinterpret_cast<unsigned long long *>(a.keys + 2 * size_t(label) + 1), p.keyMax);
+  recordStart(r, a.keys, number, kIsoRegionOutside, [&] {       // `first` comes from the first kernel
+    r.neighbour = int32_t(n);                         // parked for the finish kernel, which needs the component's word
+    r.saddle = r.depth = 0.f;
+  });
 }
 
 __global__ __launch_bounds__(kIsoBlock) void isoBasinStatsKernel(const IsoBasinArgs a)
 {
-  const uint32_t lane = threadIdx.x & 63u;
-  // isoRegionStatsKernel's scheme: a lane gathers its tiles as long as the label stays, the wave reduces the leading
-  // lane's label twice, what is left goes lane by lane
-  bool in = false;
-  uint32_t label = 0;
-  RegionPart own = regionNothing();
-#pragma unroll 1
-  for (uint32_t t = 0; t < kIsoRegionTiles; t++) {
-    const uint64_t at = (uint64_t(blockIdx.x) * kIsoRegionTiles + t) * kIsoBlock + threadIdx.x;
-    if (at >= a.numPoints) break;
-    const uint32_t L = uint32_t(at);
-    const uint32_t c = a.comp[L];
-    if (c == kIsoRegionOutside) continue;
-    const uint32_t mine = c < a.numRaw ? a.finalOf[c] : kIsoRegionOutside;
-    if (mine >= a.numBasins) {                        // not what the passes before leave behind: nothing is added anywhere
-      atomicExch(a.errorFlag, 1);
-      continue;
-    }
-    a.comp[L] = mine;
-    if (in && mine != label) {
-      basinAdd(a, label, own);
-      own = regionNothing();
-    }
-    in = true;
-    label = mine;
-    const float v = a.values[L];
-    const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
-    const unsigned long long key = (unsigned long long)regionKey(v) << 32;
-    own.points++;
-    own.sum += __double2ll_rn(double(v) * a.scale);
-    own.si += i; own.sj += j; own.sk += k;
-    own.lo[0] = min(own.lo[0], int32_t(i)); own.lo[1] = min(own.lo[1], int32_t(j)); own.lo[2] = min(own.lo[2], int32_t(k));
-    own.hi[0] = max(own.hi[0], int32_t(i)); own.hi[1] = max(own.hi[1], int32_t(j)); own.hi[2] = max(own.hi[2], int32_t(k));
-    own.keyMin = min(own.keyMin, key | L);
-    own.keyMax = max(own.keyMax, key | (~L));
-  }
-  unsigned long long pending = __ballot(in);
-#pragma unroll 1
-  for (int round = 0; round < 2; round++) {
-    if (!pending) return;                             // wave-uniform
-    const uint32_t leader = uint32_t(__ffsll(pending)) - 1u;
-    const uint32_t lb = uint32_t(__builtin_amdgcn_readlane(int(label), int(leader)));
-    const bool same = in && label == lb;
-    const unsigned long long m = __ballot(same);
-    RegionPart part = own;
-    if (!same) part = regionNothing();
-    if (__popcll(m) > 1) regionReduce(part);          // wave-uniform
-    if (lane == leader) basinAdd(a, lb, part);
-    in = in && !same;
-    pending &= ~m;
-  }
-  if (in) basinAdd(a, label, own);
+  recordStats(a, a.comp, a.basins, a.numBasins, [&](uint32_t, uint32_t c) { return c < a.numRaw ? a.finalOf[c] : kIsoRegionOutside; });
 }
 
 // `first` of every basin, behind the stats pass: the labels are final, and a thirteenth value per lane would take the stats
@@ -1105,12 +1053,8 @@ __global__ __launch_bounds__(kIsoBlock) void isoBasinFinishKernel(const IsoBasin
 {
   const uint32_t b = blockIdx.x * kIsoBlock + threadIdx.x;
   if (b >= a.numBasins) return;
-  const uint64_t kmin = a.keys[2 * size_t(b)], kmax = a.keys[2 * size_t(b) + 1];
   ExaHipBasin &r = a.basins[b];
-  r.min = regionValueOfKey(uint32_t(kmin >> 32));
-  r.argMin = uint32_t(kmin);
-  r.max = regionValueOfKey(uint32_t(kmax >> 32));
-  r.argMax = ~uint32_t(kmax);
+  recordRange(r, a.keys, b);
   const uint32_t n = uint32_t(r.neighbour);           // the component's raw number, parked by the final kernel
   const unsigned long long w = n < a.numRaw ? a.pass[n] : 0ull;
   const uint32_t B = ~uint32_t(w);
@@ -1456,104 +1400,55 @@ __global__ __launch_bounds__(kIsoBlock) void isoCriticalPackKernel(const IsoCrit
   out[1] = g[0]; out[2] = g[1]; out[3] = g[2];
 }
 
+// ---- the launchers: every kernel runs in blocks of kIsoBlock lanes and takes its argument struct by value ----
+template <typename A>
+hipError_t launch(void (*kernel)(A), dim3 grid, hipStream_t s, const A &a)
+{
+  hipLaunchKernelGGL(kernel, grid, dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// blocks of `per` items that hold n of them
+constexpr uint32_t blocksOf(uint64_t n, uint32_t per = kIsoBlock) { return uint32_t((n + per - 1) / per); }
+
 } // namespace
 
-hipError_t launchIsoCriticalCells(const IsoCriticalArgs &a, hipStream_t s)
+hipError_t launchIsoScans(const IsoScanArgs &a, int counts, hipStream_t s)
 {
-  hipLaunchKernelGGL(isoCriticalCellKernel, dim3((a.numBlocks + kIsoCriticalTiles - 1) / kIsoCriticalTiles), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = launch(isoScanChunksKernel, dim3(a.numChunks, counts), s, a);
+  if (e == hipSuccess) e = launch(isoScanTopKernel, dim3(counts), s, a);
+  return e;
 }
 
-// the iso-surface's scans over one count (grid y = 1): the candidates per block of the lattice, or (found) the found points
-// per block of candidates; the total goes to totals[0] or totals[1]
-hipError_t launchIsoCriticalScans(const IsoCriticalArgs &a, bool found, hipStream_t s)
+hipError_t launchIsoCubePass(const IsoMeshArgs &a, hipStream_t s) { return launch(isoCubeKernel, a.numBlocks, s, a); }
+hipError_t launchIsoPointPass(const IsoMeshArgs &a, hipStream_t s) { return launch(isoPointKernel, a.numBlocks, s, a); }
+hipError_t launchIsoEmit(const IsoMeshArgs &a, hipStream_t s)
 {
-  IsoMeshArgs m = {};
-  m.numBlocks = found ? a.numCandBlocks : a.numBlocks; m.numChunks = found ? a.numCandChunks : a.numChunks;
-  m.blockCount = found ? a.candCount : a.blockCount; m.blockBase = found ? a.candBase : a.blockBase;
-  m.chunkBase = found ? a.candChunkBase : a.chunkBase; m.totals = a.totals + (found ? 1 : 0);
-  hipLaunchKernelGGL(isoScanChunksKernel, dim3(m.numChunks, 1), dim3(kIsoBlock), 0, s, m);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoScanTopKernel, dim3(1), dim3(kIsoBlock), 0, s, m);
-  return hipGetLastError();
+  hipError_t e = launch(isoEmitVerticesKernel, a.numBlocks, s, a);
+  if (e == hipSuccess) e = launch(isoEmitTrianglesKernel, a.numBlocks, s, a);
+  return e;
 }
 
-hipError_t launchIsoCriticalCompact(const IsoCriticalArgs &a, hipStream_t s)
+hipError_t launchIsolinePositions(const IsoLineArgs &a, hipStream_t s) { return launch(isolinePositionsKernel, a.numBlocks, s, a); }
+hipError_t launchIsolineSquarePass(const IsoLineArgs &a, hipStream_t s) { return launch(isolineSquareKernel, a.numBlocks, s, a); }
+hipError_t launchIsolinePointPass(const IsoLineArgs &a, hipStream_t s) { return launch(isolinePointKernel, a.numBlocks, s, a); }
+hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s)
 {
-  hipLaunchKernelGGL(isoCriticalCompactKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = launch(isolineEmitVerticesKernel, a.numBlocks, s, a);
+  if (e == hipSuccess) e = launch(isolineEmitSegmentsKernel, a.numBlocks, s, a);
+  return e;
 }
 
-hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoCriticalRefineKernel, dim3(a.numCandBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoCriticalEmitKernel, dim3(a.numCandBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoCriticalPack(const IsoCriticalArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoCriticalPackKernel, dim3(uint32_t((3ull * a.numFound + kIsoBlock - 1) / kIsoBlock)), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoLatticeStretchKernel, dim3((a.numPoints + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoRegionInit(const IsoRegionArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoRegionInitKernel, dim3((a.numBlocks + kIsoRegionTiles - 1) / kIsoRegionTiles), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoRegionMerge(const IsoRegionArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoRegionMergeKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoRegionFlatten(const IsoRegionArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoRegionFlattenKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-// the iso-surface's scans over the one count of the flatten pass (grid y = 1): they read nothing of their arguments but it
-hipError_t launchIsoRegionScans(const IsoRegionArgs &a, hipStream_t s)
-{
-  IsoMeshArgs m = {};
-  m.numBlocks = a.numBlocks; m.numChunks = a.numChunks;
-  m.blockCount = a.blockCount; m.blockBase = a.blockBase; m.chunkBase = a.chunkBase; m.totals = a.totals;
-  hipLaunchKernelGGL(isoScanChunksKernel, dim3(a.numChunks, 1), dim3(kIsoBlock), 0, s, m);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoScanTopKernel, dim3(1), dim3(kIsoBlock), 0, s, m);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoRegionRankKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
+hipError_t launchIsoRegionInit(const IsoRegionArgs &a, hipStream_t s) { return launch(isoRegionInitKernel, blocksOf(a.numBlocks, kIsoRegionTiles), s, a); }
+hipError_t launchIsoRegionMerge(const IsoRegionArgs &a, hipStream_t s) { return launch(isoRegionMergeKernel, a.numBlocks, s, a); }
+hipError_t launchIsoRegionFlatten(const IsoRegionArgs &a, hipStream_t s) { return launch(isoRegionFlattenKernel, a.numBlocks, s, a); }
+hipError_t launchIsoRegionRank(const IsoRegionArgs &a, hipStream_t s) { return launch(isoRegionRankKernel, a.numBlocks, s, a); }
 // the labels and the measurements, then min / max / argMin / argMax out of the keys
 hipError_t launchIsoRegionStats(const IsoRegionArgs &a, hipStream_t s)
 {
-  hipLaunchKernelGGL(isoRegionStatsKernel, dim3((a.numBlocks + kIsoRegionTiles - 1) / kIsoRegionTiles), dim3(kIsoBlock), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoRegionFinishKernel, dim3((a.numRegions + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = launch(isoRegionStatsKernel, blocksOf(a.numBlocks, kIsoRegionTiles), s, a);
+  if (e == hipSuccess) e = launch(isoRegionFinishKernel, blocksOf(a.numRegions), s, a);
+  return e;
 }
 
 // the regions' init pass as it is: comp[L] = L or the outside mark, the inside count and max |V| into totals[1], totals[2]
@@ -1566,150 +1461,47 @@ hipError_t launchIsoBasinInit(const IsoBasinArgs &a, hipStream_t s)
   return launchIsoRegionInit(r, s);
 }
 
-hipError_t launchIsoBasinUp(const IsoBasinArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoBasinUpKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
+hipError_t launchIsoBasinUp(const IsoBasinArgs &a, hipStream_t s) { return launch(isoBasinUpKernel, a.numBlocks, s, a); }
 // one pass of pointer doubling over array[0, size); *jumpCount, zeroed by the caller, counts the waves that are not done
 hipError_t launchIsoBasinJump(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s)
 {
   IsoBasinArgs j = a;
   j.jumpArray = array; j.jumpSize = size;
-  hipLaunchKernelGGL(isoBasinJumpKernel, dim3((size + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, j);
-  return hipGetLastError();
+  return launch(isoBasinJumpKernel, blocksOf(size), s, j);
 }
-
-// the fixed points of array[0, size) per block, and the iso-surface's scans over that one count: totals[0] = their number
+// the fixed points of array[0, size) per block into blockCount
 hipError_t launchIsoBasinCount(const IsoBasinArgs &a, uint32_t *array, uint32_t size, hipStream_t s)
 {
   IsoBasinArgs j = a;
   j.jumpArray = array; j.jumpSize = size;
-  IsoMeshArgs m = {};
-  m.numBlocks = (size + kIsoBlock - 1) / kIsoBlock; m.numChunks = (m.numBlocks + kIsoChunk - 1) / kIsoChunk;
-  m.blockCount = a.blockCount; m.blockBase = a.blockBase; m.chunkBase = a.chunkBase; m.totals = a.totals;
-  hipLaunchKernelGGL(isoBasinCountKernel, dim3(m.numBlocks), dim3(kIsoBlock), 0, s, j);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoScanChunksKernel, dim3(m.numChunks, 1), dim3(kIsoBlock), 0, s, m);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoScanTopKernel, dim3(1), dim3(kIsoBlock), 0, s, m);
-  return hipGetLastError();
+  return launch(isoBasinCountKernel, blocksOf(size), s, j);
 }
-
 // the peaks' raw numbers, then every point's
 hipError_t launchIsoBasinRank(const IsoBasinArgs &a, hipStream_t s)
 {
-  hipLaunchKernelGGL(isoBasinRankKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoBasinLabelKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = launch(isoBasinRankKernel, a.numBlocks, s, a);
+  if (e == hipSuccess) e = launch(isoBasinLabelKernel, a.numBlocks, s, a);
+  return e;
 }
-
-hipError_t launchIsoBasinPass(const IsoBasinArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoBasinPassKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoBasinLink(const IsoBasinArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoBasinLinkKernel, dim3((a.numRaw + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoBasinMerge(const IsoBasinArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoBasinMergeKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoBasinFinal(const IsoBasinArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoBasinFinalKernel, dim3((a.numRaw + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
+hipError_t launchIsoBasinPass(const IsoBasinArgs &a, hipStream_t s) { return launch(isoBasinPassKernel, a.numBlocks, s, a); }
+hipError_t launchIsoBasinLink(const IsoBasinArgs &a, hipStream_t s) { return launch(isoBasinLinkKernel, blocksOf(a.numRaw), s, a); }
+hipError_t launchIsoBasinMerge(const IsoBasinArgs &a, hipStream_t s) { return launch(isoBasinMergeKernel, a.numBlocks, s, a); }
+hipError_t launchIsoBasinFinal(const IsoBasinArgs &a, hipStream_t s) { return launch(isoBasinFinalKernel, blocksOf(a.numRaw), s, a); }
 // the labels and the measurements, then what the keys and the last round's words hold
 hipError_t launchIsoBasinStats(const IsoBasinArgs &a, hipStream_t s)
 {
-  hipLaunchKernelGGL(isoBasinStatsKernel, dim3((a.numBlocks + kIsoRegionTiles - 1) / kIsoRegionTiles), dim3(kIsoBlock), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoBasinFirstKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoBasinFinishKernel, dim3((a.numBasins + kIsoBlock - 1) / kIsoBlock), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = launch(isoBasinStatsKernel, blocksOf(a.numBlocks, kIsoRegionTiles), s, a);
+  if (e == hipSuccess) e = launch(isoBasinFirstKernel, a.numBlocks, s, a);
+  if (e == hipSuccess) e = launch(isoBasinFinishKernel, blocksOf(a.numBasins), s, a);
+  return e;
 }
 
-hipError_t launchIsolinePositions(const IsoLineArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isolinePositionsKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
+hipError_t launchIsoLatticeStretch(const IsoStretchArgs &a, hipStream_t s) { return launch(isoLatticeStretchKernel, blocksOf(a.numPoints), s, a); }
 
-hipError_t launchIsolineSquarePass(const IsoLineArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isolineSquareKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsolinePointPass(const IsoLineArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isolinePointKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-// the iso-surface's scans over the block counts of the two passes: they read nothing of their arguments but these
-hipError_t launchIsolineScans(const IsoLineArgs &a, hipStream_t s)
-{
-  IsoMeshArgs m = {};
-  m.numBlocks = a.numBlocks; m.numChunks = a.numChunks;
-  m.blockCount = a.blockCount; m.blockBase = a.blockBase; m.chunkBase = a.chunkBase; m.totals = a.totals;
-  return launchIsoScans(m, s);
-}
-
-hipError_t launchIsolineEmit(const IsoLineArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isolineEmitVerticesKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isolineEmitSegmentsKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoCubePass(const IsoMeshArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoCubeKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoPointPass(const IsoMeshArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoPointKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoScans(const IsoMeshArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoScanChunksKernel, dim3(a.numChunks, 2), dim3(kIsoBlock), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoScanTopKernel, dim3(2), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launchIsoEmit(const IsoMeshArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(isoEmitVerticesKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(isoEmitTrianglesKernel, dim3(a.numBlocks), dim3(kIsoBlock), 0, s, a);
-  return hipGetLastError();
-}
+hipError_t launchIsoCriticalCells(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalCellKernel, blocksOf(a.numBlocks, kIsoCriticalTiles), s, a); }
+hipError_t launchIsoCriticalCompact(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalCompactKernel, a.numBlocks, s, a); }
+hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalRefineKernel, a.numCandBlocks, s, a); }
+hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalEmitKernel, a.numCandBlocks, s, a); }
+hipError_t launchIsoCriticalPack(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalPackKernel, blocksOf(3ull * a.numFound), s, a); }
 
 } // namespace exa

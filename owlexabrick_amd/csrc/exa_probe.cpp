@@ -132,6 +132,15 @@ static int derivedComponents(ExaHipRenderer *h, const char *fn, const int32_t *c
   return quantity == EXA_DERIVED_VORTICITY ? 3 : 1;
 }
 
+// the same for a call that needs a one-component quantity: false after h->fail, for three components in the caller's words
+// ("a surface needs", "regions need")
+static bool oneComponent(ExaHipRenderer *h, const char *fn, const int32_t *channels, int32_t quantity, const char *needs)
+{
+  const int comps = derivedComponents(h, fn, channels, quantity);
+  if (comps > 1) h->fail(std::string(fn) + ": " + needs + " a one-component quantity (EXA_DERIVED_VORTICITY has three)");
+  return comps == 1;
+}
+
 static void derivedArgs(SampleArgs &a, const ExaHipRenderer *r, const int32_t *channels, int32_t quantity, int components)
 {
   a.numChannels = 3;
@@ -572,6 +581,145 @@ int exa_hip_raycast_iso_ms(ExaHipRenderer *h, float *ms)
   return 0;
 }
 
+} // extern "C"
+
+// ---- what the extractions on a lattice share (exa_isomesh.hip); outside the extern "C" block for the templates ----
+// a call of another entry point on behalf of fn failed with rc: its message with fn in front
+static int failedIn(ExaHipRenderer *h, const char *fn, int rc)
+{
+  h->fail(std::string(fn) + ": " + h->err);
+  return rc;
+}
+
+// The number of points of the lattice `dims`, 0 after h has failed with one of the caller's texts, axis by axis: boxText
+// where lo or hi is not finite or, with `ordered`, hi <= lo (nullptr: the box is left to the resampling call), then
+// dimsText where the axis has fewer than minDim points
+static uint64_t latticePoints(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                              int32_t minDim, const char *dimsText, const char *boxText, bool ordered)
+{
+  for (int k = 0; k < 3; k++) {
+    if (boxText && !(std::isfinite(lo[k]) && std::isfinite(hi[k]) && (!ordered || hi[k] > lo[k]))) { h->fail(std::string(fn) + ": " + boxText); return 0; }
+    if (dims[k] < minDim) { h->fail(std::string(fn) + ": " + dimsText); return 0; }
+  }
+  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
+  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
+    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
+    return 0;
+  }
+  return n;
+}
+
+// The blocks and chunks of n lattice points and the scans' work space for `counts` block counts, carved out of `work`
+// (freed when the call returns; every part aligned to its element): chunkBase | totals | extra64 more 64-bit words |
+// blockCount | blockBase | tailBytes more.  The six fields go to two places: `scan` is what launchIsoScans takes, and the
+// family's own kernels read the same fields out of their own arguments `a`, whose layout stays as it is.  The extra words
+// begin at scan.totals + counts, the tail at scan.blockBase + counts * scan.numBlocks.
+template <typename A>
+static hipError_t allocScans(DevBuf<char> &work, uint64_t n, int counts, size_t extra64, size_t tailBytes, A &a, IsoScanArgs &scan)
+{
+  scan.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  scan.numChunks = (scan.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  const size_t n64 = size_t(counts) * (size_t(scan.numChunks) + 1) + extra64, n32 = 2 * size_t(counts) * scan.numBlocks;
+  const hipError_t e = work.alloc(n64 * 8 + n32 * 4 + tailBytes);
+  if (e != hipSuccess) return e;
+  scan.chunkBase = reinterpret_cast<uint64_t *>(work.p);
+  scan.totals = scan.chunkBase + size_t(counts) * scan.numChunks;
+  scan.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
+  scan.blockBase = scan.blockCount + size_t(counts) * scan.numBlocks;
+  a.numBlocks = scan.numBlocks; a.numChunks = scan.numChunks;
+  a.blockCount = scan.blockCount; a.blockBase = scan.blockBase; a.chunkBase = scan.chunkBase; a.totals = scan.totals;
+  return hipSuccess;
+}
+
+// The lattice: exa_hip_resample of channels[0] or (quantity >= 0) exa_hip_resample_derived of channels[0..2], with a NaN
+// fill into the device buffer (its checks of the box, the channels, the quantity, the kd tree and the frame state apply;
+// synchronous, with the descent's loop guard checked)
+static int fillLattice(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                       const int32_t *channels, int32_t quantity, int32_t worldFlag, float *values, void *hipStream)
+{
+  const int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], worldFlag, NAN, values, 1, hipStream, 0)
+                              : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, worldFlag, NAN, values, 1, hipStream, 0);
+  return rc ? failedIn(h, fn, rc) : 0;
+}
+
+// a small read-back that steers the call: the stream is idle behind it
+static int readBack(ExaHipRenderer *h, void *dst, const void *src, size_t bytes, hipStream_t s)
+{
+  HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+// the exponent of the fixed-point sums of the regions and basins out of their totals: .., inside points, bits of max |V|
+static int32_t sumExponentOf(const uint64_t totals[3])
+{
+  const uint32_t maxBits = uint32_t(totals[2]);
+  float maxAbs;
+  std::memcpy(&maxAbs, &maxBits, sizeof(maxAbs));
+  if (!totals[1] || maxAbs == 0.f) return 0;
+  int ex = 0;
+  (void)std::frexp(maxAbs, &ex);
+  return 30 - ex;
+}
+
+// What regionsExtract and basinsExtract do alike in front of their passes (A: IsoRegionArgs or IsoBasinArgs): the common
+// fields of the kernels' arguments, the result's values and labels, and the scans' work space with extra64 words behind
+// the three totals ...
+template <typename A, typename R>
+static int labelledSetup(ExaHipRenderer *h, const char *fn, const int32_t dims[3], float iso, int32_t flags, size_t extra64,
+                         LabelledLattice<R> &res, DevBuf<char> &work, A &a, IsoScanArgs &scan)
+{
+  const size_t n = size_t(dims[0]) * size_t(dims[1]) * size_t(dims[2]);       // checked by the caller (latticePoints)
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.iso = iso;
+  a.below = (flags & EXA_REGIONS_BELOW) ? 1 : 0;
+  a.faces = (flags & EXA_REGIONS_FACES) ? 1 : 0;
+  a.errorFlag = firstChild(h)->errorFlag.p;
+  hipError_t e = res.values.alloc(n);
+  if (e == hipSuccess) e = res.labels.alloc(n);
+  if (e == hipSuccess) e = allocScans(work, n, 1, 2 + extra64, 0, a, scan);
+  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the labels (4 more)", e);
+  a.values = res.values.p;
+  return 0;
+}
+
+// ... and behind them: the values kept or dropped, the result committed, the out-parameters that both have
+template <typename R>
+static void labelledCommit(LabelledLattice<R> &res, DropUnlessCommitted<LabelledLattice<R>> &guard, int32_t flags,
+                           const uint64_t totals[3], int32_t exponent, uint64_t *numInside, int32_t *sumExponent)
+{
+  res.keptValues = (flags & EXA_REGIONS_KEEP_VALUES) != 0;
+  if (!res.keptValues) res.values.release();
+  res.have = true;
+  guard.commit();
+  if (numInside) *numInside = totals[1];
+  if (sumExponent) *sumExponent = exponent;
+}
+
+// exa_hip_regions_read and exa_hip_basins_read, each with its own two texts
+template <typename R>
+static int labelledRead(ExaHipRenderer *h, const char *fn, LabelledLattice<R> ExaHipRenderer::*which, const char *noneText,
+                        const char *noValuesText, int32_t *labels, R *table, float *values, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  const LabelledLattice<R> &res = r->*which;
+  if (!res.have) { h->fail(std::string(fn) + ": " + noneText); return 1; }
+  if (values && !res.keptValues) { h->fail(std::string(fn) + ": " + noValuesText); return 1; }
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  HIP_TRY(h, copyOut(labels, res.labels, kind, s));
+  HIP_TRY(h, copyOut(table, res.table, kind, s));
+  HIP_TRY(h, copyOut(values, res.values, kind, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" {
+
 // ---- iso-surface extraction (exa_isomesh.hip) ----
 // exa_hip_isosurface (quantity < 0: the lattice holds the one channel channels[0]) and exa_hip_isosurface_derived (it holds
 // the quantity of channels[0..2]; no gradients: the caller has refused the flag).  Filling the lattice is the one step in
@@ -582,10 +730,8 @@ static int isoExtract(ExaHipRenderer *h, const char *fn, const float lo[3], cons
 {
   if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument"); return 1; }
   if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
-  for (int k = 0; k < 3; k++)
-    if (dims[k] < 2) { h->fail(std::string(fn) + ": dims must be >= 2 on every axis (a lattice of cubes)"); return 1; }
-  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);
-  if (n > uint64_t(INT32_MAX)) { h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points"); return 1; }
+  const uint64_t n = latticePoints(h, fn, lo, hi, dims, 2, "dims must be >= 2 on every axis (a lattice of cubes)", nullptr, false);
+  if (!n) return 1;
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
@@ -600,47 +746,32 @@ static int isoExtract(ExaHipRenderer *h, const char *fn, const float lo[3], cons
   a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
   a.iso = iso;
   for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
-  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
-  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
-  // the work space of one extraction, freed when the call returns: values | chunkBase, totals | blockCount, blockBase |
-  // rel | cubeInfo, mask (every part aligned to its element)
+  // the work space of one extraction: the scans' for the two counts (vertices, triangles) | rel | cubeInfo, mask
   DevBuf<float> values;
   DevBuf<char> work;
-  const size_t n64 = 2 * size_t(a.numChunks) + 2, n32 = 4 * size_t(a.numBlocks);
-  const size_t n16 = n + (n & 1), workBytes = n64 * 8 + n32 * 4 + n16 * 2 + 2 * n;
+  IsoScanArgs scan;
+  const size_t n16 = n + (n & 1);
   hipError_t e = values.alloc(n);
-  if (e == hipSuccess) e = work.alloc(workBytes);
+  if (e == hipSuccess) e = allocScans(work, n, 2, 0, n16 * 2 + 2 * n, a, scan);
   if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the work space (4 more)", e);
   a.values = values.p;
-  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
-  a.totals = a.chunkBase + 2 * size_t(a.numChunks);
-  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
-  a.blockBase = a.blockCount + 2 * size_t(a.numBlocks);
-  a.rel = reinterpret_cast<uint16_t *>(work.p + n64 * 8 + n32 * 4);
-  a.cubeInfo = reinterpret_cast<uint8_t *>(work.p + n64 * 8 + n32 * 4 + n16 * 2);
+  a.rel = reinterpret_cast<uint16_t *>(scan.blockBase + 2 * size_t(scan.numBlocks));
+  a.cubeInfo = reinterpret_cast<uint8_t *>(a.rel + n16);
   a.mask = a.cubeInfo + n;
 
   TimingEvents<7> t;
   HIP_TRY(h, t.create());
-  // the lattice: exa_hip_resample, or exa_hip_resample_derived, with a NaN fill into the device buffer (its checks of the
-  // box, the channels, the quantity, the kd tree and the frame state apply; synchronous, with the loop guard's check)
   HIP_TRY(h, hipEventRecord(t.ev[0], s));
-  const int32_t wf = world ? EXA_SAMPLE_WORLD_SPACE : 0;
-  if (int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], wf, NAN, values.p, 1, hipStream, 0)
-                            : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, wf, NAN, values.p, 1, hipStream, 0)) {
-    h->fail(std::string(fn) + ": " + h->err);
-    return rc;
-  }
+  if (int rc = fillLattice(h, fn, lo, hi, dims, channels, quantity, world ? EXA_SAMPLE_WORLD_SPACE : 0, values.p, hipStream)) return rc;
   HIP_TRY(h, hipEventRecord(t.ev[1], s));
   HIP_TRY(h, launchIsoCubePass(a, s));
   HIP_TRY(h, hipEventRecord(t.ev[2], s));
   HIP_TRY(h, launchIsoPointPass(a, s));
   HIP_TRY(h, hipEventRecord(t.ev[3], s));
-  HIP_TRY(h, launchIsoScans(a, s));
+  HIP_TRY(h, launchIsoScans(scan, 2, s));
   HIP_TRY(h, hipEventRecord(t.ev[4], s));
   uint64_t totals[2] = { 0, 0 };                 // vertices, triangles
-  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
+  if (readBack(h, totals, a.totals, sizeof(totals), s)) return 1;
   if (totals[0] > uint64_t(INT32_MAX) || totals[1] > uint64_t(INT32_MAX)) {
     h->fail(std::string(fn) + ": the surface has " + std::to_string(totals[0]) + " vertices and " + std::to_string(totals[1]) +
             " triangles: more than INT32_MAX, the indices are int32 (extract it in parts)");
@@ -667,10 +798,8 @@ static int isoExtract(ExaHipRenderer *h, const char *fn, const float lo[3], cons
       vals = scratch.p;
     }
     const int32_t pf = (world ? EXA_SAMPLE_WORLD_SPACE : 0) | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
-    if (int rc = exa_hip_sample_points(h, r->isoMesh.vertices.p, totals[0], channels, 1, pf, NAN, vals, r->isoMesh.gradients.p, nullptr, 1, hipStream, 0)) {
-      h->fail(std::string(fn) + ": " + h->err);
-      return rc;
-    }
+    if (int rc = exa_hip_sample_points(h, r->isoMesh.vertices.p, totals[0], channels, 1, pf, NAN, vals, r->isoMesh.gradients.p, nullptr, 1, hipStream, 0))
+      return failedIn(h, fn, rc);
   }
   HIP_TRY(h, hipEventRecord(t.ev[6], s));
   HIP_TRY(h, hipStreamSynchronize(s));
@@ -706,9 +835,7 @@ int exa_hip_isosurface_derived(ExaHipRenderer *h, const float lo[3], const float
     return 1;
   }
   if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE, " (only EXA_SAMPLE_WORLD_SPACE applies)")) return 1;
-  const int comps = derivedComponents(h, fn, channels, quantity);
-  if (!comps) return 1;
-  if (comps != 1) { h->fail(std::string(fn) + ": a surface needs a one-component quantity (EXA_DERIVED_VORTICITY has three)"); return 1; }
+  if (!oneComponent(h, fn, channels, quantity, "a surface needs")) return 1;
   return isoExtract(h, fn, lo, hi, dims, channels, quantity, iso, flags, numVertices, numTriangles, hipStream);
 }
 
@@ -718,34 +845,21 @@ int exa_hip_isosurface_read(ExaHipRenderer *h, float *vertices, float *gradients
   if (!h) return 1;
   const char *fn = "exa_hip_isosurface_read";
   ExaHipRenderer *r = firstChild(h);
-  if (!r->isoMesh.have) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
-  if (gradients && r->isoMesh.vertices.n && !r->isoMesh.gradients.n) { h->fail(std::string(fn) + ": the mesh was extracted without EXA_SAMPLE_GRADIENT"); return 1; }
+  const ExaHipRenderer::IsoMesh &res = r->isoMesh;
+  if (!res.have) { h->fail(std::string(fn) + ": no mesh (exa_hip_isosurface comes first; a release or a failed extraction drops it)"); return 1; }
+  if (gradients && res.vertices.n && !res.gradients.n) { h->fail(std::string(fn) + ": the mesh was extracted without EXA_SAMPLE_GRADIENT"); return 1; }
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (vertices && r->isoMesh.vertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, r->isoMesh.vertices.p, r->isoMesh.vertices.n * sizeof(float), kind, s));
-  if (gradients && r->isoMesh.gradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, r->isoMesh.gradients.p, r->isoMesh.gradients.n * sizeof(float), kind, s));
-  if (triangles && r->isoMesh.triangles.n) HIP_TRY(h, hipMemcpyAsync(triangles, r->isoMesh.triangles.p, r->isoMesh.triangles.n * sizeof(int32_t), kind, s));
+  HIP_TRY(h, copyOut(vertices, res.vertices, kind, s));
+  HIP_TRY(h, copyOut(gradients, res.gradients, kind, s));
+  HIP_TRY(h, copyOut(triangles, res.triangles, kind, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   return 0;
 }
 
-int exa_hip_isosurface_release(ExaHipRenderer *h)
-{
-  if (!h) return 1;
-  ExaHipRenderer *r = firstChild(h);
-  EXA_ON_DEVICE_OF(h, r);
-  r->isoMesh.release();
-  return 0;
-}
-
-int exa_hip_isosurface_stage_ms(ExaHipRenderer *h, float ms[6])
-{
-  if (!h || !ms) return 1;
-  const ExaHipRenderer *r = firstChild(h);
-  for (int k = 0; k < 6; k++) ms[k] = r->isoMesh.stageMs[k];
-  return 0;
-}
+int exa_hip_isosurface_release(ExaHipRenderer *h) { return releaseResult(h, &ExaHipRenderer::isoMesh); }
+int exa_hip_isosurface_stage_ms(ExaHipRenderer *h, float ms[6]) { return readStageMs(h, &ExaHipRenderer::isoMesh, ms); }
 
 // ---- contour lines on a plane lattice (exa_isomesh.hip) ----
 // exa_hip_isolines (quantity < 0: the lattice holds the one channel channels[0]) and exa_hip_isolines_derived (it holds the
@@ -785,8 +899,7 @@ static int isolinesExtract(ExaHipRenderer *h, const char *fn, const ExaHipPlane 
   a.numPoints = uint32_t(n);
   a.nu = uint32_t(plane->nu); a.nv = uint32_t(plane->nv);
   for (int k = 0; k < 3; k++) { a.origin[k] = plane->origin[k]; a.du[k] = plane->du[k]; a.dv[k] = plane->dv[k]; }
-  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
-  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);      // for the positions; once more with the work space
 
   TimingEvents<5> t;
   HIP_TRY(h, t.create());
@@ -803,29 +916,22 @@ static int isolinesExtract(ExaHipRenderer *h, const char *fn, const ExaHipPlane 
     HIP_TRY(h, hipEventRecord(t.ev[0], s));
     HIP_TRY(h, launchIsolinePositions(a, s));
     if (int rc = quantity < 0 ? exa_hip_sample_points(h, positions.p, n, channels, 1, wf, NAN, res.values.p, nullptr, nullptr, 1, hipStream, 0)
-                              : exa_hip_sample_derived(h, positions.p, n, channels, quantity, wf, NAN, res.values.p, nullptr, 1, hipStream, 0)) {
-      h->fail(std::string(fn) + ": " + h->err);
-      return rc;
-    }
+                              : exa_hip_sample_derived(h, positions.p, n, channels, quantity, wf, NAN, res.values.p, nullptr, 1, hipStream, 0))
+      return failedIn(h, fn, rc);
     HIP_TRY(h, hipEventRecord(t.ev[1], s));
     HIP_TRY(h, hipStreamSynchronize(s));
     HIP_TRY(h, t.elapsed(0, 1, &res.stageMs[0]));
     a.positions = nullptr;
   }
   a.values = res.values.p;
-  // the work space of one level, freed when the call returns: chunkBase, totals | blockCount, blockBase | rel | squareInfo,
-  // mask (every part aligned to its element)
+  // the work space of one level: the scans' for the two counts (vertices, segments) | rel | squareInfo, mask
   DevBuf<char> work;
-  const size_t n64 = 2 * size_t(a.numChunks) + 2, n32 = 4 * size_t(a.numBlocks);
-  const size_t n16 = n + (n & 1), workBytes = n64 * 8 + n32 * 4 + n16 * 2 + 2 * n;
-  e = work.alloc(workBytes);
+  IsoScanArgs scan;
+  const size_t n16 = n + (n & 1);
+  e = allocScans(work, n, 2, 0, n16 * 2 + 2 * n, a, scan);
   if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the work space (4 bytes per lattice point)", e);
-  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
-  a.totals = a.chunkBase + 2 * size_t(a.numChunks);
-  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
-  a.blockBase = a.blockCount + 2 * size_t(a.numBlocks);
-  a.rel = reinterpret_cast<uint16_t *>(work.p + n64 * 8 + n32 * 4);
-  a.squareInfo = reinterpret_cast<uint8_t *>(work.p + n64 * 8 + n32 * 4 + n16 * 2);
+  a.rel = reinterpret_cast<uint16_t *>(scan.blockBase + 2 * size_t(scan.numBlocks));
+  a.squareInfo = reinterpret_cast<uint8_t *>(a.rel + n16);
   a.mask = a.squareInfo + n;
 
   // square pass, point pass and scans of the level a.iso, timed into stages 1..3; the level's totals {vertices, segments}
@@ -835,10 +941,9 @@ static int isolinesExtract(ExaHipRenderer *h, const char *fn, const ExaHipPlane 
     HIP_TRY(h, hipEventRecord(t.ev[1], s));
     HIP_TRY(h, launchIsolinePointPass(a, s));
     HIP_TRY(h, hipEventRecord(t.ev[2], s));
-    HIP_TRY(h, launchIsolineScans(a, s));
+    HIP_TRY(h, launchIsoScans(scan, 2, s));
     HIP_TRY(h, hipEventRecord(t.ev[3], s));
-    HIP_TRY(h, hipMemcpyAsync(totals, a.totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    if (readBack(h, totals, a.totals, 2 * sizeof(uint64_t), s)) return 1;
     for (int k = 0; k < 3; k++) { HIP_TRY(h, t.elapsed(k, k + 1, &ms)); res.stageMs[1 + k] += ms; }
     return 0;
   };
@@ -892,10 +997,8 @@ static int isolinesExtract(ExaHipRenderer *h, const char *fn, const ExaHipPlane 
     }
     HIP_TRY(h, hipEventRecord(t.ev[0], s));
     const int32_t pf = wf | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
-    if (int rc = exa_hip_sample_points(h, res.vertices.p, nv, channels, 1, pf, NAN, vals, res.gradients.p, nullptr, 1, hipStream, 0)) {
-      h->fail(std::string(fn) + ": " + h->err);
-      return rc;
-    }
+    if (int rc = exa_hip_sample_points(h, res.vertices.p, nv, channels, 1, pf, NAN, vals, res.gradients.p, nullptr, 1, hipStream, 0))
+      return failedIn(h, fn, rc);
     HIP_TRY(h, hipEventRecord(t.ev[1], s));
     HIP_TRY(h, hipStreamSynchronize(s));
     HIP_TRY(h, t.elapsed(0, 1, &res.stageMs[5]));
@@ -938,12 +1041,9 @@ int exa_hip_isolines_derived(ExaHipRenderer *h, const ExaHipPlane *plane, const 
   if (flags & EXA_SAMPLE_GRADIENT)
     h->fail(std::string(fn) + ": EXA_SAMPLE_GRADIENT does not apply (a gradient of a derived quantity would need second derivatives)");
   else if (checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_ISOLINES_KEEP_VALUES,
-                      " (EXA_SAMPLE_WORLD_SPACE and EXA_ISOLINES_KEEP_VALUES apply)")) {
-    const int comps = derivedComponents(h, fn, channels, quantity);
-    if (comps > 1) h->fail(std::string(fn) + ": contour lines need a one-component quantity (EXA_DERIVED_VORTICITY has three)");
-    else if (comps == 1)
-      rc = isolinesExtract(h, fn, plane, channels, quantity, isos, numIsos, flags, numVertices, numSegments, hipStream);
-  }
+                      " (EXA_SAMPLE_WORLD_SPACE and EXA_ISOLINES_KEEP_VALUES apply)") &&
+           oneComponent(h, fn, channels, quantity, "contour lines need"))
+    rc = isolinesExtract(h, fn, plane, channels, quantity, isos, numIsos, flags, numVertices, numSegments, hipStream);
   if (rc) (void)exa_hip_isolines_release(h);
   return rc;
 }
@@ -961,11 +1061,11 @@ int exa_hip_isolines_read(ExaHipRenderer *h, float *vertices, float *uv, float *
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (vertices && res.vertices.n) HIP_TRY(h, hipMemcpyAsync(vertices, res.vertices.p, res.vertices.n * sizeof(float), kind, s));
-  if (uv && res.uv.n) HIP_TRY(h, hipMemcpyAsync(uv, res.uv.p, res.uv.n * sizeof(float), kind, s));
-  if (gradients && res.gradients.n) HIP_TRY(h, hipMemcpyAsync(gradients, res.gradients.p, res.gradients.n * sizeof(float), kind, s));
-  if (segments && res.segments.n) HIP_TRY(h, hipMemcpyAsync(segments, res.segments.p, res.segments.n * sizeof(int32_t), kind, s));
-  if (values && res.values.n) HIP_TRY(h, hipMemcpyAsync(values, res.values.p, res.values.n * sizeof(float), kind, s));
+  HIP_TRY(h, copyOut(vertices, res.vertices, kind, s));
+  HIP_TRY(h, copyOut(uv, res.uv, kind, s));
+  HIP_TRY(h, copyOut(gradients, res.gradients, kind, s));
+  HIP_TRY(h, copyOut(segments, res.segments, kind, s));
+  HIP_TRY(h, copyOut(values, res.values, kind, s));
   // the offsets live on the host
   const size_t offBytes = res.vertexOffsets.size() * sizeof(uint64_t);
   if (pointersAreDevice) {
@@ -979,22 +1079,8 @@ int exa_hip_isolines_read(ExaHipRenderer *h, float *vertices, float *uv, float *
   return 0;
 }
 
-int exa_hip_isolines_release(ExaHipRenderer *h)
-{
-  if (!h) return 1;
-  ExaHipRenderer *r = firstChild(h);
-  EXA_ON_DEVICE_OF(h, r);
-  r->isolines.release();
-  return 0;
-}
-
-int exa_hip_isolines_stage_ms(ExaHipRenderer *h, float ms[6])
-{
-  if (!h || !ms) return 1;
-  const ExaHipRenderer *r = firstChild(h);
-  for (int k = 0; k < 6; k++) ms[k] = r->isolines.stageMs[k];
-  return 0;
-}
+int exa_hip_isolines_release(ExaHipRenderer *h) { return releaseResult(h, &ExaHipRenderer::isolines); }
+int exa_hip_isolines_stage_ms(ExaHipRenderer *h, float ms[6]) { return readStageMs(h, &ExaHipRenderer::isolines, ms); }
 
 // ---- connected regions of the inside set on a lattice (exa_isomesh.hip) ----
 const char *const kRegionGuard = ": the union-find's loop guard tripped (a parent link that does not descend)";
@@ -1009,58 +1095,27 @@ static int regionsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], 
 {
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
-  r->isoRegions.release();
-  DropUnlessCommitted<ExaHipRenderer::IsoRegions> regions(r->isoRegions);     // whatever fails from here on leaves no result
-  ExaHipRenderer::IsoRegions &res = r->isoRegions;
+  LabelledLattice<ExaHipRegion> &res = r->isoRegions;
+  res.release();
+  DropUnlessCommitted<LabelledLattice<ExaHipRegion>> regions(res);     // whatever fails from here on leaves no result
   for (float &ms : res.stageMs) ms = 0.f;
   if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument (lo, hi or dims)"); return 1; }
   if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
-  for (int k = 0; k < 3; k++) {
-    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) { h->fail(std::string(fn) + ": the box must be finite"); return 1; }
-    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
-  }
-  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
-  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
-    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
-    return 1;
-  }
+  const uint64_t n = latticePoints(h, fn, lo, hi, dims, 1, "dims must be >= 1 on every axis", "the box must be finite", false);
+  if (!n) return 1;
   hipStream_t s = (hipStream_t)hipStream;
-  const int32_t wf = flags & EXA_SAMPLE_WORLD_SPACE;
 
+  // the work space: the scans' with totals[3]; and the keys further down
   IsoRegionArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.numPoints = uint32_t(n);
-  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
-  a.iso = iso;
-  a.below = (flags & EXA_REGIONS_BELOW) ? 1 : 0;
-  a.faces = (flags & EXA_REGIONS_FACES) ? 1 : 0;
-  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
-  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
-  a.errorFlag = r->errorFlag.p;
-  // the work space, freed when the call returns: chunkBase, totals | blockCount, blockBase; and the keys further down
   DevBuf<char> work;
-  const size_t n64 = size_t(a.numChunks) + 3;
-  hipError_t e = res.values.alloc(n);
-  if (e == hipSuccess) e = res.labels.alloc(n);
-  if (e == hipSuccess) e = work.alloc(n64 * 8 + 2 * size_t(a.numBlocks) * 4);
-  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the labels (4 more)", e);
-  a.values = res.values.p;
+  IsoScanArgs scan;
+  if (labelledSetup(h, fn, dims, iso, flags, 0, res, work, a, scan)) return 1;
   a.parent = reinterpret_cast<uint32_t *>(res.labels.p);
-  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
-  a.totals = a.chunkBase + a.numChunks;
-  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
-  a.blockBase = a.blockCount + a.numBlocks;
 
   TimingEvents<9> t;
   HIP_TRY(h, t.create());
-  // the lattice: exa_hip_resample, or exa_hip_resample_derived, with a NaN fill into the device buffer (its checks of the
-  // box, the kd tree and the frame state apply; synchronous, with the descent's loop guard checked)
   HIP_TRY(h, hipEventRecord(t.ev[0], s));
-  if (int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], wf, NAN, res.values.p, 1, hipStream, 0)
-                            : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, wf, NAN, res.values.p, 1, hipStream, 0)) {
-    h->fail(std::string(fn) + ": " + h->err);
-    return rc;
-  }
+  if (int rc = fillLattice(h, fn, lo, hi, dims, channels, quantity, flags & EXA_SAMPLE_WORLD_SPACE, res.values.p, hipStream)) return rc;
   HIP_TRY(h, hipEventRecord(t.ev[1], s));
   HIP_TRY(h, hipMemsetAsync(a.totals, 0, 3 * sizeof(uint64_t), s));
   HIP_TRY(h, launchIsoRegionInit(a, s));
@@ -1069,29 +1124,20 @@ static int regionsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], 
   HIP_TRY(h, hipEventRecord(t.ev[3], s));
   HIP_TRY(h, launchIsoRegionFlatten(a, s));
   HIP_TRY(h, hipEventRecord(t.ev[4], s));
-  HIP_TRY(h, launchIsoRegionScans(a, s));
+  HIP_TRY(h, launchIsoScans(scan, 1, s));
   HIP_TRY(h, hipEventRecord(t.ev[5], s));
   uint64_t totals[3] = { 0, 0, 0 };              // regions, inside points, bits of max |V|
-  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  uint32_t maxBits = uint32_t(totals[2]);
-  float maxAbs;
-  std::memcpy(&maxAbs, &maxBits, sizeof(maxAbs));
-  int32_t exponent = 0;
-  if (totals[1] && maxAbs != 0.f) {
-    int ex = 0;
-    (void)std::frexp(maxAbs, &ex);
-    exponent = 30 - ex;
-  }
+  if (readBack(h, totals, a.totals, sizeof(totals), s)) return 1;
+  const int32_t exponent = sumExponentOf(totals);
   a.scale = std::ldexp(1.0, exponent);
   a.numRegions = uint32_t(totals[0]);            // <= n
   float rankMs = 0.f;
   if (totals[0]) {
     DevBuf<uint64_t> keys;
-    e = res.regions.alloc(size_t(totals[0]));
+    hipError_t e = res.table.alloc(size_t(totals[0]));
     if (e == hipSuccess) e = keys.alloc(2 * size_t(totals[0]));
     if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the table of regions (88 bytes each, and 16 while the call runs)", e);
-    a.regions = res.regions.p;
+    a.regions = res.table.p;
     a.keys = keys.p;
     HIP_TRY(h, hipEventRecord(t.ev[6], s));
     HIP_TRY(h, launchIsoRegionRank(a, s));
@@ -1105,13 +1151,8 @@ static int regionsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], 
   for (int k = 0; k < 5; k++) HIP_TRY(h, t.elapsed(k, k + 1, &res.stageMs[k]));
   res.stageMs[4] += rankMs;
   if (int rc = checkLoopGuard(h, r, fn, kRegionGuard)) return rc;
-  res.keptValues = (flags & EXA_REGIONS_KEEP_VALUES) != 0;
-  if (!res.keptValues) res.values.release();
-  res.have = true;
-  regions.commit();
+  labelledCommit(res, regions, flags, totals, exponent, numInside, sumExponent);
   if (numRegions) *numRegions = totals[0];
-  if (numInside) *numInside = totals[1];
-  if (sumExponent) *sumExponent = exponent;
   return 0;
 }
 
@@ -1143,12 +1184,8 @@ int exa_hip_regions_derived(ExaHipRenderer *h, const float lo[3], const float hi
   if (numInside) *numInside = 0;
   if (sumExponent) *sumExponent = 0;
   int rc = 1;
-  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint)) {
-    const int comps = derivedComponents(h, fn, channels, quantity);
-    if (comps > 1) h->fail(std::string(fn) + ": regions need a one-component quantity (EXA_DERIVED_VORTICITY has three)");
-    else if (comps == 1)
-      rc = regionsExtract(h, fn, lo, hi, dims, channels, quantity, iso, flags, numRegions, numInside, sumExponent, hipStream);
-  }
+  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint) && oneComponent(h, fn, channels, quantity, "regions need"))
+    rc = regionsExtract(h, fn, lo, hi, dims, channels, quantity, iso, flags, numRegions, numInside, sumExponent, hipStream);
   if (rc) (void)exa_hip_regions_release(h);
   return rc;
 }
@@ -1156,38 +1193,13 @@ int exa_hip_regions_derived(ExaHipRenderer *h, const float lo[3], const float hi
 int exa_hip_regions_read(ExaHipRenderer *h, int32_t *labels, ExaHipRegion *regions, float *values, int32_t pointersAreDevice,
                          void *hipStream)
 {
-  if (!h) return 1;
-  const char *fn = "exa_hip_regions_read";
-  ExaHipRenderer *r = firstChild(h);
-  const ExaHipRenderer::IsoRegions &res = r->isoRegions;
-  if (!res.have) { h->fail(std::string(fn) + ": no regions (exa_hip_regions comes first; a release or a failed call drops them)"); return 1; }
-  if (values && !res.keptValues) { h->fail(std::string(fn) + ": the regions were extracted without EXA_REGIONS_KEEP_VALUES"); return 1; }
-  EXA_ON_DEVICE_OF(h, r);
-  hipStream_t s = (hipStream_t)hipStream;
-  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (labels && res.labels.n) HIP_TRY(h, hipMemcpyAsync(labels, res.labels.p, res.labels.n * sizeof(int32_t), kind, s));
-  if (regions && res.regions.n) HIP_TRY(h, hipMemcpyAsync(regions, res.regions.p, res.regions.n * sizeof(ExaHipRegion), kind, s));
-  if (values && res.values.n) HIP_TRY(h, hipMemcpyAsync(values, res.values.p, res.values.n * sizeof(float), kind, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  return 0;
+  return labelledRead(h, "exa_hip_regions_read", &ExaHipRenderer::isoRegions,
+                      "no regions (exa_hip_regions comes first; a release or a failed call drops them)",
+                      "the regions were extracted without EXA_REGIONS_KEEP_VALUES", labels, regions, values, pointersAreDevice, hipStream);
 }
 
-int exa_hip_regions_release(ExaHipRenderer *h)
-{
-  if (!h) return 1;
-  ExaHipRenderer *r = firstChild(h);
-  EXA_ON_DEVICE_OF(h, r);
-  r->isoRegions.release();
-  return 0;
-}
-
-int exa_hip_regions_stage_ms(ExaHipRenderer *h, float ms[6])
-{
-  if (!h || !ms) return 1;
-  const ExaHipRenderer *r = firstChild(h);
-  for (int k = 0; k < 6; k++) ms[k] = r->isoRegions.stageMs[k];
-  return 0;
-}
+int exa_hip_regions_release(ExaHipRenderer *h) { return releaseResult(h, &ExaHipRenderer::isoRegions); }
+int exa_hip_regions_stage_ms(ExaHipRenderer *h, float ms[6]) { return readStageMs(h, &ExaHipRenderer::isoRegions, ms); }
 
 // ---- basins of the inside set on a lattice: one per peak, shallow ones merged in rounds (exa_isomesh.hip) ----
 const char *const kBasinGuard = ": a loop guard of the basins tripped (a chain of links longer than the lattice, or more rounds than raw basins)";
@@ -1202,51 +1214,25 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
 {
   ExaHipRenderer *r = firstChild(h);
   EXA_ON_DEVICE_OF(h, r);
-  r->isoBasins.release();
-  DropUnlessCommitted<ExaHipRenderer::IsoBasins> basins(r->isoBasins);       // whatever fails from here on leaves no result
-  ExaHipRenderer::IsoBasins &res = r->isoBasins;
+  LabelledLattice<ExaHipBasin> &res = r->isoBasins;
+  res.release();
+  DropUnlessCommitted<LabelledLattice<ExaHipBasin>> basins(res);       // whatever fails from here on leaves no result
   for (float &ms : res.stageMs) ms = 0.f;
   if (!lo || !hi || !dims) { h->fail(std::string(fn) + ": null argument (lo, hi or dims)"); return 1; }
   if (!std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
   if (!(minDepth >= 0.f)) { h->fail(std::string(fn) + ": minDepth must be >= 0 (+INFINITY is allowed, NaN is not)"); return 1; }
-  for (int k = 0; k < 3; k++) {
-    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) { h->fail(std::string(fn) + ": the box must be finite"); return 1; }
-    if (dims[k] < 1) { h->fail(std::string(fn) + ": dims must be >= 1 on every axis"); return 1; }
-  }
-  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
-  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
-    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
-    return 1;
-  }
+  const uint64_t n = latticePoints(h, fn, lo, hi, dims, 1, "dims must be >= 1 on every axis", "the box must be finite", false);
+  if (!n) return 1;
   hipStream_t s = (hipStream_t)hipStream;
-  const int32_t wf = flags & EXA_SAMPLE_WORLD_SPACE;
 
+  // the work space: the scans' with totals[3] and the jump count; the raw basins' arrays and the keys further down
   IsoBasinArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.numPoints = uint32_t(n);
-  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
-  a.iso = iso;
-  a.minDepth = minDepth;
-  a.below = (flags & EXA_REGIONS_BELOW) ? 1 : 0;
-  a.faces = (flags & EXA_REGIONS_FACES) ? 1 : 0;
-  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
-  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
-  a.errorFlag = r->errorFlag.p;
-  // the work space, freed when the call returns: chunkBase, totals, the jump count | blockCount, blockBase; the raw basins'
-  // arrays and the keys further down
   DevBuf<char> work;
-  const size_t n64 = size_t(a.numChunks) + 4;
-  hipError_t e = res.values.alloc(n);
-  if (e == hipSuccess) e = res.labels.alloc(n);
-  if (e == hipSuccess) e = work.alloc(n64 * 8 + 2 * size_t(a.numBlocks) * 4);
-  if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the lattice (4 bytes per point) and the labels (4 more)", e);
-  a.values = res.values.p;
+  IsoScanArgs scan;
+  if (labelledSetup(h, fn, dims, iso, flags, 1, res, work, a, scan)) return 1;
+  a.minDepth = minDepth;
   a.comp = reinterpret_cast<uint32_t *>(res.labels.p);
-  a.chunkBase = reinterpret_cast<uint64_t *>(work.p);
-  a.totals = a.chunkBase + a.numChunks;
   a.jumpCount = reinterpret_cast<uint32_t *>(a.totals + 3);
-  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
-  a.blockBase = a.blockCount + a.numBlocks;
 
   TimingEvents<3> t;
   HIP_TRY(h, t.create());
@@ -1264,8 +1250,7 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
       uint32_t left = 0;
       HIP_TRY(h, hipMemsetAsync(a.jumpCount, 0, sizeof(uint32_t), s));
       HIP_TRY(h, launchIsoBasinJump(a, array, size, s));
-      HIP_TRY(h, hipMemcpyAsync(&left, a.jumpCount, sizeof(left), hipMemcpyDeviceToHost, s));
-      HIP_TRY(h, hipStreamSynchronize(s));
+      if (readBack(h, &left, a.jumpCount, sizeof(left), s)) return 1;
       if (!left) return 0;
       if (pass >= 32) {
         if (int rc = checkLoopGuard(h, r, fn, kBasinGuard)) return rc;
@@ -1274,15 +1259,19 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
       }
     }
   };
+  // the fixed points of array[0, size), which are fewer than the lattice's points, counted per block and scanned: their
+  // number into totals[0]
+  auto count = [&](uint32_t *array, uint32_t size) -> int {
+    IsoScanArgs part = scan;
+    part.numBlocks = (size + kIsoBlock - 1) / kIsoBlock;
+    part.numChunks = (part.numBlocks + kIsoChunk - 1) / kIsoChunk;
+    HIP_TRY(h, launchIsoBasinCount(a, array, size, s));
+    HIP_TRY(h, launchIsoScans(part, 1, s));
+    return 0;
+  };
 
-  // the lattice: exa_hip_resample, or exa_hip_resample_derived, with a NaN fill into the device buffer (its checks of the
-  // box, the kd tree and the frame state apply; synchronous, with the descent's loop guard checked)
   HIP_TRY(h, hipEventRecord(t.ev[0], s));
-  if (int rc = quantity < 0 ? exa_hip_resample(h, lo, hi, dims, channels[0], wf, NAN, res.values.p, 1, hipStream, 0)
-                            : exa_hip_resample_derived(h, lo, hi, dims, channels, quantity, wf, NAN, res.values.p, 1, hipStream, 0)) {
-    h->fail(std::string(fn) + ": " + h->err);
-    return rc;
-  }
+  if (int rc = fillLattice(h, fn, lo, hi, dims, channels, quantity, flags & EXA_SAMPLE_WORLD_SPACE, res.values.p, hipStream)) return rc;
   HIP_TRY(h, hipEventRecord(t.ev[1], s));
   if (int rc = lap(0, 0)) return rc;
 
@@ -1297,19 +1286,10 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
 
   // the peaks, counted and numbered
   HIP_TRY(h, hipEventRecord(t.ev[0], s));
-  HIP_TRY(h, launchIsoBasinCount(a, a.comp, a.numPoints, s));
+  if (int rc = count(a.comp, a.numPoints)) return rc;
   uint64_t totals[3] = { 0, 0, 0 };              // raw basins, inside points, bits of max |V|
-  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  uint32_t maxBits = uint32_t(totals[2]);
-  float maxAbs;
-  std::memcpy(&maxAbs, &maxBits, sizeof(maxAbs));
-  int32_t exponent = 0;
-  if (totals[1] && maxAbs != 0.f) {
-    int ex = 0;
-    (void)std::frexp(maxAbs, &ex);
-    exponent = 30 - ex;
-  }
+  if (readBack(h, totals, a.totals, sizeof(totals), s)) return 1;
+  const int32_t exponent = sumExponentOf(totals);
   a.scale = std::ldexp(1.0, exponent);
   a.numRaw = uint32_t(totals[0]);                // <= n
   uint64_t numFinal = 0;
@@ -1318,7 +1298,7 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
     // per raw basin: the word of its pass | its peak, its link, its final number
     DevBuf<char> raw;
     DevBuf<uint64_t> keys;
-    e = raw.alloc(size_t(a.numRaw) * 20);
+    hipError_t e = raw.alloc(size_t(a.numRaw) * 20);
     if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the raw basins (20 bytes each)", e);
     a.pass = reinterpret_cast<uint64_t *>(raw.p);
     a.peakOf = reinterpret_cast<uint32_t *>(raw.p + size_t(a.numRaw) * 8);
@@ -1337,8 +1317,7 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
       HIP_TRY(h, hipEventRecord(t.ev[1], s));
       HIP_TRY(h, hipMemsetAsync(a.jumpCount, 0, sizeof(uint32_t), s));
       HIP_TRY(h, launchIsoBasinLink(a, s));
-      HIP_TRY(h, hipMemcpyAsync(&links, a.jumpCount, sizeof(links), hipMemcpyDeviceToHost, s));
-      HIP_TRY(h, hipStreamSynchronize(s));
+      if (readBack(h, &links, a.jumpCount, sizeof(links), s)) return 1;
       if (links) {
         if (uint32_t(numRounds) >= a.numRaw) {   // every round but the last removes a component
           if (int rc = checkLoopGuard(h, r, fn, kBasinGuard)) return rc;
@@ -1357,14 +1336,13 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
 
     // the components, counted and numbered; the table
     HIP_TRY(h, hipEventRecord(t.ev[0], s));
-    HIP_TRY(h, launchIsoBasinCount(a, a.link, a.numRaw, s));
-    HIP_TRY(h, hipMemcpyAsync(&numFinal, a.totals, sizeof(numFinal), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    if (int rc = count(a.link, a.numRaw)) return rc;
+    if (readBack(h, &numFinal, a.totals, sizeof(numFinal), s)) return 1;
     a.numBasins = uint32_t(numFinal);            // 1 <= numBasins <= numRaw
-    e = res.basins.alloc(size_t(numFinal));
+    e = res.table.alloc(size_t(numFinal));
     if (e == hipSuccess) e = keys.alloc(2 * size_t(numFinal));
     if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the table of basins (96 bytes each, and 16 while the call runs)", e);
-    a.basins = res.basins.p;
+    a.basins = res.table.p;
     a.keys = keys.p;
     HIP_TRY(h, launchIsoBasinFinal(a, s));
     HIP_TRY(h, hipEventRecord(t.ev[1], s));
@@ -1377,14 +1355,9 @@ static int basinsExtract(ExaHipRenderer *h, const char *fn, const float lo[3], c
     if (int rc = lap(0, 4)) return rc;
   }
   if (int rc = checkLoopGuard(h, r, fn, kBasinGuard)) return rc;
-  res.keptValues = (flags & EXA_REGIONS_KEEP_VALUES) != 0;
-  if (!res.keptValues) res.values.release();
-  res.have = true;
-  basins.commit();
+  labelledCommit(res, basins, flags, totals, exponent, numInside, sumExponent);
   if (numBasins) *numBasins = numFinal;
   if (numRawBasins) *numRawBasins = totals[0];
-  if (numInside) *numInside = totals[1];
-  if (sumExponent) *sumExponent = exponent;
   if (rounds) *rounds = numRounds;
   return 0;
 }
@@ -1421,13 +1394,9 @@ int exa_hip_basins_derived(ExaHipRenderer *h, const float lo[3], const float hi[
   const char *fn = "exa_hip_basins_derived";
   basinsZero(numBasins, numRawBasins, numInside, sumExponent, rounds);
   int rc = 1;
-  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint)) {
-    const int comps = derivedComponents(h, fn, channels, quantity);
-    if (comps > 1) h->fail(std::string(fn) + ": basins need a one-component quantity (EXA_DERIVED_VORTICITY has three)");
-    else if (comps == 1)
-      rc = basinsExtract(h, fn, lo, hi, dims, channels, quantity, iso, minDepth, flags, numBasins, numRawBasins, numInside, sumExponent,
-                         rounds, hipStream);
-  }
+  if (checkFlags(h, fn, flags, kRegionFlags, kRegionFlagsHint) && oneComponent(h, fn, channels, quantity, "basins need"))
+    rc = basinsExtract(h, fn, lo, hi, dims, channels, quantity, iso, minDepth, flags, numBasins, numRawBasins, numInside, sumExponent,
+                       rounds, hipStream);
   if (rc) (void)exa_hip_basins_release(h);
   return rc;
 }
@@ -1435,38 +1404,13 @@ int exa_hip_basins_derived(ExaHipRenderer *h, const float lo[3], const float hi[
 int exa_hip_basins_read(ExaHipRenderer *h, int32_t *labels, ExaHipBasin *basins, float *values, int32_t pointersAreDevice,
                         void *hipStream)
 {
-  if (!h) return 1;
-  const char *fn = "exa_hip_basins_read";
-  ExaHipRenderer *r = firstChild(h);
-  const ExaHipRenderer::IsoBasins &res = r->isoBasins;
-  if (!res.have) { h->fail(std::string(fn) + ": no basins (exa_hip_basins comes first; a release or a failed call drops them)"); return 1; }
-  if (values && !res.keptValues) { h->fail(std::string(fn) + ": the basins were extracted without EXA_REGIONS_KEEP_VALUES"); return 1; }
-  EXA_ON_DEVICE_OF(h, r);
-  hipStream_t s = (hipStream_t)hipStream;
-  const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (labels && res.labels.n) HIP_TRY(h, hipMemcpyAsync(labels, res.labels.p, res.labels.n * sizeof(int32_t), kind, s));
-  if (basins && res.basins.n) HIP_TRY(h, hipMemcpyAsync(basins, res.basins.p, res.basins.n * sizeof(ExaHipBasin), kind, s));
-  if (values && res.values.n) HIP_TRY(h, hipMemcpyAsync(values, res.values.p, res.values.n * sizeof(float), kind, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  return 0;
+  return labelledRead(h, "exa_hip_basins_read", &ExaHipRenderer::isoBasins,
+                      "no basins (exa_hip_basins comes first; a release or a failed call drops them)",
+                      "the basins were extracted without EXA_REGIONS_KEEP_VALUES", labels, basins, values, pointersAreDevice, hipStream);
 }
 
-int exa_hip_basins_release(ExaHipRenderer *h)
-{
-  if (!h) return 1;
-  ExaHipRenderer *r = firstChild(h);
-  EXA_ON_DEVICE_OF(h, r);
-  r->isoBasins.release();
-  return 0;
-}
-
-int exa_hip_basins_stage_ms(ExaHipRenderer *h, float ms[6])
-{
-  if (!h || !ms) return 1;
-  const ExaHipRenderer *r = firstChild(h);
-  for (int k = 0; k < 6; k++) ms[k] = r->isoBasins.stageMs[k];
-  return 0;
-}
+int exa_hip_basins_release(ExaHipRenderer *h) { return releaseResult(h, &ExaHipRenderer::isoBasins); }
+int exa_hip_basins_stage_ms(ExaHipRenderer *h, float ms[6]) { return readStageMs(h, &ExaHipRenderer::isoBasins, ms); }
 
 // ---- critical points of a vector field on a lattice (exa_isomesh.hip) ----
 // The three lattices are three exa_hip_resample calls into one device buffer.  Two small read-backs size what follows: the
@@ -1492,15 +1436,9 @@ int exa_hip_critical_points(ExaHipRenderer *h, const float lo[3], const float hi
     if (!checkChannel(h, fn, channels[c])) return 1;
   if (iterations < 1 || iterations > EXA_CRITICAL_MAX_ITERATIONS) { h->fail(std::string(fn) + ": iterations must be 1 .. EXA_CRITICAL_MAX_ITERATIONS (32)"); return 1; }
   if (!(std::isfinite(tolerance) && tolerance > 0.f && tolerance <= 1.f)) { h->fail(std::string(fn) + ": the tolerance must be finite and in (0, 1]"); return 1; }
-  for (int k = 0; k < 3; k++) {
-    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && hi[k] > lo[k])) { h->fail(std::string(fn) + ": the box needs finite lo < hi on every axis"); return 1; }
-    if (dims[k] < 2) { h->fail(std::string(fn) + ": dims must be >= 2 on every axis (a lattice of cells)"); return 1; }
-  }
-  const uint64_t n = uint64_t(dims[0]) * uint64_t(dims[1]) * uint64_t(dims[2]);     // each < 2^31: no overflow of the first product
-  if (uint64_t(dims[0]) * uint64_t(dims[1]) > uint64_t(INT32_MAX) || n > uint64_t(INT32_MAX)) {
-    h->fail(std::string(fn) + ": a lattice of more than 2^31 - 1 points");
-    return 1;
-  }
+  const uint64_t n = latticePoints(h, fn, lo, hi, dims, 2, "dims must be >= 2 on every axis (a lattice of cells)",
+                                   "the box needs finite lo < hi on every axis", true);
+  if (!n) return 1;
   hipStream_t s = (hipStream_t)hipStream;
   const int32_t wf = flags & EXA_SAMPLE_WORLD_SPACE;
   const bool probe = (flags & EXA_CRITICAL_PROBE) != 0;
@@ -1512,41 +1450,30 @@ int exa_hip_critical_points(ExaHipRenderer *h, const float lo[3], const float hi
   for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
   a.iterations = iterations;
   a.tolerance = tolerance;
-  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
-  a.numChunks = (a.numBlocks + kIsoChunk - 1) / kIsoChunk;
-  // the work space of the lattice, freed when the call returns: marks | chunkBase | totals, counters | blockCount, blockBase
+  // the work space of the lattice: the scans' with totals[2] (candidates, found), then the counters and the marks
   DevBuf<float> values;
   DevBuf<char> work;
-  const size_t waves = size_t(a.numBlocks) * (kIsoBlock / 64), n64 = waves + a.numChunks + 2 + 7;
+  IsoScanArgs scan;
+  const size_t waves = size_t((n + kIsoBlock - 1) / kIsoBlock) * (kIsoBlock / 64);
   hipError_t e = values.alloc(3 * size_t(n));
-  if (e == hipSuccess) e = work.alloc(n64 * 8 + 2 * size_t(a.numBlocks) * 4);
+  if (e == hipSuccess) e = allocScans(work, n, 1, 1 + 7 + waves, 0, a, scan);
   if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the three lattices (12 bytes per point) and the work space", e);
   a.values = values.p;
-  a.marks = reinterpret_cast<unsigned long long *>(work.p);
-  a.chunkBase = reinterpret_cast<uint64_t *>(work.p) + waves;
-  a.totals = a.chunkBase + a.numChunks;
   a.counters = reinterpret_cast<unsigned long long *>(a.totals + 2);
-  a.blockCount = reinterpret_cast<uint32_t *>(work.p + n64 * 8);
-  a.blockBase = a.blockCount + a.numBlocks;
+  a.marks = a.counters + 7;
 
   TimingEvents<8> t;
   HIP_TRY(h, t.create());
-  // the lattices: exa_hip_resample with a NaN fill into the device buffer (its checks of the kd tree and the frame state
-  // apply; synchronous, with the descent's loop guard checked)
   HIP_TRY(h, hipEventRecord(t.ev[0], s));
   for (int c = 0; c < 3; c++)
-    if (int rc = exa_hip_resample(h, lo, hi, dims, channels[c], wf, NAN, values.p + size_t(c) * n, 1, hipStream, 0)) {
-      h->fail(std::string(fn) + ": " + h->err);
-      return rc;
-    }
+    if (int rc = fillLattice(h, fn, lo, hi, dims, channels + c, -1, wf, values.p + size_t(c) * n, hipStream)) return rc;
   HIP_TRY(h, hipEventRecord(t.ev[1], s));
   HIP_TRY(h, hipMemsetAsync(a.totals, 0, 9 * sizeof(uint64_t), s));
   HIP_TRY(h, launchIsoCriticalCells(a, s));
   HIP_TRY(h, hipEventRecord(t.ev[2], s));
-  HIP_TRY(h, launchIsoCriticalScans(a, false, s));
+  HIP_TRY(h, launchIsoScans(scan, 1, s));
   uint64_t totals[2] = { 0, 0 };                 // candidates, found
-  HIP_TRY(h, hipMemcpyAsync(totals, a.totals, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
+  if (readBack(h, totals, a.totals, sizeof(uint64_t), s)) return 1;
   a.numCandidates = uint32_t(totals[0]);         // <= n
   a.numCandBlocks = uint32_t((totals[0] + kIsoBlock - 1) / kIsoBlock);
   a.numCandChunks = (a.numCandBlocks + kIsoChunk - 1) / kIsoChunk;
@@ -1569,9 +1496,10 @@ int exa_hip_critical_points(ExaHipRenderer *h, const float lo[3], const float hi
   if (a.numCandidates) HIP_TRY(h, launchIsoCriticalRefine(a, s));
   HIP_TRY(h, hipEventRecord(t.ev[4], s));
   if (a.numCandidates) {
-    HIP_TRY(h, launchIsoCriticalScans(a, true, s));
-    HIP_TRY(h, hipMemcpyAsync(totals + 1, a.totals + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    // the found points per block of candidates, scanned: their number into totals[1]
+    const IsoScanArgs found = { a.numCandBlocks, a.numCandChunks, a.candCount, a.candBase, a.candChunkBase, a.totals + 1 };
+    HIP_TRY(h, launchIsoScans(found, 1, s));
+    if (readBack(h, totals + 1, a.totals + 1, sizeof(uint64_t), s)) return 1;
   }
   HIP_TRY(h, hipEventRecord(t.ev[5], s));
   a.numFound = uint32_t(totals[1]);              // <= the candidates
@@ -1594,10 +1522,8 @@ int exa_hip_critical_points(ExaHipRenderer *h, const float lo[3], const float hi
     if (e == hipSuccess) e = res.probeStatus.alloc(3 * nf);
     if (e != hipSuccess) return failNoMemory(h, fn, "no device memory for the probe (120 bytes per point)", e);
     const int32_t pf = wf | EXA_SAMPLE_GRADIENT | EXA_SAMPLE_GRADIENT_NORMALIZED;
-    if (int rc = exa_hip_sample_points(h, positions.p, nf, channels, 3, pf, NAN, probeValues.p, probeGradients.p, res.probeStatus.p, 1, hipStream, 0)) {
-      h->fail(std::string(fn) + ": " + h->err);
-      return rc;
-    }
+    if (int rc = exa_hip_sample_points(h, positions.p, nf, channels, 3, pf, NAN, probeValues.p, probeGradients.p, res.probeStatus.p, 1, hipStream, 0))
+      return failedIn(h, fn, rc);
     a.probeValues = probeValues.p;
     a.probeGradients = probeGradients.p;
     a.probe = res.probe.p;
@@ -1605,8 +1531,7 @@ int exa_hip_critical_points(ExaHipRenderer *h, const float lo[3], const float hi
   }
   HIP_TRY(h, hipEventRecord(t.ev[7], s));
   uint64_t counters[7] = { 0, 0, 0, 0, 0, 0, 0 };
-  HIP_TRY(h, hipMemcpyAsync(counters, a.counters, sizeof(counters), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));             // the work spaces are freed behind it
+  if (readBack(h, counters, a.counters, sizeof(counters), s)) return 1;      // the work spaces are freed behind it
   float ms[7];
   for (int k = 0; k < 7; k++) HIP_TRY(h, t.elapsed(k, k + 1, &ms[k]));
   res.stageMs[0] = ms[0]; res.stageMs[1] = ms[1]; res.stageMs[2] = ms[2] + ms[4];
@@ -1635,28 +1560,14 @@ int exa_hip_critical_points_read(ExaHipRenderer *h, ExaHipCriticalPoint *points,
   EXA_ON_DEVICE_OF(h, r);
   hipStream_t s = (hipStream_t)hipStream;
   const hipMemcpyKind kind = pointersAreDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (points && res.points.n) HIP_TRY(h, hipMemcpyAsync(points, res.points.p, res.points.n * sizeof(ExaHipCriticalPoint), kind, s));
-  if (probe && res.probe.n) HIP_TRY(h, hipMemcpyAsync(probe, res.probe.p, res.probe.n * sizeof(float), kind, s));
-  if (probeStatus && res.probeStatus.n) HIP_TRY(h, hipMemcpyAsync(probeStatus, res.probeStatus.p, res.probeStatus.n * sizeof(int32_t), kind, s));
+  HIP_TRY(h, copyOut(points, res.points, kind, s));
+  HIP_TRY(h, copyOut(probe, res.probe, kind, s));
+  HIP_TRY(h, copyOut(probeStatus, res.probeStatus, kind, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   return 0;
 }
 
-int exa_hip_critical_points_release(ExaHipRenderer *h)
-{
-  if (!h) return 1;
-  ExaHipRenderer *r = firstChild(h);
-  EXA_ON_DEVICE_OF(h, r);
-  r->isoCritical.release();
-  return 0;
-}
-
-int exa_hip_critical_points_stage_ms(ExaHipRenderer *h, float ms[6])
-{
-  if (!h || !ms) return 1;
-  const ExaHipRenderer *r = firstChild(h);
-  for (int k = 0; k < 6; k++) ms[k] = r->isoCritical.stageMs[k];
-  return 0;
-}
+int exa_hip_critical_points_release(ExaHipRenderer *h) { return releaseResult(h, &ExaHipRenderer::isoCritical); }
+int exa_hip_critical_points_stage_ms(ExaHipRenderer *h, float ms[6]) { return readStageMs(h, &ExaHipRenderer::isoCritical, ms); }
 
 } // extern "C"

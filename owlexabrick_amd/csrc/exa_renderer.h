@@ -108,6 +108,18 @@ struct DropUnlessCommitted {
   DropUnlessCommitted &operator=(const DropUnlessCommitted &) = delete;
 };
 
+// What exa_hip_regions and exa_hip_basins keep on the handle: a label per lattice point, the table of records the labels
+// number, and the lattice values where EXA_REGIONS_KEEP_VALUES kept them
+template <typename Record>
+struct LabelledLattice {
+  DevBuf<int32_t> labels;
+  DevBuf<Record> table;
+  DevBuf<float> values;
+  bool have = false, keptValues = false;
+  float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
+  void release() { labels.release(); table.release(); values.release(); have = keptValues = false; }
+};
+
 struct ExaHipRenderer {
   int device = 0;
   std::string err;
@@ -320,16 +332,8 @@ struct ExaHipRenderer {
   } isolines;
   // the regions of the last exa_hip_regions (in the renderer of devices[0] as well), independent of the mesh and of the
   // lines: the labels (the union-find's parent links while the call runs), the table, the lattice values where
-  // EXA_REGIONS_KEEP_VALUES kept them, the counts the call returned, and the time of the stages (values, init, merge,
-  // flatten, rank, stats)
-  struct IsoRegions {
-    DevBuf<int32_t> labels;
-    DevBuf<ExaHipRegion> regions;
-    DevBuf<float> values;
-    bool have = false, keptValues = false;
-    float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
-    void release() { labels.release(); regions.release(); values.release(); have = keptValues = false; }
-  } isoRegions;
+  // EXA_REGIONS_KEEP_VALUES kept them, and the time of the stages (values, init, merge, flatten, rank, stats)
+  LabelledLattice<ExaHipRegion> isoRegions;
   // the critical points of the last exa_hip_critical_points (in the renderer of devices[0] as well), independent of the mesh,
   // the lines and the regions: the records, the probe's arrays where EXA_CRITICAL_PROBE asked for them, and the time of the
   // stages (values, cells, scans, refine, emit, probe)
@@ -345,14 +349,7 @@ struct ExaHipRenderer {
   // regions and the critical points: the labels (the up links, then the components while the call runs), the table, the
   // lattice values where EXA_REGIONS_KEEP_VALUES kept them, and the time of the stages (values, ascent, passes, links, rank,
   // stats)
-  struct IsoBasins {
-    DevBuf<int32_t> labels;
-    DevBuf<ExaHipBasin> basins;
-    DevBuf<float> values;
-    bool have = false, keptValues = false;
-    float stageMs[6] = { 0, 0, 0, 0, 0, 0 };
-    void release() { labels.release(); basins.release(); values.release(); have = keptValues = false; }
-  } isoBasins;
+  LabelledLattice<ExaHipBasin> isoBasins;
   // exa_hip_histogram (on a multi-device handle: in the renderer of devices[0]): the work list of the pass — segments
   // {brick, first cell} by level and the offsets of the runs, built by the first call (exa_stats.cpp) —, whether the scene's
   // volume-weighted cell count fits 64 bits, the device copy of a call's result and the device time of its kernel
@@ -503,6 +500,30 @@ inline int failNoMemory(ExaHipRenderer *h, const char *fn, const char *what, hip
   (void)hipGetLastError();
   h->fail(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
   return 1;
+}
+
+// What the _read, _release and _stage_ms calls of the results on the handle share (`which`: the result's member of the
+// renderer, of devices[0] on a multi-device handle).  An array the caller does not ask for, or that is empty, is not copied.
+template <typename T>
+hipError_t copyOut(T *dst, const DevBuf<T> &src, hipMemcpyKind kind, hipStream_t s)
+{
+  return dst && src.n ? hipMemcpyAsync(dst, src.p, src.n * sizeof(T), kind, s) : hipSuccess;
+}
+template <typename T>
+int releaseResult(ExaHipRenderer *h, T ExaHipRenderer::*which)
+{
+  if (!h) return 1;
+  ExaHipRenderer *r = firstChild(h);
+  EXA_ON_DEVICE_OF(h, r);
+  (r->*which).release();
+  return 0;
+}
+template <typename T>
+int readStageMs(ExaHipRenderer *h, T ExaHipRenderer::*which, float ms[6])
+{
+  if (!h || !ms) return 1;
+  for (int k = 0; k < 6; k++) ms[k] = (firstChild(h)->*which).stageMs[k];
+  return 0;
 }
 
 // Reads and clears the loop guard of r's kernels; when it tripped, h (r or its multi-device handle) fails with fn + what

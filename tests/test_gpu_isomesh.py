@@ -194,6 +194,8 @@ def test_empty_surface_and_refused_arguments():
         rc, nv, nt, msg = _raw(R, **kw)
         assert rc != 0 and (nv, nt) == (0, 0) and msg.startswith("exa_hip_isosurface: "), (kw, rc, msg)
         assert R.render().shape == frame.shape, kw             # the handle still renders
+    rc, nv, nt, msg = _raw(R, dims=(2 ** 22, 2 ** 21, 2 ** 21))        # 2^64 lattice points: the product is 0 in 64 bits
+    assert rc != 0 and (nv, nt) == (0, 0) and "more than 2^31 - 1 points" in msg, msg
     # a failed extraction dropped the mesh
     assert L.exa_hip_isosurface_read(R.h, buf.ctypes.data, None, None, 0, None) != 0
     with pytest.raises(RuntimeError, match="exa_hip_isosurface"):
