@@ -230,3 +230,19 @@ def test_every_kind_of_point_occurs_somewhere():
     # an axis of one point, on every axis, among the shapes of the GPU test
     for axis in range(3):
         assert any(s[axis] == 1 and max(s) > 1 for s in fr.SHAPES)
+
+
+@pytest.mark.parametrize("backward", [False, True])
+def test_a_nan_velocity_ends_a_point_left(backward):
+    """tests/nan_scenes.py: the case tests/test_gpu_nan_cells.py holds the module to.  A NaN velocity is a value: the next
+    position is NaN, its lookup ends the point LEFT at its last finite position, and the point has no stretch"""
+    import nan_scenes as ns
+    S = ns.case(ns.flow_scene(), basis_form=1).oracle_scene()
+    lo, hi = ns.FLOW_BOX
+    res = fr.flowmap(fr.oracle_feed(S, ns.FLOW_CHANNELS), lo, hi, ns.FLOW_DIMS, ns.FLOW_STEP, ns.FLOW_NUM_STEPS, backward)
+    hs = -ns.FLOW_STEP if backward else ns.FLOW_STEP
+    ended = ns.directions_ended_by_nan(S, fr.positions(lo, hi, ns.FLOW_DIMS), hs, ns.FLOW_NUM_STEPS).reshape(res["reasons"].shape)
+    print(f"backward {backward}: {int(ended.sum())} points end for a NaN velocity; {fr.coverage(res)}")
+    assert ended.sum() >= 5 and (fr.valid(res["reasons"]) & ~ended).sum() >= 20
+    assert np.all(res["reasons"][ended] == fr.END_LEFT) and not np.isnan(res["end"]).any()
+    assert np.all(np.isnan(res["stretch"][ended]))

@@ -104,3 +104,19 @@ def test_refused_planes():
     assert lr.metric(lr.plane((0, 0, 0), (0, 0, 0), (0, 1, 0), (4, 4))) is None              # a zero vector
     assert lr.metric(lr.plane((0, 0, 0), (1e30, 0, 0), (0, 1e30, 0), (4, 4))) is None        # det overflows
     assert lr.metric(lr.oblique_plane()) is not None
+
+
+def test_a_nan_velocity_ends_a_direction_stagnant():
+    """tests/nan_scenes.py: the case tests/test_gpu_nan_cells.py holds the module to.  A NaN velocity is a value; the speed of
+    the in-plane direction is then NaN and !(s > 0) ends the direction STAGNANT (a NaN centre: both, count 1)"""
+    import nan_scenes as ns
+    S = ns.case(ns.flow_scene(), basis_form=1).oracle_scene()
+    evaluate = ns.counting_evaluator(lr.oracle_evaluator(S, ns.FLOW_CHANNELS))
+    res = lr.lic(evaluate, lr.plane(*ns.FLOW_PLANE), ns.FLOW_LIC_STEP, ns.FLOW_LIC_HALF_LENGTH, seed=4)
+    n = lr.reason_counts(res)
+    print(evaluate.nan, n)
+    # every evaluation with a NaN velocity ends its direction (a NaN centre: both directions, counted once)
+    assert evaluate.nan >= 5 and n[lr.END_STAGNANT] >= evaluate.nan and n[lr.END_MAXSTEPS] >= 50
+    nan_centre = np.isnan(res["speed"]) & (res["count"] == 1)
+    assert np.all(res["reasons"][nan_centre] == lr.END_STAGNANT)
+    assert not np.isnan(res["lic"][res["count"] > 0]).any()

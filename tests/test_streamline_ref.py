@@ -102,3 +102,29 @@ def test_zero_field_stagnates_after_one_vertex(normalize):
                                                               backward=True, normalize=normalize)
     assert np.array_equal(offsets, np.arange(len(seeds) + 1, dtype=np.uint64))      # one vertex each
     assert np.all(reasons[inside] == sr.END_STAGNANT) and np.all(reasons[~inside] == sr.END_LEFT)
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+def test_a_nan_velocity_ends_a_line_left_or_stagnant(normalize):
+    """tests/nan_scenes.py: 1 % of the cells NaN in one of three channels (the case tests/test_gpu_nan_cells.py holds the
+    module to).  A NaN velocity is a value: the line ends at the next evaluation — LEFT at the NaN position without
+    EXA_STREAM_NORMALIZE, STAGNANT by !(s > 0) with it — and no NaN position is appended"""
+    import nan_scenes as ns
+    S = ns.case(ns.flow_scene(), basis_form=1).oracle_scene()
+    seeds = sr.uniform_seeds(S, ns.FLOW_SEEDS)
+    v, off, _, reasons, w = sr.streamlines(S, seeds, ns.FLOW_CHANNELS, ns.FLOW_STEP, ns.FLOW_MAX_STEPS, True, False, normalize)
+    ended = ns.directions_ended_by_nan(S, seeds, ns.FLOW_STEP, ns.FLOW_MAX_STEPS, normalize)
+    print(f"normalize {normalize}: {int(ended.sum())} lines end for a NaN velocity; {sr.reason_counts(reasons, 1)}")
+    assert ended.sum() >= 5 and (~ended).sum() >= 5
+    assert np.all(reasons[ended, 1] == (sr.END_STAGNANT if normalize else sr.END_LEFT))
+    assert not np.isnan(v).any()
+    first, last = off[:-1].astype(np.int64), off[1:].astype(np.int64) - 1
+    failed_seed = np.zeros(len(w), dtype=bool)
+    failed_seed[first[np.isnan(w[first]).all(axis=1)]] = True           # a failed seed's velocity is three NaN by contract
+    assert failed_seed.sum() >= 1 and np.all((last - first)[failed_seed[first]] == 0)
+    nan_vertex = np.isnan(w).any(axis=1) & ~failed_seed
+    if normalize:
+        assert not nan_vertex.any()                                   # the evaluation that meets the NaN fails: nothing is appended
+    else:
+        # the vertex whose own velocity is NaN is appended (its position is finite) and is the last of its line
+        assert set(np.nonzero(nan_vertex)[0]) <= set(last[ended]) and nan_vertex.sum() >= 1
