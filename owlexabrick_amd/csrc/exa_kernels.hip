@@ -8,6 +8,7 @@
 // compared against the CPU oracle operation for operation.
 #include "exa_device.h"
 #include <cfloat>
+#include <type_traits>
 
 // Instruction trims of the kd march that keep every pixel bit for bit (measured one by one in rounds 2-4,
 // profiles/design_history_r01_r03.md, profiles/r04_experiments.txt; the build-time switches they were A/B-timed with are gone):
@@ -414,9 +415,15 @@ __device__ __forceinline__ Pair loadPair(const float *__restrict__ p) { return *
 // 2^cubeLog2, a wave-uniform kernel argument, and b0 is the brick's cube record (exa_cube.h; b1 is not looked at): the sizes
 // are scalar operands of the compares and clamps, the row offsets shifts instead of multiplies, 2^-level is b0.w << 23.  The
 // same integers and floats enter every address and every float operation as from the brick's march header.
-template <bool DERIV, int STATS, bool SMALL, bool VOXEL = false, bool CUBE = false>
+//
+// Two phases around `between`: position, clamps, row offsets and the issue of the four pair loads in front of it; the pick
+// out of the pairs, the masked weights and the sums behind it.  A caller puts there what can run while the loads are on their
+// way and may change B (the cube march: the previous sample's epilogue); when it returns false the visit is abandoned with
+// its loads in flight and B as `between` left it.  The default does nothing and leaves no trace in the code.
+struct NothingBetween { __device__ __forceinline__ bool operator()() const { return true; } };
+template <bool DERIV, int STATS, bool SMALL, bool VOXEL = false, bool CUBE = false, class Between = NothingBetween>
 __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4 b0, const int4 b1,
-                                             const float *__restrict__ field, V3 pos, const int cubeLog2 = 0)
+                                             const float *__restrict__ field, V3 pos, const int cubeLog2 = 0, Between between = Between())
 {
   static_assert(!CUBE || SMALL, "cube records: the 32-bit address form only");
   // march header (exa_module: leafHdr): b0 = (float(lower.xyz), 2^-level) as float bits, b1 = (size.xyz, begin)
@@ -490,6 +497,7 @@ __device__ __forceinline__ void addBasisFast(Ctx<STATS> &C, Basis &B, const int4
       pLL = loadPair(field + rowLL); pHL = loadPair(field + rowHL);
       pLH = loadPair(field + rowLH); pHH = loadPair(field + rowHH);
     }
+    if constexpr (!std::is_same<Between, NothingBetween>::value) { if (!between()) return; }
     s000 = lFirst ? pLL.a : pLL.b; s100 = hFirst ? pLL.a : pLL.b;
     s010 = lFirst ? pHL.a : pHL.b; s110 = hFirst ? pHL.a : pHL.b;
     s001 = lFirst ? pLH.a : pLH.b; s101 = hFirst ? pLH.a : pLH.b;
@@ -2397,7 +2405,20 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
 #ifndef EXA_CUBE_LEAN
 #define EXA_CUBE_LEAN 0
 #endif
-  constexpr bool LEAN = marchWaves(MULTI, STATS, SMALL, NCH, ROPE) >= 7 && (!CUBE || EXA_CUBE_LEAN);
+  // The cube variants shade a finished sample one visit late (DEFER): nothing of a sample's epilogue — TF lookup, gradient
+  // shading, opacity correction, "over" — enters the next sample's position or addresses, only the end of the ray does, once
+  // per ray.  So the epilogue of sample k runs between the issue of the cell loads of sample k+1's first brick and their
+  // first use, inside a wait the wave pays anyway, instead of with no load in flight.  Same operations on the same values in
+  // the same order per sample: the frames are the same bit for bit (tests/test_gpu_march_defer.py); a ray that the pending
+  // sample ends has taken part in one more walk burst, pop or visit's loads (positions it would have sampled, clamped
+  // addresses).  -DEXA_MARCH_DEFER=0 builds the cube variants with the epilogue in place (profiles/march_defer_bench.txt).
+#ifndef EXA_MARCH_DEFER
+#define EXA_MARCH_DEFER 1
+#endif
+  constexpr bool DEFER = CUBE && EXA_MARCH_DEFER;
+  // ... and with gradient shading the deferred epilogue runs with a visit's eight cells and its position in the brick live:
+  // LEAN again, or a register is reloaded from scratch in the epilogue behind a wait for all loads (72 VGPRs, no scratch).
+  constexpr bool LEAN = marchWaves(MULTI, STATS, SMALL, NCH, ROPE) >= 7 && (!CUBE || EXA_CUBE_LEAN || (DEFER && GRAD));
   // Does the queue hand over the region's packed record (the march tree's leaf reference) or its id?  The 32-bit variants of the
   // rope march are launched only for scenes whose records pack (launchRenderKdT: `small`), its counting variant takes ids: known
   // when the kernel is compiled (no test of a kernel argument in the pop and at the leaf: C4 17.11 -> 17.03 ms).  Everything else
@@ -2523,6 +2544,22 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       xfRcpRangeN[c] = (FAST && IL) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__builtin_amdgcn_rcpf(xfRangeN[c])))) : 0.f;
     }
 
+    // DEFER: the finished sample whose sums stand in B has not been shaded yet.  Its step and its region's cell width are
+    // carried with it: a pop may have made flcw another region's before its epilogue runs.
+    bool pending = false;
+    float pendDt = 0.f, pendFlcw = 1.f;
+    // the sample epilogue of the one-channel march on the pending sample (:800-806, :910-927), then B at its start values
+    auto shadePending = [&]() {
+      if (B.sumW > 1e-20f) {
+        const float cellValue = fdivExact<FAST>(B.sumWV, B.sumW);
+        V3 grad = mk(0.f, 0.f, 0.f);
+        if (GRAD) grad = gradOf(B.sumW, B.sumWV, B.sumD, B.sumDC);
+        integrateVolume<FAST, STATS, (FAST && !MULTI), LEAN>(C, ray, pixelColor, pendDt, cellValue, grad, pendFlcw, 0, xfRcpRange0, xfRange0);
+      }
+      B.sumWV = 0.f; B.sumW = 0.f; B.sumD = mk(0.f, 0.f, 0.f); B.sumDC = mk(0.f, 0.f, 0.f);
+      pending = false;
+    };
+
     unsigned iter = 0;
     for (;; iter++) {
       if (iter == 0xfffffff0u) { C.guardTripped = true; break; }
@@ -2611,6 +2648,42 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       }
       // (two consecutive samples of a one-brick segment per iteration, so that both samples' cell loads are in flight together, was
       // built and measured at 5 and 4 waves per SIMD: C4 17.34 -> 25.05 ms; profiles/r05_experiments.txt 9)
+      if (DEFER) {
+        // this visit's cell loads go out, the previous sample is shaded while they are on their way, then they are used
+        bool ended = false;
+        addBasisFast<GRAD, STATS, SMALL, false, CUBE>(C, B, hb0, hb1, field0, rayAt(ray.org, t_sample, ray.dir), a.cubeLog2, [&]() {
+          if (pending) {                                     // the first brick of the next sample: B is still the last one's
+            shadePending();
+            ended = pixelColor.w >= EXA_TERMINATION_THRESHOLD;   // the end of the ray (:1180): the loads in flight are abandoned
+          }
+          return !ended;
+        });
+        if (ended) {
+          pixelColor.x = pixelColor.x * pixelColor.w;                                // :1694-1696
+          pixelColor.y = pixelColor.y * pixelColor.w;
+          pixelColor.z = pixelColor.z * pixelColor.w;
+          pixelColor.w = 1.f;
+          break;
+        }
+        child++;
+        if (child < listSize) continue;
+        // all bricks of the region seen: the sample waits in B for the next visit's loads (or the flush behind the loop)
+        child = 0;
+        pending = true; pendDt = actual_dt; pendFlcw = flcw;
+        // ---- end of this step (:1180-1183), without the test of the colour ----
+        const float t_last = fminf(t_i, t1);
+        if (t_last >= t1) {
+          haveSeg = false;
+          continue;
+        }
+        t_i += a.p.dt * flcw;
+        {
+          const float t_next = fminf(t_i, t1);
+          t_sample = 0.5f * (fminf(t1, t_next) + t_last);
+          actual_dt = t_next - t_last;
+        }
+        continue;
+      }
       if (IL) addBasisFastIl<GRAD, SMALL, (IL ? IL : 2)>(B, xWV, xD, hb0, hb1, a.cellsIl, rayAt(ray.org, t_sample, ray.dir));
       else if (CUBE) addBasisFast<GRAD, STATS, SMALL, false, CUBE>(C, B, hb0, hb1, field0, rayAt(ray.org, t_sample, ray.dir), a.cubeLog2);
       else addBasisFast<GRAD, STATS, SMALL>(C, B, hb0, hb1, MULTI ? field : field0, rayAt(ray.org, t_sample, ray.dir));   // :1166
@@ -2676,6 +2749,16 @@ __global__ __launch_bounds__(kKdBlock, marchWaves(MULTI, STATS, SMALL, NCH, ROPE
       C.count(ST_SAMPLE_EVALS);
     }
 
+    if (DEFER && pending) {
+      // the ray's last sample, on every way out of the loop but the one it took itself: shaded, and the end of the ray's test
+      shadePending();
+      if (pixelColor.w >= EXA_TERMINATION_THRESHOLD) {
+        pixelColor.x = pixelColor.x * pixelColor.w;                                  // :1694-1696
+        pixelColor.y = pixelColor.y * pixelColor.w;
+        pixelColor.z = pixelColor.z * pixelColor.w;
+        pixelColor.w = 1.f;
+      }
+    }
     C.lap(ST_T_OTHER);
     marchIters = iter;
     // The pixel's framebuffer slot is worked out again from the thread id (and, in a shard, the tile number fetched again)
