@@ -131,14 +131,572 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <iostream>
 
 using namespace exa;
 
 namespace {
+using ull = unsigned long long;
+[[noreturn]] void fail(const std::string &text) { throw std::runtime_error(text); }
+
+// printf into a string: the line that a file's header and stdout share
+__attribute__((format(printf, 1, 2))) std::string format(const char *fmt, ...)
+{
+  char line[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(line, sizeof(line), fmt, ap);
+  va_end(ap);
+  return line;
+}
+
+// ---- the options: one struct per output, with today's defaults; a file name says that the output is requested
+struct PlaneOpts { vec3f origin, du, dv; vec2i size; };      // the lattice of --isolines and --lic: (i,j) at origin + (i + .5) du + (j + .5) dv
+struct DerivedOpts {                                         // --derived: resample, isomesh, isolines, regions and basins work on it
+  int quantity = -1;                                         // EXA_DERIVED_*, -1: on their channel
+  vec3i channels{ 0, 1, 2 };
+  bool on() const { return quantity >= 0; }
+};
+struct LatticeFlags { box3f box; bool haveBox = false, world = false, below = false, faces = false; };   // --regions-*: regions and basins
+struct ResampleOpts { std::string name; vec3i dims; int channel = 0; bool haveChannel = false, world = false, haveBox = false; box3f box; float fill = NAN; };
+struct IsoMeshOpts { std::string name; float iso = 0.f; vec3i dims; int channel = 0; bool haveChannel = false, world = false, haveBox = false; box3f box; };
+struct IsolinesOpts { std::string name; int channel = 0; PlaneOpts plane; std::vector<float> isos; bool world = false; };
+struct LicOpts { std::string name; vec3i channels{ 0, 1, 2 }; PlaneOpts plane; float step = 0.5f; int halfLength = 20; uint32_t seed = 0; };
+struct FtleOpts { std::string name; vec3i channels{ 0, 1, 2 }, dims{ 1, 1, 1 }; box3f box; float step = 0.5f; int numSteps = 20; bool backward = false; };
+struct CriticalOpts { std::string name; vec3i channels{ 0, 1, 2 }, dims{ 2, 2, 2 }; box3f box; int iterations = 8; float tolerance = 0.0009765625f; };
+struct RegionsOpts { std::string name; int channel = 0; float iso = 0.f; vec3i dims; };
+struct BasinsOpts { std::string name; int channel = 0; float iso = 0.f, minDepth = 0.f; vec3i dims; };
+struct SurfaceOpts { std::string name, mesh; std::vector<int> channels; float spacing = 0.f; int maxN = 0; bool world = false; };   // mesh: a file, or `iso`
+struct HistogramOpts { std::string name; int bins = 0, channel = 0; bool haveRange = false, haveBox = false; float range[2] = { 0, 1 }; box3i box; };
+struct StreamlinesOpts { std::string seedsName, name; float step = 0.f; int maxSteps = 0; vec3i channels{ 0, 1, 2 }; bool both = false, backward = false, normalize = false; };
+struct ProjectOpts { std::string name; int channel = 0, samples = 0; float dt = 0.f; };
+struct RaycastOpts { std::string name; int channel = 0, samples = 0, refine = 0; float iso = 0.f, dt = 0.f; };
+struct FrameOpts {                                           // what the reference's viewer takes, the devices and the frame loop
+  std::string cfgName, outName, xfFile;
+  vec2i size{ 600, 400 };                                    // viewer default window
+  vec3f vp, vi, vu;                                          // --camera
+  float fov = 70.f, dt = 0.5f, xfScale = 1.f, aoLength = 1e20f;
+  float isoVals[2] = { 0, 0 }; int isoChans[2] = { 0, 0 }, isoOn[2] = { 0, 0 };
+  bool haveRange = false, ao = false, pg = true, skipping = true, gradDVR = true, gradISO = true, info = false, clip = false, stats = false;
+  float range[2] = { 0, 1 }; box3f clipBox;
+  int frames = 1;
+  std::vector<int> devices;
+  bool pipeline = false, allowEmptyCells = false;
+  std::vector<float> contourPlanes;                          // 4 floats per --contourplane (normal, offset)
+  std::vector<int> contourChans;
+  std::vector<std::pair<std::string, int>> options;          // --option key=value
+};
+struct Options {
+  FrameOpts frame; DerivedOpts derived; LatticeFlags lattice; ResampleOpts resample; IsoMeshOpts isomesh; IsolinesOpts isolines; LicOpts lic;
+  FtleOpts ftle; CriticalOpts critical; RegionsOpts regions; BasinsOpts basins; SurfaceOpts surface; HistogramOpts histogram;
+  StreamlinesOpts streamlines; ProjectOpts project; RaycastOpts raycast;
+};
+
+// ---- the command line: a cursor over argv.  Numbers are read leniently (atof: `1e2` is 100, `x` is 0)
+struct Args {
+  int argc; char **argv; int i;
+  std::string flag;                                          // the word that next() stopped at
+  bool next() { if (++i >= argc) return false; flag = argv[i]; return true; }
+  // the next word, the error `text` unless `need` more words are there (word(text, 2) makes sure of the word("") after it)
+  const char *word(const std::string &text, int need = 1) { if (i + need >= argc) fail(text); return argv[++i]; }
+  float number() { return (float)atof(word("missing value after " + flag)); }
+  int count() { return (int)number(); }
+  int integer() { return (int)std::strtol(word("missing value after " + flag), nullptr, 10); }
+  vec3f vec3() { const float x = number(), y = number(), z = number(); return vec3f(x, y, z); }
+  vec3i int3() { const int x = count(), y = count(), z = count(); return vec3i(x, y, z); }
+  box3f box() { const vec3f lower = vec3(), upper = vec3(); return box3f(lower, upper); }
+  PlaneOpts plane() { PlaneOpts p; p.origin = vec3(); p.du = vec3(); p.dv = vec3(); p.size.x = count(); p.size.y = count(); return p; }
+  vec3i channels3()                                          // C0,C1,C2 in one word
+  {
+    vec3i c;
+    char tail = 0;
+    if (std::sscanf(word("missing channels after " + flag), "%d,%d,%d%c", &c.x, &c.y, &c.z, &tail) != 3)
+      fail(flag + " wants three comma-separated channels C0,C1,C2");
+    return c;
+  }
+};
+
+// appends comma-separated numbers within [lo, hi]; the empty list and a comma at the end pass, anything else is the error `text`
+template <class T, class Parse>
+void appendList(std::vector<T> &out, const char *p, const char *text, Parse parse, double lo = -INFINITY, double hi = INFINITY)
+{
+  while (*p) {
+    char *end = nullptr;
+    const auto v = parse(p, &end);
+    if (end == p || (*end != ',' && *end != 0) || v < lo || v > hi) fail(text);
+    out.push_back((T)v);
+    p = *end == ',' ? end + 1 : end;
+  }
+}
+float floatOf(const char *p, char **end) { return std::strtof(p, end); }
+long longOf(const char *p, char **end) { return std::strtol(p, end, 10); }
+
+// --derived QUANTITY: a name or a number; EXA_DERIVED_* (the module refuses an unknown number)
+int derivedQuantity(const std::string &s)
+{
+  static const char *const names[EXA_DERIVED_QUANTITIES] = { "speed", "divergence", "vorticity", "vorticity_magnitude", "q", "helicity" };
+  for (int q = 0; q < EXA_DERIVED_QUANTITIES; q++)
+    if (s == names[q]) return q;
+  char *end = nullptr;
+  const long q = std::strtol(s.c_str(), &end, 10);
+  if (end == s.c_str() || *end || q < 0) fail("--derived wants speed, divergence, vorticity, vorticity_magnitude, q, helicity or a number, not " + s);
+  return (int)q;
+}
+
+// every parse...Flag(): takes the flag the cursor stands on if it is one of its own; false if it is not
+bool parseFrameFlag(Args &a, FrameOpts &o)
+{
+  const std::string &f = a.flag;
+  if (f == "--size" || f == "-win") { o.size.x = a.count(); o.size.y = a.count(); }
+  else if (f == "--camera") { o.vp = a.vec3(); o.vi = a.vec3(); o.vu = a.vec3(); }
+  else if (f == "--fov") o.fov = a.number();
+  else if (f == "--dt") o.dt = a.number();
+  else if (f == "--xf") o.xfFile = a.word("missing file after --xf");
+  else if (f == "--xf-scale") o.xfScale = a.number();
+  else if (f == "--range") { o.range[0] = a.number(); o.range[1] = a.number(); o.haveRange = true; }
+  else if (f == "--isovals") { o.isoVals[0] = a.number(); o.isoVals[1] = a.number(); o.isoOn[0] = o.isoOn[1] = 1; }
+  else if (f == "--isochans") { o.isoChans[0] = a.count(); o.isoChans[1] = a.count(); }
+  else if (f == "--contourplane") { for (int k = 0; k < 4; k++) o.contourPlanes.push_back(a.number()); }   // viewer.cpp:1199-1205
+  else if (f == "--contourchan") o.contourChans.push_back(a.count());                                      // viewer.cpp:1206-1207
+  else if (f == "--clip-box") { o.clipBox = a.box(); o.clip = true; }
+  else if (f == "--ao") o.ao = true;
+  else if (f == "--ao-length") o.aoLength = a.number();
+  else if (f == "--no-pg") o.pg = false;
+  else if (f == "--no-space-skipping") o.skipping = false;
+  else if (f == "--gradientShadingDVR") o.gradDVR = a.number() != 0.f;
+  else if (f == "--gradientShadingISO") o.gradISO = a.number() != 0.f;
+  else if (f == "--frames") o.frames = a.count();
+  else if (f == "-o") o.outName = a.word("missing file after -o");
+  else if (f == "--info") o.info = true;
+  else if (f == "--stats") o.stats = true;
+  else if (f == "--gpus") { const int n = a.count(); o.devices.clear(); for (int d = 0; d < n; d++) o.devices.push_back(d); }
+  else if (f == "--devices") {                               // stricter than the other lists: not empty, no comma at the end
+    const char *text = "--devices wants a comma-separated list of device indices";
+    const std::string list = a.word("missing list after --devices");
+    o.devices.clear();
+    appendList(o.devices, list.c_str(), text, longOf, 0, 1023);
+    if (o.devices.empty() || list.back() == ',') fail(text);
+  }
+  else if (f == "--pipeline") o.pipeline = true;
+  else if (f == "--allow-empty-cells") o.allowEmptyCells = true;  // the reference built with -DALLOW_EMPTY_CELLS=1
+  else if (f == "--option") {                                // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
+    const std::string kv = a.word("missing key=value after --option");
+    const size_t eq = kv.find('=');
+    char *end = nullptr;
+    const long v = eq == std::string::npos ? 0 : std::strtol(kv.c_str() + eq + 1, &end, 10);
+    if (eq == std::string::npos || eq == 0 || end == kv.c_str() + eq + 1 || *end) fail("--option wants key=integer");
+    o.options.emplace_back(kv.substr(0, eq), (int)v);
+  }
+  else return false;
+  return true;
+}
+
+// the outputs on a lattice in a box, and what they share
+bool parseLatticeOutputFlag(Args &a, Options &o)
+{
+  const std::string &f = a.flag;
+  if (f == "--resample") { o.resample.dims = a.int3(); o.resample.name = a.word("missing file after --resample NX NY NZ"); }
+  else if (f == "--resample-box") { o.resample.box = a.box(); o.resample.haveBox = true; }
+  else if (f == "--resample-world") o.resample.world = true;
+  else if (f == "--resample-channel") { o.resample.channel = a.count(); o.resample.haveChannel = true; }
+  else if (f == "--resample-fill") o.resample.fill = a.number();
+  else if (f == "--isomesh") {
+    o.isomesh.iso = a.number(); o.isomesh.dims = a.int3();
+    o.isomesh.name = a.word("missing file after --isomesh ISO NX NY NZ");
+  }
+  else if (f == "--isomesh-box") { o.isomesh.box = a.box(); o.isomesh.haveBox = true; }
+  else if (f == "--isomesh-world") o.isomesh.world = true;
+  else if (f == "--isomesh-channel") { o.isomesh.channel = a.count(); o.isomesh.haveChannel = true; }
+  else if (f == "--ftle") {
+    FtleOpts &t = o.ftle;
+    t.channels = a.channels3(); t.box = a.box(); t.dims = a.int3(); t.step = a.number(); t.numSteps = a.count();
+    const std::string dir = a.word("missing direction and file after --ftle C0,C1,C2 l u NX NY NZ STEP NUMSTEPS", 2);
+    if (dir != "fwd" && dir != "bwd") fail("--ftle wants the direction fwd or bwd");
+    t.backward = dir == "bwd";
+    t.name = a.word("");
+  }
+  else if (f == "--critical") {
+    CriticalOpts &c = o.critical;
+    c.channels = a.channels3(); c.box = a.box(); c.dims = a.int3(); c.iterations = a.count(); c.tolerance = a.number();
+    c.name = a.word("missing file after --critical C0,C1,C2 l u NX NY NZ ITERATIONS TOLERANCE");
+  }
+  else if (f == "--regions") {
+    o.regions.channel = a.count(); o.regions.iso = a.number(); o.regions.dims = a.int3();
+    o.regions.name = a.word("missing file after --regions CHANNEL ISO NX NY NZ");
+  }
+  else if (f == "--basins") {
+    o.basins.channel = a.count(); o.basins.iso = a.number(); o.basins.minDepth = a.number(); o.basins.dims = a.int3();
+    o.basins.name = a.word("missing file after --basins CHANNEL ISO MINDEPTH NX NY NZ");
+  }
+  else if (f == "--regions-box") { o.lattice.box = a.box(); o.lattice.haveBox = true; }
+  else if (f == "--regions-world") o.lattice.world = true;
+  else if (f == "--regions-below") o.lattice.below = true;
+  else if (f == "--regions-faces") o.lattice.faces = true;
+  else if (f == "--derived") {
+    o.derived.quantity = derivedQuantity(a.word("missing quantity after --derived"));
+    o.derived.channels = a.int3();
+  }
+  else return false;
+  return true;
+}
+
+// the outputs on a plane, on a mesh, on seeds, on the image and on the cells
+bool parseOtherOutputFlag(Args &a, Options &o)
+{
+  const std::string &f = a.flag;
+  if (f == "--isolines") {
+    o.isolines.channel = a.count(); o.isolines.plane = a.plane();
+    const char *levels = a.word("missing levels and file after --isolines CHANNEL o u v NU NV", 2);
+    appendList(o.isolines.isos, levels, "--isolines wants a comma-separated list of levels", floatOf);
+    o.isolines.name = a.word("");
+  }
+  else if (f == "--isolines-world") o.isolines.world = true;
+  else if (f == "--lic") {
+    o.lic.channels = a.channels3(); o.lic.plane = a.plane(); o.lic.step = a.number(); o.lic.halfLength = a.count();
+    o.lic.name = a.word("missing file after --lic C0,C1,C2 o u v NU NV STEP HALFLENGTH");
+  }
+  else if (f == "--lic-seed") o.lic.seed = (uint32_t)std::strtoul(a.word("missing value after --lic-seed"), nullptr, 10);
+  else if (f == "--surface") {
+    o.surface.mesh = a.word("missing mesh and channels after --surface", 2);
+    appendList(o.surface.channels, a.word(""), "--surface: channels are C0[,C1,C2,C3]", longOf);
+    o.surface.spacing = a.number(); o.surface.maxN = a.count();
+    o.surface.name = a.word("missing file after --surface MESH CHANNELS SPACING MAXN");
+  }
+  else if (f == "--surface-world") o.surface.world = true;
+  else if (f == "--histogram") { o.histogram.bins = a.count(); o.histogram.name = a.word("missing file after --histogram BINS"); }
+  else if (f == "--histogram-channel") o.histogram.channel = a.count();
+  else if (f == "--histogram-range") { o.histogram.range[0] = a.number(); o.histogram.range[1] = a.number(); o.histogram.haveRange = true; }
+  else if (f == "--histogram-box") {                         // integer voxel coordinates: strtol
+    for (vec3i *v : { &o.histogram.box.lower, &o.histogram.box.upper }) { v->x = a.integer(); v->y = a.integer(); v->z = a.integer(); }
+    o.histogram.haveBox = true;
+  }
+  else if (f == "--streamlines") {
+    o.streamlines.seedsName = a.word("missing seed file after --streamlines");
+    o.streamlines.step = a.number(); o.streamlines.maxSteps = a.count();
+    o.streamlines.name = a.word("missing file after --streamlines SEEDS.txt STEP MAXSTEPS");
+  }
+  else if (f == "--streamlines-channels") o.streamlines.channels = a.int3();
+  else if (f == "--streamlines-both") o.streamlines.both = true;
+  else if (f == "--streamlines-backward") o.streamlines.backward = true;
+  else if (f == "--streamlines-normalize") o.streamlines.normalize = true;
+  else if (f == "--project") {
+    o.project.channel = a.count(); o.project.dt = a.number(); o.project.samples = a.count();
+    o.project.name = a.word("missing file after --project CHANNEL DT NSAMPLES");
+  }
+  else if (f == "--raycast") {
+    RaycastOpts &r = o.raycast;
+    r.channel = a.count(); r.iso = a.number(); r.dt = a.number(); r.samples = a.count(); r.refine = a.count();
+    r.name = a.word("missing file after --raycast CHANNEL ISO DT NSAMPLES REFINE");
+  }
+  else return false;
+  return true;
+}
+
+Options parseOptions(int argc, char **argv)
+{
+  Options o;
+  Args a{ argc, argv, 0, "" };
+  while (a.next()) {
+    if (parseFrameFlag(a, o.frame) || parseLatticeOutputFlag(a, o) || parseOtherOutputFlag(a, o)) continue;
+    if (a.flag[0] != '-') o.frame.cfgName = a.flag;          // a word that is no flag: the config
+    else fail("unknown flag " + a.flag);
+  }
+  if (o.frame.cfgName.empty()) fail("usage: exaRender cfg.exa [flags]");
+  if (o.derived.on() && (o.resample.haveChannel || o.isomesh.haveChannel))
+    fail("--derived takes its three channels itself: --resample-channel / --isomesh-channel do not go with it");
+  return o;
+}
+
+// ---- what the outputs share: files, the words for the field they work on, the default box
+FILE *openFile(const std::string &name, const char *mode)
+{
+  FILE *f = std::fopen(name.c_str(), mode);
+  if (!f) fail("cannot write " + name);
+  return f;
+}
+void closeFile(FILE *f, const std::string &name) { if (std::fclose(f)) fail("cannot write " + name); }
+
+// a file of one header line (none if empty) and raw arrays
+struct Array { const void *data; size_t elementSize, count; };
+void writeRaw(const std::string &name, const std::string &header, std::initializer_list<Array> arrays)
+{
+  FILE *f = openFile(name, "wb");
+  bool ok = std::fputs(header.c_str(), f) >= 0;
+  for (const Array &a : arrays) ok = ok && std::fwrite(a.data, a.elementSize, a.count, f) == a.count;
+  if (std::fclose(f) || !ok) fail("cannot write " + name);
+}
+
+std::string fieldWords(const DerivedOpts &dv, int channel)
+{
+  return dv.on() ? format("derived %d channels %d %d %d ", dv.quantity, dv.channels.x, dv.channels.y, dv.channels.z)
+                 : format("channel %d ", channel);
+}
+
+// the box of an output that was given none: everything, in the space it works in
+box3f boxOr(bool have, const box3f &box, bool world, const Renderer &r) { return have ? box : (world ? r.worldSpaceBounds : r.voxelSpaceBounds); }
+
+std::string latticeWords(const char *what, vec3i dims, const box3f &box)
+{
+  return format("%s %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g ", what, dims.x, dims.y, dims.z, box.lower.x, box.lower.y, box.lower.z,
+                box.upper.x, box.upper.y, box.upper.z);
+}
+
+// ---- the outputs, one function each: the call, the file, the line on stdout.  The next one gets a struct above, its flags in
+// a parse...Flag(), a function here and a line in writeOutputs below.
+void writeResample(const ResampleOpts &o, const DerivedOpts &dv, Renderer &r)
+{
+  const box3f box = boxOr(o.haveBox, o.box, o.world, r);
+  if (o.dims.x < 1 || o.dims.y < 1 || o.dims.z < 1) fail("--resample wants NX NY NZ >= 1");
+  const size_t comps = dv.quantity == EXA_DERIVED_VORTICITY ? 3 : 1;
+  std::vector<float> grid(size_t(o.dims.x) * size_t(o.dims.y) * size_t(o.dims.z) * comps);
+  // sampled with a NaN fill to count the points outside every region (a reconstructed value is never NaN for a field
+  // without NaNs), then the requested fill written in their place
+  if (dv.on()) r.resampleDerived(box, o.dims, dv.channels, dv.quantity, grid.data(), o.world, NAN);
+  else r.resample(box, o.dims, o.channel, grid.data(), o.world, NAN);
+  size_t invalid = 0;                                        // floats: `comps` per lattice point
+  for (float &v : grid)
+    if (std::isnan(v)) { v = o.fill; invalid++; }
+  writeRaw(o.name, "", { { grid.data(), sizeof(float), grid.size() } });
+  std::printf("%s%s", latticeWords("resample", o.dims, box).c_str(), fieldWords(dv, o.channel).c_str());
+  if (dv.on()) std::printf("components %zu ", comps);
+  std::printf("invalid %zu\n", invalid);
+}
+
+// what --surface iso needs of this invocation's --isomesh: the mesh that the module kept
+struct KeptIsoMesh { bool present; bool world; size_t triangles; };
+
+KeptIsoMesh writeIsoMesh(const IsoMeshOpts &o, const DerivedOpts &dv, bool keep, Renderer &r)
+{
+  const box3f box = boxOr(o.haveBox, o.box, o.world, r);
+  TriangleMesh::SP mesh = dv.on() ? r.extractIsoSurfaceDerived(box, o.dims, dv.channels, dv.quantity, o.iso, o.world, keep)
+                                  : r.extractIsoSurface(box, o.dims, o.channel, o.iso, o.world, nullptr, keep);
+  TriangleMesh::save(o.name, { mesh });
+  std::printf("%s%siso %.9g vertices %zu triangles %zu\n", latticeWords("isomesh", o.dims, box).c_str(), fieldWords(dv, o.channel).c_str(),
+              o.iso, mesh->vertex.size(), mesh->index.size());
+  return { true, o.world, mesh->index.size() };
+}
+
+void writeIsolines(const IsolinesOpts &o, const DerivedOpts &dv, Renderer &r)
+{
+  const PlaneOpts &p = o.plane;
+  const Renderer::Isolines L = dv.on() ? r.isolinesDerived(p.origin, p.du, p.dv, p.size, o.isos, dv.channels, dv.quantity, o.world)
+                                       : r.isolines(p.origin, p.du, p.dv, p.size, o.isos, o.channel, o.world);
+  const size_t n = o.isos.size(), nv = L.vertex.size(), ns = L.segment.size() / 2;
+  writeRaw(o.name, format("isolines %d %d levels %zu vertices %zu segments %zu\n", p.size.x, p.size.y, n, nv, ns),
+           { { o.isos.data(), 4, n }, { L.vertexOffsets.data(), 8, n + 1 }, { L.segmentOffsets.data(), 8, n + 1 },
+             { L.vertex.data(), 12, nv }, { L.uv.data(), 8, nv }, { L.segment.data(), 8, ns } });
+  std::printf("isolines %d %d %sworld %d levels %zu vertices %zu segments %zu\n", p.size.x, p.size.y, fieldWords(dv, o.channel).c_str(),
+              o.world ? 1 : 0, n, nv, ns);
+}
+
+void writeLic(const LicOpts &o, Renderer &r)
+{
+  const PlaneOpts &p = o.plane;
+  const Renderer::Lic L = r.lic(p.origin, p.du, p.dv, p.size, o.channels, o.step, o.halfLength, nullptr, o.seed);
+  const std::string head = format("lic %d %d channels %d %d %d step %.9g halfLength %d seed %u", p.size.x, p.size.y, o.channels.x,
+                                  o.channels.y, o.channels.z, o.step, o.halfLength, o.seed);
+  writeRaw(o.name, head + "\n", { { L.lic.data(), 4, L.lic.size() } });
+  size_t covered = 0;
+  ull samples = 0;
+  for (uint32_t c : L.count) { covered += c > 0; samples += c; }
+  std::printf("%s pixels_covered %zu samples %llu\n", head.c_str(), covered, samples);
+}
+
+void writeFtle(const FtleOpts &o, Renderer &r)
+{
+  const Renderer::Flowmap M = r.flowmap(o.box.lower, o.box.upper, o.dims, o.channels, o.step, o.numSteps, o.backward);
+  const std::string head = format("ftle %d %d %d channels %d %d %d step %.9g numSteps %d direction %s", o.dims.x, o.dims.y, o.dims.z,
+                                  o.channels.x, o.channels.y, o.channels.z, o.step, o.numSteps, o.backward ? "bwd" : "fwd");
+  const size_t n = M.stretch.size();
+  writeRaw(o.name, head + "\n",
+           { { M.end.data(), 12, n }, { M.steps.data(), 4, n }, { M.reason.data(), 4, n }, { M.stretch.data(), 4, n }, { M.ftle.data(), 4, n } });
+  size_t valid = 0;
+  for (float v : M.ftle) valid += !std::isnan(v);
+  std::printf("%s points_with_ftle %zu\n", head.c_str(), valid);
+}
+
+void writeCritical(const CriticalOpts &o, Renderer &r)
+{
+  const Renderer::CriticalPoints P = r.criticalPoints(o.box, o.dims, o.channels, o.iterations, o.tolerance);
+  const ExaHipCriticalStats &st = P.stats;
+  const std::string head = latticeWords("critical", o.dims, o.box)
+                         + format("channels %d %d %d iterations %d tolerance %.9g cells %llu invalidCells %llu candidates %llu found %llu "
+                                  "nonFinite %llu leftCell %llu notConverged %llu", o.channels.x, o.channels.y, o.channels.z, o.iterations,
+                                  o.tolerance, ull(st.cells), ull(st.invalidCells), ull(st.candidates), ull(st.found), ull(st.nonFinite),
+                                  ull(st.leftCell), ull(st.notConverged));
+  writeRaw(o.name, head + "\n", { { P.points.data(), sizeof(ExaHipCriticalPoint), P.points.size() } });
+  // the found points by n+ (sink, the two saddles, source) and, of each, the spiralling ones
+  size_t kind[4] = { 0, 0, 0, 0 }, spiral[4] = { 0, 0, 0, 0 }, degenerate = 0;
+  for (const ExaHipCriticalPoint &p : P.points) {
+    kind[p.type & 3]++;
+    spiral[p.type & 3] += (p.type & EXA_CRITICAL_SPIRAL) ? 1 : 0;
+    degenerate += (p.type & EXA_CRITICAL_DEGENERATE) ? 1 : 0;
+  }
+  std::printf("%s sinks %zu spiral %zu saddles1 %zu spiral %zu saddles2 %zu spiral %zu sources %zu spiral %zu degenerate %zu\n", head.c_str(),
+              kind[0], spiral[0], kind[1], spiral[1], kind[2], spiral[2], kind[3], spiral[3], degenerate);
+}
+
+void writeRegions(const RegionsOpts &o, const LatticeFlags &lf, const DerivedOpts &dv, Renderer &r)
+{
+  const box3f box = boxOr(lf.haveBox, lf.box, lf.world, r);
+  const Renderer::Regions R = dv.on() ? r.regionsDerived(box, o.dims, dv.channels, dv.quantity, o.iso, lf.world, lf.below, lf.faces)
+                                      : r.regions(box, o.dims, o.channel, o.iso, lf.world, lf.below, lf.faces);
+  const std::string counts = format("count %zu inside %llu exponent %d\n", R.regions.size(), ull(R.numInside), R.sumExponent);
+  writeRaw(o.name, format("regions %d %d %d ", o.dims.x, o.dims.y, o.dims.z) + counts,
+           { { R.regions.data(), sizeof(ExaHipRegion), R.regions.size() }, { R.labels.data(), 4, R.labels.size() } });
+  std::printf("regions %d %d %d %siso %.9g world %d below %d faces %d %s", o.dims.x, o.dims.y, o.dims.z, fieldWords(dv, o.channel).c_str(),
+              o.iso, lf.world ? 1 : 0, lf.below ? 1 : 0, lf.faces ? 1 : 0, counts.c_str());
+}
+
+void writeBasins(const BasinsOpts &o, const LatticeFlags &lf, const DerivedOpts &dv, Renderer &r)
+{
+  const box3f box = boxOr(lf.haveBox, lf.box, lf.world, r);
+  const Renderer::Basins B = dv.on() ? r.basinsDerived(box, o.dims, dv.channels, dv.quantity, o.iso, o.minDepth, lf.world, lf.below, lf.faces)
+                                     : r.basins(box, o.dims, o.channel, o.iso, o.minDepth, lf.world, lf.below, lf.faces);
+  const std::string counts = format("count %zu raw %llu rounds %d inside %llu exponent %d\n", B.basins.size(), ull(B.numRaw), B.rounds,
+                                    ull(B.numInside), B.sumExponent);
+  writeRaw(o.name, format("basins %d %d %d ", o.dims.x, o.dims.y, o.dims.z) + counts,
+           { { B.basins.data(), sizeof(ExaHipBasin), B.basins.size() }, { B.labels.data(), 4, B.labels.size() } });
+  std::printf("basins %d %d %d %siso %.9g minDepth %.9g world %d below %d faces %d %s", o.dims.x, o.dims.y, o.dims.z,
+              fieldWords(dv, o.channel).c_str(), o.iso, o.minDepth, lf.world ? 1 : 0, lf.below ? 1 : 0, lf.faces ? 1 : 0, counts.c_str());
+}
+
+void writeSurface(const SurfaceOpts &o, const KeptIsoMesh &iso, Renderer &r)
+{
+  const bool fromIso = o.mesh == "iso";
+  if (fromIso && !iso.present) fail("--surface iso needs --isomesh in the same invocation");
+  Renderer::SurfaceSamples S;
+  const bool world = fromIso ? iso.world : o.world;
+  if (fromIso) S = r.sampleIsoSurface(iso.triangles, o.channels.data(), (int)o.channels.size(), o.spacing, o.maxN, world);
+  else {
+    TriangleMesh all;                                        // the file's meshes as one
+    for (const TriangleMesh::SP &m : TriangleMesh::load(o.mesh)) {
+      const int base = (int)all.vertex.size();
+      all.vertex.insert(all.vertex.end(), m->vertex.begin(), m->vertex.end());
+      for (const vec3i &t : m->index) all.index.push_back(vec3i(t.x + base, t.y + base, t.z + base));
+    }
+    S = r.sampleTriangles(all, o.channels.data(), (int)o.channels.size(), o.spacing, o.maxN, world);
+  }
+  const Renderer::SurfaceIntegrals I = Renderer::surfaceIntegrals(S);
+  const size_t nt = S.subdiv.size(), nc = o.channels.size();
+  FILE *f = openFile(o.name, "wb");
+  std::fprintf(f, "surface triangles %zu channels %zu", nt, nc);
+  for (int c : o.channels) std::fprintf(f, " %d", c);
+  std::fprintf(f, " spacing %.9g maxN %d world %d\n", o.spacing, o.maxN, world ? 1 : 0);
+  for (size_t t = 0; t < nt; t++) {
+    std::fprintf(f, "%d %.9g %.9g %.9g %.17g", S.subdiv[t], S.areaNormal[t].x, S.areaNormal[t].y, S.areaNormal[t].z, I.area[t]);
+    for (size_t c = 0; c < nc; c++)
+      std::fprintf(f, " %u %.17g %.17g %.17g", S.count[t * nc + c], S.sum[t * nc + c], I.mean[t * nc + c], I.integral[t * nc + c]);
+    std::fprintf(f, "\n");
+  }
+  std::fprintf(f, "invalid %llu\n", ull(I.invalidTriangles));
+  for (size_t c = 0; c < nc; c++)
+    std::fprintf(f, "total %d covered_area %.17g uncovered_area %.17g uncovered_triangles %llu integral %.17g force %.17g %.17g %.17g\n",
+                 o.channels[c], I.coveredArea[c], I.uncoveredArea[c], ull(I.uncoveredTriangles[c]), I.totalIntegral[c], I.force[3 * c],
+                 I.force[3 * c + 1], I.force[3 * c + 2]);
+  if (nc == 3) std::fprintf(f, "flux %.17g\n", I.flux);
+  closeFile(f, o.name);
+  std::printf("surface triangles %zu channels %zu spacing %.9g maxN %d invalid %llu\n", nt, nc, o.spacing, o.maxN, ull(I.invalidTriangles));
+}
+
+void writeHistogram(const HistogramOpts &o, Renderer &r)
+{
+  if (o.bins < 1) fail("--histogram wants BINS >= 1");
+  const box3i *box = o.haveBox ? &o.box : nullptr;
+  interval<float> range(o.range[0], o.range[1]);
+  if (!o.haveRange) {
+    const ExaHipFieldStats s = r.fieldStats(o.channel, box);
+    if (!(s.min < s.max)) fail("--histogram: the field is constant (or has no value) there: give --histogram-range lo hi");
+    range = interval<float>(s.min, s.max);
+  }
+  std::vector<uint64_t> cells, volume;
+  ExaHipFieldStats st;
+  r.computeHistogram(o.channel, range, o.bins, cells, &volume, &st, box);
+  FILE *f = openFile(o.name, "w");
+  for (size_t b = 0; b < cells.size(); b++) std::fprintf(f, "%llu %llu\n", ull(cells[b]), ull(volume[b]));
+  closeFile(f, o.name);
+  std::printf("histogram channel %d bins %d range %.9g %.9g slots %llu empty %llu nan %llu under %llu over %llu binned %llu\n", o.channel,
+              o.bins, range.lower, range.upper, ull(st.slots), ull(st.empty), ull(st.nan), ull(st.under), ull(st.over), ull(st.binned));
+}
+
+void writeStreamlines(const StreamlinesOpts &o, Renderer &r)
+{
+  std::vector<vec3f> seeds;
+  FILE *f = std::fopen(o.seedsName.c_str(), "r");
+  if (!f) fail("cannot read " + o.seedsName);
+  char word[3][64];
+  int got;
+  while ((got = std::fscanf(f, "%63s %63s %63s", word[0], word[1], word[2])) == 3)     // strtof: nan and inf are seeds too
+    seeds.push_back(vec3f(std::strtof(word[0], nullptr), std::strtof(word[1], nullptr), std::strtof(word[2], nullptr)));
+  std::fclose(f);
+  if (got != EOF) fail(o.seedsName + ": a seed is three numbers `x y z`");
+  const Renderer::Streamlines L = r.streamlines(seeds.data(), seeds.size(), o.channels, o.step, o.maxSteps, o.both || !o.backward,
+                                                o.both || o.backward, o.normalize);
+  f = openFile(o.name, "w");
+  for (size_t i = 0; i < seeds.size(); i++) {
+    std::fprintf(f, "%u %d %d %llu", L.seedVertex[i], L.reason[2 * i], L.reason[2 * i + 1], ull(L.offset[i + 1] - L.offset[i]));
+    for (uint64_t v = L.offset[i]; v < L.offset[i + 1]; v++) std::fprintf(f, " %.9g %.9g %.9g", L.vertex[v].x, L.vertex[v].y, L.vertex[v].z);
+    std::fprintf(f, "\n");
+  }
+  closeFile(f, o.name);
+  std::printf("streamlines seeds %zu channels %d %d %d step %.9g maxSteps %d vertices %zu\n", seeds.size(), o.channels.x, o.channels.y,
+              o.channels.z, o.step, o.maxSteps, L.vertex.size());
+}
+
+void writeProject(const ProjectOpts &o, vec2i size, Renderer &r)
+{
+  const Renderer::Projection P = r.project(r.cameraRays(size, 0.f, o.dt, o.samples), o.channel, true, true);
+  std::vector<float> integral(P.sum.size());
+  size_t hit = 0;
+  for (size_t k = 0; k < integral.size(); k++) { integral[k] = float(P.sum[k] * double(o.dt)); hit += P.count[k] != 0; }
+  const std::string head = format("project %d %d channel %d dt %.9g samples %d", size.x, size.y, o.channel, o.dt, o.samples);
+  const size_t n = integral.size();
+  writeRaw(o.name, head + "\n", { { integral.data(), 4, n }, { P.count.data(), 4, n }, { P.max.data(), 4, n }, { P.min.data(), 4, n } });
+  std::printf("%s pixels_hit %zu\n", head.c_str(), hit);
+}
+
+void writeRaycast(const RaycastOpts &o, vec2i size, Renderer &r)
+{
+  const Renderer::IsoHits R = r.raycastIso(r.cameraRays(size, 0.f, o.dt, o.samples), o.channel, o.iso, o.refine, true, true);
+  const std::string head = format("raycast %d %d channel %d iso %.9g dt %.9g samples %d refine %d", size.x, size.y, o.channel, o.iso, o.dt,
+                                  o.samples, o.refine);
+  const size_t n = R.t.size();
+  writeRaw(o.name, head + "\n",
+           { { R.t.data(), 4, n }, { R.position.data(), 12, n }, { R.value.data(), 4, n }, { R.gradient.data(), 12, n },
+             { R.index.data(), 4, n }, { R.side.data(), 4, n }, { R.crossings.data(), 4, n } });
+  size_t hit = 0;
+  for (int32_t k : R.index) hit += k >= 0;
+  std::printf("%s pixels_hit %zu\n", head.c_str(), hit);
+}
+
+// the requested outputs, in the order of their lines on stdout; whether there was any
+bool writeOutputs(const Options &o, Renderer &r)
+{
+  bool any = false;
+  auto wanted = [&any](const std::string &name) { any |= !name.empty(); return !name.empty(); };
+  KeptIsoMesh isoMesh{ false, false, 0 };
+  if (wanted(o.resample.name)) writeResample(o.resample, o.derived, r);
+  if (wanted(o.isomesh.name)) isoMesh = writeIsoMesh(o.isomesh, o.derived, o.surface.mesh == "iso", r);   // --surface iso reads the module's copy
+  if (wanted(o.isolines.name)) writeIsolines(o.isolines, o.derived, r);
+  if (wanted(o.lic.name)) writeLic(o.lic, r);
+  if (wanted(o.ftle.name)) writeFtle(o.ftle, r);
+  if (wanted(o.critical.name)) writeCritical(o.critical, r);
+  if (wanted(o.regions.name)) writeRegions(o.regions, o.lattice, o.derived, r);
+  if (wanted(o.basins.name)) writeBasins(o.basins, o.lattice, o.derived, r);
+  if (wanted(o.surface.name)) writeSurface(o.surface, isoMesh, r);
+  if (wanted(o.histogram.name)) writeHistogram(o.histogram, r);
+  if (wanted(o.streamlines.name)) writeStreamlines(o.streamlines, r);
+  if (wanted(o.project.name)) writeProject(o.project, o.frame.size, r);
+  if (wanted(o.raycast.name)) writeRaycast(o.raycast, o.frame.size, r);
+  return any;
+}
+
+// ---- the renderer and its frames
 // glutViewer/Camera.cpp:94-120 + glutViewer/OWLViewer.cpp:69-109 + exa/viewer.cpp:226-238
 void setupCamera(Renderer &r, vec3f origin, vec3f interest, vec3f up, float fovy, vec2i size)
 {
@@ -160,313 +718,148 @@ void setupCamera(Renderer &r, vec3f origin, vec3f interest, vec3f up, float fovy
   r.updateCamera(origin, lower_left, du, dv);
 }
 
-// --derived QUANTITY: a name or a number; EXA_DERIVED_* (the module refuses an unknown number)
-int derivedQuantity(const std::string &s)
+// the state of a new renderer as the viewer sets it before its first frame
+void setupRenderer(Renderer &renderer, const FrameOpts &o, const Config &config, const box3f &bounds, std::vector<uint32_t> &fb)
 {
-  static const char *const names[EXA_DERIVED_QUANTITIES] = { "speed", "divergence", "vorticity", "vorticity_magnitude", "q", "helicity" };
-  for (int q = 0; q < EXA_DERIVED_QUANTITIES; q++)
-    if (s == names[q]) return q;
-  char *end = nullptr;
-  const long q = std::strtol(s.c_str(), &end, 10);
-  if (end == s.c_str() || *end || q < 0) throw std::runtime_error("--derived wants speed, divergence, vorticity, vorticity_magnitude, q, helicity or a number, not " + s);
-  return (int)q;
+  for (const auto &kv : o.options) renderer.setOption(kv.first, kv.second);
+  if (o.devices.size() > 1) std::printf("devices %zu\n", o.devices.size());
+  renderer.setVoxelSpaceTransform(config.bricks.voxelSpaceTransform);
+  renderer.resizeFrameBuffer(fb.data(), o.size);
+  if (o.vu != vec3f(0.f)) setupCamera(renderer, o.vp, o.vi, o.vu, o.fov, o.size);
+  else setupCamera(renderer, bounds.center() + vec3f(-.3f, .7f, 1.f) * bounds.span(), bounds.center(), vec3f(0, 1, 0), 70.f, o.size);
+
+  // default transfer function: alpha ramp, grey ramp colour (the PNG colormaps are UI assets)
+  std::vector<float> alpha(NUM_XF_VALUES);
+  std::vector<vec3f> color(NUM_XF_VALUES);
+  for (int i = 0; i < NUM_XF_VALUES; i++) { alpha[i] = i / float(NUM_XF_VALUES - 1); color[i] = vec3f(alpha[i]); }
+  if (!o.xfFile.empty()) {                                   // 128 raw floats (viewer.cpp:139-145,1147-1152)
+    FILE *f = std::fopen(o.xfFile.c_str(), "rb");
+    if (!f || std::fread(alpha.data(), sizeof(float), NUM_XF_VALUES, f) != (size_t)NUM_XF_VALUES) fail("cannot read " + o.xfFile);
+    std::fclose(f);
+  }
+  for (size_t c = 0; c < config.scalarFields.size(); c++) {  // viewer.cpp:567-575
+    interval<float> dom = config.scalarFields[c]->valueRange;
+    if (o.haveRange) dom = interval<float>(o.range[0], o.range[1]);
+    renderer.updateXF((int)c, alpha.data(), color, dom, o.xfScale);
+  }
+  renderer.updateIsoValues(o.isoVals, o.isoChans, o.isoOn);
+  if (!o.contourPlanes.empty()) {
+    // the viewer's contour panel set-up (viewer.cpp:673-690): planes given on the command line are enabled, the
+    // others keep their defaults (axis i % 3, offset .5, off); the channels apply when more than one was given
+    vec3f n[MAX_CONTOUR_PLANES]; float off[MAX_CONTOUR_PLANES]; int ch[MAX_CONTOUR_PLANES], en[MAX_CONTOUR_PLANES];
+    if (o.contourPlanes.size() / 4 > (size_t)MAX_CONTOUR_PLANES) fail("too many contour planes");
+    for (int i = 0; i < MAX_CONTOUR_PLANES; i++) {
+      if (o.contourPlanes.size() / 4 > (size_t)i) {
+        n[i] = vec3f(o.contourPlanes[4 * i], o.contourPlanes[4 * i + 1], o.contourPlanes[4 * i + 2]);
+        off[i] = o.contourPlanes[4 * i + 3]; en[i] = 1;
+      } else {
+        n[i] = vec3f(i % 3 == 0 ? 1.f : 0.f, i % 3 == 1 ? 1.f : 0.f, i % 3 == 2 ? 1.f : 0.f);
+        off[i] = .5f; en[i] = 0;
+      }
+      ch[i] = (o.contourChans.size() > 1 && (size_t)i < o.contourChans.size()) ? o.contourChans[i] : 0;
+    }
+    renderer.updateContourPlanes(n, off, ch, en);
+  }
+  renderer.setSpaceSkipping(o.skipping);
+  renderer.setGradientShadingDVR(o.gradDVR);
+  renderer.setGradientShadingISO(o.gradISO);
+  renderer.frameState.ao.enabled = o.ao;                     // viewer.cpp:944-959
+  renderer.frameState.ao.length = o.aoLength;
+  renderer.frameState.clipBox.enabled = o.clip;
+  if (o.clip) {
+    const box3f wb = renderer.worldSpaceBounds;
+    renderer.frameState.clipBox.coords.lower = wb.lower + o.clipBox.lower * wb.span();
+    renderer.frameState.clipBox.coords.upper = wb.lower + o.clipBox.upper * wb.span();
+  }
+}
+
+// --pipeline: two device frames + two pinned host frames, the march of frame k+1 runs while frame k travels to the host.
+// Leaves the last frame in fb and returns the kernel time of all frames
+double renderPipelined(Renderer &renderer, const FrameOpts &o, std::vector<uint32_t> &fb)
+{
+  auto ok = [](hipError_t e, const char *what) { if (e != hipSuccess) fail(std::string(what) + ": " + hipGetErrorString(e)); };
+  ok(hipSetDevice(o.devices[0]), "hipSetDevice");
+  const size_t bytes = fb.size() * sizeof(uint32_t);
+  const int frames = o.frames;
+  uint32_t *dev[2], *host[2];
+  hipStream_t march, copy;
+  hipEvent_t rendered[2], copied[2];
+  ok(hipStreamCreateWithFlags(&march, hipStreamNonBlocking), "hipStreamCreate");
+  ok(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking), "hipStreamCreate");
+  for (int k = 0; k < 2; k++) {
+    ok(hipMalloc((void **)&dev[k], bytes), "hipMalloc");
+    ok(hipHostMalloc((void **)&host[k], bytes, hipHostMallocDefault), "hipHostMalloc");
+    ok(hipEventCreateWithFlags(&rendered[k], hipEventDisableTiming), "hipEventCreate");
+    ok(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming), "hipEventCreate");
+  }
+  renderer.updateDt(o.dt);
+  renderer.updateFrameID(0);
+  renderer.render();                                   // one synchronous frame first: launch-order feedback
+  const auto t1 = std::chrono::steady_clock::now();
+  int accumID = 0;
+  for (int fr = 0; fr < frames; fr++) {
+    const int k = fr & 1;
+    renderer.updateFrameID(accumID);
+    if (o.pg) ++accumID;
+    if (fr >= 2) ok(hipStreamWaitEvent(march, copied[k], 0), "hipStreamWaitEvent");   // buffer k has left the device
+    renderer.renderAsync(dev[k], march);
+    ok(hipEventRecord(rendered[k], march), "hipEventRecord");
+    ok(hipStreamWaitEvent(copy, rendered[k], 0), "hipStreamWaitEvent");
+    ok(hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, copy), "hipMemcpyAsync");
+    ok(hipEventRecord(copied[k], copy), "hipEventRecord");
+  }
+  ok(hipStreamSynchronize(copy), "hipStreamSynchronize");
+  ok(hipStreamSynchronize(march), "hipStreamSynchronize");
+  const double secP = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+  std::memcpy(fb.data(), host[(frames - 1) & 1], bytes);
+  std::printf("pipelined: %d frames in %.3f ms (%.3f ms per frame incl. copy to host)\n", frames, 1000.0 * secP, 1000.0 * secP / frames);
+  for (int k = 0; k < 2; k++) { (void)hipFree(dev[k]); (void)hipHostFree(host[k]); (void)hipEventDestroy(rendered[k]); (void)hipEventDestroy(copied[k]); }
+  (void)hipStreamDestroy(march); (void)hipStreamDestroy(copy);
+  return renderer.stats().kernel_ms * frames;
+}
+
+// --stats, the frames, their average and the last of them as binary PPM
+void renderFrames(Renderer &renderer, const FrameOpts &o, std::vector<uint32_t> &fb)
+{
+  if (o.stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
+    renderer.updateDt(o.dt);
+    renderer.updateFrameID(0);
+    const ExaHipStats s = renderer.renderStats();
+    std::printf("regions %zu leafEntries %zu\n", renderer.numRegions, renderer.numLeafEntries);
+    std::printf("stats segments %llu samples %llu brick_visits %llu corner_loads %llu nodes_visited %llu\n", ull(s.segments), ull(s.samples),
+                ull(s.brick_visits), ull(s.corner_loads), ull(s.nodes_visited));
+  }
+  int accumID = 0;
+  double kernelMs = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (o.pipeline) kernelMs = renderPipelined(renderer, o, fb);
+  else
+    for (int fr = 0; fr < o.frames; fr++) {                  // viewer.cpp:279-288
+      renderer.updateDt(o.dt);
+      renderer.updateFrameID(accumID);
+      if (o.pg) ++accumID;
+      renderer.render();
+      kernelMs += renderer.stats().kernel_ms;
+    }
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  std::printf("Avg. after %d frames: %.3f FPS (%.3f ms), kernel %.3f ms\n", o.frames, o.frames / sec, 1000.0 * sec / o.frames, kernelMs / o.frames);
+  if (o.outName.empty()) return;
+  FILE *f = openFile(o.outName, "wb");
+  std::fprintf(f, "P6\n%d %d\n255\n", o.size.x, o.size.y);
+  for (int y = o.size.y - 1; y >= 0; y--)
+    for (int x = 0; x < o.size.x; x++) { const uint32_t p = fb[size_t(y) * o.size.x + x]; const unsigned char rgb[3] = { (unsigned char)(p & 255), (unsigned char)((p >> 8) & 255), (unsigned char)((p >> 16) & 255) }; std::fwrite(rgb, 1, 3, f); }
+  std::fclose(f);
 }
 } // namespace
 
 int main(int argc, char **argv)
 {
   try {
-    std::string cfgName, outName;
-    vec2i size(600, 400);                                         // viewer default window
-    vec3f vp, vi, vu;                                             // --camera
-    float fov = 70.f, dt = 0.5f, xfScale = 1.f, aoLength = 1e20f;
-    float isoVals[2] = { 0, 0 }; int isoChans[2] = { 0, 0 }, isoOn[2] = { 0, 0 };
-    bool haveRange = false, ao = false, pg = true, skipping = true, gradDVR = true, gradISO = true, info = false, clip = false, stats = false;
-    float range[2] = { 0, 1 }; box3f clipBox;
-    std::string xfFile;
-    int frames = 1;
-    std::vector<int> devices;
-    bool pipeline = false;
-    bool allowEmptyCells = false;
-    std::vector<float> contourPlanes;                             // 4 floats per --contourplane (normal, offset)
-    std::vector<std::pair<std::string, int>> options;             // --option key=value
-    std::vector<int> contourChans;
-    int resampleDims[3] = { 0, 0, 0 }, resampleChannel = 0;
-    std::string resampleName;
-    bool resampleWorld = false, haveResampleBox = false;
-    box3f resampleBox;
-    float resampleFill = NAN;
-    int isoDims[3] = { 0, 0, 0 }, isoChannel = 0;
-    float isoValue = 0.f;
-    std::string isoName;
-    bool isoWorld = false, haveIsoBox = false;
-    box3f isoBox;
-    int histBins = 0, histChannel = 0;
-    std::string histName;
-    bool haveHistRange = false, haveHistBox = false;
-    float histRange[2] = { 0, 1 };
-    box3i histBox;
-    std::string streamSeedsName, streamName;
-    float streamStep = 0.f;
-    int streamMaxSteps = 0;
-    vec3i streamChannels(0, 1, 2);
-    bool streamBoth = false, streamBackward = false, streamNormalize = false;
-    std::string projectName;
-    int projectChannel = 0, projectSamples = 0;
-    float projectDt = 0.f;
-    std::string raycastName;
-    std::string surfaceName, surfaceMesh;
-    std::vector<int> surfaceChannels;
-    float surfaceSpacing = 0.f;
-    int surfaceMaxN = 0;
-    bool surfaceWorld = false;
-    int raycastChannel = 0, raycastSamples = 0, raycastRefine = 0;
-    float raycastIso = 0.f, raycastDt = 0.f;
-    int derived = -1;                                            // --derived: EXA_DERIVED_*
-    vec3i derivedChannels(0, 1, 2);
-    bool haveResampleChannel = false, haveIsoChannel = false;
-    std::string regionsName;
-    int regionsChannel = 0, regionsDims[3] = { 0, 0, 0 };
-    float regionsIso = 0.f;
-    bool regionsWorld = false, regionsBelow = false, regionsFaces = false, haveRegionsBox = false;
-    box3f regionsBox;
-    std::string basinsName;
-    int basinsChannel = 0, basinsDims[3] = { 0, 0, 0 };
-    float basinsIso = 0.f, basinsMinDepth = 0.f;
-    std::string linesName;
-    int linesChannel = 0;
-    vec3f linesOrigin, linesDu, linesDv;
-    vec2i linesSize;
-    std::vector<float> linesIsos;
-    bool linesWorld = false;
-    std::string licName;
-    vec3i licChannels(0, 1, 2);
-    vec3f licOrigin, licDu, licDv;
-    vec2i licSize;
-    float licStep = 0.5f;
-    int licHalfLength = 20;
-    uint32_t licSeed = 0;
-    std::string criticalName;
-    vec3i criticalChannels(0, 1, 2), criticalDims(2, 2, 2);
-    vec3f criticalLo, criticalHi;
-    int criticalIterations = 8;
-    float criticalTolerance = 0.0009765625f;
-    std::string ftleName;
-    vec3i ftleChannels(0, 1, 2), ftleDims(1, 1, 1);
-    vec3f ftleLo, ftleHi;
-    float ftleStep = 0.5f;
-    int ftleNumSteps = 20;
-    bool ftleBackward = false;
-    for (int i = 1; i < argc; i++) {
-      const std::string a = argv[i];
-      auto f = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (float)atof(argv[++i]); };
-      if (a == "--size" || a == "-win") { size.x = (int)f(); size.y = (int)f(); }
-      else if (a == "--camera") { vp = { f(), f(), f() }; vi = { f(), f(), f() }; vu = { f(), f(), f() }; }
-      else if (a == "--fov") fov = f();
-      else if (a == "--dt") dt = f();
-      else if (a == "--xf") { if (i + 1 >= argc) throw std::runtime_error("missing file after --xf"); xfFile = argv[++i]; }
-      else if (a == "--xf-scale") xfScale = f();
-      else if (a == "--range") { range[0] = f(); range[1] = f(); haveRange = true; }
-      else if (a == "--isovals") { isoVals[0] = f(); isoVals[1] = f(); isoOn[0] = isoOn[1] = 1; }
-      else if (a == "--isochans") { isoChans[0] = (int)f(); isoChans[1] = (int)f(); }
-      else if (a == "--contourplane") { for (int k = 0; k < 4; k++) contourPlanes.push_back(f()); }   // viewer.cpp:1199-1205
-      else if (a == "--contourchan") contourChans.push_back((int)f());                                // viewer.cpp:1206-1207
-      else if (a == "--clip-box") { clipBox.lower = { f(), f(), f() }; clipBox.upper = { f(), f(), f() }; clip = true; }
-      else if (a == "--ao") ao = true;
-      else if (a == "--ao-length") aoLength = f();
-      else if (a == "--no-pg") pg = false;
-      else if (a == "--no-space-skipping") skipping = false;
-      else if (a == "--gradientShadingDVR") gradDVR = f() != 0.f;
-      else if (a == "--gradientShadingISO") gradISO = f() != 0.f;
-      else if (a == "--frames") frames = (int)f();
-      else if (a == "-o") { if (i + 1 >= argc) throw std::runtime_error("missing file after -o"); outName = argv[++i]; }
-      else if (a == "--info") info = true;
-      else if (a == "--stats") stats = true;
-      else if (a == "--gpus") { const int n = (int)f(); devices.clear(); for (int d = 0; d < n; d++) devices.push_back(d); }
-      else if (a == "--devices") {
-        if (i + 1 >= argc) throw std::runtime_error("missing list after --devices");
-        devices.clear();
-        for (const char *p = argv[++i]; *p;) {
-          char *end = nullptr;
-          const long d = strtol(p, &end, 10);
-          if (end == p || d < 0 || d > 1023 || (*end != ',' && *end != 0)) throw std::runtime_error("--devices wants a comma-separated list of device indices");
-          devices.push_back((int)d);
-          p = *end == ',' ? end + 1 : end;
-          if (*end == ',' && !*p) throw std::runtime_error("--devices wants a comma-separated list of device indices");
-        }
-        if (devices.empty()) throw std::runtime_error("--devices wants a comma-separated list of device indices");
-      }
-      else if (a == "--resample") {
-        for (int k = 0; k < 3; k++) resampleDims[k] = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --resample NX NY NZ");
-        resampleName = argv[++i];
-      }
-      else if (a == "--resample-box") { resampleBox.lower = { f(), f(), f() }; resampleBox.upper = { f(), f(), f() }; haveResampleBox = true; }
-      else if (a == "--resample-world") resampleWorld = true;
-      else if (a == "--resample-channel") { resampleChannel = (int)f(); haveResampleChannel = true; }
-      else if (a == "--resample-fill") resampleFill = f();
-      else if (a == "--isomesh") {
-        isoValue = f();
-        for (int k = 0; k < 3; k++) isoDims[k] = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --isomesh ISO NX NY NZ");
-        isoName = argv[++i];
-      }
-      else if (a == "--isomesh-box") { isoBox.lower = { f(), f(), f() }; isoBox.upper = { f(), f(), f() }; haveIsoBox = true; }
-      else if (a == "--isomesh-world") isoWorld = true;
-      else if (a == "--isomesh-channel") { isoChannel = (int)f(); haveIsoChannel = true; }
-      else if (a == "--isolines") {
-        linesChannel = (int)f();
-        linesOrigin = { f(), f(), f() }; linesDu = { f(), f(), f() }; linesDv = { f(), f(), f() };
-        linesSize.x = (int)f(); linesSize.y = (int)f();
-        if (i + 2 >= argc) throw std::runtime_error("missing levels and file after --isolines CHANNEL o u v NU NV");
-        for (const char *p = argv[++i]; *p;) {
-          char *end = nullptr;
-          const float v = std::strtof(p, &end);
-          if (end == p || (*end != ',' && *end != 0)) throw std::runtime_error("--isolines wants a comma-separated list of levels");
-          linesIsos.push_back(v);
-          p = *end == ',' ? end + 1 : end;
-        }
-        linesName = argv[++i];
-      }
-      else if (a == "--isolines-world") linesWorld = true;
-      else if (a == "--lic") {
-        if (i + 1 >= argc) throw std::runtime_error("missing channels after --lic");
-        char tail = 0;
-        if (std::sscanf(argv[++i], "%d,%d,%d%c", &licChannels.x, &licChannels.y, &licChannels.z, &tail) != 3)
-          throw std::runtime_error("--lic wants three comma-separated channels C0,C1,C2");
-        licOrigin = { f(), f(), f() }; licDu = { f(), f(), f() }; licDv = { f(), f(), f() };
-        licSize.x = (int)f(); licSize.y = (int)f();
-        licStep = f();
-        licHalfLength = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --lic C0,C1,C2 o u v NU NV STEP HALFLENGTH");
-        licName = argv[++i];
-      }
-      else if (a == "--critical") {
-        if (i + 1 >= argc) throw std::runtime_error("missing channels after --critical");
-        char tail = 0;
-        if (std::sscanf(argv[++i], "%d,%d,%d%c", &criticalChannels.x, &criticalChannels.y, &criticalChannels.z, &tail) != 3)
-          throw std::runtime_error("--critical wants three comma-separated channels C0,C1,C2");
-        criticalLo = { f(), f(), f() }; criticalHi = { f(), f(), f() };
-        criticalDims.x = (int)f(); criticalDims.y = (int)f(); criticalDims.z = (int)f();
-        criticalIterations = (int)f();
-        criticalTolerance = f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --critical C0,C1,C2 l u NX NY NZ ITERATIONS TOLERANCE");
-        criticalName = argv[++i];
-      }
-      else if (a == "--ftle") {
-        if (i + 1 >= argc) throw std::runtime_error("missing channels after --ftle");
-        char tail = 0;
-        if (std::sscanf(argv[++i], "%d,%d,%d%c", &ftleChannels.x, &ftleChannels.y, &ftleChannels.z, &tail) != 3)
-          throw std::runtime_error("--ftle wants three comma-separated channels C0,C1,C2");
-        ftleLo = { f(), f(), f() }; ftleHi = { f(), f(), f() };
-        ftleDims.x = (int)f(); ftleDims.y = (int)f(); ftleDims.z = (int)f();
-        ftleStep = f();
-        ftleNumSteps = (int)f();
-        if (i + 2 >= argc) throw std::runtime_error("missing direction and file after --ftle C0,C1,C2 l u NX NY NZ STEP NUMSTEPS");
-        const std::string dir = argv[++i];
-        if (dir != "fwd" && dir != "bwd") throw std::runtime_error("--ftle wants the direction fwd or bwd");
-        ftleBackward = dir == "bwd";
-        ftleName = argv[++i];
-      }
-      else if (a == "--lic-seed") { if (i + 1 >= argc) throw std::runtime_error("missing value after --lic-seed"); licSeed = (uint32_t)std::strtoul(argv[++i], nullptr, 10); }
-      else if (a == "--regions") {
-        regionsChannel = (int)f();
-        regionsIso = f();
-        for (int k = 0; k < 3; k++) regionsDims[k] = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --regions CHANNEL ISO NX NY NZ");
-        regionsName = argv[++i];
-      }
-      else if (a == "--basins") {
-        basinsChannel = (int)f();
-        basinsIso = f();
-        basinsMinDepth = f();
-        for (int k = 0; k < 3; k++) basinsDims[k] = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --basins CHANNEL ISO MINDEPTH NX NY NZ");
-        basinsName = argv[++i];
-      }
-      else if (a == "--regions-box") { regionsBox.lower = { f(), f(), f() }; regionsBox.upper = { f(), f(), f() }; haveRegionsBox = true; }
-      else if (a == "--regions-world") regionsWorld = true;
-      else if (a == "--regions-below") regionsBelow = true;
-      else if (a == "--regions-faces") regionsFaces = true;
-      else if (a == "--derived") {
-        if (i + 1 >= argc) throw std::runtime_error("missing quantity after --derived");
-        derived = derivedQuantity(argv[++i]);
-        derivedChannels.x = (int)f(); derivedChannels.y = (int)f(); derivedChannels.z = (int)f();
-      }
-      else if (a == "--histogram") {
-        histBins = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --histogram BINS");
-        histName = argv[++i];
-      }
-      else if (a == "--histogram-channel") histChannel = (int)f();
-      else if (a == "--histogram-range") { histRange[0] = f(); histRange[1] = f(); haveHistRange = true; }
-      else if (a == "--histogram-box") {
-        auto n = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value after " + a); return (int)std::strtol(argv[++i], nullptr, 10); };
-        histBox.lower = { n(), n(), n() }; histBox.upper = { n(), n(), n() }; haveHistBox = true;
-      }
-      else if (a == "--streamlines") {
-        if (i + 1 >= argc) throw std::runtime_error("missing seed file after --streamlines");
-        streamSeedsName = argv[++i];
-        streamStep = f();
-        streamMaxSteps = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --streamlines SEEDS.txt STEP MAXSTEPS");
-        streamName = argv[++i];
-      }
-      else if (a == "--streamlines-channels") { streamChannels.x = (int)f(); streamChannels.y = (int)f(); streamChannels.z = (int)f(); }
-      else if (a == "--streamlines-both") streamBoth = true;
-      else if (a == "--streamlines-backward") streamBackward = true;
-      else if (a == "--streamlines-normalize") streamNormalize = true;
-      else if (a == "--project") {
-        projectChannel = (int)f();
-        projectDt = f();
-        projectSamples = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --project CHANNEL DT NSAMPLES");
-        projectName = argv[++i];
-      }
-      else if (a == "--raycast") {
-        raycastChannel = (int)f();
-        raycastIso = f();
-        raycastDt = f();
-        raycastSamples = (int)f();
-        raycastRefine = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --raycast CHANNEL ISO DT NSAMPLES REFINE");
-        raycastName = argv[++i];
-      }
-      else if (a == "--surface") {
-        if (i + 2 >= argc) throw std::runtime_error("missing mesh and channels after --surface");
-        surfaceMesh = argv[++i];
-        for (const char *c = argv[++i]; *c;) {
-          char *end = nullptr;
-          surfaceChannels.push_back((int)std::strtol(c, &end, 10));
-          if (end == c || (*end && *end != ',')) throw std::runtime_error("--surface: channels are C0[,C1,C2,C3]");
-          c = *end ? end + 1 : end;
-        }
-        surfaceSpacing = f();
-        surfaceMaxN = (int)f();
-        if (i + 1 >= argc) throw std::runtime_error("missing file after --surface MESH CHANNELS SPACING MAXN");
-        surfaceName = argv[++i];
-      }
-      else if (a == "--surface-world") surfaceWorld = true;
-      else if (a == "--pipeline") pipeline = true;
-      else if (a == "--allow-empty-cells") allowEmptyCells = true;    // the reference built with -DALLOW_EMPTY_CELLS=1
-      else if (a == "--option") {                                     // exa_hip_set_option: --option walk=2, --option ao_overlap=0 ...
-        if (i + 1 >= argc) throw std::runtime_error("missing key=value after --option");
-        const std::string kv = argv[++i];
-        const size_t eq = kv.find('=');
-        char *end = nullptr;
-        const long v = eq == std::string::npos ? 0 : std::strtol(kv.c_str() + eq + 1, &end, 10);
-        if (eq == std::string::npos || eq == 0 || end == kv.c_str() + eq + 1 || *end) throw std::runtime_error("--option wants key=integer");
-        options.emplace_back(kv.substr(0, eq), (int)v);
-      }
-      else if (a[0] != '-') cfgName = a;
-      else throw std::runtime_error("unknown flag " + a);
-    }
-    if (cfgName.empty()) throw std::runtime_error("usage: exaRender cfg.exa [flags]");
-    if (derived != -1 && (haveResampleChannel || haveIsoChannel))
-      throw std::runtime_error("--derived takes its three channels itself: --resample-channel / --isomesh-channel do not go with it");
-    Config::SP config = Config::parseConfigFile(cfgName);
-    if (!config->bricks.sp) throw std::runtime_error("no bricks file specified");
-    config->bricks.sp->allowEmptyCells = allowEmptyCells;
+    Options o = parseOptions(argc, argv);
+    FrameOpts &fo = o.frame;
+    Config::SP config = Config::parseConfigFile(fo.cfgName);
+    if (!config->bricks.sp) fail("no bricks file specified");
+    config->bricks.sp->allowEmptyCells = fo.allowEmptyCells;
     const box3f bounds = config->getBounds();
     std::printf("bricks %zu cells %zu fields %zu\n", config->bricks.sp->numBricks(), config->bricks.sp->totalNumCells,
                 config->scalarFields.size());
@@ -474,398 +867,15 @@ int main(int argc, char **argv)
       std::printf("field %s range %.9g %.9g elements %zu\n", sf->name.c_str(), sf->valueRange.lower, sf->valueRange.upper, sf->value.size());
     std::printf("bounds %.9g %.9g %.9g  %.9g %.9g %.9g\n", bounds.lower.x, bounds.lower.y, bounds.lower.z,
                 bounds.upper.x, bounds.upper.y, bounds.upper.z);
-    if (info) return 0;
+    if (fo.info) return 0;
 
-    std::vector<uint32_t> fb(size_t(size.x) * size.y);
-    if (devices.empty()) devices.push_back(0);
-    Renderer renderer(config->bricks.sp, config->surfaces, config->scalarFields, devices);  // viewer.cpp:1256-1260
-    for (const auto &kv : options) renderer.setOption(kv.first, kv.second);
-    if (devices.size() > 1) std::printf("devices %zu\n", devices.size());
-    renderer.setVoxelSpaceTransform(config->bricks.voxelSpaceTransform);
-    renderer.resizeFrameBuffer(fb.data(), size);
-    if (vu != vec3f(0.f)) setupCamera(renderer, vp, vi, vu, fov, size);
-    else setupCamera(renderer, bounds.center() + vec3f(-.3f, .7f, 1.f) * bounds.span(), bounds.center(), vec3f(0, 1, 0), 70.f, size);
-
-    // default transfer function: alpha ramp, grey ramp colour (the PNG colormaps are UI assets)
-    std::vector<float> alpha(NUM_XF_VALUES);
-    std::vector<vec3f> color(NUM_XF_VALUES);
-    for (int i = 0; i < NUM_XF_VALUES; i++) { alpha[i] = i / float(NUM_XF_VALUES - 1); color[i] = vec3f(alpha[i]); }
-    if (!xfFile.empty()) {                                          // 128 raw floats (viewer.cpp:139-145,1147-1152)
-      FILE *f = std::fopen(xfFile.c_str(), "rb");
-      if (!f || std::fread(alpha.data(), sizeof(float), NUM_XF_VALUES, f) != (size_t)NUM_XF_VALUES) throw std::runtime_error("cannot read " + xfFile);
-      std::fclose(f);
-    }
-    for (size_t c = 0; c < config->scalarFields.size(); c++) {      // viewer.cpp:567-575
-      interval<float> dom = config->scalarFields[c]->valueRange;
-      if (haveRange) dom = interval<float>(range[0], range[1]);
-      renderer.updateXF((int)c, alpha.data(), color, dom, xfScale);
-    }
-    renderer.updateIsoValues(isoVals, isoChans, isoOn);
-    if (!contourPlanes.empty()) {
-      // the viewer's contour panel set-up (viewer.cpp:673-690): planes given on the command line are enabled, the
-      // others keep their defaults (axis i % 3, offset .5, off); the channels apply when more than one was given
-      vec3f n[MAX_CONTOUR_PLANES]; float off[MAX_CONTOUR_PLANES]; int ch[MAX_CONTOUR_PLANES], en[MAX_CONTOUR_PLANES];
-      if (contourPlanes.size() / 4 > (size_t)MAX_CONTOUR_PLANES) throw std::runtime_error("too many contour planes");
-      for (int i = 0; i < MAX_CONTOUR_PLANES; i++) {
-        if (contourPlanes.size() / 4 > (size_t)i) {
-          n[i] = vec3f(contourPlanes[4 * i], contourPlanes[4 * i + 1], contourPlanes[4 * i + 2]);
-          off[i] = contourPlanes[4 * i + 3]; en[i] = 1;
-        } else {
-          n[i] = vec3f(i % 3 == 0 ? 1.f : 0.f, i % 3 == 1 ? 1.f : 0.f, i % 3 == 2 ? 1.f : 0.f);
-          off[i] = .5f; en[i] = 0;
-        }
-        ch[i] = (contourChans.size() > 1 && (size_t)i < contourChans.size()) ? contourChans[i] : 0;
-      }
-      renderer.updateContourPlanes(n, off, ch, en);
-    }
-    renderer.setSpaceSkipping(skipping);
-    renderer.setGradientShadingDVR(gradDVR);
-    renderer.setGradientShadingISO(gradISO);
-    renderer.frameState.ao.enabled = ao;                            // viewer.cpp:944-959
-    renderer.frameState.ao.length = aoLength;
-    renderer.frameState.clipBox.enabled = clip;
-    if (clip) {
-      const box3f wb = renderer.worldSpaceBounds;
-      renderer.frameState.clipBox.coords.lower = wb.lower + clipBox.lower * wb.span();
-      renderer.frameState.clipBox.coords.upper = wb.lower + clipBox.upper * wb.span();
-    }
-    if (!resampleName.empty()) {
-      const box3f box = haveResampleBox ? resampleBox : (resampleWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
-      const vec3i dims(resampleDims[0], resampleDims[1], resampleDims[2]);
-      if (dims.x < 1 || dims.y < 1 || dims.z < 1) throw std::runtime_error("--resample wants NX NY NZ >= 1");
-      const size_t comps = derived == EXA_DERIVED_VORTICITY ? 3 : 1;
-      std::vector<float> grid(size_t(dims.x) * size_t(dims.y) * size_t(dims.z) * comps);
-      // sampled with a NaN fill to count the points outside every region (a reconstructed value is never NaN for a field
-      // without NaNs), then the requested fill written in their place
-      if (derived < 0) renderer.resample(box, dims, resampleChannel, grid.data(), resampleWorld, NAN);
-      else renderer.resampleDerived(box, dims, derivedChannels, derived, grid.data(), resampleWorld, NAN);
-      size_t invalid = 0;                                             // floats: `comps` per lattice point
-      for (float &v : grid)
-        if (std::isnan(v)) { v = resampleFill; invalid++; }
-      FILE *f = std::fopen(resampleName.c_str(), "wb");
-      if (!f || std::fwrite(grid.data(), sizeof(float), grid.size(), f) != grid.size()) throw std::runtime_error("cannot write " + resampleName);
-      std::fclose(f);
-      std::printf("resample %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g ", dims.x, dims.y, dims.z,
-                  box.lower.x, box.lower.y, box.lower.z, box.upper.x, box.upper.y, box.upper.z);
-      if (derived < 0) std::printf("channel %d invalid %zu\n", resampleChannel, invalid);
-      else std::printf("derived %d channels %d %d %d components %zu invalid %zu\n", derived, derivedChannels.x, derivedChannels.y,
-                       derivedChannels.z, comps, invalid);
-    }
-    size_t isoTriangles = 0;
-    if (!isoName.empty()) {
-      const box3f box = haveIsoBox ? isoBox : (isoWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
-      const vec3i dims(isoDims[0], isoDims[1], isoDims[2]);
-      const bool keep = surfaceMesh == "iso";          // --surface iso reads the module's copy
-      TriangleMesh::SP mesh = derived < 0 ? renderer.extractIsoSurface(box, dims, isoChannel, isoValue, isoWorld, nullptr, keep)
-                                          : renderer.extractIsoSurfaceDerived(box, dims, derivedChannels, derived, isoValue, isoWorld, keep);
-      isoTriangles = mesh->index.size();
-      TriangleMesh::save(isoName, { mesh });
-      std::printf("isomesh %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g ", dims.x, dims.y, dims.z, box.lower.x, box.lower.y,
-                  box.lower.z, box.upper.x, box.upper.y, box.upper.z);
-      if (derived < 0) std::printf("channel %d ", isoChannel);
-      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
-      std::printf("iso %.9g vertices %zu triangles %zu\n", isoValue, mesh->vertex.size(), mesh->index.size());
-    }
-    if (!linesName.empty()) {
-      const Renderer::Isolines L = derived < 0 ? renderer.isolines(linesOrigin, linesDu, linesDv, linesSize, linesIsos, linesChannel, linesWorld)
-                                               : renderer.isolinesDerived(linesOrigin, linesDu, linesDv, linesSize, linesIsos, derivedChannels, derived, linesWorld);
-      FILE *f = std::fopen(linesName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + linesName);
-      const size_t n = linesIsos.size(), nv = L.vertex.size(), ns = L.segment.size() / 2;
-      std::fprintf(f, "isolines %d %d levels %zu vertices %zu segments %zu\n", linesSize.x, linesSize.y, n, nv, ns);
-      const bool ok = std::fwrite(linesIsos.data(), 4, n, f) == n && std::fwrite(L.vertexOffsets.data(), 8, n + 1, f) == n + 1
-                   && std::fwrite(L.segmentOffsets.data(), 8, n + 1, f) == n + 1 && std::fwrite(L.vertex.data(), 12, nv, f) == nv
-                   && std::fwrite(L.uv.data(), 8, nv, f) == nv && std::fwrite(L.segment.data(), 8, ns, f) == ns;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + linesName);
-      std::printf("isolines %d %d ", linesSize.x, linesSize.y);
-      if (derived < 0) std::printf("channel %d ", linesChannel);
-      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
-      std::printf("world %d levels %zu vertices %zu segments %zu\n", linesWorld ? 1 : 0, n, nv, ns);
-    }
-    if (!licName.empty()) {
-      const Renderer::Lic L = renderer.lic(licOrigin, licDu, licDv, licSize, licChannels, licStep, licHalfLength, nullptr, licSeed);
-      FILE *f = std::fopen(licName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + licName);
-      const size_t n = L.lic.size();
-      std::fprintf(f, "lic %d %d channels %d %d %d step %.9g halfLength %d seed %u\n", licSize.x, licSize.y, licChannels.x, licChannels.y,
-                   licChannels.z, licStep, licHalfLength, licSeed);
-      const bool ok = std::fwrite(L.lic.data(), 4, n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + licName);
-      size_t covered = 0;
-      unsigned long long samples = 0;
-      for (uint32_t c : L.count) { covered += c > 0; samples += c; }
-      std::printf("lic %d %d channels %d %d %d step %.9g halfLength %d seed %u pixels_covered %zu samples %llu\n", licSize.x, licSize.y,
-                  licChannels.x, licChannels.y, licChannels.z, licStep, licHalfLength, licSeed, covered, samples);
-    }
-    if (!ftleName.empty()) {
-      const Renderer::Flowmap M = renderer.flowmap(ftleLo, ftleHi, ftleDims, ftleChannels, ftleStep, ftleNumSteps, ftleBackward);
-      FILE *f = std::fopen(ftleName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + ftleName);
-      const size_t n = M.stretch.size();
-      std::fprintf(f, "ftle %d %d %d channels %d %d %d step %.9g numSteps %d direction %s\n", ftleDims.x, ftleDims.y, ftleDims.z,
-                   ftleChannels.x, ftleChannels.y, ftleChannels.z, ftleStep, ftleNumSteps, ftleBackward ? "bwd" : "fwd");
-      const bool ok = std::fwrite(M.end.data(), 12, n, f) == n && std::fwrite(M.steps.data(), 4, n, f) == n
-                      && std::fwrite(M.reason.data(), 4, n, f) == n && std::fwrite(M.stretch.data(), 4, n, f) == n
-                      && std::fwrite(M.ftle.data(), 4, n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + ftleName);
-      size_t valid = 0;
-      for (float v : M.ftle) valid += !std::isnan(v);
-      std::printf("ftle %d %d %d channels %d %d %d step %.9g numSteps %d direction %s points_with_ftle %zu\n", ftleDims.x, ftleDims.y,
-                  ftleDims.z, ftleChannels.x, ftleChannels.y, ftleChannels.z, ftleStep, ftleNumSteps, ftleBackward ? "bwd" : "fwd", valid);
-    }
-    if (!criticalName.empty()) {
-      const Renderer::CriticalPoints P = renderer.criticalPoints(box3f(criticalLo, criticalHi), criticalDims, criticalChannels,
-                                                                 criticalIterations, criticalTolerance);
-      FILE *f = std::fopen(criticalName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + criticalName);
-      const ExaHipCriticalStats &st = P.stats;
-      char line[512];
-      std::snprintf(line, sizeof(line), "critical %d %d %d box %.9g %.9g %.9g %.9g %.9g %.9g channels %d %d %d iterations %d tolerance %.9g "
-                    "cells %llu invalidCells %llu candidates %llu found %llu nonFinite %llu leftCell %llu notConverged %llu",
-                    criticalDims.x, criticalDims.y, criticalDims.z, criticalLo.x, criticalLo.y, criticalLo.z, criticalHi.x, criticalHi.y,
-                    criticalHi.z, criticalChannels.x, criticalChannels.y, criticalChannels.z, criticalIterations, criticalTolerance,
-                    (unsigned long long)st.cells, (unsigned long long)st.invalidCells, (unsigned long long)st.candidates,
-                    (unsigned long long)st.found, (unsigned long long)st.nonFinite, (unsigned long long)st.leftCell,
-                    (unsigned long long)st.notConverged);
-      std::fprintf(f, "%s\n", line);
-      const size_t n = P.points.size();
-      const bool ok = std::fwrite(P.points.data(), sizeof(ExaHipCriticalPoint), n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + criticalName);
-      // the found points by n+ (sink, the two saddles, source) and, of each, the spiralling ones
-      size_t kind[4] = { 0, 0, 0, 0 }, spiral[4] = { 0, 0, 0, 0 }, degenerate = 0;
-      for (const ExaHipCriticalPoint &p : P.points) {
-        kind[p.type & 3]++;
-        spiral[p.type & 3] += (p.type & EXA_CRITICAL_SPIRAL) ? 1 : 0;
-        degenerate += (p.type & EXA_CRITICAL_DEGENERATE) ? 1 : 0;
-      }
-      std::printf("%s sinks %zu spiral %zu saddles1 %zu spiral %zu saddles2 %zu spiral %zu sources %zu spiral %zu degenerate %zu\n", line,
-                  kind[0], spiral[0], kind[1], spiral[1], kind[2], spiral[2], kind[3], spiral[3], degenerate);
-    }
-    if (!regionsName.empty()) {
-      const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
-      const vec3i dims(regionsDims[0], regionsDims[1], regionsDims[2]);
-      const Renderer::Regions R = derived < 0 ? renderer.regions(box, dims, regionsChannel, regionsIso, regionsWorld, regionsBelow, regionsFaces)
-                                              : renderer.regionsDerived(box, dims, derivedChannels, derived, regionsIso, regionsWorld, regionsBelow, regionsFaces);
-      FILE *f = std::fopen(regionsName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + regionsName);
-      const size_t nr = R.regions.size(), n = R.labels.size();
-      std::fprintf(f, "regions %d %d %d count %zu inside %llu exponent %d\n", dims.x, dims.y, dims.z, nr,
-                   (unsigned long long)R.numInside, R.sumExponent);
-      const bool ok = std::fwrite(R.regions.data(), sizeof(ExaHipRegion), nr, f) == nr && std::fwrite(R.labels.data(), 4, n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + regionsName);
-      std::printf("regions %d %d %d ", dims.x, dims.y, dims.z);
-      if (derived < 0) std::printf("channel %d ", regionsChannel);
-      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
-      std::printf("iso %.9g world %d below %d faces %d count %zu inside %llu exponent %d\n", regionsIso, regionsWorld ? 1 : 0,
-                  regionsBelow ? 1 : 0, regionsFaces ? 1 : 0, nr, (unsigned long long)R.numInside, R.sumExponent);
-    }
-    if (!basinsName.empty()) {
-      const box3f box = haveRegionsBox ? regionsBox : (regionsWorld ? renderer.worldSpaceBounds : renderer.voxelSpaceBounds);
-      const vec3i dims(basinsDims[0], basinsDims[1], basinsDims[2]);
-      const Renderer::Basins B = derived < 0 ? renderer.basins(box, dims, basinsChannel, basinsIso, basinsMinDepth, regionsWorld, regionsBelow, regionsFaces)
-                                             : renderer.basinsDerived(box, dims, derivedChannels, derived, basinsIso, basinsMinDepth, regionsWorld, regionsBelow, regionsFaces);
-      FILE *f = std::fopen(basinsName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + basinsName);
-      const size_t nb = B.basins.size(), n = B.labels.size();
-      std::fprintf(f, "basins %d %d %d count %zu raw %llu rounds %d inside %llu exponent %d\n", dims.x, dims.y, dims.z, nb,
-                   (unsigned long long)B.numRaw, B.rounds, (unsigned long long)B.numInside, B.sumExponent);
-      const bool ok = std::fwrite(B.basins.data(), sizeof(ExaHipBasin), nb, f) == nb && std::fwrite(B.labels.data(), 4, n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + basinsName);
-      std::printf("basins %d %d %d ", dims.x, dims.y, dims.z);
-      if (derived < 0) std::printf("channel %d ", basinsChannel);
-      else std::printf("derived %d channels %d %d %d ", derived, derivedChannels.x, derivedChannels.y, derivedChannels.z);
-      std::printf("iso %.9g minDepth %.9g world %d below %d faces %d count %zu raw %llu rounds %d inside %llu exponent %d\n", basinsIso,
-                  basinsMinDepth, regionsWorld ? 1 : 0, regionsBelow ? 1 : 0, regionsFaces ? 1 : 0, nb, (unsigned long long)B.numRaw, B.rounds,
-                  (unsigned long long)B.numInside, B.sumExponent);
-    }
-    if (!surfaceName.empty()) {
-      const bool fromIso = surfaceMesh == "iso";
-      if (fromIso && isoName.empty()) throw std::runtime_error("--surface iso needs --isomesh in the same invocation");
-      Renderer::SurfaceSamples S;
-      const bool world = fromIso ? isoWorld : surfaceWorld;
-      if (fromIso) S = renderer.sampleIsoSurface(isoTriangles, surfaceChannels.data(), (int)surfaceChannels.size(), surfaceSpacing, surfaceMaxN, world);
-      else {
-        TriangleMesh all;                                // the file's meshes as one
-        for (const TriangleMesh::SP &m : TriangleMesh::load(surfaceMesh)) {
-          const int base = (int)all.vertex.size();
-          all.vertex.insert(all.vertex.end(), m->vertex.begin(), m->vertex.end());
-          for (const vec3i &t : m->index) all.index.push_back(vec3i(t.x + base, t.y + base, t.z + base));
-        }
-        S = renderer.sampleTriangles(all, surfaceChannels.data(), (int)surfaceChannels.size(), surfaceSpacing, surfaceMaxN, world);
-      }
-      const Renderer::SurfaceIntegrals I = Renderer::surfaceIntegrals(S);
-      const size_t nt = S.subdiv.size(), nc = surfaceChannels.size();
-      FILE *f = std::fopen(surfaceName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + surfaceName);
-      std::fprintf(f, "surface triangles %zu channels %zu", nt, nc);
-      for (int c : surfaceChannels) std::fprintf(f, " %d", c);
-      std::fprintf(f, " spacing %.9g maxN %d world %d\n", surfaceSpacing, surfaceMaxN, world ? 1 : 0);
-      for (size_t t = 0; t < nt; t++) {
-        std::fprintf(f, "%d %.9g %.9g %.9g %.17g", S.subdiv[t], S.areaNormal[t].x, S.areaNormal[t].y, S.areaNormal[t].z, I.area[t]);
-        for (size_t c = 0; c < nc; c++)
-          std::fprintf(f, " %u %.17g %.17g %.17g", S.count[t * nc + c], S.sum[t * nc + c], I.mean[t * nc + c], I.integral[t * nc + c]);
-        std::fprintf(f, "\n");
-      }
-      std::fprintf(f, "invalid %llu\n", (unsigned long long)I.invalidTriangles);
-      for (size_t c = 0; c < nc; c++)
-        std::fprintf(f, "total %d covered_area %.17g uncovered_area %.17g uncovered_triangles %llu integral %.17g force %.17g %.17g %.17g\n",
-                     surfaceChannels[c], I.coveredArea[c], I.uncoveredArea[c], (unsigned long long)I.uncoveredTriangles[c],
-                     I.totalIntegral[c], I.force[3 * c], I.force[3 * c + 1], I.force[3 * c + 2]);
-      if (nc == 3) std::fprintf(f, "flux %.17g\n", I.flux);
-      if (std::fclose(f)) throw std::runtime_error("cannot write " + surfaceName);
-      std::printf("surface triangles %zu channels %zu spacing %.9g maxN %d invalid %llu\n", nt, nc, surfaceSpacing, surfaceMaxN,
-                  (unsigned long long)I.invalidTriangles);
-    }
-    if (!histName.empty()) {
-      if (histBins < 1) throw std::runtime_error("--histogram wants BINS >= 1");
-      const box3i *box = haveHistBox ? &histBox : nullptr;
-      interval<float> range(histRange[0], histRange[1]);
-      if (!haveHistRange) {
-        const ExaHipFieldStats r = renderer.fieldStats(histChannel, box);
-        if (!(r.min < r.max)) throw std::runtime_error("--histogram: the field is constant (or has no value) there: give --histogram-range lo hi");
-        range = interval<float>(r.min, r.max);
-      }
-      std::vector<uint64_t> cells, volume;
-      ExaHipFieldStats st;
-      renderer.computeHistogram(histChannel, range, histBins, cells, &volume, &st, box);
-      FILE *f = std::fopen(histName.c_str(), "w");
-      if (!f) throw std::runtime_error("cannot write " + histName);
-      for (size_t b = 0; b < cells.size(); b++) std::fprintf(f, "%llu %llu\n", (unsigned long long)cells[b], (unsigned long long)volume[b]);
-      if (std::fclose(f)) throw std::runtime_error("cannot write " + histName);
-      std::printf("histogram channel %d bins %d range %.9g %.9g slots %llu empty %llu nan %llu under %llu over %llu binned %llu\n", histChannel,
-                  histBins, range.lower, range.upper, (unsigned long long)st.slots, (unsigned long long)st.empty, (unsigned long long)st.nan,
-                  (unsigned long long)st.under, (unsigned long long)st.over, (unsigned long long)st.binned);
-    }
-    if (!streamName.empty()) {
-      std::vector<vec3f> seeds;
-      FILE *f = std::fopen(streamSeedsName.c_str(), "r");
-      if (!f) throw std::runtime_error("cannot read " + streamSeedsName);
-      char word[3][64];
-      int got;
-      while ((got = std::fscanf(f, "%63s %63s %63s", word[0], word[1], word[2])) == 3)     // strtof: nan and inf are seeds too
-        seeds.push_back(vec3f(std::strtof(word[0], nullptr), std::strtof(word[1], nullptr), std::strtof(word[2], nullptr)));
-      std::fclose(f);
-      if (got != EOF) throw std::runtime_error(streamSeedsName + ": a seed is three numbers `x y z`");
-      const Renderer::Streamlines L = renderer.streamlines(seeds.data(), seeds.size(), streamChannels, streamStep, streamMaxSteps,
-                                                           streamBoth || !streamBackward, streamBoth || streamBackward, streamNormalize);
-      f = std::fopen(streamName.c_str(), "w");
-      if (!f) throw std::runtime_error("cannot write " + streamName);
-      for (size_t i = 0; i < seeds.size(); i++) {
-        std::fprintf(f, "%u %d %d %llu", L.seedVertex[i], L.reason[2 * i], L.reason[2 * i + 1], (unsigned long long)(L.offset[i + 1] - L.offset[i]));
-        for (uint64_t v = L.offset[i]; v < L.offset[i + 1]; v++) std::fprintf(f, " %.9g %.9g %.9g", L.vertex[v].x, L.vertex[v].y, L.vertex[v].z);
-        std::fprintf(f, "\n");
-      }
-      if (std::fclose(f)) throw std::runtime_error("cannot write " + streamName);
-      std::printf("streamlines seeds %zu channels %d %d %d step %.9g maxSteps %d vertices %zu\n", seeds.size(), streamChannels.x,
-                  streamChannels.y, streamChannels.z, streamStep, streamMaxSteps, L.vertex.size());
-    }
-    if (!projectName.empty()) {
-      const ExaHipRays rays = renderer.cameraRays(size, 0.f, projectDt, projectSamples);
-      const Renderer::Projection P = renderer.project(rays, projectChannel, true, true);
-      std::vector<float> integral(P.sum.size());
-      size_t hit = 0;
-      for (size_t k = 0; k < integral.size(); k++) { integral[k] = float(P.sum[k] * double(projectDt)); hit += P.count[k] != 0; }
-      FILE *f = std::fopen(projectName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + projectName);
-      std::fprintf(f, "project %d %d channel %d dt %.9g samples %d\n", size.x, size.y, projectChannel, projectDt, projectSamples);
-      const size_t n = integral.size();
-      const bool ok = std::fwrite(integral.data(), 4, n, f) == n && std::fwrite(P.count.data(), 4, n, f) == n
-                   && std::fwrite(P.max.data(), 4, n, f) == n && std::fwrite(P.min.data(), 4, n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + projectName);
-      std::printf("project %d %d channel %d dt %.9g samples %d pixels_hit %zu\n", size.x, size.y, projectChannel, projectDt,
-                  projectSamples, hit);
-    }
-    if (!raycastName.empty()) {
-      const ExaHipRays rays = renderer.cameraRays(size, 0.f, raycastDt, raycastSamples);
-      const Renderer::IsoHits R = renderer.raycastIso(rays, raycastChannel, raycastIso, raycastRefine, true, true);
-      FILE *f = std::fopen(raycastName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + raycastName);
-      std::fprintf(f, "raycast %d %d channel %d iso %.9g dt %.9g samples %d refine %d\n", size.x, size.y, raycastChannel, raycastIso,
-                   raycastDt, raycastSamples, raycastRefine);
-      const size_t n = R.t.size();
-      const bool ok = std::fwrite(R.t.data(), 4, n, f) == n && std::fwrite(R.position.data(), 12, n, f) == n
-                   && std::fwrite(R.value.data(), 4, n, f) == n && std::fwrite(R.gradient.data(), 12, n, f) == n
-                   && std::fwrite(R.index.data(), 4, n, f) == n && std::fwrite(R.side.data(), 4, n, f) == n
-                   && std::fwrite(R.crossings.data(), 4, n, f) == n;
-      if (std::fclose(f) || !ok) throw std::runtime_error("cannot write " + raycastName);
-      size_t hit = 0;
-      for (int32_t k : R.index) hit += k >= 0;
-      std::printf("raycast %d %d channel %d iso %.9g dt %.9g samples %d refine %d pixels_hit %zu\n", size.x, size.y, raycastChannel,
-                  raycastIso, raycastDt, raycastSamples, raycastRefine, hit);
-    }
-    if (frames == 0 && (!resampleName.empty() || !isoName.empty() || !histName.empty() || !streamName.empty() || !projectName.empty()
-                        || !raycastName.empty() || !surfaceName.empty() || !linesName.empty() || !regionsName.empty() || !basinsName.empty()
-                        || !licName.empty() || !ftleName.empty() || !criticalName.empty())) return 0;
-    if (stats) {       // region statistics as Regions::buildFrom prints them, and the work counters of the first frame
-      renderer.updateDt(dt);
-      renderer.updateFrameID(0);
-      const ExaHipStats s = renderer.renderStats();
-      std::printf("regions %zu leafEntries %zu\n", renderer.numRegions, renderer.numLeafEntries);
-      std::printf("stats segments %llu samples %llu brick_visits %llu corner_loads %llu nodes_visited %llu\n",
-                  (unsigned long long)s.segments, (unsigned long long)s.samples, (unsigned long long)s.brick_visits,
-                  (unsigned long long)s.corner_loads, (unsigned long long)s.nodes_visited);
-    }
-    int accumID = 0;
-    double kernelMs = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!pipeline) {
-      for (int fr = 0; fr < frames; fr++) {                          // viewer.cpp:279-288
-        renderer.updateDt(dt);
-        renderer.updateFrameID(accumID);
-        if (pg) ++accumID;
-        renderer.render();
-        kernelMs += renderer.stats().kernel_ms;
-      }
-    } else {
-      // two device frames + two pinned host frames: the march of frame k+1 runs while frame k travels to the host
-      auto ok = [](hipError_t e, const char *what) { if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e)); };
-      ok(hipSetDevice(devices[0]), "hipSetDevice");
-      const size_t bytes = fb.size() * sizeof(uint32_t);
-      uint32_t *dev[2], *host[2];
-      hipStream_t march, copy;
-      hipEvent_t rendered[2], copied[2];
-      ok(hipStreamCreateWithFlags(&march, hipStreamNonBlocking), "hipStreamCreate");
-      ok(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking), "hipStreamCreate");
-      for (int k = 0; k < 2; k++) {
-        ok(hipMalloc((void **)&dev[k], bytes), "hipMalloc");
-        ok(hipHostMalloc((void **)&host[k], bytes, hipHostMallocDefault), "hipHostMalloc");
-        ok(hipEventCreateWithFlags(&rendered[k], hipEventDisableTiming), "hipEventCreate");
-        ok(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming), "hipEventCreate");
-      }
-      renderer.updateDt(dt);
-      renderer.updateFrameID(0);
-      renderer.render();                                   // one synchronous frame first: launch-order feedback
-      const auto t1 = std::chrono::steady_clock::now();
-      for (int fr = 0; fr < frames; fr++) {
-        const int k = fr & 1;
-        renderer.updateFrameID(accumID);
-        if (pg) ++accumID;
-        if (fr >= 2) ok(hipStreamWaitEvent(march, copied[k], 0), "hipStreamWaitEvent");   // buffer k has left the device
-        renderer.renderAsync(dev[k], march);
-        ok(hipEventRecord(rendered[k], march), "hipEventRecord");
-        ok(hipStreamWaitEvent(copy, rendered[k], 0), "hipStreamWaitEvent");
-        ok(hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, copy), "hipMemcpyAsync");
-        ok(hipEventRecord(copied[k], copy), "hipEventRecord");
-      }
-      ok(hipStreamSynchronize(copy), "hipStreamSynchronize");
-      ok(hipStreamSynchronize(march), "hipStreamSynchronize");
-      const double secP = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-      std::memcpy(fb.data(), host[(frames - 1) & 1], bytes);
-      kernelMs = renderer.stats().kernel_ms * frames;
-      std::printf("pipelined: %d frames in %.3f ms (%.3f ms per frame incl. copy to host)\n", frames, 1000.0 * secP, 1000.0 * secP / frames);
-      for (int k = 0; k < 2; k++) { (void)hipFree(dev[k]); (void)hipHostFree(host[k]); (void)hipEventDestroy(rendered[k]); (void)hipEventDestroy(copied[k]); }
-      (void)hipStreamDestroy(march); (void)hipStreamDestroy(copy);
-    }
-    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    std::printf("Avg. after %d frames: %.3f FPS (%.3f ms), kernel %.3f ms\n", frames, frames / sec, 1000.0 * sec / frames, kernelMs / frames);
-    if (!outName.empty()) {
-      FILE *f = std::fopen(outName.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot write " + outName);
-      std::fprintf(f, "P6\n%d %d\n255\n", size.x, size.y);
-      for (int y = size.y - 1; y >= 0; y--)
-        for (int x = 0; x < size.x; x++) { const uint32_t p = fb[size_t(y) * size.x + x]; const unsigned char rgb[3] = { (unsigned char)(p & 255), (unsigned char)((p >> 8) & 255), (unsigned char)((p >> 16) & 255) }; std::fwrite(rgb, 1, 3, f); }
-      std::fclose(f);
-    }
+    std::vector<uint32_t> fb(size_t(fo.size.x) * fo.size.y);
+    if (fo.devices.empty()) fo.devices.push_back(0);
+    Renderer renderer(config->bricks.sp, config->surfaces, config->scalarFields, fo.devices);  // viewer.cpp:1256-1260
+    setupRenderer(renderer, fo, *config, bounds, fb);
+    const bool anyOutput = writeOutputs(o, renderer);
+    if (fo.frames == 0 && anyOutput) return 0;
+    renderFrames(renderer, fo, fb);
     return 0;
   } catch (const std::exception &e) {
     std::cerr << "Fatal error " << e.what() << std::endl;

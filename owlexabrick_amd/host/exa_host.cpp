@@ -2,6 +2,7 @@
 #include "exa_host.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -540,29 +541,88 @@ ExaHipStats Renderer::renderStats()
 
 void Renderer::setOption(const std::string &key, int value) { check(exa_hip_set_option(handle, key.c_str(), value), handle); }
 
+// ---- the analysis calls.  What they hand the ABI alike: the space flag, a box with its lattice, three channels, the field
+
+static int spaceFlag(bool worldSpace) { return worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0; }
+
+static std::array<int32_t, 3> chan3(vec3i channels) { return { channels.x, channels.y, channels.z }; }
+
+namespace {
+struct Lattice {
+  float lo[3], hi[3];
+  int32_t d[3];
+  Lattice(const box3f &b, vec3i dims) : lo{ b.lower.x, b.lower.y, b.lower.z }, hi{ b.upper.x, b.upper.y, b.upper.z }, d{ dims.x, dims.y, dims.z } {}
+};
+// a channel, or a quantity of the vector field of three channels: which of an ABI call and its ..._derived twin to make
+struct Field {
+  bool derived;
+  int32_t channel, quantity;
+  std::array<int32_t, 3> ch;
+  Field(int channel) : derived(false), channel(channel), quantity(0), ch{} {}
+  Field(vec3i channels, int quantity) : derived(true), channel(0), quantity(quantity), ch(chan3(channels)) {}
+};
+} // namespace
+
+// the elements of a result on an image or on a lattice, 0 for a size the module refuses (it checks the size)
+static size_t imagePixels(int width, int height)
+{
+  return width > 0 && height > 0 && uint64_t(width) * uint64_t(height) <= uint64_t(INT32_MAX) ? size_t(width) * size_t(height) : 0;
+}
+
+static size_t latticePoints(vec3i dims)
+{
+  return dims.z > 0 && uint64_t(imagePixels(dims.x, dims.y)) * uint64_t(dims.z) <= uint64_t(INT32_MAX)
+             ? imagePixels(dims.x, dims.y) * size_t(dims.z) : 0;
+}
+
 void Renderer::samplePoints(const vec3f *points, size_t n, const int *channels, int numChannels, float *values,
                             float *gradients, int *status, bool worldSpace, bool normalized, float fill)
 {
   static_assert(sizeof(vec3f) == 3 * sizeof(float), "points are 3 floats each");
   if (worldSpace) pushState();
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0)
+  const int flags = spaceFlag(worldSpace) | (gradients ? EXA_SAMPLE_GRADIENT : 0)
                   | (gradients && normalized ? EXA_SAMPLE_GRADIENT_NORMALIZED : 0);
   check(exa_hip_sample_points(handle, reinterpret_cast<const float *>(points), n, channels, numChannels, flags, fill, values,
                               gradients, status, 0, nullptr, 0), handle);
 }
 
+void Renderer::sampleDerived(const vec3f *points, size_t n, vec3i channels, int quantity, float *out, int *status,
+                             bool worldSpace, float fill)
+{
+  if (worldSpace) pushState();
+  check(exa_hip_sample_derived(handle, reinterpret_cast<const float *>(points), n, chan3(channels).data(), quantity,
+                               spaceFlag(worldSpace), fill, out, status, 0, nullptr, 0), handle);
+}
+
+static void resampleField(ExaHipRenderer *handle, const box3f &box, vec3i dims, const Field &f, float *out, bool worldSpace, float fill)
+{
+  const Lattice L(box, dims);
+  const int flags = spaceFlag(worldSpace);
+  check(f.derived ? exa_hip_resample_derived(handle, L.lo, L.hi, L.d, f.ch.data(), f.quantity, flags, fill, out, 0, nullptr, 0)
+                  : exa_hip_resample(handle, L.lo, L.hi, L.d, f.channel, flags, fill, out, 0, nullptr, 0), handle);
+}
+
 void Renderer::resample(const box3f &box, vec3i dims, int channel, float *out, bool worldSpace, float fill)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z };
-  check(exa_hip_resample(handle, lo, hi, d, channel, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, 0, nullptr, 0), handle);
+  resampleField(handle, box, dims, Field(channel), out, worldSpace, fill);
 }
 
-// the mesh of the last extraction (exa_hip_isosurface or exa_hip_isosurface_derived) out of the module, which then drops it
-// (unless it is to keep it)
-static TriangleMesh::SP readIsoMesh(ExaHipRenderer *handle, uint64_t nv, uint64_t nt, std::vector<vec3f> *gradients, bool keep = false)
+void Renderer::resampleDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float *out, bool worldSpace, float fill)
 {
+  if (worldSpace) pushState();
+  resampleField(handle, box, dims, Field(channels, quantity), out, worldSpace, fill);
+}
+
+// extracts, then takes the mesh out of the module, which drops it (unless it is to keep it)
+static TriangleMesh::SP isoSurfaceOf(ExaHipRenderer *handle, const box3f &box, vec3i dims, const Field &f, float iso, bool worldSpace,
+                                     std::vector<vec3f> *gradients, bool keep)
+{
+  const Lattice L(box, dims);
+  const int flags = spaceFlag(worldSpace) | (gradients ? EXA_SAMPLE_GRADIENT : 0);
+  uint64_t nv = 0, nt = 0;
+  check(f.derived ? exa_hip_isosurface_derived(handle, L.lo, L.hi, L.d, f.ch.data(), f.quantity, iso, flags, &nv, &nt, nullptr)
+                  : exa_hip_isosurface(handle, L.lo, L.hi, L.d, f.channel, iso, flags, &nv, &nt, nullptr), handle);
   auto mesh = std::make_shared<TriangleMesh>();
   mesh->vertex.resize(nv);
   mesh->index.resize(nt);
@@ -578,106 +638,73 @@ TriangleMesh::SP Renderer::extractIsoSurface(const box3f &box, vec3i dims, int c
                                              std::vector<vec3f> *gradients, bool keep)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z };
-  uint64_t nv = 0, nt = 0;
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0);
-  check(exa_hip_isosurface(handle, lo, hi, d, channel, iso, flags, &nv, &nt, nullptr), handle);
-  return readIsoMesh(handle, nv, nt, gradients, keep);
-}
-
-void Renderer::sampleDerived(const vec3f *points, size_t n, vec3i channels, int quantity, float *out, int *status,
-                             bool worldSpace, float fill)
-{
-  if (worldSpace) pushState();
-  const int32_t ch[3] = { channels.x, channels.y, channels.z };
-  check(exa_hip_sample_derived(handle, reinterpret_cast<const float *>(points), n, ch, quantity,
-                               worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, status, 0, nullptr, 0), handle);
-}
-
-void Renderer::resampleDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float *out, bool worldSpace, float fill)
-{
-  if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
-  check(exa_hip_resample_derived(handle, lo, hi, d, ch, quantity, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, fill, out, 0, nullptr, 0),
-        handle);
+  return isoSurfaceOf(handle, box, dims, Field(channel), iso, worldSpace, gradients, keep);
 }
 
 TriangleMesh::SP Renderer::extractIsoSurfaceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso,
                                                     bool worldSpace, bool keep)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
-  uint64_t nv = 0, nt = 0;
-  check(exa_hip_isosurface_derived(handle, lo, hi, d, ch, quantity, iso, worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0, &nv, &nt, nullptr),
-        handle);
-  return readIsoMesh(handle, nv, nt, nullptr, keep);
-}
-
-// the regions of the last exa_hip_regions or exa_hip_regions_derived out of the module, which then drops them
-static Renderer::Regions readRegions(ExaHipRenderer *handle, vec3i dims, uint64_t numRegions, uint64_t numInside, int32_t sumExponent,
-                                     bool values)
-{
-  Renderer::Regions R;
-  const size_t n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
-  R.dims = dims;
-  R.numInside = numInside;
-  R.sumExponent = sumExponent;
-  R.labels.resize(n);
-  R.regions.resize(numRegions);
-  if (values) R.values.resize(n);
-  check(exa_hip_regions_read(handle, R.labels.data(), R.regions.data(), values ? R.values.data() : nullptr, 0, nullptr), handle);
-  check(exa_hip_regions_release(handle), handle);
-  return R;
+  return isoSurfaceOf(handle, box, dims, Field(channels, quantity), iso, worldSpace, nullptr, keep);
 }
 
 static int regionFlags(bool worldSpace, bool below, bool faces, bool values)
 {
-  return (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (below ? EXA_REGIONS_BELOW : 0) | (faces ? EXA_REGIONS_FACES : 0) |
-         (values ? EXA_REGIONS_KEEP_VALUES : 0);
+  return spaceFlag(worldSpace) | (below ? EXA_REGIONS_BELOW : 0) | (faces ? EXA_REGIONS_FACES : 0) | (values ? EXA_REGIONS_KEEP_VALUES : 0);
+}
+
+// the arrays of Regions or Basins for the module's read call: the labels and (if kept) the values of the lattice, the table
+template <class Labelling, class Record>
+static void sizeLabelling(Labelling &out, std::vector<Record> &table, vec3i dims, uint64_t count, bool values)
+{
+  const size_t n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
+  out.dims = dims;
+  out.labels.resize(n);
+  table.resize(count);
+  if (values) out.values.resize(n);
+}
+
+// labels, then takes the regions out of the module, which drops them
+static Renderer::Regions regionsOf(ExaHipRenderer *handle, const box3f &box, vec3i dims, const Field &f, float iso, int flags)
+{
+  const Lattice L(box, dims);
+  const bool values = flags & EXA_REGIONS_KEEP_VALUES;
+  Renderer::Regions R;
+  uint64_t nr = 0;
+  check(f.derived ? exa_hip_regions_derived(handle, L.lo, L.hi, L.d, f.ch.data(), f.quantity, iso, flags, &nr, &R.numInside, &R.sumExponent, nullptr)
+                  : exa_hip_regions(handle, L.lo, L.hi, L.d, f.channel, iso, flags, &nr, &R.numInside, &R.sumExponent, nullptr), handle);
+  sizeLabelling(R, R.regions, dims, nr, values);
+  check(exa_hip_regions_read(handle, R.labels.data(), R.regions.data(), values ? R.values.data() : nullptr, 0, nullptr), handle);
+  check(exa_hip_regions_release(handle), handle);
+  return R;
 }
 
 Renderer::Regions Renderer::regions(const box3f &box, vec3i dims, int channel, float iso, bool worldSpace, bool below, bool faces,
                                     bool values)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z };
-  uint64_t nr = 0, ni = 0;
-  int32_t se = 0;
-  check(exa_hip_regions(handle, lo, hi, d, channel, iso, regionFlags(worldSpace, below, faces, values), &nr, &ni, &se, nullptr), handle);
-  return readRegions(handle, dims, nr, ni, se, values);
+  return regionsOf(handle, box, dims, Field(channel), iso, regionFlags(worldSpace, below, faces, values));
 }
 
 Renderer::Regions Renderer::regionsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, bool worldSpace,
                                            bool below, bool faces, bool values)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
-  uint64_t nr = 0, ni = 0;
-  int32_t se = 0;
-  check(exa_hip_regions_derived(handle, lo, hi, d, ch, quantity, iso, regionFlags(worldSpace, below, faces, values), &nr, &ni, &se,
-                                nullptr), handle);
-  return readRegions(handle, dims, nr, ni, se, values);
+  return regionsOf(handle, box, dims, Field(channels, quantity), iso, regionFlags(worldSpace, below, faces, values));
 }
 
-// the basins of the last exa_hip_basins or exa_hip_basins_derived out of the module, which then drops them
-static Renderer::Basins readBasins(ExaHipRenderer *handle, vec3i dims, uint64_t numBasins, uint64_t numRaw, uint64_t numInside,
-                                   int32_t sumExponent, int32_t rounds, bool values)
+// the same for the basins
+static Renderer::Basins basinsOf(ExaHipRenderer *handle, const box3f &box, vec3i dims, const Field &f, float iso, float minDepth, int flags)
 {
+  const Lattice L(box, dims);
+  const bool values = flags & EXA_REGIONS_KEEP_VALUES;
   Renderer::Basins B;
-  const size_t n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
-  B.dims = dims;
-  B.numInside = numInside;
-  B.numRaw = numRaw;
-  B.sumExponent = sumExponent;
-  B.rounds = rounds;
-  B.labels.resize(n);
-  B.basins.resize(numBasins);
-  if (values) B.values.resize(n);
+  uint64_t nb = 0;
+  check(f.derived ? exa_hip_basins_derived(handle, L.lo, L.hi, L.d, f.ch.data(), f.quantity, iso, minDepth, flags, &nb, &B.numRaw,
+                                           &B.numInside, &B.sumExponent, &B.rounds, nullptr)
+                  : exa_hip_basins(handle, L.lo, L.hi, L.d, f.channel, iso, minDepth, flags, &nb, &B.numRaw, &B.numInside,
+                                   &B.sumExponent, &B.rounds, nullptr), handle);
+  sizeLabelling(B, B.basins, dims, nb, values);
   check(exa_hip_basins_read(handle, B.labels.data(), B.basins.data(), values ? B.values.data() : nullptr, 0, nullptr), handle);
   check(exa_hip_basins_release(handle), handle);
   return B;
@@ -687,38 +714,25 @@ Renderer::Basins Renderer::basins(const box3f &box, vec3i dims, int channel, flo
                                   bool faces, bool values)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z };
-  uint64_t nb = 0, nr = 0, ni = 0;
-  int32_t se = 0, rounds = 0;
-  check(exa_hip_basins(handle, lo, hi, d, channel, iso, minDepth, regionFlags(worldSpace, below, faces, values), &nb, &nr, &ni, &se,
-                       &rounds, nullptr), handle);
-  return readBasins(handle, dims, nb, nr, ni, se, rounds, values);
+  return basinsOf(handle, box, dims, Field(channel), iso, minDepth, regionFlags(worldSpace, below, faces, values));
 }
 
 Renderer::Basins Renderer::basinsDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, float minDepth,
                                          bool worldSpace, bool below, bool faces, bool values)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
-  uint64_t nb = 0, nr = 0, ni = 0;
-  int32_t se = 0, rounds = 0;
-  check(exa_hip_basins_derived(handle, lo, hi, d, ch, quantity, iso, minDepth, regionFlags(worldSpace, below, faces, values), &nb, &nr,
-                               &ni, &se, &rounds, nullptr), handle);
-  return readBasins(handle, dims, nb, nr, ni, se, rounds, values);
+  return basinsOf(handle, box, dims, Field(channels, quantity), iso, minDepth, regionFlags(worldSpace, below, faces, values));
 }
 
 Renderer::CriticalPoints Renderer::criticalPoints(const box3f &box, vec3i dims, vec3i channels, int iterations, float tolerance,
                                                   bool worldSpace, bool probe)
 {
   if (worldSpace) pushState();
-  const float lo[3] = { box.lower.x, box.lower.y, box.lower.z }, hi[3] = { box.upper.x, box.upper.y, box.upper.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
+  const Lattice L(box, dims);
   CriticalPoints P;
   uint64_t n = 0;
-  check(exa_hip_critical_points(handle, lo, hi, d, ch, iterations, tolerance,
-                                (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (probe ? EXA_CRITICAL_PROBE : 0), &n, &P.stats, nullptr), handle);
+  check(exa_hip_critical_points(handle, L.lo, L.hi, L.d, chan3(channels).data(), iterations, tolerance,
+                                spaceFlag(worldSpace) | (probe ? EXA_CRITICAL_PROBE : 0), &n, &P.stats, nullptr), handle);
   P.points.resize(n);
   if (probe) { P.probe.resize(12 * n); P.probeStatus.resize(3 * n); }
   check(exa_hip_critical_points_read(handle, P.points.data(), probe ? P.probe.data() : nullptr, probe ? P.probeStatus.data() : nullptr, 0,
@@ -727,17 +741,28 @@ Renderer::CriticalPoints Renderer::criticalPoints(const box3f &box, vec3i dims, 
   return P;
 }
 
-// the lines of the last extraction (exa_hip_isolines or exa_hip_isolines_derived) out of the module, which then drops them
-static Renderer::Isolines readIsolines(ExaHipRenderer *handle, uint64_t nv, uint64_t ns, size_t levels, bool gradients, size_t values)
+static ExaHipPlane planeOf(vec3f origin, vec3f du, vec3f dv, vec2i size)
 {
+  return ExaHipPlane{ { origin.x, origin.y, origin.z }, { du.x, du.y, du.z }, { dv.x, dv.y, dv.z }, size.x, size.y };
+}
+
+// extracts, then takes the lines out of the module, which drops them
+static Renderer::Isolines isolinesOf(ExaHipRenderer *handle, const ExaHipPlane &plane, const std::vector<float> &isos, const Field &f,
+                                     bool worldSpace, bool gradients, bool values)
+{
+  const int flags = spaceFlag(worldSpace) | (gradients ? EXA_SAMPLE_GRADIENT : 0) | (values ? EXA_ISOLINES_KEEP_VALUES : 0);
+  const int32_t levels = (int32_t)isos.size();
+  uint64_t nv = 0, ns = 0;
+  check(f.derived ? exa_hip_isolines_derived(handle, &plane, f.ch.data(), f.quantity, isos.data(), levels, flags, &nv, &ns, nullptr)
+                  : exa_hip_isolines(handle, &plane, f.channel, isos.data(), levels, flags, &nv, &ns, nullptr), handle);
   Renderer::Isolines L;
   L.vertex.resize(nv);
   L.uv.resize(2 * nv);
   L.segment.resize(2 * ns);
-  L.vertexOffsets.resize(levels + 1);
-  L.segmentOffsets.resize(levels + 1);
+  L.vertexOffsets.resize(isos.size() + 1);
+  L.segmentOffsets.resize(isos.size() + 1);
   if (gradients) L.gradient.resize(nv);
-  L.values.resize(values);
+  if (values) L.values.resize(size_t(plane.nu) * size_t(plane.nv));
   check(exa_hip_isolines_read(handle, reinterpret_cast<float *>(L.vertex.data()), L.uv.data(),
                               gradients ? reinterpret_cast<float *>(L.gradient.data()) : nullptr, L.segment.data(),
                               L.vertexOffsets.data(), L.segmentOffsets.data(), values ? L.values.data() : nullptr, 0, nullptr), handle);
@@ -745,32 +770,18 @@ static Renderer::Isolines readIsolines(ExaHipRenderer *handle, uint64_t nv, uint
   return L;
 }
 
-static ExaHipPlane planeOf(vec3f origin, vec3f du, vec3f dv, vec2i size)
-{
-  return ExaHipPlane{ { origin.x, origin.y, origin.z }, { du.x, du.y, du.z }, { dv.x, dv.y, dv.z }, size.x, size.y };
-}
-
 Renderer::Isolines Renderer::isolines(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos, int channel,
                                       bool worldSpace, bool gradients, bool values)
 {
   if (worldSpace) pushState();
-  const ExaHipPlane plane = planeOf(origin, du, dv, size);
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (gradients ? EXA_SAMPLE_GRADIENT : 0) | (values ? EXA_ISOLINES_KEEP_VALUES : 0);
-  uint64_t nv = 0, ns = 0;
-  check(exa_hip_isolines(handle, &plane, channel, isos.data(), (int32_t)isos.size(), flags, &nv, &ns, nullptr), handle);
-  return readIsolines(handle, nv, ns, isos.size(), gradients, values ? size_t(size.x) * size_t(size.y) : 0);
+  return isolinesOf(handle, planeOf(origin, du, dv, size), isos, Field(channel), worldSpace, gradients, values);
 }
 
 Renderer::Isolines Renderer::isolinesDerived(vec3f origin, vec3f du, vec3f dv, vec2i size, const std::vector<float> &isos,
                                              vec3i channels, int quantity, bool worldSpace, bool values)
 {
   if (worldSpace) pushState();
-  const ExaHipPlane plane = planeOf(origin, du, dv, size);
-  const int32_t ch[3] = { channels.x, channels.y, channels.z };
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (values ? EXA_ISOLINES_KEEP_VALUES : 0);
-  uint64_t nv = 0, ns = 0;
-  check(exa_hip_isolines_derived(handle, &plane, ch, quantity, isos.data(), (int32_t)isos.size(), flags, &nv, &ns, nullptr), handle);
-  return readIsolines(handle, nv, ns, isos.size(), false, values ? size_t(size.x) * size_t(size.y) : 0);
+  return isolinesOf(handle, planeOf(origin, du, dv, size), isos, Field(channels, quantity), worldSpace, false, values);
 }
 
 void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
@@ -799,9 +810,8 @@ Renderer::Streamlines Renderer::streamlines(const vec3f *seeds, size_t n, vec3i 
   static_assert(sizeof(vec3f) == 3 * sizeof(float), "seeds are 3 floats each");
   const int flags = (forward ? EXA_STREAM_FORWARD : 0) | (backward ? EXA_STREAM_BACKWARD : 0)
                   | (normalize ? EXA_STREAM_NORMALIZE : 0) | (velocities ? EXA_STREAM_VELOCITIES : 0);
-  const int32_t ch[3] = { channels.x, channels.y, channels.z };
   uint64_t nv = 0;
-  check(exa_hip_streamlines(handle, reinterpret_cast<const float *>(seeds), n, ch, step, maxSteps, flags, &nv, nullptr), handle);
+  check(exa_hip_streamlines(handle, reinterpret_cast<const float *>(seeds), n, chan3(channels).data(), step, maxSteps, flags, &nv, nullptr), handle);
   Streamlines L;
   L.vertex.resize(nv);
   if (velocities) L.velocity.resize(nv);
@@ -820,28 +830,21 @@ Renderer::Lic Renderer::lic(vec3f origin, vec3f du, vec3f dv, vec2i size, vec3i 
                             const uint8_t *noise, uint32_t seed, float fill)
 {
   const ExaHipPlane plane = planeOf(origin, du, dv, size);
-  const int32_t ch[3] = { channels.x, channels.y, channels.z };
-  // 0 pixels for a size the module refuses (it checks the size)
-  const size_t n = size.x > 0 && size.y > 0 && uint64_t(size.x) * uint64_t(size.y) <= uint64_t(INT32_MAX) ? size_t(size.x) * size_t(size.y) : 0;
+  const size_t n = imagePixels(size.x, size.y);
   Lic L;
   L.lic.resize(n); L.speed.resize(n); L.sum.resize(n); L.count.resize(n); L.reason.resize(2 * n);
-  check(exa_hip_lic(handle, &plane, ch, step, halfLength, noise, seed, 0, fill, L.lic.data(), L.sum.data(), L.count.data(),
+  check(exa_hip_lic(handle, &plane, chan3(channels).data(), step, halfLength, noise, seed, 0, fill, L.lic.data(), L.sum.data(), L.count.data(),
                     L.speed.data(), L.reason.data(), 0, nullptr), handle);
   return L;
 }
 
 Renderer::Flowmap Renderer::flowmap(vec3f lo, vec3f hi, vec3i dims, vec3i channels, float step, int numSteps, bool backward, float fill)
 {
-  const float l[3] = { lo.x, lo.y, lo.z }, u[3] = { hi.x, hi.y, hi.z };
-  const int32_t d[3] = { dims.x, dims.y, dims.z }, ch[3] = { channels.x, channels.y, channels.z };
-  // 0 points for dims the module refuses (it checks them)
-  size_t n = 0;
-  if (dims.x > 0 && dims.y > 0 && dims.z > 0 && uint64_t(dims.x) * uint64_t(dims.y) <= uint64_t(INT32_MAX)
-      && uint64_t(dims.x) * uint64_t(dims.y) * uint64_t(dims.z) <= uint64_t(INT32_MAX))
-    n = size_t(dims.x) * size_t(dims.y) * size_t(dims.z);
+  const Lattice L(box3f(lo, hi), dims);
+  const size_t n = latticePoints(dims);
   Flowmap M;
   M.end.resize(n); M.steps.resize(n); M.reason.resize(n); M.stretch.resize(n); M.ftle.resize(n);
-  check(exa_hip_flowmap(handle, l, u, d, ch, step, numSteps, backward ? EXA_FLOWMAP_BACKWARD : EXA_FLOWMAP_FORWARD, fill,
+  check(exa_hip_flowmap(handle, L.lo, L.hi, L.d, chan3(channels).data(), step, numSteps, backward ? EXA_FLOWMAP_BACKWARD : EXA_FLOWMAP_FORWARD, fill,
                         reinterpret_cast<float *>(M.end.data()), M.steps.data(), M.reason.data(), M.stretch.data(), 0, nullptr), handle);
   // FTLE = log(stretch) / (2 |T|) in double, rounded once; fill where the stretch holds the bits of fill
   const double twoT = 2.0 * double(numSteps) * double(step);
@@ -854,20 +857,13 @@ Renderer::Flowmap Renderer::flowmap(vec3f lo, vec3f hi, vec3i dims, vec3i channe
   return M;
 }
 
-// the pixels of the rays' image, 0 for a size the module refuses (it checks the size)
-static size_t rayPixels(const ExaHipRays &rays)
-{
-  return rays.width > 0 && rays.height > 0 && uint64_t(rays.width) * uint64_t(rays.height) <= uint64_t(INT32_MAX)
-             ? size_t(rays.width) * size_t(rays.height) : 0;
-}
-
 Renderer::Projection Renderer::project(const ExaHipRays &rays, int channel, bool worldSpace, bool normalize)
 {
   if (worldSpace) pushState();
   Projection P;
-  const size_t n = rayPixels(rays);
+  const size_t n = imagePixels(rays.width, rays.height);
   P.sum.resize(n); P.count.resize(n); P.max.resize(n); P.min.resize(n); P.maxIndex.resize(n);
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
+  const int flags = spaceFlag(worldSpace) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
   check(exa_hip_project(handle, &rays, channel, flags, P.sum.data(), P.count.data(), P.max.data(), P.min.data(),
                         P.maxIndex.data(), 0, nullptr), handle);
   return P;
@@ -879,9 +875,9 @@ Renderer::IsoHits Renderer::raycastIso(const ExaHipRays &rays, int channel, floa
   static_assert(sizeof(vec3f) == 3 * sizeof(float), "positions and gradients are 3 floats each");
   if (worldSpace) pushState();
   IsoHits R;
-  const size_t n = rayPixels(rays);
+  const size_t n = imagePixels(rays.width, rays.height);
   R.t.resize(n); R.value.resize(n); R.position.resize(n); R.gradient.resize(n); R.index.resize(n); R.side.resize(n); R.crossings.resize(n);
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
+  const int flags = spaceFlag(worldSpace) | (normalize ? EXA_PROJECT_NORMALIZE : 0);
   check(exa_hip_raycast_iso(handle, &rays, channel, iso, refine, flags, fill, R.t.data(), reinterpret_cast<float *>(R.position.data()),
                             R.value.data(), reinterpret_cast<float *>(R.gradient.data()), R.index.data(), R.side.data(),
                             R.crossings.data(), 0, nullptr), handle);
@@ -897,7 +893,7 @@ static Renderer::SurfaceSamples sampleSurface(ExaHipRenderer *handle, const Tria
   S.numChannels = numChannels;
   const size_t nc = numChannels > 0 && numChannels <= EXA_SURFACE_MAX_CHANNELS ? size_t(numChannels) : 0;   // the module checks it
   S.sum.resize(numTriangles * nc); S.count.resize(numTriangles * nc); S.areaNormal.resize(numTriangles); S.subdiv.resize(numTriangles);
-  const int flags = (worldSpace ? EXA_SAMPLE_WORLD_SPACE : 0) | (mesh ? 0 : EXA_SURFACE_FROM_ISOSURFACE);
+  const int flags = spaceFlag(worldSpace) | (mesh ? 0 : EXA_SURFACE_FROM_ISOSURFACE);
   std::vector<int32_t> ch(channels, channels + nc);
   check(exa_hip_sample_triangles(handle, mesh ? reinterpret_cast<const float *>(mesh->vertex.data()) : nullptr, mesh ? mesh->vertex.size() : 0,
                                  mesh ? reinterpret_cast<const int32_t *>(mesh->index.data()) : nullptr, mesh ? mesh->index.size() : 0,
