@@ -775,6 +775,104 @@ int exa_hip_histogram(ExaHipRenderer *, int32_t channel, float lo, float hi, int
 /* the device time of the last exa_hip_histogram's kernel in ms (0 after a call with an empty box, or before any) */
 int exa_hip_histogram_ms(ExaHipRenderer *, float *ms);
 
+/* ---- profiles and phase plots: the points of a lattice binned by one or two keys (a field, a derived quantity, the radius
+ * about a centre, a coordinate, or the labels of exa_hip_regions / exa_hip_basins), with the count, the exact sums and the
+ * min / max of up to four other quantities per bin, optionally weighted — the mean pressure inside every vortex, the fall-off
+ * of a field with radius, the joint distribution of two quantities, the mean of one field binned by another, as a table of
+ * a few kilobytes instead of a lattice per quantity.  New relative to the reference.  Every output is an integer or a float
+ * bit pattern that depends on no schedule: two runs give the same bytes. ----
+ *
+ * Lattice and positions.  lo, hi, dims (each >= 1, nx*ny*nz <= 2^31 - 1) and EXA_SAMPLE_WORLD_SPACE as for exa_hip_resample.
+ * Linear index L = (k*ny + j)*nx + i.  P(L) is the lattice position in the caller's space, per axis
+ * lo + (float(i) + 0.5f) * ((hi - lo) / float(n)) in float32, nothing contracted: what exa_hip_resample forms before any world
+ * mapping.
+ *
+ * Sources.  EXA_SOURCE_CHANNEL: V(L) = what exa_hip_resample(lo, hi, dims, channels[0], the same flag, fill = NaN) returns,
+ * bit for bit, in the handle's current basis_form.  EXA_SOURCE_DERIVED: what exa_hip_resample_derived(channels, quantity, ...)
+ * returns (one-component quantities only).  EXA_SOURCE_RADIUS: d = P - centre per component, sqrtf((d.x*d.x + d.y*d.y) +
+ * d.z*d.z), every operation rounded separately.  EXA_SOURCE_COORDINATE: P[channels[0]], channels[0] in 0..2.  The last two
+ * are formed in the kernels from (i, j, k) and take no memory.  The fields a kind does not name are ignored.  Identical
+ * channel / derived sources are evaluated once.
+ *
+ * Bins.  B = axes[0].numBins (x axes[1].numBins), bin index b1 * axes[0].numBins + b0, 1 <= B <= EXA_PROFILE_MAX_BINS.
+ * Uniform axis (edges == NULL, labels == NULL): exa_hip_histogram's rule, t = (v - lo) * (float(numBins) / (hi - lo)) in
+ * float32, every operation rounded separately, bin = min(numBins - 1, (int)t); under: v < lo, over: v > hi; lo and hi finite,
+ * lo < hi, hi - lo and float(numBins) / (hi - lo) finite in float32.  Edges axis: numBins + 1 strictly ascending finite
+ * floats; bin b holds edges[b] <= v < edges[b+1], the last bin also v == edges[numBins]; under: v < edges[0], over:
+ * v > edges[numBins] — logarithmic or any other spacing, exactly; no transcendental function is evaluated on the device.
+ * Label axis (labels != NULL, the first axis only; the axis' source is ignored): bin = labels[L], numBins = the number of
+ * labels, a label < 0 puts the point outside.  A label >= numBins is an error, found on the device: the call fails with a
+ * message that names the smallest such L and returns no result.  labels is host memory, or with EXA_PROFILE_LABELS_DEVICE
+ * memory of the handle's first device (what exa_hip_regions_read hands out with pointersAreDevice).
+ *
+ * Classes, tested in this order per lattice point.  outside: the label is < 0.  invalid: a key value is NaN, or the weight,
+ * a value or a term (below) is not finite.  under / over: the first axis, in axis order, on which the key is out of range
+ * takes the count; +-Inf keys are under / over.  binned: everything else.  points = the sum of all of them.
+ *
+ * Per bin.  count.  With a weight w the terms are w and float32(w * v_f), one float32 product, nothing contracted: sumWeight
+ * accumulates q(w), sums[f] q(w * v_f).  Without a weight the term is v_f and sums[f] accumulates q(v_f).  A point whose
+ * product overflows float32 is invalid (w and v_f are finite, their term is not).  mins[f] / maxs[f] over the unweighted v_f
+ * by the ordered 32-bit key of exa_hip_histogram's value range (-0.0 < +0.0); +INFINITY / -INFINITY in an empty bin.
+ * q is the Sum rule of exa_hip_regions, per series (the weight's, then each value's): M = max |term| over the binned points of
+ * the call; exponent s = 0 if there is no binned point or M == 0, else s = 30 - e with M = f * 2^e, f in [0.5, 1);
+ * q(v) = (double)v * 2^s rounded to the nearest integer, ties to even, summed in 64-bit integers.  A series' sum is
+ * fixed * 2^-s; stats.weightExponent and stats.valueExponent[f] are the s (0 for a series the call does not have).
+ *
+ * Outputs.  Host memory: count B, sumWeight B, sums numValues x B, mins / maxs numValues x B (both or neither; neither skips
+ * the keys).  sumWeight is given exactly when there is a weight.  stats.ldsTable says which variant of the accumulate pass
+ * ran (1: the table privatised in LDS per workgroup; 0: atomics to the table in HBM); the choice hangs on B and numValues
+ * alone and does not change a byte of the result.
+ *
+ * Independence.  The result depends only on the scene, the lattice, the axes, values and weight, basis_form and (world space)
+ * the transform — on nothing a frame sets, nor on walk, accel, brick_order, interleave, sample_patch or sample_uniform.
+ *
+ * Calls.  Synchronous on hipStream.  A multi-device handle runs on devices[0]; a pending brick_order change is applied
+ * first.  Whatever exa_hip_resample[_derived] refuses for a channel / derived source (no kd tree, world space before a frame
+ * state, a bad channel or quantity) is refused here with this function's name in front.  Further errors, each with a message
+ * that starts with the function's name and leaves the handle usable: a NULL lo, hi, dims, axes or count; a box that is not
+ * finite with lo < hi; dims < 1; too many points; numAxes not 1 or 2; labels on the second axis; numValues outside
+ * 0..EXA_PROFILE_MAX_VALUES or NULL values / sums with numValues > 0; an unknown source kind, a coordinate axis outside 0..2,
+ * a centre that is not finite; a quantity of more than one component; numBins < 1, the range errors of exa_hip_histogram,
+ * edges that are not finite or not strictly ascending; B out of range; sumWeight without a weight or a weight without it;
+ * only one of mins / maxs; unknown flag bits; a label >= numBins; a failed allocation.  The kd descent's loop guard returns 3.
+ * exa_hip_profile_stage_ms: device ms of the last call's stages — values (the resampled sources), classify, accumulate,
+ * finish.
+ *
+ * Memory.  While the call runs: 4 bytes per lattice point and distinct channel / derived source, 4 per point for the bin
+ * indices, 4 per point for labels that came from the host; per bin 8 for the count, 8 per series (weight, values) and 8 per
+ * value with mins / maxs; 4 per edge.  Nothing is kept afterwards. */
+#define EXA_SOURCE_CHANNEL    0  /* V = exa_hip_resample(lo, hi, dims, channels[0], world?, fill = NaN)            */
+#define EXA_SOURCE_DERIVED    1  /* V = exa_hip_resample_derived(channels, quantity, ...); one-component only      */
+#define EXA_SOURCE_RADIUS     2  /* d = P - centre per component; sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z)              */
+#define EXA_SOURCE_COORDINATE 3  /* P[channels[0]], channels[0] in 0..2                                            */
+typedef struct ExaHipSource { int32_t kind; int32_t channels[3]; int32_t quantity; float centre[3]; } ExaHipSource;
+
+typedef struct ExaHipProfileAxis {
+  ExaHipSource   source;     /* ignored when labels != NULL */
+  int32_t        numBins;
+  float          lo, hi;     /* uniform bins, used when edges == NULL && labels == NULL */
+  const float   *edges;      /* numBins + 1 strictly ascending finite floats, or NULL (host memory) */
+  const int32_t *labels;     /* numPoints labels, or NULL; first axis only */
+} ExaHipProfileAxis;
+
+typedef struct ExaHipProfileStats {
+  uint64_t points, outside, invalid, under[2], over[2], binned;  /* points = the sum of the others */
+  int32_t  weightExponent, valueExponent[4];                     /* the regions' sumExponent rule, per series */
+  int32_t  ldsTable;                                             /* 1: the accumulate pass kept the table in LDS */
+} ExaHipProfileStats;
+
+#define EXA_PROFILE_LABELS_DEVICE 16   /* flag: axes[0].labels is memory of the handle's first device */
+#define EXA_PROFILE_MAX_VALUES    4
+#define EXA_PROFILE_MAX_BINS      (1 << 24)
+
+int exa_hip_profile(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3], int32_t flags,
+                    const ExaHipProfileAxis *axes, int32_t numAxes /* 1 or 2 */,
+                    const ExaHipSource *values, int32_t numValues /* 0..4 */, const ExaHipSource *weight /* or NULL */,
+                    uint64_t *count /* B */, int64_t *sumWeight /* B; NULL iff weight == NULL */,
+                    int64_t *sums /* numValues x B */, float *mins, float *maxs /* numValues x B, or both NULL */,
+                    ExaHipProfileStats *stats /* or NULL */, void *hipStream);
+int exa_hip_profile_stage_ms(ExaHipRenderer *, float ms[4]);   /* values, classify, accumulate, finish */
+
 /* ---- streamlines: field lines of the vector field formed by three channels, integrated from seed points with classical
  * RK4 at a fixed step and handed out as packed polylines.  An extraction, not the viewer's animation: the reference's tracer
  * (exa_hip_reset_tracer / exa_hip_advance_tracer) takes one step per rendered frame, forward only, at a trace count and

@@ -161,6 +161,34 @@ CRITICAL_POINT_DTYPE = np.dtype(dict(names=["cell", "type", "local", "position",
                                      offsets=[0, 4, 8, 20, 32, 36, 72, 96], itemsize=104))
 CRITICAL_STATS = ("cells", "invalidCells", "candidates", "found", "nonFinite", "leftCell", "notConverged")
 
+# exa_hip_profile (include/exa_hip.h): the source kinds, the flag, the caps and the structs
+SOURCE_CHANNEL, SOURCE_DERIVED, SOURCE_RADIUS, SOURCE_COORDINATE = range(4)
+PROFILE_LABELS_DEVICE = 16
+PROFILE_MAX_VALUES = 4
+PROFILE_MAX_BINS = 1 << 24
+
+
+class ExaHipSource(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("channels", C.c_int32 * 3), ("quantity", C.c_int32), ("centre", C.c_float * 3)]
+
+
+class ExaHipProfileAxis(C.Structure):
+    _fields_ = [("source", ExaHipSource), ("numBins", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("edges", C.c_void_p), ("labels", C.c_void_p)]
+
+
+class ExaHipProfileStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("outside", C.c_uint64), ("invalid", C.c_uint64), ("under", C.c_uint64 * 2),
+                ("over", C.c_uint64 * 2), ("binned", C.c_uint64), ("weightExponent", C.c_int32),
+                ("valueExponent", C.c_int32 * 4), ("ldsTable", C.c_int32)]
+
+    def asdict(self):
+        d = {k: int(getattr(self, k)) for k in ("points", "outside", "invalid", "binned", "weightExponent", "ldsTable")}
+        d["under"], d["over"] = [int(v) for v in self.under], [int(v) for v in self.over]
+        d["valueExponent"] = [int(v) for v in self.valueExponent]
+        return d
+
+
 # exa_hip_raycast_iso (include/exa_hip.h)
 CROSS_MAX_REFINE = 32
 RAYCAST_KEYS = ("t", "position", "value", "gradient", "index", "side", "crossings")
@@ -293,6 +321,9 @@ _ABI = {
     "exa_hip_critical_points_read": (None, [_vp, _vp, _vp, _vp, _i32, _vp]),
     "exa_hip_critical_points_release": (None, [_vp]),
     "exa_hip_critical_points_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_profile": (None, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _P(ExaHipProfileStats), _vp]),
+    "exa_hip_profile_stage_ms": (None, [_vp, _vp]),
     "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
     "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),
@@ -926,6 +957,43 @@ class Renderer:
         finally:
             self.releaseRegions()
 
+    # ---- profiles and phase plots on a lattice (exa_hip_profile; include/exa_hip.h states the contract) ----
+    def profile(self, lo, hi, dims, axes, values=(), weight=None, world=False, minmax=True, stream=None):
+        """the points of the lattice of resample(lo, hi, dims) binned by one or two `axes` (uniform(), edges() or, first
+        axis only, labels()), with `values` (up to four sources: channel(), derived(), radius(), coordinate()) accumulated
+        per bin, weighted by the source `weight` if given.  Returns a dict: count uint64 [B...], sum_weight int64 [B...] or
+        None, sums int64 [numValues, B...], mins / maxs float32 [numValues, B...] or None (minmax=False), stats (the dict of
+        ExaHipProfileStats) — B... is (numBins,) or (numBins1, numBins0), the first axis fastest.  profile_measures turns
+        the fixed-point sums into sums, means and volumes."""
+        if isinstance(axes, ProfileAxis):
+            axes = (axes,)
+        axes, values = tuple(axes), tuple(values)
+        ax = (ExaHipProfileAxis * max(1, len(axes)))(*[a.struct for a in axes])
+        flags = self._probe_world(world) | (PROFILE_LABELS_DEVICE if any(a.device for a in axes) else 0)
+        shape = tuple(int(a.struct.numBins) for a in axes[:2])[::-1]
+        bins = int(np.prod(shape, dtype=np.int64)) if shape else 0
+        nv = len(values)
+        room = bins if 0 < bins <= PROFILE_MAX_BINS and all(n > 0 for n in shape) else 0     # a refused call writes nothing
+        vals = (ExaHipSource * max(1, nv))(*values)
+        count = np.zeros(room, np.uint64)
+        sum_weight = np.zeros(room, np.int64) if weight is not None else None
+        sums = np.zeros((nv, room), np.int64)
+        mins, maxs = (np.zeros((nv, room), np.float32), np.zeros((nv, room), np.float32)) if minmax else (None, None)
+        st = ExaHipProfileStats()
+        ptr = lambda a: a.ctypes.data if a is not None else None                              # noqa: E731
+        self._check(lib().exa_hip_profile(self.h, _f3(lo), _f3(hi), _i3(dims), flags, ax, len(axes), vals if nv else None, nv,
+                                          C.byref(weight) if weight is not None else None, ptr(count), ptr(sum_weight),
+                                          ptr(sums) if nv else None, ptr(mins), ptr(maxs), C.byref(st), C.c_void_p(stream or 0)))
+        grid = lambda a: a.reshape(a.shape[:-1] + shape) if a is not None else None           # noqa: E731
+        return dict(count=grid(count), sum_weight=grid(sum_weight), sums=grid(sums), mins=grid(mins), maxs=grid(maxs),
+                    stats=st.asdict(), weighted=weight is not None)
+
+    def profileStageMs(self):
+        """device ms of the last profile's stages: values, classify, accumulate, finish"""
+        ms = (C.c_float * 4)()
+        self._check(lib().exa_hip_profile_stage_ms(self.h, ms))
+        return [float(v) for v in ms]
+
     # ---- basins: one per peak of field >= iso, merged by depth (exa_hip_basins*; include/exa_hip.h states the contract) ----
     def extractBasins(self, lo, hi, dims, iso, min_depth, channel=0, world=False, below=False, faces=False, keep_values=False,
                       quantity=None, channels=(0, 1, 2), stream=None):
@@ -1314,6 +1382,71 @@ def ftle_of_stretch(stretch, step, num_steps, fill=float("nan")):
         ftle = (np.log(stretch.astype(np.float64)) / (2.0 * num_steps * np.float64(np.float32(step)))).astype(np.float32)
     filled = stretch.view(np.uint32) == np.float32(fill).view(np.uint32)
     return np.where(filled, np.float32(fill), ftle).astype(np.float32)
+
+
+# ---- the sources and axes of Renderer.profile ----
+def channel(c):
+    """the source `channel c` on the lattice: what resample returns with a NaN fill"""
+    return ExaHipSource(SOURCE_CHANNEL, (C.c_int32 * 3)(int(c), 0, 0), 0, (C.c_float * 3)())
+
+
+def derived(quantity, channels=(0, 1, 2)):
+    """the source `derived quantity of the vector field channels` (one component): what resampleDerived returns"""
+    return ExaHipSource(SOURCE_DERIVED, _i3(channels), derived_quantity(quantity), (C.c_float * 3)())
+
+
+def radius(centre):
+    """the source `distance of the lattice position from centre`, in the space of lo / hi"""
+    return ExaHipSource(SOURCE_RADIUS, (C.c_int32 * 3)(), 0, _f3(centre))
+
+
+def coordinate(axis):
+    """the source `component axis (0, 1, 2) of the lattice position`"""
+    return ExaHipSource(SOURCE_COORDINATE, (C.c_int32 * 3)(int(axis), 0, 0), 0, (C.c_float * 3)())
+
+
+class ProfileAxis:
+    """an axis of Renderer.profile: the struct, and what it points to kept alive"""
+
+    def __init__(self, struct, keep=None, device=False):
+        self.struct, self.keep, self.device = struct, keep, device
+
+
+def uniform(src, lo, hi, n):
+    """n uniform bins of the source over [lo, hi], by exa_hip_histogram's rule"""
+    return ProfileAxis(ExaHipProfileAxis(src, int(n), float(lo), float(hi), None, None))
+
+
+def edges(src, array):
+    """bins between the strictly ascending float32 `array` of numBins + 1 edges, the last bin closed"""
+    e = np.ascontiguousarray(array, np.float32).reshape(-1)
+    return ProfileAxis(ExaHipProfileAxis(src, e.size - 1, 0.0, 0.0, e.ctypes.data, None), keep=e)
+
+
+def labels(array_or_device_ptr, n):
+    """the bin of every lattice point given directly, n of them: an int32 array of numPoints labels (what Renderer.regions /
+    basins return under `labels`; < 0: outside), or a device pointer (an int, or an int32 torch CUDA tensor) to them"""
+    if isinstance(array_or_device_ptr, np.ndarray):
+        a = np.ascontiguousarray(array_or_device_ptr, np.int32).reshape(-1)
+        return ProfileAxis(ExaHipProfileAxis(ExaHipSource(), int(n), 0.0, 0.0, None, a.ctypes.data), keep=a)
+    ptr = _dev_ptr(array_or_device_ptr)
+    return ProfileAxis(ExaHipProfileAxis(ExaHipSource(), int(n), 0.0, 0.0, None, ptr), keep=array_or_device_ptr, device=True)
+
+
+def profile_measures(result, lo, hi, dims):
+    """what follows from the dict of Renderer.profile over the lattice (lo, hi, dims), per bin, in float64: `sums`
+    [numValues, B...] (fixed * 2^-exponent of the series), `sum_weight` (or None), `means` (sum of w*v over sum of w, or sum
+    of v over count; NaN in an empty bin) and `volume` (count times the volume of a lattice cell), as region_measures does"""
+    st = result["stats"]
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    cell = float(np.prod((hi - lo) / np.asarray(dims, np.float64).reshape(3)))
+    count = result["count"].astype(np.float64)
+    sums = np.stack([np.ldexp(s.astype(np.float64), -int(st["valueExponent"][f])) for f, s in enumerate(result["sums"])]) \
+        if len(result["sums"]) else np.zeros(result["sums"].shape, np.float64)
+    sum_weight = None if result["sum_weight"] is None else np.ldexp(result["sum_weight"].astype(np.float64), -int(st["weightExponent"]))
+    with np.errstate(all="ignore"):
+        means = sums / (count if sum_weight is None else sum_weight)
+    return dict(sums=sums, sum_weight=sum_weight, means=means, volume=count * cell)
 
 
 def _f3(v):

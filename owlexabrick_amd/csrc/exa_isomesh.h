@@ -290,4 +290,79 @@ hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s);
 hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s);
 hipError_t launchIsoCriticalPack(const IsoCriticalArgs &a, hipStream_t s);
 
+// ---- profiles and phase plots on the lattice (exa_hip_profile): the lattice points binned by one or two keys, other
+// quantities accumulated per bin.  One lane per lattice point L = (k*ny + j)*nx + i, blocks of kIsoBlock consecutive L, a
+// block of the launch taking kIsoProfileTiles of them one after the other.  A source is a lattice in memory (a channel or a
+// derived quantity, resampled by the host), or the radius about a centre or a coordinate, formed from (i, j, k).
+//   classify    the keys (or the label) and the bin of every point into bins[L], kIsoProfileUnbinned for the classes that are
+//               not binned; the class counts and, over the binned points, the largest |term| of every series (as float bits),
+//               gathered by a lane over its tiles and added once per block of the launch; the smallest L whose label is not
+//               below numBins by an atomic min
+//   accumulate  per binned point the terms quantised with the series' scales; count, sums and min / max keys to the bin's
+//               record.  The lanes of a wave that share the leading pending lane's bin are reduced before that lane issues the
+//               atomics, twice (a radial profile, one giant region or a constant key put whole waves into one bin), what is
+//               left goes lane by lane.  The table is columns of B entries: the sums (64 bit; the weight's where there is a
+//               weight, then one per value), the counts, the min keys and the max keys (32 bit, one column per value).  Small
+//               table: a copy per workgroup in LDS (the counts 32 bit there), its records with a count flushed once by
+//               64-bit atomics.  Large table: the atomics go to HBM directly.
+//   finish      the keys of the table to floats in place
+// The LDS copy holds kIsoProfileLdsBinBytes(numValues) per bin, laid out as if there were a weight and min / max, so that the
+// choice hangs on B and numValues alone; it is taken when that fits EXA_PROFILE_LDS_BYTES (dynamic shared memory; at most
+// 64 KiB, and 160 KiB per CU are shared by the workgroups in flight).
+#ifndef EXA_PROFILE_LDS_BYTES
+#define EXA_PROFILE_LDS_BYTES 32768
+#endif
+static const uint32_t kIsoProfileTiles = 16;              // blocks of the lattice per block of the classify and accumulate passes
+static const uint32_t kIsoProfileUnbinned = 0xffffffffu;  // bins[L] of a point that is outside, invalid, under or over
+static const int32_t kIsoProfileSeries = 1 + EXA_PROFILE_MAX_VALUES;      // the weight's series, then the values'
+static const int32_t kIsoProfileUniform = 0, kIsoProfileEdges = 1, kIsoProfileLabels = 2;     // IsoProfileKey::mode
+// the counters of the classify pass, 64-bit words zeroed by the host except the last, which starts at ~0
+static const int kIsoProfileOutside = 0, kIsoProfileInvalid = 1, kIsoProfileUnder = 2, kIsoProfileOver = 4, kIsoProfileBinned = 6,
+                 kIsoProfileBadLabel = 7, kIsoProfileCounters = 8;
+
+constexpr size_t kIsoProfileLdsBinBytes(int32_t numValues) { return 8 * size_t(1 + numValues) + 4 + 8 * size_t(numValues); }
+constexpr bool isoProfileLdsTable(uint64_t numBins, int32_t numValues) { return numBins * kIsoProfileLdsBinBytes(numValues) <= size_t(EXA_PROFILE_LDS_BYTES); }
+
+// What the kernels hold of the call they keep in scalar registers for the whole pass: a source is 16 bytes, its kind a
+// nibble of `kinds`, and the flags share a word (the first form of the arguments, one struct per source with its kind and
+// every field, spilled 34 scalar registers in the classify and the accumulate pass).
+union IsoProfileSource {
+  const float *values;        // kIsoProfileMemory: numPoints floats
+  int32_t axis;               // EXA_SOURCE_COORDINATE
+  float centre[3];            // EXA_SOURCE_RADIUS
+};
+static const int kIsoProfileWeightSlot = 2, kIsoProfileValueSlot = 3, kIsoProfileSlots = 3 + EXA_PROFILE_MAX_VALUES;    // slots 0, 1: the axes' keys
+static const int32_t kIsoProfileMemoryKind = 0;           // a nibble of `kinds`; else EXA_SOURCE_RADIUS / EXA_SOURCE_COORDINATE
+
+struct IsoProfileKey {
+  int32_t mode, numBins;
+  float lo, hi, scale;        // uniform: scale = float(numBins) / (hi - lo); edges: lo, hi = the first and the last edge
+  const float *edges;         // edges: numBins + 1 floats in device memory
+};
+
+struct IsoProfileArgs {
+  uint32_t numPoints;         // nx*ny*nz <= 2^31 - 1
+  uint32_t nx, ny;
+  float lo[3], step[3];       // lattice point i on axis a: lo[a] + (float(i) + 0.5f) * step[a]
+  uint32_t kinds;             // nibble s: the kind of sources[s]
+  uint32_t needPosition : 1;  // a source is a radius or a coordinate
+  uint32_t hasWeight : 1, minMax : 1, numAxes : 2, numValues : 3;
+  IsoProfileSource sources[kIsoProfileSlots];
+  IsoProfileKey axes[2];
+  const int32_t *labels;      // axes[0].mode == kIsoProfileLabels: numPoints
+  uint32_t numBlocks;         // of kIsoBlock points
+  uint32_t *bins;             // numPoints
+  unsigned long long *counters;   // [kIsoProfileCounters], and behind them the [kIsoProfileSeries] 32-bit words of the bits of
+                              // max |term| over the binned points, zeroed by the host
+  int32_t exponent[kIsoProfileSeries];  // accumulate: the series' exponents
+  uint32_t numBins;           // B
+  unsigned long long *sums;   // [hasWeight + numValues][B]
+  unsigned long long *count;  // [B]
+  uint32_t *keyMin, *keyMax;  // [numValues][B] each, with minMax; finish turns them into floats in place
+};
+
+hipError_t launchIsoProfileClassify(const IsoProfileArgs &a, hipStream_t s);
+hipError_t launchIsoProfileAccumulate(const IsoProfileArgs &a, hipStream_t s);     // LDS or HBM by isoProfileLdsTable
+hipError_t launchIsoProfileFinish(const IsoProfileArgs &a, hipStream_t s);
+
 } // namespace exa

@@ -8,6 +8,8 @@
 // which place their output with the same scans.
 #include "exa_isomesh.h"
 
+#include <type_traits>
+
 namespace exa {
 namespace {
 
@@ -1400,6 +1402,289 @@ __global__ __launch_bounds__(kIsoBlock) void isoCriticalPackKernel(const IsoCrit
   out[1] = g[0]; out[2] = g[1]; out[3] = g[2];
 }
 
+// ---- profiles and phase plots (exa_hip_profile): the passes of exa_isomesh.h ----
+// the lattice position of L in the caller's space, as exa_hip_resample forms it before any world mapping
+__device__ __forceinline__ void profilePosition(const IsoProfileArgs &a, uint32_t L, float (&P)[3])
+{
+  const uint32_t i = L % a.nx, jk = L / a.nx, j = jk % a.ny, k = jk / a.ny;
+  P[0] = a.lo[0] + (float(i) + 0.5f) * a.step[0];
+  P[1] = a.lo[1] + (float(j) + 0.5f) * a.step[1];
+  P[2] = a.lo[2] + (float(k) + 0.5f) * a.step[2];
+}
+
+// source `slot` of the call at L; the slot is wave-uniform, and the kinds' and the source's words are read where they are
+// needed, not held over the pass
+__device__ __forceinline__ float profileSource(const IsoProfileArgs &a, uint32_t slot, uint32_t L, const float (&P)[3])
+{
+  const IsoProfileSource &s = a.sources[slot];
+  const int32_t kind = int32_t((a.kinds >> (4u * slot)) & 15u);
+  if (kind == kIsoProfileMemoryKind) return s.values[L];
+  if (kind == EXA_SOURCE_COORDINATE) return s.axis == 0 ? P[0] : s.axis == 1 ? P[1] : P[2];
+  const float dx = P[0] - s.centre[0], dy = P[1] - s.centre[1], dz = P[2] - s.centre[2];
+  return sqrtf((dx * dx + dy * dy) + dz * dz);
+}
+
+// the slots of the call's series, the weight's first: [first, end)
+__device__ __forceinline__ uint32_t profileFirstSeries(const IsoProfileArgs &a) { return a.hasWeight ? uint32_t(kIsoProfileWeightSlot) : uint32_t(kIsoProfileValueSlot); }
+__device__ __forceinline__ uint32_t profileEndSeries(const IsoProfileArgs &a) { return uint32_t(kIsoProfileValueSlot) + a.numValues; }
+
+// The key of axis ax (wave-uniform) at L: false if it is NaN.  range: 0, or 1 + ax (under) / 3 + ax (over) of the first axis
+// out of range; bin: the axis' part of the bin index, times `stride`, where the key is in range.
+__device__ __forceinline__ bool profileKey(const IsoProfileArgs &a, uint32_t ax, uint32_t L, const float (&P)[3], uint32_t stride,
+                                           uint32_t &range, uint32_t &bin)
+{
+  const IsoProfileKey &key = a.axes[ax];
+  const float x = profileSource(a, ax, L, P);
+  if (x != x) return false;
+  const bool under = x < key.lo, over = x > key.hi;     // edges: lo, hi = the first and the last edge
+  if (!range) range = under ? 1u + ax : over ? 3u + ax : 0u;
+  uint32_t b = 0;
+  if (!under && !over) {
+    if (key.mode == kIsoProfileUniform) {
+      const float t = (x - key.lo) * key.scale;
+      b = uint32_t(min(key.numBins - 1, int32_t(t)));
+    } else {
+      // the last b with edges[b] <= x, which for x == edges[numBins] is numBins - 1: the last bin is closed
+      uint32_t top = uint32_t(key.numBins);
+      while (top - b > 1u) {
+        const uint32_t mid = (b + top) >> 1;
+        if (key.edges[mid] <= x) b = mid; else top = mid;
+      }
+    }
+  }
+  bin += b * stride;
+  return true;
+}
+
+// The series go one after the other in loops that are not unrolled, and what a lane learns of one of them does not wait in
+// a register for the others: unrolled over the seven sources, the pass held every source's words in scalar registers and
+// spilled 34 of them.
+__global__ __launch_bounds__(kIsoBlock) void isoProfileClassifyKernel(const IsoProfileArgs a)
+{
+  constexpr int kCounts = kIsoProfileBinned + 1;
+  __shared__ uint32_t sStat[kCounts + kIsoProfileSeries];
+  if (threadIdx.x < kCounts + kIsoProfileSeries) sStat[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t n[kCounts] = {};                             // per lane
+#pragma unroll 1
+  for (uint32_t t = 0; t < kIsoProfileTiles; t++) {
+    const uint64_t first = (uint64_t(blockIdx.x) * kIsoProfileTiles + t) * kIsoBlock;
+    if (first >= a.numPoints) break;                    // block-uniform
+    const bool there = first + threadIdx.x < a.numPoints;
+    const uint32_t L = there ? uint32_t(first) + threadIdx.x : 0u;      // a lane beyond the lattice reads point 0 and counts nothing
+    float P[3] = { 0.f, 0.f, 0.f };
+    if (a.needPosition) profilePosition(a, L, P);
+    bool outside = false, valid = true;
+    uint32_t range = 0, bin = 0;
+    uint32_t stride = 1;
+#pragma unroll 1
+    for (uint32_t ax = 0; ax < a.numAxes; ax++) {
+      if (a.axes[ax].mode == kIsoProfileLabels) {       // the first axis only
+        const int32_t label = a.labels[L];
+        outside = label < 0;
+        if (there && label >= a.axes[ax].numBins) atomicMin(a.counters + kIsoProfileBadLabel, (unsigned long long)L);
+        bin = uint32_t(label);
+      } else {
+        valid = profileKey(a, ax, L, P, stride, range, bin) && valid;
+      }
+      stride *= uint32_t(a.axes[ax].numBins);
+    }
+    const uint32_t sBegin = profileFirstSeries(a), sEnd = profileEndSeries(a);
+    float w = 1.f;
+#pragma unroll 1
+    for (uint32_t q = sBegin; q < sEnd; q++) {
+      const float x = profileSource(a, q, L, P);
+      if (q == uint32_t(kIsoProfileWeightSlot)) w = x;
+      // w * x: the term of a value (1 * x without a weight)
+      valid = valid && __builtin_isfinite(x) && (q == uint32_t(kIsoProfileWeightSlot) || __builtin_isfinite(w * x));
+    }
+    const bool binned = there && !outside && valid && !range;
+    n[kIsoProfileOutside] += there && outside;
+    n[kIsoProfileInvalid] += there && !outside && !valid;
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) n[kIsoProfileUnder + c] += there && !outside && valid && range == c + 1u;
+    n[kIsoProfileBinned] += binned;
+    if (there) a.bins[L] = binned ? bin : kIsoProfileUnbinned;
+    // the largest |term| of every series over the wave's binned points (its bits order as unsigned integers), once more
+    // series by series: whether a point is binned hangs on all of them
+    if (__ballot(binned)) {                             // wave-uniform
+#pragma unroll 1
+      for (uint32_t q = sBegin; q < sEnd; q++) {
+        const float x = profileSource(a, q, L, P);
+        const float term = q == uint32_t(kIsoProfileWeightSlot) || !a.hasWeight ? x : w * x;
+        uint32_t m = binned ? __float_as_uint(term) & 0x7fffffffu : 0u;
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+          const uint32_t other = uint32_t(__shfl_xor(int(m), o));
+          m = other > m ? other : m;
+        }
+        if (lane == 0u && m) atomicMax(&sStat[kCounts + q - uint32_t(kIsoProfileWeightSlot)], m);
+      }
+    }
+  }
+  for (int o = 32; o; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < kCounts; c++) n[c] += uint32_t(__shfl_xor(int(n[c]), o));
+  }
+  if (lane == 0u) {
+#pragma unroll
+    for (int c = 0; c < kCounts; c++) if (n[c]) atomicAdd(&sStat[c], n[c]);
+  }
+  __syncthreads();
+  // one set of atomics per block of the launch
+  if (threadIdx.x < kCounts + kIsoProfileSeries) {
+    const uint32_t x = sStat[threadIdx.x];
+    if (x && threadIdx.x < kCounts) atomicAdd(a.counters + threadIdx.x, (unsigned long long)x);
+    if (x && threadIdx.x >= kCounts) atomicMax(reinterpret_cast<uint32_t *>(a.counters + kIsoProfileCounters) + (threadIdx.x - kCounts), x);
+  }
+}
+
+// what a lane, or the lanes of a wave that share a bin, add to the bin's record for one series
+struct ProfilePart {
+  uint32_t count;
+  long long sum;
+  uint32_t keyMin, keyMax;
+};
+
+__device__ __forceinline__ ProfilePart profileNothing() { return { 0u, 0ll, 0xffffffffu, 0u }; }
+
+__device__ __forceinline__ void profileReduce(ProfilePart &p)
+{
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    p.count += uint32_t(__shfl_xor(int(p.count), o));
+    p.sum += __shfl_xor(p.sum, o);
+    const uint32_t kmin = uint32_t(__shfl_xor(int(p.keyMin), o)), kmax = uint32_t(__shfl_xor(int(p.keyMax), o));
+    p.keyMin = kmin < p.keyMin ? kmin : p.keyMin;
+    p.keyMax = kmax > p.keyMax ? kmax : p.keyMax;
+  }
+}
+
+// The table the accumulate pass adds to: the call's in HBM, or the workgroup's copy in LDS, whose counts are 32 bit and which
+// always has the weight's column.
+template <bool LDS>
+struct ProfileTable {
+  typedef typename std::conditional<LDS, uint32_t, unsigned long long>::type Count;
+  unsigned long long *sums;
+  Count *count;
+  uint32_t *keyMin, *keyMax;
+};
+
+// one series' part into record `bin`: the count with the first series, the sum into column `column` if the call has a
+// series at all, the keys of value `value` where it is one and min / max are asked for (all wave-uniform)
+template <bool LDS>
+__device__ __forceinline__ void profileAdd(const ProfileTable<LDS> &t, uint32_t numBins, uint32_t bin, const ProfilePart &p,
+                                           bool withCount, bool withSum, uint32_t column, bool withKeys, uint32_t value)
+{
+  if (withCount) atomicAdd(t.count + bin, typename ProfileTable<LDS>::Count(p.count));
+  if (withSum) atomicAdd(t.sums + size_t(column) * numBins + bin, (unsigned long long)p.sum);
+  if (withKeys) {
+    atomicMin(t.keyMin + size_t(value) * numBins + bin, p.keyMin);
+    atomicMax(t.keyMax + size_t(value) * numBins + bin, p.keyMax);
+  }
+}
+
+// A workgroup goes over its tiles once per series (once for the count alone where the call has none): the bin indices come
+// out of the cache from the second time on, and a pass holds one source, one sum and one pair of keys.
+template <bool LDS>
+__global__ __launch_bounds__(kIsoBlock) void isoProfileAccumulateKernel(const IsoProfileArgs a)
+{
+  extern __shared__ unsigned long long profileLds[];
+  const uint32_t B = a.numBins, nv = a.numValues, lane = threadIdx.x & 63u;
+  ProfileTable<LDS> table;
+  if constexpr (LDS) {
+    table.sums = profileLds;
+    table.count = reinterpret_cast<uint32_t *>(profileLds + size_t(1u + nv) * B);
+    table.keyMin = table.count + B;
+    table.keyMax = table.keyMin + size_t(nv) * B;
+    for (uint32_t b = threadIdx.x; b < (1u + nv) * B; b += kIsoBlock) table.sums[b] = 0ull;
+    for (uint32_t b = threadIdx.x; b < B; b += kIsoBlock) table.count[b] = 0;
+    for (uint32_t b = threadIdx.x; b < nv * B; b += kIsoBlock) { table.keyMin[b] = 0xffffffffu; table.keyMax[b] = 0u; }
+    __syncthreads();
+  } else {
+    table.sums = a.sums;
+    table.count = a.count;
+    table.keyMin = a.keyMin; table.keyMax = a.keyMax;
+  }
+  const uint32_t sBegin = profileFirstSeries(a), sEnd = profileEndSeries(a);
+  const bool anySeries = sEnd > sBegin;
+#pragma unroll 1
+  for (uint32_t q = sBegin; q < (anySeries ? sEnd : sBegin + 1u); q++) {
+    const bool withCount = q == sBegin, isValue = anySeries && q >= uint32_t(kIsoProfileValueSlot);
+    const bool withKeys = isValue && a.minMax, weighted = isValue && a.hasWeight;
+    const uint32_t value = q - uint32_t(kIsoProfileValueSlot);
+    // the column of the series: the copy in LDS always has the weight's in front, the table only where there is a weight
+    const uint32_t column = LDS ? q - uint32_t(kIsoProfileWeightSlot) : q - sBegin;
+    const int32_t exponent = a.exponent[q - uint32_t(kIsoProfileWeightSlot)];
+#pragma unroll 1
+    for (uint32_t t = 0; t < kIsoProfileTiles; t++) {
+      const uint64_t first = (uint64_t(blockIdx.x) * kIsoProfileTiles + t) * kIsoBlock;
+      if (first >= a.numPoints) break;                  // block-uniform
+      const uint64_t at = first + threadIdx.x;
+      const uint32_t L = uint32_t(at);
+      const uint32_t bin = at < a.numPoints ? a.bins[L] : kIsoProfileUnbinned;
+      bool on = bin < B;                                // the mark is not below B
+      ProfilePart own = profileNothing();
+      if (on) {
+        own.count = 1;
+        if (anySeries) {
+          float P[3] = { 0.f, 0.f, 0.f };
+          if (a.needPosition) profilePosition(a, L, P);
+          const float x = profileSource(a, q, L, P);
+          const float term = weighted ? profileSource(a, kIsoProfileWeightSlot, L, P) * x : x;
+          own.sum = __double2ll_rn(ldexp(double(term), exponent));
+          if (withKeys) own.keyMin = own.keyMax = regionKey(x);
+        }
+      }
+      // the bin of the first pending lane is reduced over the wave and added by that lane, twice (recordStats' scheme);
+      // what is left then goes lane by lane
+      unsigned long long pending = __ballot(on);
+#pragma unroll 1
+      for (int round = 0; round < 2; round++) {
+        if (!pending) break;                            // wave-uniform
+        const uint32_t leader = uint32_t(__ffsll(pending)) - 1u;
+        const uint32_t lb = uint32_t(__builtin_amdgcn_readlane(int(bin), int(leader)));
+        const bool same = on && bin == lb;
+        const unsigned long long m = __ballot(same);
+        ProfilePart part = own;
+        if (!same) part = profileNothing();
+        if (__popcll(m) > 1) profileReduce(part);       // wave-uniform
+        if (lane == leader) profileAdd(table, B, lb, part, withCount, anySeries, column, withKeys, value);
+        on = on && !same;
+        pending &= ~m;
+      }
+      if (on) profileAdd(table, B, bin, own, withCount, anySeries, column, withKeys, value);
+    }
+  }
+  if constexpr (LDS) {
+    // the flush: the records of the copy that hold a point, the only accesses of this variant to the table
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < B; b += kIsoBlock) {
+      const uint32_t c = table.count[b];
+      if (!c) continue;
+      atomicAdd(a.count + b, (unsigned long long)c);
+      if (a.hasWeight) atomicAdd(a.sums + b, table.sums[b]);
+      for (uint32_t f = 0; f < nv; f++) {
+        atomicAdd(a.sums + size_t(a.hasWeight + f) * B + b, table.sums[size_t(1u + f) * B + b]);
+        if (!a.minMax) continue;
+        atomicMin(a.keyMin + size_t(f) * B + b, table.keyMin[size_t(f) * B + b]);
+        atomicMax(a.keyMax + size_t(f) * B + b, table.keyMax[size_t(f) * B + b]);
+      }
+    }
+  }
+}
+
+// min and max of every bin and value out of the keys, in place; an empty bin holds +INFINITY / -INFINITY
+__global__ __launch_bounds__(kIsoBlock) void isoProfileFinishKernel(const IsoProfileArgs a)
+{
+  const uint64_t at = uint64_t(blockIdx.x) * kIsoBlock + threadIdx.x;
+  if (at >= uint64_t(a.numValues) * a.numBins) return;
+  const bool any = a.count[at % a.numBins] != 0ull;
+  a.keyMin[at] = any ? __float_as_uint(regionValueOfKey(a.keyMin[at])) : 0x7f800000u;
+  a.keyMax[at] = any ? __float_as_uint(regionValueOfKey(a.keyMax[at])) : 0xff800000u;
+}
+
 // ---- the launchers: every kernel runs in blocks of kIsoBlock lanes and takes its argument struct by value ----
 template <typename A>
 hipError_t launch(void (*kernel)(A), dim3 grid, hipStream_t s, const A &a)
@@ -1503,5 +1788,18 @@ hipError_t launchIsoCriticalCompact(const IsoCriticalArgs &a, hipStream_t s) { r
 hipError_t launchIsoCriticalRefine(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalRefineKernel, a.numCandBlocks, s, a); }
 hipError_t launchIsoCriticalEmit(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalEmitKernel, a.numCandBlocks, s, a); }
 hipError_t launchIsoCriticalPack(const IsoCriticalArgs &a, hipStream_t s) { return launch(isoCriticalPackKernel, blocksOf(3ull * a.numFound), s, a); }
+
+hipError_t launchIsoProfileClassify(const IsoProfileArgs &a, hipStream_t s) { return launch(isoProfileClassifyKernel, blocksOf(a.numBlocks, kIsoProfileTiles), s, a); }
+// the workgroup's copy of a small table in dynamic shared memory, else the atomics straight to the table
+hipError_t launchIsoProfileAccumulate(const IsoProfileArgs &a, hipStream_t s)
+{
+  const dim3 grid(blocksOf(a.numBlocks, kIsoProfileTiles));
+  if (isoProfileLdsTable(a.numBins, a.numValues))
+    hipLaunchKernelGGL(isoProfileAccumulateKernel<true>, grid, dim3(kIsoBlock), a.numBins * kIsoProfileLdsBinBytes(a.numValues), s, a);
+  else
+    hipLaunchKernelGGL(isoProfileAccumulateKernel<false>, grid, dim3(kIsoBlock), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launchIsoProfileFinish(const IsoProfileArgs &a, hipStream_t s) { return launch(isoProfileFinishKernel, blocksOf(uint64_t(a.numValues) * a.numBins), s, a); }
 
 } // namespace exa

@@ -5,8 +5,8 @@
 // the iso-surface extraction on a sampled lattice (exa_hip_isosurface, exa_hip_isosurface_derived; exa_isomesh.hip) with the
 // contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit) and the connected
 // regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit), its basins, one per peak
-// (exa_hip_basins, exa_hip_basins_derived; the same unit), and the critical points of a flow on it (exa_hip_critical_points;
-// the same unit).
+// (exa_hip_basins, exa_hip_basins_derived; the same unit), the critical points of a flow on it (exa_hip_critical_points;
+// the same unit), and the profiles and phase plots of fields on it (exa_hip_profile; the same unit).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -1569,5 +1569,228 @@ int exa_hip_critical_points_read(ExaHipRenderer *h, ExaHipCriticalPoint *points,
 
 int exa_hip_critical_points_release(ExaHipRenderer *h) { return releaseResult(h, &ExaHipRenderer::isoCritical); }
 int exa_hip_critical_points_stage_ms(ExaHipRenderer *h, float ms[6]) { return readStageMs(h, &ExaHipRenderer::isoCritical, ms); }
+
+} // extern "C"
+
+// ---- profiles and phase plots on a lattice (exa_isomesh.hip) ----
+// the lattices the call's channel / derived sources need, each once, and where every such source reads
+struct ProfileLattices {
+  struct Lattice { int32_t channels[3]; int32_t quantity; };      // quantity < 0: the one channel channels[0]
+  std::vector<Lattice> distinct;
+  std::vector<std::pair<int, size_t>> users;                      // the slot of IsoProfileArgs::sources, the lattice
+};
+
+// One source of the call into slot `slot` of the kernels' arguments, false after h->fail.  A channel / derived source is
+// noted in `lat`: its values pointer follows once the lattices are allocated.
+static bool profileSourceOf(ExaHipRenderer *h, const char *fn, const ExaHipSource &src, ProfileLattices &lat, IsoProfileArgs &a, int slot)
+{
+  IsoProfileSource &out = a.sources[slot];
+  a.kinds |= uint32_t(src.kind == EXA_SOURCE_DERIVED ? kIsoProfileMemoryKind : src.kind) << (4 * slot);
+  static_assert(EXA_SOURCE_CHANNEL == kIsoProfileMemoryKind, "a channel's lattice is a lattice in memory");
+  switch (src.kind) {
+  case EXA_SOURCE_CHANNEL:
+  case EXA_SOURCE_DERIVED: {
+    ProfileLattices::Lattice want = { { src.channels[0], 0, 0 }, -1 };
+    if (src.kind == EXA_SOURCE_CHANNEL) {
+      if (!checkChannel(h, fn, src.channels[0])) return false;
+    } else {
+      if (!oneComponent(h, fn, src.channels, src.quantity, "a source needs")) return false;
+      want = { { src.channels[0], src.channels[1], src.channels[2] }, src.quantity };
+    }
+    size_t at = 0;
+    while (at < lat.distinct.size() && std::memcmp(&lat.distinct[at], &want, sizeof(want)) != 0) at++;
+    if (at == lat.distinct.size()) lat.distinct.push_back(want);
+    lat.users.push_back({ slot, at });
+    return true;
+  }
+  case EXA_SOURCE_RADIUS:
+    for (int k = 0; k < 3; k++) {
+      if (!std::isfinite(src.centre[k])) { h->fail(std::string(fn) + ": the centre of a radius source must be finite"); return false; }
+      out.centre[k] = src.centre[k];
+    }
+    a.needPosition = 1;
+    return true;
+  case EXA_SOURCE_COORDINATE:
+    if (src.channels[0] < 0 || src.channels[0] > 2) { h->fail(std::string(fn) + ": a coordinate source needs its axis 0..2 in channels[0]"); return false; }
+    out.axis = src.channels[0];
+    a.needPosition = 1;
+    return true;
+  default:
+    h->fail(std::string(fn) + ": unknown source kind (EXA_SOURCE_*)");
+    return false;
+  }
+}
+
+// the exponent of a series out of the number of binned points and the bits of its max |term|: the regions' rule
+static int32_t profileExponent(uint64_t binned, uint32_t maxBits)
+{
+  const uint64_t totals[3] = { 0, binned, maxBits };
+  return sumExponentOf(totals);
+}
+
+extern "C" {
+
+int exa_hip_profile(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t flags,
+                    const ExaHipProfileAxis *axes, int32_t numAxes, const ExaHipSource *values, int32_t numValues,
+                    const ExaHipSource *weight, uint64_t *count, int64_t *sumWeight, int64_t *sums, float *mins, float *maxs,
+                    ExaHipProfileStats *stats, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_profile";
+  ExaHipRenderer *r = firstChild(h);
+  for (float &ms : r->profile.stageMs) ms = 0.f;
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_PROFILE_LABELS_DEVICE, " (EXA_SAMPLE_WORLD_SPACE and EXA_PROFILE_LABELS_DEVICE apply)")) return 1;
+  if (!lo || !hi || !dims || !axes || !count) { h->fail(std::string(fn) + ": null argument (lo, hi, dims, axes or count)"); return 1; }
+  if (numAxes != 1 && numAxes != 2) { h->fail(std::string(fn) + ": numAxes must be 1 or 2"); return 1; }
+  if (numAxes == 2 && axes[1].labels) { h->fail(std::string(fn) + ": labels on the second axis (only the first axis takes labels)"); return 1; }
+  if (numValues < 0 || numValues > EXA_PROFILE_MAX_VALUES) { h->fail(std::string(fn) + ": numValues must be 0..4"); return 1; }
+  if (numValues > 0 && (!values || !sums)) { h->fail(std::string(fn) + ": null values or sums with numValues > 0"); return 1; }
+  if ((weight != nullptr) != (sumWeight != nullptr)) { h->fail(std::string(fn) + ": sumWeight needs a weight, and a weight needs sumWeight"); return 1; }
+  if ((mins != nullptr) != (maxs != nullptr)) { h->fail(std::string(fn) + ": mins and maxs come together (both or neither)"); return 1; }
+  const uint64_t n = latticePoints(h, fn, lo, hi, dims, 1, "dims must be >= 1 on every axis", "the box must be finite with lo < hi on every axis", true);
+  if (!n) return 1;
+
+  // the sources and the axes
+  IsoProfileArgs a;
+  std::memset(&a, 0, sizeof(a));
+  ProfileLattices lat;
+  std::vector<float> edges;                                   // both axes' one behind the other
+  size_t edgesAt[2] = { 0, 0 };
+  uint64_t bins = 1;
+  for (int ax = 0; ax < numAxes; ax++) {
+    const ExaHipProfileAxis &in = axes[ax];
+    IsoProfileKey &key = a.axes[ax];
+    if (in.numBins < 1) { h->fail(std::string(fn) + ": numBins must be >= 1 on every axis"); return 1; }
+    key.numBins = in.numBins;
+    bins *= uint64_t(in.numBins);                              // two factors below 2^31
+    if (in.labels) { key.mode = kIsoProfileLabels; continue; }
+    if (!profileSourceOf(h, fn, in.source, lat, a, ax)) return 1;
+    if (in.edges) {
+      if (bins > uint64_t(EXA_PROFILE_MAX_BINS)) break;        // refused below, before the edges are read
+      for (int32_t b = 0; b <= in.numBins; b++)
+        if (!std::isfinite(in.edges[b]) || (b && !(in.edges[b] > in.edges[b - 1]))) { h->fail(std::string(fn) + ": edges must be finite and strictly ascending"); return 1; }
+      key.mode = kIsoProfileEdges;
+      key.lo = in.edges[0]; key.hi = in.edges[in.numBins];
+      edgesAt[ax] = edges.size();
+      edges.insert(edges.end(), in.edges, in.edges + in.numBins + 1);
+    } else {
+      if (!(std::isfinite(in.lo) && std::isfinite(in.hi) && in.lo < in.hi)) { h->fail(std::string(fn) + ": the range needs finite lo < hi"); return 1; }
+      const float width = in.hi - in.lo;
+      key.mode = kIsoProfileUniform;
+      key.lo = in.lo; key.hi = in.hi; key.scale = float(in.numBins) / width;
+      if (!std::isfinite(width) || !std::isfinite(key.scale)) { h->fail(std::string(fn) + ": hi - lo and numBins / (hi - lo) must be finite in float32"); return 1; }
+    }
+  }
+  if (bins > uint64_t(EXA_PROFILE_MAX_BINS)) { h->fail(std::string(fn) + ": the number of bins must be 1 .. 2^24"); return 1; }
+  for (int f = 0; f < numValues; f++)
+    if (!profileSourceOf(h, fn, values[f], lat, a, kIsoProfileValueSlot + f)) return 1;
+  if (weight && !profileSourceOf(h, fn, *weight, lat, a, kIsoProfileWeightSlot)) return 1;
+  const size_t B = size_t(bins), nv = size_t(numValues), ns = nv + (weight ? 1 : 0);
+  const bool minMax = mins != nullptr && nv > 0;
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]);
+  for (int k = 0; k < 3; k++) { a.lo[k] = lo[k]; a.step[k] = (hi[k] - lo[k]) / float(dims[k]); }
+  a.numAxes = uint32_t(numAxes); a.numValues = uint32_t(numValues); a.hasWeight = weight ? 1 : 0; a.minMax = minMax ? 1 : 0;
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  a.numBins = uint32_t(B);
+
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  if (r->applyBrickOrder(s)) { h->fail(r->err); return 1; }
+
+  // the work space: the lattices, the bin indices, labels that come from the host, the edges, the counters, the table
+  // (sums | count | max keys | min keys: what starts as zeros, then what starts as ones)
+  const bool hostLabels = axes[0].labels && !(flags & EXA_PROFILE_LABELS_DEVICE);
+  const size_t counterWords = kIsoProfileCounters + (kIsoProfileSeries + 1) / 2, zeroWords = (ns + 1) * B + (minMax ? (nv * B + 1) / 2 : 0),
+               tableWords = zeroWords + (minMax ? (nv * B + 1) / 2 : 0);
+  DevBuf<float> lattices, devEdges;
+  DevBuf<uint32_t> binOf;
+  DevBuf<int32_t> devLabels;
+  DevBuf<unsigned long long> counters, table;
+  hipError_t e = lattices.alloc(lat.distinct.size() * size_t(n));
+  if (e == hipSuccess) e = binOf.alloc(size_t(n));
+  if (e == hipSuccess && hostLabels) e = devLabels.alloc(size_t(n));
+  if (e == hipSuccess) e = devEdges.alloc(edges.size());
+  if (e == hipSuccess) e = counters.alloc(counterWords);
+  if (e == hipSuccess) e = table.alloc(tableWords);
+  if (e != hipSuccess)
+    return failNoMemory(h, fn, "no device memory for the lattices (4 bytes per point and distinct source), the bin indices (4 more) and the table (8 bytes per bin and series, 8 for the count, 8 per value with min / max)", e);
+  for (auto &user : lat.users) a.sources[user.first].values = lattices.p + user.second * size_t(n);
+  for (int ax = 0; ax < numAxes; ax++) a.axes[ax].edges = a.axes[ax].mode == kIsoProfileEdges ? devEdges.p + edgesAt[ax] : nullptr;
+  a.labels = hostLabels ? devLabels.p : axes[0].labels;
+  a.bins = binOf.p;
+  a.counters = counters.p;
+  a.sums = table.p;
+  a.count = table.p + ns * B;
+  a.keyMax = reinterpret_cast<uint32_t *>(table.p + (ns + 1) * B);
+  a.keyMin = reinterpret_cast<uint32_t *>(table.p + zeroWords);
+
+  TimingEvents<6> t;
+  HIP_TRY(h, t.create());
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  for (size_t k = 0; k < lat.distinct.size(); k++)
+    if (int rc = fillLattice(h, fn, lo, hi, dims, lat.distinct[k].channels, lat.distinct[k].quantity, flags & EXA_SAMPLE_WORLD_SPACE,
+                             lattices.p + k * size_t(n), hipStream)) return rc;
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  unsigned long long start[kIsoProfileCounters + (kIsoProfileSeries + 1) / 2] = {};
+  start[kIsoProfileBadLabel] = ~0ull;
+  HIP_TRY(h, hipMemcpyAsync(counters.p, start, sizeof(start), hipMemcpyHostToDevice, s));
+  if (hostLabels) HIP_TRY(h, hipMemcpyAsync(devLabels.p, axes[0].labels, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (!edges.empty()) HIP_TRY(h, hipMemcpyAsync(devEdges.p, edges.data(), edges.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemsetAsync(table.p, 0, zeroWords * 8, s));
+  if (tableWords > zeroWords) HIP_TRY(h, hipMemsetAsync(table.p + zeroWords, 0xff, (tableWords - zeroWords) * 8, s));
+  HIP_TRY(h, launchIsoProfileClassify(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[2], s));
+  unsigned long long got[kIsoProfileCounters + (kIsoProfileSeries + 1) / 2];
+  if (readBack(h, got, counters.p, sizeof(got), s)) return 1;
+  if (got[kIsoProfileBadLabel] != ~0ull) {
+    h->fail(std::string(fn) + ": a label >= numBins, first at L = " + std::to_string(got[kIsoProfileBadLabel]));
+    return 1;
+  }
+  uint32_t magnitudes[kIsoProfileSeries];
+  std::memcpy(magnitudes, got + kIsoProfileCounters, sizeof(magnitudes));
+  int32_t exponent[kIsoProfileSeries] = {};
+  for (int q = 0; q < kIsoProfileSeries; q++) {
+    const bool have = q == 0 ? weight != nullptr : q - 1 < numValues;
+    exponent[q] = have ? profileExponent(got[kIsoProfileBinned], magnitudes[q]) : 0;
+    a.exponent[q] = exponent[q];
+  }
+  HIP_TRY(h, hipEventRecord(t.ev[3], s));
+  if (got[kIsoProfileBinned]) HIP_TRY(h, launchIsoProfileAccumulate(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[4], s));
+  if (minMax) HIP_TRY(h, launchIsoProfileFinish(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[5], s));
+  HIP_TRY(h, hipMemcpyAsync(count, a.count, B * 8, hipMemcpyDeviceToHost, s));
+  if (weight) HIP_TRY(h, hipMemcpyAsync(sumWeight, a.sums, B * 8, hipMemcpyDeviceToHost, s));
+  if (nv) HIP_TRY(h, hipMemcpyAsync(sums, a.sums + (ns - nv) * B, nv * B * 8, hipMemcpyDeviceToHost, s));
+  if (minMax) {
+    HIP_TRY(h, hipMemcpyAsync(mins, a.keyMin, nv * B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(maxs, a.keyMax, nv * B * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(h, hipStreamSynchronize(s));                  // the work space is freed behind it
+  float *ms = r->profile.stageMs;
+  HIP_TRY(h, t.elapsed(0, 1, &ms[0]));
+  HIP_TRY(h, t.elapsed(1, 2, &ms[1]));
+  HIP_TRY(h, t.elapsed(3, 4, &ms[2]));
+  HIP_TRY(h, t.elapsed(4, 5, &ms[3]));
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->points = n;
+    stats->outside = got[kIsoProfileOutside]; stats->invalid = got[kIsoProfileInvalid];
+    for (int ax = 0; ax < 2; ax++) { stats->under[ax] = got[kIsoProfileUnder + ax]; stats->over[ax] = got[kIsoProfileOver + ax]; }
+    stats->binned = got[kIsoProfileBinned];
+    stats->weightExponent = exponent[0];
+    for (int f = 0; f < EXA_PROFILE_MAX_VALUES; f++) stats->valueExponent[f] = exponent[1 + f];
+    stats->ldsTable = isoProfileLdsTable(B, numValues) ? 1 : 0;
+  }
+  return 0;
+}
+
+int exa_hip_profile_stage_ms(ExaHipRenderer *h, float ms[4])
+{
+  if (!h || !ms) return 1;
+  for (int k = 0; k < 4; k++) ms[k] = firstChild(h)->profile.stageMs[k];
+  return 0;
+}
 
 } // extern "C"

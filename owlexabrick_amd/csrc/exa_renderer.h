@@ -409,6 +409,11 @@ struct ExaHipRenderer {
   struct Derived {
     float kernelMs = 0.f;
   } derived;
+  // the device time of the stages of the last exa_hip_profile (in the renderer of devices[0]): values, classify,
+  // accumulate, finish; the call keeps nothing else
+  struct Profile {
+    float stageMs[4] = { 0.f, 0.f, 0.f, 0.f };
+  } profile;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 

@@ -86,6 +86,21 @@
 //                                            include/exa_hip.h) and the labels (NX*NY*NZ int32, x fastest: the basin's number, -1
 //                                            outside); --frames 0 renders nothing; --regions-box, --regions-world,
 //                                            --regions-below and --regions-faces apply to it as well
+//             [--profile AXIS[/AXIS] VALUES NX NY NZ out.profile] the points of that lattice binned by one or two axes, with the
+//                                            count, the exact sums and the min / max of VALUES per bin (exa_hip_profile).
+//                                            SOURCE is cN (channel N), QUANTITY:C0,C1,C2 (the names of --derived), r:x,y,z (the
+//                                            distance from that centre) or x, y, z (a coordinate); AXIS is SOURCE@LO:HI:BINS
+//                                            (uniform bins) or, as the first axis, the word regions or basins: the labels of
+//                                            this invocation's --regions / --basins, which must be on the same lattice; VALUES
+//                                            is up to four sources joined with +, or none.  One text line `profile NX NY NZ bins
+//                                            B0 B1 values V weighted W points .. outside .. invalid .. under .. .. over .. ..
+//                                            binned .. weightExponent .. valueExponents .. .. .. ..` (B1 = 1 with one axis),
+//                                            then raw little-endian arrays over the B0*B1 bins, the first axis fastest: count
+//                                            (uint64), with a weight its sums (int64), the V sums (int64: a sum is fixed *
+//                                            2^-exponent), the V minima and the V maxima (float32); --frames 0 renders nothing; with
+//             [--profile-weight SOURCE]      sums of weight * value, and the weight's own sums
+//             [--profile-box lx ly lz ux uy uz] [--profile-world] (box default as for --resample)
+//             [--profile-log]                the uniform axes' bins spaced logarithmically: edges float(LO * (HI / LO)^(b / BINS))
 //             [--histogram BINS file.txt]   the exact histogram of a channel's cell values (exa_hip_histogram), one line
 //                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
 //             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
@@ -171,6 +186,12 @@ struct FtleOpts { std::string name; vec3i channels{ 0, 1, 2 }, dims{ 1, 1, 1 }; 
 struct CriticalOpts { std::string name; vec3i channels{ 0, 1, 2 }, dims{ 2, 2, 2 }; box3f box; int iterations = 8; float tolerance = 0.0009765625f; };
 struct RegionsOpts { std::string name; int channel = 0; float iso = 0.f; vec3i dims; };
 struct BasinsOpts { std::string name; int channel = 0; float iso = 0.f, minDepth = 0.f; vec3i dims; };
+struct ProfileOpts {
+  std::string name, axes, values, weight; vec3i dims; box3f box; bool haveBox = false, world = false, log = false;
+  // what parseProfile makes of the words: per axis the struct, the edges of --profile-log, `regions` / `basins` for a label axis
+  std::vector<ExaHipProfileAxis> axis; std::vector<std::vector<float>> edges; std::vector<std::string> labelsOf;
+  std::vector<ExaHipSource> value; ExaHipSource weightSource = {};
+};
 struct SurfaceOpts { std::string name, mesh; std::vector<int> channels; float spacing = 0.f; int maxN = 0; bool world = false; };   // mesh: a file, or `iso`
 struct HistogramOpts { std::string name; int bins = 0, channel = 0; bool haveRange = false, haveBox = false; float range[2] = { 0, 1 }; box3i box; };
 struct StreamlinesOpts { std::string seedsName, name; float step = 0.f; int maxSteps = 0; vec3i channels{ 0, 1, 2 }; bool both = false, backward = false, normalize = false; };
@@ -193,7 +214,7 @@ struct FrameOpts {                                           // what the referen
 };
 struct Options {
   FrameOpts frame; DerivedOpts derived; LatticeFlags lattice; ResampleOpts resample; IsoMeshOpts isomesh; IsolinesOpts isolines; LicOpts lic;
-  FtleOpts ftle; CriticalOpts critical; RegionsOpts regions; BasinsOpts basins; SurfaceOpts surface; HistogramOpts histogram;
+  FtleOpts ftle; CriticalOpts critical; RegionsOpts regions; BasinsOpts basins; ProfileOpts profile; SurfaceOpts surface; HistogramOpts histogram;
   StreamlinesOpts streamlines; ProjectOpts project; RaycastOpts raycast;
 };
 
@@ -333,6 +354,16 @@ bool parseLatticeOutputFlag(Args &a, Options &o)
     o.basins.channel = a.count(); o.basins.iso = a.number(); o.basins.minDepth = a.number(); o.basins.dims = a.int3();
     o.basins.name = a.word("missing file after --basins CHANNEL ISO MINDEPTH NX NY NZ");
   }
+  else if (f == "--profile") {
+    o.profile.axes = a.word("missing axes after --profile");
+    o.profile.values = a.word("missing values after --profile AXIS[/AXIS]");
+    o.profile.dims = a.int3();
+    o.profile.name = a.word("missing file after --profile AXIS[/AXIS] VALUES NX NY NZ");
+  }
+  else if (f == "--profile-weight") o.profile.weight = a.word("missing source after --profile-weight");
+  else if (f == "--profile-box") { o.profile.box = a.box(); o.profile.haveBox = true; }
+  else if (f == "--profile-world") o.profile.world = true;
+  else if (f == "--profile-log") o.profile.log = true;
   else if (f == "--regions-box") { o.lattice.box = a.box(); o.lattice.haveBox = true; }
   else if (f == "--regions-world") o.lattice.world = true;
   else if (f == "--regions-below") o.lattice.below = true;
@@ -397,6 +428,74 @@ bool parseOtherOutputFlag(Args &a, Options &o)
   return true;
 }
 
+// --profile: a SOURCE word
+ExaHipSource profileSource(const std::string &w)
+{
+  ExaHipSource s = {};
+  char tail = 0;
+  const size_t colon = w.find(':');
+  if (w == "x" || w == "y" || w == "z") { s.kind = EXA_SOURCE_COORDINATE; s.channels[0] = w[0] - 'x'; }
+  else if (w.size() > 1 && w[0] == 'c' && std::sscanf(w.c_str() + 1, "%d%c", &s.channels[0], &tail) == 1) s.kind = EXA_SOURCE_CHANNEL;
+  else if (w.compare(0, 2, "r:") == 0 && std::sscanf(w.c_str() + 2, "%f,%f,%f%c", &s.centre[0], &s.centre[1], &s.centre[2], &tail) == 3) s.kind = EXA_SOURCE_RADIUS;
+  else if (colon != std::string::npos && colon >= 1
+           && std::sscanf(w.c_str() + colon + 1, "%d,%d,%d%c", &s.channels[0], &s.channels[1], &s.channels[2], &tail) == 3) {
+    s.kind = EXA_SOURCE_DERIVED;
+    s.quantity = derivedQuantity(w.substr(0, colon));
+  }
+  else fail("--profile wants a source cN, QUANTITY:C0,C1,C2, r:x,y,z, x, y or z, not " + w);
+  return s;
+}
+
+std::vector<std::string> splitWords(const std::string &s, char at)
+{
+  std::vector<std::string> out(1);
+  for (char c : s) { if (c == at) out.emplace_back(); else out.back() += c; }
+  return out;
+}
+
+// the words of --profile and --profile-weight, once every flag is read: the sources, the axes with the edges of --profile-log,
+// and whether the --regions / --basins that a label axis names is there on the same lattice
+void parseProfile(Options &all)
+{
+  ProfileOpts &o = all.profile;
+  const std::vector<std::string> axisWords = splitWords(o.axes, '/');
+  if (axisWords.size() > 2) fail("--profile wants one or two axes AXIS[/AXIS]");
+  o.edges.resize(axisWords.size());
+  for (size_t k = 0; k < axisWords.size(); k++) {
+    const std::string &w = axisWords[k];
+    ExaHipProfileAxis ax = {};
+    o.labelsOf.push_back(w == "regions" || w == "basins" ? w : "");
+    if (!o.labelsOf[k].empty()) {
+      if (k) fail("--profile takes " + w + " as its first axis only");
+      const bool regions = w == "regions";
+      const vec3i d = regions ? all.regions.dims : all.basins.dims;
+      const LatticeFlags &lf = all.lattice;
+      if ((regions ? all.regions.name : all.basins.name).empty() || lf.world != o.world || d.x != o.dims.x || d.y != o.dims.y || d.z != o.dims.z
+          || lf.haveBox != o.haveBox || (o.haveBox && std::memcmp(&lf.box, &o.box, sizeof(o.box)) != 0))
+        fail("--profile " + w + " needs --" + w + " on the same lattice in the same invocation");
+    } else {
+      const size_t at = w.find('@');
+      char tail = 0;
+      if (at == std::string::npos || std::sscanf(w.c_str() + at + 1, "%f:%f:%d%c", &ax.lo, &ax.hi, &ax.numBins, &tail) != 3)
+        fail("--profile wants an axis SOURCE@LO:HI:BINS, regions or basins, not " + w);
+      ax.source = profileSource(w.substr(0, at));
+      if (o.log) {
+        const char *text = "--profile-log wants edges LO * (HI / LO)^(b / BINS) that ascend strictly (0 < LO < HI, BINS >= 1 and not too many)";
+        if (!(ax.lo > 0.f && ax.hi > ax.lo && ax.numBins >= 1 && ax.numBins <= EXA_PROFILE_MAX_BINS)) fail(text);
+        for (int b = 0; b <= ax.numBins; b++) {
+          o.edges[k].push_back(float(double(ax.lo) * std::pow(double(ax.hi) / double(ax.lo), double(b) / double(ax.numBins))));
+          if (b && !(o.edges[k][b] > o.edges[k][b - 1])) fail(text);
+        }
+      }
+    }
+    o.axis.push_back(ax);
+  }
+  if (o.values != "none")
+    for (const std::string &w : splitWords(o.values, '+')) o.value.push_back(profileSource(w));
+  if (o.value.size() > EXA_PROFILE_MAX_VALUES) fail("--profile wants at most 4 values");
+  if (!o.weight.empty()) o.weightSource = profileSource(o.weight);
+}
+
 Options parseOptions(int argc, char **argv)
 {
   Options o;
@@ -409,6 +508,7 @@ Options parseOptions(int argc, char **argv)
   if (o.frame.cfgName.empty()) fail("usage: exaRender cfg.exa [flags]");
   if (o.derived.on() && (o.resample.haveChannel || o.isomesh.haveChannel))
     fail("--derived takes its three channels itself: --resample-channel / --isomesh-channel do not go with it");
+  if (!o.profile.name.empty()) parseProfile(o);
   return o;
 }
 
@@ -541,7 +641,17 @@ void writeCritical(const CriticalOpts &o, Renderer &r)
               kind[0], spiral[0], kind[1], spiral[1], kind[2], spiral[2], kind[3], spiral[3], degenerate);
 }
 
-void writeRegions(const RegionsOpts &o, const LatticeFlags &lf, const DerivedOpts &dv, Renderer &r)
+// the labels of this invocation's --regions or --basins for --profile regions / basins, kept the way --surface iso keeps the mesh
+struct KeptLabels { bool present = false, world = false; vec3i dims; box3f box; int32_t count = 0; std::vector<int32_t> labels; };
+
+template <class Labelling>
+void keepLabels(KeptLabels *keep, const Labelling &L, size_t count, vec3i dims, const box3f &box, bool world)
+{
+  if (!keep) return;
+  keep->present = true; keep->world = world; keep->dims = dims; keep->box = box; keep->count = int32_t(count); keep->labels = L.labels;
+}
+
+void writeRegions(const RegionsOpts &o, const LatticeFlags &lf, const DerivedOpts &dv, KeptLabels *keep, Renderer &r)
 {
   const box3f box = boxOr(lf.haveBox, lf.box, lf.world, r);
   const Renderer::Regions R = dv.on() ? r.regionsDerived(box, o.dims, dv.channels, dv.quantity, o.iso, lf.world, lf.below, lf.faces)
@@ -551,9 +661,10 @@ void writeRegions(const RegionsOpts &o, const LatticeFlags &lf, const DerivedOpt
            { { R.regions.data(), sizeof(ExaHipRegion), R.regions.size() }, { R.labels.data(), 4, R.labels.size() } });
   std::printf("regions %d %d %d %siso %.9g world %d below %d faces %d %s", o.dims.x, o.dims.y, o.dims.z, fieldWords(dv, o.channel).c_str(),
               o.iso, lf.world ? 1 : 0, lf.below ? 1 : 0, lf.faces ? 1 : 0, counts.c_str());
+  keepLabels(keep, R, R.regions.size(), o.dims, box, lf.world);
 }
 
-void writeBasins(const BasinsOpts &o, const LatticeFlags &lf, const DerivedOpts &dv, Renderer &r)
+void writeBasins(const BasinsOpts &o, const LatticeFlags &lf, const DerivedOpts &dv, KeptLabels *keep, Renderer &r)
 {
   const box3f box = boxOr(lf.haveBox, lf.box, lf.world, r);
   const Renderer::Basins B = dv.on() ? r.basinsDerived(box, o.dims, dv.channels, dv.quantity, o.iso, o.minDepth, lf.world, lf.below, lf.faces)
@@ -564,6 +675,33 @@ void writeBasins(const BasinsOpts &o, const LatticeFlags &lf, const DerivedOpts 
            { { B.basins.data(), sizeof(ExaHipBasin), B.basins.size() }, { B.labels.data(), 4, B.labels.size() } });
   std::printf("basins %d %d %d %siso %.9g minDepth %.9g world %d below %d faces %d %s", o.dims.x, o.dims.y, o.dims.z,
               fieldWords(dv, o.channel).c_str(), o.iso, o.minDepth, lf.world ? 1 : 0, lf.below ? 1 : 0, lf.faces ? 1 : 0, counts.c_str());
+  keepLabels(keep, B, B.basins.size(), o.dims, box, lf.world);
+}
+
+void writeProfile(const ProfileOpts &o, const KeptLabels &regions, const KeptLabels &basins, Renderer &r)
+{
+  const box3f box = boxOr(o.haveBox, o.box, o.world, r);
+  std::vector<ExaHipProfileAxis> axes = o.axis;
+  for (size_t k = 0; k < axes.size(); k++) {
+    if (!o.edges[k].empty()) axes[k].edges = o.edges[k].data();
+    if (o.labelsOf[k].empty()) continue;
+    const KeptLabels &kept = o.labelsOf[k] == "regions" ? regions : basins;       // on the same lattice: parseProfile has seen to it
+    axes[k].numBins = kept.count;
+    axes[k].labels = kept.labels.data();
+  }
+  const std::vector<ExaHipSource> &values = o.value;
+  const ExaHipSource &weight = o.weightSource;
+  const Renderer::Profile P = r.profile(box, o.dims, axes, values, o.weight.empty() ? nullptr : &weight, o.world);
+  const ExaHipProfileStats &st = P.stats;
+  const std::string head = format("profile %d %d %d bins %d %d values %zu weighted %d points %llu outside %llu invalid %llu under %llu %llu "
+                                  "over %llu %llu binned %llu weightExponent %d valueExponents %d %d %d %d", o.dims.x, o.dims.y, o.dims.z,
+                                  axes[0].numBins, axes.size() > 1 ? axes[1].numBins : 1, values.size(), o.weight.empty() ? 0 : 1,
+                                  ull(st.points), ull(st.outside), ull(st.invalid), ull(st.under[0]), ull(st.under[1]), ull(st.over[0]),
+                                  ull(st.over[1]), ull(st.binned), st.weightExponent, st.valueExponent[0], st.valueExponent[1],
+                                  st.valueExponent[2], st.valueExponent[3]);
+  writeRaw(o.name, head + "\n", { { P.count.data(), 8, P.count.size() }, { P.sumWeight.data(), 8, P.sumWeight.size() },
+                                  { P.sums.data(), 8, P.sums.size() }, { P.mins.data(), 4, P.mins.size() }, { P.maxs.data(), 4, P.maxs.size() } });
+  std::printf("%s world %d log %d lds %d\n", head.c_str(), o.world ? 1 : 0, o.log ? 1 : 0, st.ldsTable);
 }
 
 void writeSurface(const SurfaceOpts &o, const KeptIsoMesh &iso, Renderer &r)
@@ -686,8 +824,11 @@ bool writeOutputs(const Options &o, Renderer &r)
   if (wanted(o.lic.name)) writeLic(o.lic, r);
   if (wanted(o.ftle.name)) writeFtle(o.ftle, r);
   if (wanted(o.critical.name)) writeCritical(o.critical, r);
-  if (wanted(o.regions.name)) writeRegions(o.regions, o.lattice, o.derived, r);
-  if (wanted(o.basins.name)) writeBasins(o.basins, o.lattice, o.derived, r);
+  const bool profile = !o.profile.name.empty();
+  KeptLabels regionLabels, basinLabels;                      // --profile regions / basins reads them
+  if (wanted(o.regions.name)) writeRegions(o.regions, o.lattice, o.derived, profile ? &regionLabels : nullptr, r);
+  if (wanted(o.basins.name)) writeBasins(o.basins, o.lattice, o.derived, profile ? &basinLabels : nullptr, r);
+  if (wanted(o.profile.name)) writeProfile(o.profile, regionLabels, basinLabels, r);
   if (wanted(o.surface.name)) writeSurface(o.surface, isoMesh, r);
   if (wanted(o.histogram.name)) writeHistogram(o.histogram, r);
   if (wanted(o.streamlines.name)) writeStreamlines(o.streamlines, r);

@@ -784,6 +784,27 @@ Renderer::Isolines Renderer::isolinesDerived(vec3f origin, vec3f du, vec3f dv, v
   return isolinesOf(handle, planeOf(origin, du, dv, size), isos, Field(channels, quantity), worldSpace, false, values);
 }
 
+Renderer::Profile Renderer::profile(const box3f &box, vec3i dims, const std::vector<ExaHipProfileAxis> &axes,
+                                    const std::vector<ExaHipSource> &values, const ExaHipSource *weight, bool worldSpace, bool minMax,
+                                    bool labelsOnDevice)
+{
+  if (worldSpace) pushState();
+  const Lattice L(box, dims);
+  // the room the module fills; what it refuses of the axes it refuses before it writes
+  uint64_t bins = axes.empty() ? 0 : 1;
+  for (size_t k = 0; k < axes.size() && k < 2; k++) bins = axes[k].numBins > 0 && bins <= EXA_PROFILE_MAX_BINS ? bins * uint64_t(axes[k].numBins) : 0;
+  const size_t B = bins <= EXA_PROFILE_MAX_BINS ? size_t(bins) : 0, nv = values.size();
+  Profile P;
+  P.count.assign(B, 0);
+  if (weight) P.sumWeight.assign(B, 0);
+  P.sums.assign(nv * B, 0);
+  if (minMax) { P.mins.assign(nv * B, 0.f); P.maxs.assign(nv * B, 0.f); }
+  check(exa_hip_profile(handle, L.lo, L.hi, L.d, spaceFlag(worldSpace) | (labelsOnDevice ? EXA_PROFILE_LABELS_DEVICE : 0), axes.data(),
+                        int32_t(axes.size()), values.data(), int32_t(nv), weight, P.count.data(), weight ? P.sumWeight.data() : nullptr,
+                        P.sums.data(), minMax ? P.mins.data() : nullptr, minMax ? P.maxs.data() : nullptr, &P.stats, nullptr), handle);
+  return P;
+}
+
 void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
                                 std::vector<uint64_t> *volume, ExaHipFieldStats *stats, const box3i *box)
 {

@@ -291,6 +291,20 @@ struct Renderer {
   CriticalPoints criticalPoints(const box3f &box, vec3i dims, vec3i channels, int iterations = 8, float tolerance = 0.0009765625f,
                                 bool worldSpace = false, bool probe = false);
 
+  // the points of the lattice of resample(box, dims) binned by one or two axes, with the count, the exact fixed-point sums
+  // and the min / max of up to four other quantities per bin, weighted if `weight` is given (exa_hip_profile; include/exa_hip.h
+  // states the contract, the sources and the axes).  Bin b1 * axes[0].numBins + b0; a series' sum is fixed * 2^-exponent
+  // (stats.weightExponent, stats.valueExponent).  An axis whose `labels` point to device memory: labelsOnDevice.
+  struct Profile {
+    std::vector<uint64_t> count;         // B
+    std::vector<int64_t> sumWeight;      // B, empty without a weight
+    std::vector<int64_t> sums;           // numValues x B
+    std::vector<float> mins, maxs;       // numValues x B, empty without minMax
+    ExaHipProfileStats stats;
+  };
+  Profile profile(const box3f &box, vec3i dims, const std::vector<ExaHipProfileAxis> &axes, const std::vector<ExaHipSource> &values,
+                  const ExaHipSource *weight = nullptr, bool worldSpace = false, bool minMax = true, bool labelsOnDevice = false);
+
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
   // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
