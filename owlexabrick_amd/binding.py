@@ -7,6 +7,7 @@ loading / creating fails loudly.
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -493,6 +494,9 @@ class Renderer:
         self.doSpaceSkipping = True
         self.fbSize = (0, 0)
         self.voxelSpaceBounds = prep.voxel_bounds()
+        # the last extraction of each family, for the read that follows it
+        self._iso_counts, self._stream_counts = _IsoMesh(0, 0, False), _StreamLines(0, 0, False)
+        self._isolines = self._regions = self._basins = self._critical = None
 
     def _check(self, rc):
         if rc:
@@ -503,6 +507,32 @@ class Renderer:
         ms = C.c_float(0)
         self._check(getter(self.h, C.byref(ms)))
         return float(ms.value)
+
+    def _stage_ms(self, getter, n):
+        """the n floats that one of the `float ms[n]` getters reports"""
+        ms = (C.c_float * n)()
+        self._check(getter(self.h, ms))
+        return [float(v) for v in ms]
+
+    def _field_call(self, of_channel, of_derived, head, channel, quantity, channels, tail):
+        """the return code of of_channel(handle, *head, channel, *tail) or, with a quantity, of its _derived form
+        of_derived(handle, *head, channels, quantity, *tail)"""
+        if quantity is None:
+            return of_channel(self.h, *head, int(channel), *tail)
+        return of_derived(self.h, *head, _i3(channels), derived_quantity(quantity), *tail)
+
+    def _refused_read(self, read, pointers, method):
+        """a read with no extraction of this renderer behind it: all null, for the module to refuse"""
+        self._check(read(self.h, *[None] * pointers, 0, None))
+        raise RuntimeError(f"{method}: no extraction of this renderer to read")
+
+    @staticmethod
+    def _one_shot(read, release):
+        """what read() returns of the extraction just made, which is released even if the read raises"""
+        try:
+            return read()
+        finally:
+            release()
 
     def close(self):
         if getattr(self, "h", None):
@@ -675,26 +705,13 @@ class Renderer:
         flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradient or normalized else 0)
         flags |= SAMPLE_GRADIENT_NORMALIZED if normalized else 0
         k = chans.size
-        if getattr(points, "is_cuda", False):
-            import torch
-            if points.dtype != torch.float32 or not points.is_contiguous() or points.numel() % 3:
-                raise TypeError("points: a contiguous float32 tensor [n, 3]")
-            n = points.numel() // 3
-            values = torch.empty((n, k), dtype=torch.float32, device=points.device)
-            grads = torch.empty((n, k, 3), dtype=torch.float32, device=points.device) if flags & SAMPLE_GRADIENT else None
-            status = torch.empty((n, k), dtype=torch.int32, device=points.device)
-            self._check(lib().exa_hip_sample_points(self.h, _dev_ptr(points), n, chans.ctypes.data, k, flags, float(fill),
-                                                    _dev_ptr(values), _dev_ptr(grads), _dev_ptr(status), 1,
-                                                    C.c_void_p(stream or 0), int(async_)))
-            return values, grads, status
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-        n = pts.shape[0]
-        values = np.empty((n, k), dtype=np.float32)
-        grads = np.empty((n, k, 3), dtype=np.float32) if flags & SAMPLE_GRADIENT else None
-        status = np.empty((n, k), dtype=np.int32)
-        self._check(lib().exa_hip_sample_points(self.h, pts.ctypes.data, n, chans.ctypes.data, k, flags, float(fill),
-                                                values.ctypes.data, grads.ctypes.data if grads is not None else None,
-                                                status.ctypes.data, 0, None, 0))
+        empty, ptr, device = _like(points)
+        pts, n = _rows3(points, np.float32, device, "points: a contiguous float32 tensor [n, 3]")
+        values = empty((n, k), np.float32)
+        grads = empty((n, k, 3), np.float32) if flags & SAMPLE_GRADIENT else None
+        status = empty((n, k), np.int32)
+        self._check(lib().exa_hip_sample_points(self.h, ptr(pts), n, chans.ctypes.data, k, flags, float(fill), ptr(values),
+                                                ptr(grads), ptr(status), *_target(device, stream, async_)))
         return values, grads, status
 
     def resample(self, lo, hi, dims, channel=0, world=False, fill=float("nan"), out_ptr=None, stream=None, async_=False):
@@ -702,46 +719,43 @@ class Renderer:
         world space with world=True).  Without out_ptr returns a float32 array [nz, ny, nx] (x fastest); out_ptr (a device
         pointer or a contiguous float32 torch CUDA tensor) takes the device path and returns None."""
         flags = self._probe_world(world)
-        lo3, hi3, d3 = _f3(lo), _f3(hi), _i3(dims)
-        if out_ptr is not None:
-            self._check(lib().exa_hip_resample(self.h, lo3, hi3, d3, int(channel), flags, float(fill), _dev_ptr(out_ptr), 1,
-                                               C.c_void_p(stream or 0), int(async_)))
-            return None
-        out = np.empty(tuple(max(int(d), 0) for d in dims[::-1]), dtype=np.float32)     # the module checks the dims
-        self._check(lib().exa_hip_resample(self.h, lo3, hi3, d3, int(channel), flags, float(fill), out.ctypes.data, 0, None, 0))
+        out, dest = _lattice_out(dims, (), out_ptr, stream, async_)
+        self._check(lib().exa_hip_resample(self.h, _f3(lo), _f3(hi), _i3(dims), int(channel), flags, float(fill), *dest))
         return out
 
     # ---- iso-surface extraction (exa_hip_isosurface*; include/exa_hip.h states the contract) ----
     def extractIsoSurface(self, lo, hi, dims, iso, channel=0, world=False, gradients=False, stream=None):
         """extract the surface field == iso on the lattice of resample(lo, hi, dims) into module-owned device memory;
         returns (numVertices, numTriangles).  readIsoSurface copies it out, releaseIsoSurface frees it."""
+        return self._extract_iso(lo, hi, dims, iso, channel, None, None, world, gradients, stream)
+
+    def _extract_iso(self, lo, hi, dims, iso, channel, quantity, channels, world, gradients, stream):
+        """extractIsoSurface of a channel or of a derived quantity, whose mesh has no gradients.  A call that fails leaves
+        the state as it was: the module then has no mesh, and refuses the read that state asks for"""
         flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradients else 0)
-        lo3, hi3, d3 = _f3(lo), _f3(hi), _i3(dims)
         nv, nt = C.c_uint64(0), C.c_uint64(0)
-        self._check(lib().exa_hip_isosurface(self.h, lo3, hi3, d3, int(channel), float(iso), flags, C.byref(nv), C.byref(nt),
-                                             C.c_void_p(stream or 0)))
-        self._iso_counts = (int(nv.value), int(nt.value), bool(gradients))
+        self._check(self._field_call(lib().exa_hip_isosurface, lib().exa_hip_isosurface_derived, (_f3(lo), _f3(hi), _i3(dims)),
+                                     channel, quantity, channels,
+                                     (float(iso), flags, C.byref(nv), C.byref(nt), C.c_void_p(stream or 0))))
+        self._iso_counts = _IsoMesh(int(nv.value), int(nt.value), bool(gradients) and quantity is None)
         return self._iso_counts[:2]
 
     def readIsoSurface(self):
         """(verts float32 [n,3], tris int32 [m,3], grads float32 [n,3] or None) of the last extractIsoSurface"""
-        nv, nt, grad = getattr(self, "_iso_counts", (0, 0, False))
-        verts = np.empty((nv, 3), dtype=np.float32)
-        tris = np.empty((nt, 3), dtype=np.int32)
-        grads = np.empty((nv, 3), dtype=np.float32) if grad else None
-        self._check(lib().exa_hip_isosurface_read(self.h, verts.ctypes.data, grads.ctypes.data if grad else None,
-                                                  tris.ctypes.data, 0, None))
+        mesh = self._iso_counts
+        verts = np.empty((mesh.vertices, 3), dtype=np.float32)
+        tris = np.empty((mesh.triangles, 3), dtype=np.int32)
+        grads = np.empty((mesh.vertices, 3), dtype=np.float32) if mesh.gradients else None
+        self._check(lib().exa_hip_isosurface_read(self.h, verts.ctypes.data, _host_ptr(grads), tris.ctypes.data, 0, None))
         return verts, tris, grads
 
     def releaseIsoSurface(self):
         self._check(lib().exa_hip_isosurface_release(self.h))
-        self._iso_counts = (0, 0, False)
+        self._iso_counts = _IsoMesh(0, 0, False)
 
     def isoSurfaceStageMs(self):
         """device ms of the last extraction's stages: lattice values, cube pass, point pass, scans, emit, gradients"""
-        ms = (C.c_float * 6)()
-        self._check(lib().exa_hip_isosurface_stage_ms(self.h, ms))
-        return [float(v) for v in ms]
+        return self._stage_ms(lib().exa_hip_isosurface_stage_ms, 6)
 
     def isosurface(self, lo, hi, dims, iso, channel=0, world=False, gradients=False):
         """the iso-surface field == iso of `channel` on the lattice of resample(lo, hi, dims), by marching tetrahedra:
@@ -749,10 +763,7 @@ class Renderer:
         samplePoints(verts, gradient=True, normalized=True) gives; the shading normal is -grad/|grad|.  The device copy
         is released before returning."""
         self.extractIsoSurface(lo, hi, dims, iso, channel=channel, world=world, gradients=gradients)
-        try:
-            return self.readIsoSurface()
-        finally:
-            self.releaseIsoSurface()
+        return self._one_shot(self.readIsoSurface, self.releaseIsoSurface)
 
     # ---- derived flow quantities (exa_hip_*_derived; include/exa_hip.h states the contract) ----
     def sampleDerived(self, points, quantity, channels=(0, 1, 2), world=False, fill=float("nan"), stream=None, async_=False):
@@ -763,22 +774,12 @@ class Renderer:
         q = derived_quantity(quantity)
         k = DERIVED_COMPONENTS.get(q, 1)                                       # the module checks the quantity
         flags, ch3 = self._probe_world(world), _i3(channels)
-        if getattr(points, "is_cuda", False):
-            import torch
-            if points.dtype != torch.float32 or not points.is_contiguous() or points.numel() % 3:
-                raise TypeError("points: a contiguous float32 tensor [n, 3]")
-            n = points.numel() // 3
-            out = torch.empty((n, k), dtype=torch.float32, device=points.device)
-            status = torch.empty(n, dtype=torch.int32, device=points.device)
-            self._check(lib().exa_hip_sample_derived(self.h, _dev_ptr(points), n, ch3, q, flags, float(fill), _dev_ptr(out),
-                                                     _dev_ptr(status), 1, C.c_void_p(stream or 0), int(async_)))
-            return (out if k == 3 else out.reshape(n)), status
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-        n = pts.shape[0]
-        out = np.empty((n, k), dtype=np.float32)
-        status = np.empty(n, dtype=np.int32)
-        self._check(lib().exa_hip_sample_derived(self.h, pts.ctypes.data, n, ch3, q, flags, float(fill), out.ctypes.data,
-                                                 status.ctypes.data, 0, None, 0))
+        empty, ptr, device = _like(points)
+        pts, n = _rows3(points, np.float32, device, "points: a contiguous float32 tensor [n, 3]")
+        out = empty((n, k), np.float32)
+        status = empty((n,), np.int32)
+        self._check(lib().exa_hip_sample_derived(self.h, ptr(pts), n, ch3, q, flags, float(fill), ptr(out), ptr(status),
+                                                 *_target(device, stream, async_)))
         return (out if k == 3 else out.reshape(n)), status
 
     def resampleDerived(self, lo, hi, dims, quantity, channels=(0, 1, 2), world=False, fill=float("nan"), out_ptr=None,
@@ -789,35 +790,21 @@ class Renderer:
         q = derived_quantity(quantity)
         k = DERIVED_COMPONENTS.get(q, 1)
         flags = self._probe_world(world)
-        lo3, hi3, d3, ch3 = _f3(lo), _f3(hi), _i3(dims), _i3(channels)
-        if out_ptr is not None:
-            self._check(lib().exa_hip_resample_derived(self.h, lo3, hi3, d3, ch3, q, flags, float(fill), _dev_ptr(out_ptr), 1,
-                                                       C.c_void_p(stream or 0), int(async_)))
-            return None
-        shape = tuple(max(int(d), 0) for d in dims[::-1])                      # the module checks the dims
-        out = np.empty(shape + (3,) if k == 3 else shape, dtype=np.float32)
-        self._check(lib().exa_hip_resample_derived(self.h, lo3, hi3, d3, ch3, q, flags, float(fill), out.ctypes.data, 0, None, 0))
+        out, dest = _lattice_out(dims, (3,) if k == 3 else (), out_ptr, stream, async_)
+        self._check(lib().exa_hip_resample_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), q, flags, float(fill), *dest))
         return out
 
     def extractIsoSurfaceDerived(self, lo, hi, dims, iso, quantity, channels=(0, 1, 2), world=False, gradients=False,
                                  stream=None):
         """extractIsoSurface on the lattice of resampleDerived(lo, hi, dims, quantity, channels): (numVertices, numTriangles).
         One-component quantities only; gradients=True is refused by the module."""
-        flags = self._probe_world(world) | (SAMPLE_GRADIENT if gradients else 0)
-        nv, nt = C.c_uint64(0), C.c_uint64(0)
-        self._check(lib().exa_hip_isosurface_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), derived_quantity(quantity),
-                                                     float(iso), flags, C.byref(nv), C.byref(nt), C.c_void_p(stream or 0)))
-        self._iso_counts = (int(nv.value), int(nt.value), False)
-        return self._iso_counts[:2]
+        return self._extract_iso(lo, hi, dims, iso, None, quantity, channels, world, gradients, stream)
 
     def isosurfaceDerived(self, lo, hi, dims, iso, quantity, channels=(0, 1, 2), world=False):
         """the iso-surface quantity == iso on the lattice of resampleDerived(lo, hi, dims, quantity, channels), as isosurface:
         (verts float32 [n,3], tris int32 [m,3]).  The device copy is released before returning."""
         self.extractIsoSurfaceDerived(lo, hi, dims, iso, quantity, channels=channels, world=world)
-        try:
-            return self.readIsoSurface()[:2]
-        finally:
-            self.releaseIsoSurface()
+        return self._one_shot(self.readIsoSurface, self.releaseIsoSurface)[:2]
 
     # ---- contour lines on a plane lattice (exa_hip_isolines*; include/exa_hip.h states the contract) ----
     def extractIsolines(self, origin, du, dv, size, isos, channel=0, world=False, gradients=False, values=False, quantity=None,
@@ -831,34 +818,26 @@ class Renderer:
         levels = np.ascontiguousarray(isos, dtype=np.float32).reshape(-1)
         nv, ns = C.c_uint64(0), C.c_uint64(0)
         self._isolines = None
-        if quantity is None:
-            rc = lib().exa_hip_isolines(self.h, C.byref(plane), int(channel), levels.ctypes.data, len(levels), flags,
-                                        C.byref(nv), C.byref(ns), C.c_void_p(stream or 0))
-        else:
-            rc = lib().exa_hip_isolines_derived(self.h, C.byref(plane), _i3(channels), derived_quantity(quantity),
-                                                levels.ctypes.data, len(levels), flags, C.byref(nv), C.byref(ns),
-                                                C.c_void_p(stream or 0))
-        self._check(rc)
-        self._isolines = (int(nv.value), int(ns.value), len(levels), bool(gradients), (int(size[1]), int(size[0])) if values else None)
+        self._check(self._field_call(lib().exa_hip_isolines, lib().exa_hip_isolines_derived, (C.byref(plane),), channel, quantity,
+                                     channels, (levels.ctypes.data, len(levels), flags, C.byref(nv), C.byref(ns),
+                                                C.c_void_p(stream or 0))))
+        self._isolines = _Isolines(int(nv.value), int(ns.value), len(levels), bool(gradients),
+                                   (int(size[1]), int(size[0])) if values else None)
         return self._isolines[:2]
 
     def readIsolines(self):
         """the last extractIsolines as a dict: vertices float32 [V,3], uv float32 [V,2], segments int32 [S,2] (global vertex
         indices), vertex_offsets and segment_offsets uint64 [levels + 1], and gradients float32 [V,3] / values float32
         [nv,nu] where the extraction kept them"""
-        if not getattr(self, "_isolines", None):
-            self._check(lib().exa_hip_isolines_read(self.h, None, None, None, None, None, None, None, 0, None))   # refused
-            raise RuntimeError("readIsolines: no extraction of this renderer to read")
-        nv, ns, nl, grad, shape = self._isolines
-        out = dict(vertices=np.empty((nv, 3), np.float32), uv=np.empty((nv, 2), np.float32), segments=np.empty((ns, 2), np.int32),
-                   vertex_offsets=np.empty(nl + 1, np.uint64), segment_offsets=np.empty(nl + 1, np.uint64))
-        if grad:
-            out["gradients"] = np.empty((nv, 3), np.float32)
-        if shape:
-            out["values"] = np.empty(shape, np.float32)
-        ptr = lambda k: out[k].ctypes.data if k in out else None                # noqa: E731
-        self._check(lib().exa_hip_isolines_read(self.h, ptr("vertices"), ptr("uv"), ptr("gradients"), ptr("segments"),
-                                                ptr("vertex_offsets"), ptr("segment_offsets"), ptr("values"), 0, None))
+        kept = self._isolines
+        if kept is None:
+            self._refused_read(lib().exa_hip_isolines_read, 7, "readIsolines")
+        table = (("vertices", (kept.vertices, 3), np.float32), ("uv", (kept.vertices, 2), np.float32),
+                 ("gradients", (kept.vertices, 3) if kept.gradients else None, np.float32),
+                 ("segments", (kept.segments, 2), np.int32), ("vertex_offsets", (kept.levels + 1,), np.uint64),
+                 ("segment_offsets", (kept.levels + 1,), np.uint64), ("values", kept.values_shape, np.float32))
+        out = _outputs(table)
+        self._check(lib().exa_hip_isolines_read(self.h, *_pointers(table, out), 0, None))
         return out
 
     def releaseIsolines(self):
@@ -868,9 +847,7 @@ class Renderer:
     def isolinesStageMs(self):
         """device ms of the last extraction's stages, summed over the levels: positions and values, square pass, point pass,
         scans, emit, gradients"""
-        ms = (C.c_float * 6)()
-        self._check(lib().exa_hip_isolines_stage_ms(self.h, ms))
-        return [float(v) for v in ms]
+        return self._stage_ms(lib().exa_hip_isolines_stage_ms, 6)
 
     def isolines(self, origin, du, dv, size, isos, channel=0, world=False, gradients=False, values=False):
         """the contour lines field == iso of `channel`, for every iso of `isos`, on the plane lattice of extractIsolines, by
@@ -878,18 +855,12 @@ class Renderer:
         level l owns vertices[vertex_offsets[l]:vertex_offsets[l+1]] and segments[segment_offsets[l]:segment_offsets[l+1]].
         The device copy is released before returning."""
         self.extractIsolines(origin, du, dv, size, isos, channel=channel, world=world, gradients=gradients, values=values)
-        try:
-            return self.readIsolines()
-        finally:
-            self.releaseIsolines()
+        return self._one_shot(self.readIsolines, self.releaseIsolines)
 
     def isolinesDerived(self, origin, du, dv, size, isos, quantity, channels=(0, 1, 2), world=False, values=False):
         """isolines of a one-component derived quantity (a key of DERIVED, or its number) of the vector field `channels`"""
         self.extractIsolines(origin, du, dv, size, isos, world=world, values=values, quantity=quantity, channels=channels)
-        try:
-            return self.readIsolines()
-        finally:
-            self.releaseIsolines()
+        return self._one_shot(self.readIsolines, self.releaseIsolines)
 
     # ---- connected regions of field >= iso on a lattice (exa_hip_regions*; include/exa_hip.h states the contract) ----
     def extractRegions(self, lo, hi, dims, iso, channel=0, world=False, below=False, faces=False, keep_values=False,
@@ -898,34 +869,39 @@ class Renderer:
         the Kuhn edges (faces: the axis edges only), into module-owned device memory; with a `quantity` the regions of that
         derived quantity of `channels`.  Returns (numRegions, numInside, sum_exponent).  readRegions copies the result out,
         releaseRegions frees it."""
-        flags = (self._probe_world(world) | (REGIONS_BELOW if below else 0) | (REGIONS_FACES if faces else 0)
-                 | (REGIONS_KEEP_VALUES if keep_values else 0))
+        flags = self._labelled_flags(world, below, faces, keep_values)
         nr, ni, se = C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
         self._regions = None
-        if quantity is None:
-            rc = lib().exa_hip_regions(self.h, _f3(lo), _f3(hi), _i3(dims), int(channel), float(iso), flags, C.byref(nr),
-                                       C.byref(ni), C.byref(se), C.c_void_p(stream or 0))
-        else:
-            rc = lib().exa_hip_regions_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), derived_quantity(quantity),
-                                               float(iso), flags, C.byref(nr), C.byref(ni), C.byref(se), C.c_void_p(stream or 0))
-        self._check(rc)
-        self._regions = (int(nr.value), int(ni.value), int(se.value), tuple(int(d) for d in dims[::-1]), bool(keep_values))
-        return self._regions[:3]
+        self._check(self._field_call(lib().exa_hip_regions, lib().exa_hip_regions_derived, (_f3(lo), _f3(hi), _i3(dims)), channel,
+                                     quantity, channels, (float(iso), flags, C.byref(nr), C.byref(ni), C.byref(se),
+                                                          C.c_void_p(stream or 0))))
+        self._regions = _Labelled(int(nr.value), tuple(int(d) for d in dims[::-1]), bool(keep_values),
+                                  dict(sum_exponent=int(se.value), num_inside=int(ni.value)))
+        return int(nr.value), int(ni.value), int(se.value)
+
+    def _labelled_flags(self, world, below, faces, keep_values):
+        """the flags of extractRegions and extractBasins"""
+        return (self._probe_world(world) | (REGIONS_BELOW if below else 0) | (REGIONS_FACES if faces else 0)
+                | (REGIONS_KEEP_VALUES if keep_values else 0))
+
+    def _read_labelled(self, kept, read, method, dtype, tables):
+        """the dict of readRegions and readBasins: labels, one zero-filled table of `dtype` under each key of `tables`, the
+        numbers the extraction returned, and the values where it kept them"""
+        if kept is None:
+            self._refused_read(read, 3, method)
+        table = np.zeros(kept.count, dtype)
+        out = dict(labels=np.empty(kept.shape, np.int32), **dict.fromkeys(tables, table), **kept.numbers)
+        if kept.keep_values:
+            out["values"] = np.empty(kept.shape, np.float32)
+        self._check(read(self.h, out["labels"].ctypes.data, table.ctypes.data if kept.count else None, _host_ptr(out.get("values")),
+                         0, None))
+        return out
 
     def readRegions(self):
         """the last extractRegions as a dict: labels int32 [nz, ny, nx] (the region's number, -1 outside), regions (a
         structured array of LABELLED_REGION_DTYPE, numbered by ascending `first`), sum_exponent, num_inside, and values float32
         [nz, ny, nx] where the extraction kept them"""
-        if not getattr(self, "_regions", None):
-            self._check(lib().exa_hip_regions_read(self.h, None, None, None, 0, None))      # refused
-            raise RuntimeError("readRegions: no extraction of this renderer to read")
-        nr, ni, se, shape, keep = self._regions
-        out = dict(labels=np.empty(shape, np.int32), regions=np.zeros(nr, LABELLED_REGION_DTYPE), sum_exponent=se, num_inside=ni)
-        if keep:
-            out["values"] = np.empty(shape, np.float32)
-        self._check(lib().exa_hip_regions_read(self.h, out["labels"].ctypes.data, out["regions"].ctypes.data if nr else None,
-                                               out["values"].ctypes.data if keep else None, 0, None))
-        return out
+        return self._read_labelled(self._regions, lib().exa_hip_regions_read, "readRegions", LABELLED_REGION_DTYPE, ("regions",))
 
     def releaseRegions(self):
         self._check(lib().exa_hip_regions_release(self.h))
@@ -933,29 +909,21 @@ class Renderer:
 
     def regionsStageMs(self):
         """device ms of the last extractRegions' stages: values, init, merge, flatten, rank, stats"""
-        ms = (C.c_float * 6)()
-        self._check(lib().exa_hip_regions_stage_ms(self.h, ms))
-        return [float(v) for v in ms]
+        return self._stage_ms(lib().exa_hip_regions_stage_ms, 6)
 
     def regions(self, lo, hi, dims, iso, channel=0, world=False, below=False, faces=False, keep_values=False):
         """the connected regions of field >= iso of `channel` on the lattice of resample(lo, hi, dims): the dict of
         readRegions (region_measures turns its table into sums, means, volumes, integrals and centroids).  The device copy
         is released before returning."""
         self.extractRegions(lo, hi, dims, iso, channel=channel, world=world, below=below, faces=faces, keep_values=keep_values)
-        try:
-            return self.readRegions()
-        finally:
-            self.releaseRegions()
+        return self._one_shot(self.readRegions, self.releaseRegions)
 
     def regionsDerived(self, lo, hi, dims, iso, quantity, channels=(0, 1, 2), world=False, below=False, faces=False,
                        keep_values=False):
         """regions of a one-component derived quantity (a key of DERIVED, or its number) of the vector field `channels`"""
         self.extractRegions(lo, hi, dims, iso, world=world, below=below, faces=faces, keep_values=keep_values,
                             quantity=quantity, channels=channels)
-        try:
-            return self.readRegions()
-        finally:
-            self.releaseRegions()
+        return self._one_shot(self.readRegions, self.releaseRegions)
 
     # ---- profiles and phase plots on a lattice (exa_hip_profile; include/exa_hip.h states the contract) ----
     def profile(self, lo, hi, dims, axes, values=(), weight=None, world=False, minmax=True, stream=None):
@@ -979,8 +947,7 @@ class Renderer:
         sum_weight = np.zeros(room, np.int64) if weight is not None else None
         sums = np.zeros((nv, room), np.int64)
         mins, maxs = (np.zeros((nv, room), np.float32), np.zeros((nv, room), np.float32)) if minmax else (None, None)
-        st = ExaHipProfileStats()
-        ptr = lambda a: a.ctypes.data if a is not None else None                              # noqa: E731
+        st, ptr = ExaHipProfileStats(), _host_ptr
         self._check(lib().exa_hip_profile(self.h, _f3(lo), _f3(hi), _i3(dims), flags, ax, len(axes), vals if nv else None, nv,
                                           C.byref(weight) if weight is not None else None, ptr(count), ptr(sum_weight),
                                           ptr(sums) if nv else None, ptr(mins), ptr(maxs), C.byref(st), C.c_void_p(stream or 0)))
@@ -990,9 +957,7 @@ class Renderer:
 
     def profileStageMs(self):
         """device ms of the last profile's stages: values, classify, accumulate, finish"""
-        ms = (C.c_float * 4)()
-        self._check(lib().exa_hip_profile_stage_ms(self.h, ms))
-        return [float(v) for v in ms]
+        return self._stage_ms(lib().exa_hip_profile_stage_ms, 4)
 
     # ---- basins: one per peak of field >= iso, merged by depth (exa_hip_basins*; include/exa_hip.h states the contract) ----
     def extractBasins(self, lo, hi, dims, iso, min_depth, channel=0, world=False, below=False, faces=False, keep_values=False,
@@ -1002,38 +967,22 @@ class Renderer:
         across it; into module-owned device memory.  With a `quantity` the basins of that derived quantity of `channels`.
         Returns (numBasins, numRawBasins, numInside, sum_exponent, rounds).  readBasins copies the result out, releaseBasins
         frees it."""
-        flags = (self._probe_world(world) | (REGIONS_BELOW if below else 0) | (REGIONS_FACES if faces else 0)
-                 | (REGIONS_KEEP_VALUES if keep_values else 0))
+        flags = self._labelled_flags(world, below, faces, keep_values)
         nb, nr, ni, se, rounds = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0), C.c_int32(0)
         self._basins = None
-        if quantity is None:
-            rc = lib().exa_hip_basins(self.h, _f3(lo), _f3(hi), _i3(dims), int(channel), float(iso), float(min_depth), flags,
-                                      C.byref(nb), C.byref(nr), C.byref(ni), C.byref(se), C.byref(rounds), C.c_void_p(stream or 0))
-        else:
-            rc = lib().exa_hip_basins_derived(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), derived_quantity(quantity),
-                                              float(iso), float(min_depth), flags, C.byref(nb), C.byref(nr), C.byref(ni),
-                                              C.byref(se), C.byref(rounds), C.c_void_p(stream or 0))
-        self._check(rc)
-        self._basins = (int(nb.value), int(nr.value), int(ni.value), int(se.value), int(rounds.value),
-                        tuple(int(d) for d in dims[::-1]), bool(keep_values))
-        return self._basins[:5]
+        self._check(self._field_call(lib().exa_hip_basins, lib().exa_hip_basins_derived, (_f3(lo), _f3(hi), _i3(dims)), channel,
+                                     quantity, channels, (float(iso), float(min_depth), flags, C.byref(nb), C.byref(nr), C.byref(ni),
+                                                          C.byref(se), C.byref(rounds), C.c_void_p(stream or 0))))
+        self._basins = _Labelled(int(nb.value), tuple(int(d) for d in dims[::-1]), bool(keep_values),
+                                 dict(sum_exponent=int(se.value), num_inside=int(ni.value), num_raw=int(nr.value),
+                                      rounds=int(rounds.value)))
+        return int(nb.value), int(nr.value), int(ni.value), int(se.value), int(rounds.value)
 
     def readBasins(self):
         """the last extractBasins as a dict: the keys of readRegions (labels int32 [nz, ny, nx], the basin's number or -1;
         sum_exponent; num_inside; values where kept) with the table under `regions` and under `basins` (a structured array of
         BASIN_DTYPE, numbered by ascending lattice index of the peak), num_raw and rounds"""
-        if not getattr(self, "_basins", None):
-            self._check(lib().exa_hip_basins_read(self.h, None, None, None, 0, None))       # refused
-            raise RuntimeError("readBasins: no extraction of this renderer to read")
-        nb, nr, ni, se, rounds, shape, keep = self._basins
-        table = np.zeros(nb, BASIN_DTYPE)
-        out = dict(labels=np.empty(shape, np.int32), regions=table, basins=table, sum_exponent=se, num_inside=ni, num_raw=nr,
-                   rounds=rounds)
-        if keep:
-            out["values"] = np.empty(shape, np.float32)
-        self._check(lib().exa_hip_basins_read(self.h, out["labels"].ctypes.data, table.ctypes.data if nb else None,
-                                              out["values"].ctypes.data if keep else None, 0, None))
-        return out
+        return self._read_labelled(self._basins, lib().exa_hip_basins_read, "readBasins", BASIN_DTYPE, ("regions", "basins"))
 
     def releaseBasins(self):
         self._check(lib().exa_hip_basins_release(self.h))
@@ -1041,29 +990,21 @@ class Renderer:
 
     def basinsStageMs(self):
         """device ms of the last extractBasins' stages: values, ascent, passes, links, rank, stats"""
-        ms = (C.c_float * 6)()
-        self._check(lib().exa_hip_basins_stage_ms(self.h, ms))
-        return [float(v) for v in ms]
+        return self._stage_ms(lib().exa_hip_basins_stage_ms, 6)
 
     def basins(self, lo, hi, dims, iso, min_depth, channel=0, world=False, below=False, faces=False, keep_values=False):
         """the basins of field >= iso of `channel` on the lattice of resample(lo, hi, dims): the dict of readBasins
         (region_measures reads its table as it reads that of regions).  The device copy is released before returning."""
         self.extractBasins(lo, hi, dims, iso, min_depth, channel=channel, world=world, below=below, faces=faces,
                            keep_values=keep_values)
-        try:
-            return self.readBasins()
-        finally:
-            self.releaseBasins()
+        return self._one_shot(self.readBasins, self.releaseBasins)
 
     def basinsDerived(self, lo, hi, dims, iso, min_depth, quantity, channels=(0, 1, 2), world=False, below=False, faces=False,
                       keep_values=False):
         """basins of a one-component derived quantity (a key of DERIVED, or its number) of the vector field `channels`"""
         self.extractBasins(lo, hi, dims, iso, min_depth, world=world, below=below, faces=faces, keep_values=keep_values,
                            quantity=quantity, channels=channels)
-        try:
-            return self.readBasins()
-        finally:
-            self.releaseBasins()
+        return self._one_shot(self.readBasins, self.releaseBasins)
 
     # ---- critical points of a flow on a lattice (exa_hip_critical_points*; include/exa_hip.h states the contract) ----
     def extractCriticalPoints(self, lo, hi, dims, channels=(0, 1, 2), iterations=8, tolerance=2.0 ** -10, world=False, probe=False,
@@ -1076,22 +1017,22 @@ class Renderer:
         self._critical = None
         self._check(lib().exa_hip_critical_points(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), int(iterations), float(tolerance),
                                                   flags, C.byref(n), st, C.c_void_p(stream or 0)))
-        self._critical = (int(n.value), bool(probe))
+        self._critical = _Critical(int(n.value), bool(probe))
         return int(n.value), dict(zip(CRITICAL_STATS, (int(v) for v in st)))
 
     def readCriticalPoints(self):
         """the last extractCriticalPoints: (points, a structured array of CRITICAL_POINT_DTYPE in ascending cell number; probe
         float32 [n, 3, 4] = value and voxel-space gradient of each channel at each position, or None; probe_status int32 [n, 3]
         or None)"""
-        if not getattr(self, "_critical", None):
-            self._check(lib().exa_hip_critical_points_read(self.h, None, None, None, 0, None))      # refused
-            raise RuntimeError("readCriticalPoints: no extraction of this renderer to read")
-        n, probed = self._critical
+        kept = self._critical
+        if kept is None:
+            self._refused_read(lib().exa_hip_critical_points_read, 3, "readCriticalPoints")
+        n = kept.points
         points = np.zeros(n, CRITICAL_POINT_DTYPE)
-        probe = np.empty((n, 3, 4), np.float32) if probed else None
-        status = np.empty((n, 3), np.int32) if probed else None
-        self._check(lib().exa_hip_critical_points_read(self.h, points.ctypes.data if n else None, probe.ctypes.data if probed and n else None,
-                                                       status.ctypes.data if probed and n else None, 0, None))
+        probe = np.empty((n, 3, 4), np.float32) if kept.probe else None
+        status = np.empty((n, 3), np.int32) if kept.probe else None
+        self._check(lib().exa_hip_critical_points_read(self.h, *[_host_ptr(a) if n else None for a in (points, probe, status)],
+                                                       0, None))
         return points, probe, status
 
     def releaseCriticalPoints(self):
@@ -1100,9 +1041,7 @@ class Renderer:
 
     def criticalPointsStageMs(self):
         """device ms of the last extractCriticalPoints' stages: values, cells, scans, refine, emit, probe"""
-        ms = (C.c_float * 6)()
-        self._check(lib().exa_hip_critical_points_stage_ms(self.h, ms))
-        return [float(v) for v in ms]
+        return self._stage_ms(lib().exa_hip_critical_points_stage_ms, 6)
 
     def criticalPoints(self, lo, hi, dims, channels=(0, 1, 2), iterations=8, tolerance=2.0 ** -10, world=False, probe=False):
         """the critical points of the vector field `channels` on the lattice of resample(lo, hi, dims): (points, stats), with
@@ -1110,10 +1049,7 @@ class Renderer:
         a positive real part; CRITICAL names the other bits.  The device copy is released before returning."""
         _, stats = self.extractCriticalPoints(lo, hi, dims, channels=channels, iterations=iterations, tolerance=tolerance,
                                               world=world, probe=probe)
-        try:
-            points, values, status = self.readCriticalPoints()
-        finally:
-            self.releaseCriticalPoints()
+        points, values, status = self._one_shot(self.readCriticalPoints, self.releaseCriticalPoints)
         return (points, stats, values, status) if probe else (points, stats)
 
     def derivedMs(self):
@@ -1155,28 +1091,28 @@ class Renderer:
         flags = (STREAM_FORWARD if forward else 0) | (STREAM_BACKWARD if backward else 0)
         flags |= (STREAM_NORMALIZE if normalize else 0) | (STREAM_VELOCITIES if velocities else 0)
         nv = C.c_uint64(0)
-        self._stream_counts = (0, 0, False)
+        self._stream_counts = _StreamLines(0, 0, False)
         self._check(lib().exa_hip_streamlines(self.h, pts.ctypes.data, pts.shape[0], ch3, float(step), int(max_steps), flags,
                                               C.byref(nv), C.c_void_p(stream or 0)))
-        self._stream_counts = (pts.shape[0], int(nv.value), bool(velocities))
+        self._stream_counts = _StreamLines(pts.shape[0], int(nv.value), bool(velocities))
         return int(nv.value)
 
     def readStreamlines(self):
         """(vertices float32 [V,3], offsets uint64 [n+1], seed_vertex uint32 [n], reasons int32 [n,2] (backward, forward),
         velocities float32 [V,3] or None) of the last extractStreamlines"""
-        n, nv, vel = getattr(self, "_stream_counts", (0, 0, False))
+        n, nv = self._stream_counts.seeds, self._stream_counts.vertices
         verts = np.empty((nv, 3), dtype=np.float32)
-        vels = np.empty((nv, 3), dtype=np.float32) if vel else None
+        vels = np.empty((nv, 3), dtype=np.float32) if self._stream_counts.velocities else None
         offsets = np.empty(n + 1, dtype=np.uint64)
         seed_vertex = np.empty(n, dtype=np.uint32)
         reasons = np.empty((n, 2), dtype=np.int32)
-        self._check(lib().exa_hip_streamlines_read(self.h, verts.ctypes.data, vels.ctypes.data if vel else None,
-                                                   offsets.ctypes.data, seed_vertex.ctypes.data, reasons.ctypes.data, 0, None))
+        self._check(lib().exa_hip_streamlines_read(self.h, verts.ctypes.data, _host_ptr(vels), offsets.ctypes.data,
+                                                   seed_vertex.ctypes.data, reasons.ctypes.data, 0, None))
         return verts, offsets, seed_vertex, reasons, vels
 
     def releaseStreamlines(self):
         self._check(lib().exa_hip_streamlines_release(self.h))
-        self._stream_counts = (0, 0, False)
+        self._stream_counts = _StreamLines(0, 0, False)
 
     def streamlinesMs(self):
         """device ms of the last extraction's two kernels (count and emit), summed"""
@@ -1191,10 +1127,7 @@ class Renderer:
         forward).  The device copy is released before returning."""
         self.extractStreamlines(seeds, channels=channels, step=step, max_steps=max_steps, forward=forward, backward=backward,
                                 normalize=normalize, velocities=velocities)
-        try:
-            return self.readStreamlines()
-        finally:
-            self.releaseStreamlines()
+        return self._one_shot(self.readStreamlines, self.releaseStreamlines)
 
     # ---- line integral convolution on a cut plane (exa_hip_lic; include/exa_hip.h states the contract) ----
     def lic(self, plane, channels=(0, 1, 2), step=0.5, half_length=20, noise=None, seed=0, fill=float("nan"), stream=None):
@@ -1210,13 +1143,10 @@ class Renderer:
             noise = np.ascontiguousarray(noise, dtype=np.uint8)
             if noise.size != nu * nv:
                 raise ValueError("lic: the noise must hold nu * nv bytes")
-        shape = (max(nv, 0), max(nu, 0))
-        out = dict(lic=np.empty(shape, np.float32), sum=np.empty(shape, np.uint32), count=np.empty(shape, np.uint32),
-                   speed=np.empty(shape, np.float32), reasons=np.empty(shape + (2,), np.int32))
-        self._check(lib().exa_hip_lic(self.h, C.byref(s), _i3(channels), float(step), int(half_length),
-                                      noise.ctypes.data if noise is not None else None, int(seed) & 0xFFFFFFFF, 0, float(fill),
-                                      out["lic"].ctypes.data, out["sum"].ctypes.data, out["count"].ctypes.data,
-                                      out["speed"].ctypes.data, out["reasons"].ctypes.data, 0, C.c_void_p(stream or 0)))
+        out = _outputs(_LIC_OUT, (max(nv, 0), max(nu, 0)))
+        self._check(lib().exa_hip_lic(self.h, C.byref(s), _i3(channels), float(step), int(half_length), _host_ptr(noise),
+                                      int(seed) & 0xFFFFFFFF, 0, float(fill), *_pointers(_LIC_OUT, out), 0,
+                                      C.c_void_p(stream or 0)))
         return out
 
     def licMs(self):
@@ -1231,21 +1161,16 @@ class Renderer:
         stretch (float32: the largest eigenvalue of the Cauchy-Green tensor; `fill` where the point or a stencil neighbour did
         not last the time) and ftle (float32: log(stretch) / (2 |T|), T = num_steps * step, formed in float64; `fill` where
         stretch is)."""
-        shape = tuple(max(int(d), 0) for d in tuple(dims)[::-1])                # the module checks the dims
-        out = dict(end=np.empty(shape + (3,), np.float32), steps=np.empty(shape, np.uint32), reasons=np.empty(shape, np.int32),
-                   stretch=np.empty(shape, np.float32))
+        out = _outputs(_FLOWMAP_OUT, _lattice_shape(dims))
         self._check(lib().exa_hip_flowmap(self.h, _f3(lo), _f3(hi), _i3(dims), _i3(channels), float(step), int(num_steps),
-                                          FLOWMAP_BACKWARD if backward else FLOWMAP_FORWARD, float(fill), out["end"].ctypes.data,
-                                          out["steps"].ctypes.data, out["reasons"].ctypes.data, out["stretch"].ctypes.data, 0,
-                                          C.c_void_p(stream or 0)))
+                                          FLOWMAP_BACKWARD if backward else FLOWMAP_FORWARD, float(fill),
+                                          *_pointers(_FLOWMAP_OUT, out), 0, C.c_void_p(stream or 0)))
         out["ftle"] = ftle_of_stretch(out["stretch"], step, num_steps, fill)
         return out
 
     def flowmapMs(self):
         """device ms of the last flowmap call's two stages: (integrate, stretch)"""
-        ms = (C.c_float * 2)(0, 0)
-        self._check(lib().exa_hip_flowmap_ms(self.h, ms))
-        return float(ms[0]), float(ms[1])
+        return tuple(self._stage_ms(lib().exa_hip_flowmap_ms, 2))
 
     # ---- projections along rays (exa_hip_project; include/exa_hip.h states the contract) ----
     def project(self, org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples, channel=0, world=False,
@@ -1258,11 +1183,9 @@ class Renderer:
         sample index of the first maximum, -1 for none)."""
         flags = self._probe_world(world) | (PROJECT_NORMALIZE if normalize else 0)
         rays, shape = _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples)
-        out = dict(sum=np.empty(shape, np.float64), count=np.empty(shape, np.uint32), max=np.empty(shape, np.float32),
-                   min=np.empty(shape, np.float32), max_index=np.empty(shape, np.int32))
-        self._check(lib().exa_hip_project(self.h, C.byref(rays), int(channel), flags, out["sum"].ctypes.data,
-                                          out["count"].ctypes.data, out["max"].ctypes.data, out["min"].ctypes.data,
-                                          out["max_index"].ctypes.data, 0, C.c_void_p(stream or 0)))
+        out = _outputs(_PROJECT_OUT, shape)
+        self._check(lib().exa_hip_project(self.h, C.byref(rays), int(channel), flags, *_pointers(_PROJECT_OUT, out), 0,
+                                          C.c_void_p(stream or 0)))
         return out
 
     def projectMs(self):
@@ -1283,31 +1206,18 @@ class Renderer:
         nc = min(len(ch), SURFACE_MAX_CHANNELS)                                 # the module checks the number
         flags = self._probe_world(world)
         args = (ch.ctypes.data, len(ch), float(spacing), int(max_n))
+        empty, ptr, device = _like(vertices)
         if vertices is None and triangles is None:
-            nt = getattr(self, "_iso_counts", (0, 0, False))[1]
-            mesh, flags, device = (None, 0, None, 0), flags | SURFACE_FROM_ISOSURFACE, False
-        elif getattr(vertices, "is_cuda", False):
-            import torch
-            if (vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous()
-                    or not triangles.is_contiguous() or vertices.numel() % 3 or triangles.numel() % 3):
-                raise TypeError("vertices: a contiguous float32 tensor [nv, 3]; triangles: a contiguous int32 tensor [m, 3]")
-            nt = triangles.numel() // 3
-            mesh, device = (_dev_ptr(vertices), vertices.numel() // 3, _dev_ptr(triangles), nt), True
-            out = dict(sum=torch.empty((nt, nc), dtype=torch.float64, device=vertices.device),
-                       count=torch.empty((nt, nc), dtype=torch.int32, device=vertices.device),
-                       areaNormal=torch.empty((nt, 3), dtype=torch.float32, device=vertices.device),
-                       subdiv=torch.empty(nt, dtype=torch.int32, device=vertices.device))
-            self._check(lib().exa_hip_sample_triangles(self.h, *mesh, *args, flags, *[C.c_void_p(out[k].data_ptr()) for k in SURFACE_KEYS], 1,
-                                                       C.c_void_p(stream or 0)))
-            return out
+            nt, mesh, flags = self._iso_counts.triangles, (None, 0, None, 0), flags | SURFACE_FROM_ISOSURFACE
         else:
-            verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
-            tris = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-            nt = tris.shape[0]
-            mesh = (verts.ctypes.data, verts.shape[0], tris.ctypes.data, nt)
-        out = dict(sum=np.zeros((nt, nc), np.float64), count=np.zeros((nt, nc), np.uint32), areaNormal=np.zeros((nt, 3), np.float32),
-                   subdiv=np.zeros(nt, np.int32))
-        self._check(lib().exa_hip_sample_triangles(self.h, *mesh, *args, flags, *[out[k].ctypes.data for k in SURFACE_KEYS], 0,
+            text = "vertices: a contiguous float32 tensor [nv, 3]; triangles: a contiguous int32 tensor [m, 3]"
+            (verts, nv), (tris, nt) = _rows3(vertices, np.float32, device, text), _rows3(triangles, np.int32, device, text)
+            mesh = (ptr(verts), nv, ptr(tris), nt)
+        # the host path hands out zero-filled arrays and a uint32 count; tensors come uninitialised, their count as int32
+        table = (("sum", (nc,), np.float64), ("count", (nc,), np.int32 if device else np.uint32),
+                 ("areaNormal", (3,), np.float32), ("subdiv", (), np.int32))
+        out = _outputs(table, (nt,), empty if device else np.zeros)
+        self._check(lib().exa_hip_sample_triangles(self.h, *mesh, *args, flags, *_pointers(table, out, ptr), int(device),
                                                    C.c_void_p(stream or 0)))
         return out
 
@@ -1333,17 +1243,90 @@ class Renderer:
             raise ValueError(f"unknown outputs {unknown} (of {', '.join(RAYCAST_KEYS)})")
         flags = self._probe_world(world) | (PROJECT_NORMALIZE if normalize else 0)
         rays, shape = _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples)
-        kinds = dict(t=((), np.float32), position=((3,), np.float32), value=((), np.float32), gradient=((3,), np.float32),
-                     index=((), np.int32), side=((), np.int32), crossings=((), np.uint32))
-        out = {k: np.empty(shape + kinds[k][0], kinds[k][1]) for k in RAYCAST_KEYS if k in outputs}
-        ptr = [out[k].ctypes.data if k in out else None for k in RAYCAST_KEYS]
+        table = [(k, tail if k in outputs else None, dtype) for k, tail, dtype in _RAYCAST_OUT]
+        out = _outputs(table, shape)
         self._check(lib().exa_hip_raycast_iso(self.h, C.byref(rays), int(channel), float(iso), int(refine), flags, float(fill),
-                                              *ptr, 0, C.c_void_p(stream or 0)))
+                                              *_pointers(table, out), 0, C.c_void_p(stream or 0)))
         return out
 
     def raycastIsoMs(self):
         """device ms of the last raycast_iso call's kernel launches, summed"""
         return self._ms(lib().exa_hip_raycast_iso_ms)
+
+
+# what a Renderer keeps of its last extraction, per family, for the read that follows
+_IsoMesh = namedtuple("_IsoMesh", "vertices triangles gradients")
+_StreamLines = namedtuple("_StreamLines", "seeds vertices velocities")
+_Isolines = namedtuple("_Isolines", "vertices segments levels gradients values_shape")
+_Labelled = namedtuple("_Labelled", "count shape keep_values numbers")          # regions and basins; numbers: those the read repeats
+_Critical = namedtuple("_Critical", "points probe")
+
+# the output arrays of a call in the order of its pointer arguments: (key, the shape behind the image's or lattice's, dtype)
+_LIC_OUT = (("lic", (), np.float32), ("sum", (), np.uint32), ("count", (), np.uint32), ("speed", (), np.float32),
+            ("reasons", (2,), np.int32))
+_FLOWMAP_OUT = (("end", (3,), np.float32), ("steps", (), np.uint32), ("reasons", (), np.int32), ("stretch", (), np.float32))
+_PROJECT_OUT = (("sum", (), np.float64), ("count", (), np.uint32), ("max", (), np.float32), ("min", (), np.float32),
+                ("max_index", (), np.int32))
+_RAYCAST_OUT = (("t", (), np.float32), ("position", (3,), np.float32), ("value", (), np.float32), ("gradient", (3,), np.float32),
+                ("index", (), np.int32), ("side", (), np.int32), ("crossings", (), np.uint32))
+assert tuple(k for k, _, _ in _RAYCAST_OUT) == RAYCAST_KEYS
+
+
+def _outputs(table, shape=(), empty=np.empty):
+    """the arrays such a table describes, over `shape`, by key; a row whose trailing shape is None is an output not wanted"""
+    return {k: empty(shape + tail, dtype) for k, tail, dtype in table if tail is not None}
+
+
+def _host_ptr(a):
+    """the pointer argument of a numpy array, null for None"""
+    return None if a is None else a.ctypes.data
+
+
+def _pointers(table, out, ptr=_host_ptr):
+    """the pointer arguments of the table's call: null for an output not wanted"""
+    return [ptr(out.get(k)) for k, _, _ in table]
+
+
+def _like(x):
+    """for the outputs of a call whose input x is a torch CUDA tensor or (anything else) host memory: (empty(shape, dtype),
+    uninitialised arrays of x's library, tensors on x's device; ptr(array or None), their pointer argument; whether it is
+    the device path)"""
+    if not getattr(x, "is_cuda", False):
+        return np.empty, _host_ptr, False
+    import torch
+    return (lambda shape, dtype: torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=x.device),
+            lambda a: None if a is None else C.c_void_p(a.data_ptr()), True)
+
+
+def _rows3(x, dtype, device, text):
+    """x as rows of three `dtype` values, and their number.  On the device path x is taken as it is, a contiguous tensor of
+    that dtype (else TypeError(text)); on the host path numpy converts it"""
+    if device:
+        import torch
+        if x.dtype != getattr(torch, np.dtype(dtype).name) or not x.is_contiguous() or x.numel() % 3:
+            raise TypeError(text)
+        return x, x.numel() // 3
+    a = np.ascontiguousarray(x, dtype=dtype).reshape(-1, 3)
+    return a, a.shape[0]
+
+
+def _target(device, stream, async_):
+    """the last three arguments of a call that writes host or device memory: only the device path has a stream to wait on"""
+    return (1, C.c_void_p(stream or 0), int(async_)) if device else (0, None, 0)
+
+
+def _lattice_shape(dims):
+    """the shape of an array over the lattice of resample, x fastest; the module checks the dims"""
+    return tuple(max(int(d), 0) for d in tuple(dims)[::-1])
+
+
+def _lattice_out(dims, tail, out_ptr, stream, async_):
+    """where a resample writes: (the float32 host array over the lattice it returns, or None with an out_ptr; the last four
+    arguments of its call)"""
+    if out_ptr is not None:
+        return None, (_dev_ptr(out_ptr),) + _target(True, stream, async_)
+    out = np.empty(_lattice_shape(dims) + tail, np.float32)
+    return out, (out.ctypes.data,) + _target(False, stream, async_)
 
 
 def _rays(org, orgDu, orgDv, dir, dirDu, dirDv, size, tmin, dt, num_samples):
