@@ -873,6 +873,91 @@ int exa_hip_profile(ExaHipRenderer *, const float lo[3], const float hi[3], cons
                     ExaHipProfileStats *stats /* or NULL */, void *hipStream);
 int exa_hip_profile_stage_ms(ExaHipRenderer *, float ms[4]);   /* values, classify, accumulate, finish */
 
+/* ---- distance transform: per point of the lattice the exact Euclidean distance to the nearest point of a set — the points
+ * where a field is >= iso (or < iso), the points that are not, or the points that carry a label — and which point that is.
+ * Wall distance (the distance to the nearest point without data), the distance from a surface field == iso for shell and
+ * boundary-layer profiles (exa_hip_profile takes labels), thickness and clearance of the blobs of exa_hip_regions /
+ * exa_hip_basins, the Voronoi partition labels[nearest].  New relative to the reference.  Every output is an integer or a
+ * float bit pattern that depends on no schedule: two runs give the same bytes. ----
+ *
+ * Lattice and values.  lo, hi, dims, EXA_SAMPLE_WORLD_SPACE, L = (k*ny + j)*nx + i and the limit of 2^31 - 1 points as for
+ * exa_hip_regions.  V(L) is exactly what exa_hip_resample(lo, hi, dims, channel, the same flag, fill = NaN) returns, for
+ * exa_hip_distance_derived what exa_hip_resample_derived(channels, quantity, ...) returns (one-component quantities only).
+ * inside(L) is the regions' rule: V(L) is finite and V(L) >= iso, with EXA_DISTANCE_BELOW finite and V(L) < iso.  NaN, +-Inf
+ * and filled points are never inside; iso must be finite.  So iso = -FLT_MAX with EXA_DISTANCE_TO_OUTSIDE gives the distance
+ * to the nearest point without data (every point with a finite value is inside, the targets are the others).
+ * exa_hip_distance_mask: inside(L) = (labels[L] == label), with label == -1 (labels[L] >= 0).  It reads no field, needs no kd
+ * tree and ignores EXA_SAMPLE_WORLD_SPACE; lo, hi and dims give only the spacing.
+ *
+ * Targets.  The target set T is the inside points, with EXA_DISTANCE_TO_OUTSIDE the points that are not inside.
+ * EXA_DISTANCE_SIGNED does both: a point that is not inside gets + its distance to the inside set, an inside point gets
+ * - its distance to the set of the others (nearest likewise); it excludes EXA_DISTANCE_TO_OUTSIDE.  Points beyond the lattice
+ * do not exist and are never targets.
+ *
+ * Spacing and terms.  h_a = (hi_a - lo_a) / float(n_a) as exa_hip_resample forms it, so distances are in the caller's space
+ * (also with EXA_SAMPLE_WORLD_SPACE).  term_a(d) = o*o with o = h_a * float(|d|).  Everything is float32, every operation is
+ * rounded separately, nothing is contracted.
+ *
+ * Passes (the contract).  X: a(i,j,k) is the target i' of row (j,k) with the least |i - i'|, of two the smaller i', -1 if the
+ * row holds none; gx = term_x(i - a), +INF without one.  Y: b(i,j,k) is the j' that minimises gx(i,j',k) + term_y(j - j'), of
+ * several the smallest j'; gy is that minimum.  Z: c is the k' that minimises gy(i,j,k') + term_z(k - k'), of several the
+ * smallest k'; d2 is that minimum.  nearest(L) is the linear index of (a(i, b(i,j,c), c), b(i,j,c), c).  A minimum of +INF
+ * (no target in reach of the pass, or a sum that overflows) has no index.
+ *
+ * Theorem.  d2 equals the minimum over all targets (i',j',k') of (term_x(i-i') + term_y(j-j')) + term_z(k-k') in float32:
+ * rounding is monotone, so x -> fl(x + c) is non-decreasing and commutes with min, pass by pass.  The separable result is the
+ * global brute-force minimum bit for bit.
+ *
+ * Reach.  maxDistance must be > 0 and may be +INF; limit = maxDistance*maxDistance, one float32 product.  A point with
+ * d2 > limit, or with no target at all (d2 = +INF), has dist = +INF (-INF on the inside branch of EXA_DISTANCE_SIGNED) and
+ * nearest = -1.  A target's own dist is +0.0 and its nearest is itself.  A finite maxDistance bounds the work: a pass stops
+ * looking once its term alone exceeds the limit.
+ *
+ * Outputs.  dist = sqrtf(d2), correctly rounded (with the sign above); nothing transcendental runs on the device.  nearest is
+ * a linear index L or -1.  stats: points = nx*ny*nz; inside = the number of inside points; reached = the number of points
+ * with a finite dist; maxDistance = the largest finite |dist|, 0 if there is none (an integer max on the bits of a
+ * non-negative float, so two runs give the same bytes).
+ *
+ * Independence.  The bytes depend only on the scene, the lattice, the channel(s) and the quantity (or the labels and the
+ * label), iso, maxDistance, the flags, basis_form and (world space) the transform — on nothing a frame sets, nor on walk,
+ * accel, brick_order, interleave, sample_patch or sample_uniform, nor on whether the arrays are host or device memory.
+ *
+ * Calls.  Synchronous on hipStream; a pending brick_order change is applied first; a multi-device handle runs on devices[0].
+ * dist and nearest are host memory, or memory of the handle's first device with pointersAreDevice; a NULL nearest skips that
+ * array and its gathers.  labels is host memory, or memory of the handle's first device with EXA_DISTANCE_LABELS_DEVICE.
+ * Whatever exa_hip_resample[_derived] refuses (no kd tree, world space before a frame state, a bad channel or quantity) the
+ * field calls refuse with their own name in front; the mask call needs none of that.  Further errors, each with a message
+ * that starts with the function's name and leaves the handle usable: a NULL lo, hi, dims, channels or dist; NULL labels; a
+ * box float that is not finite or a spacing that is not; dims < 1; too many points; a non-finite iso; a quantity of more than
+ * one component; maxDistance NaN or <= 0; EXA_DISTANCE_SIGNED together with EXA_DISTANCE_TO_OUTSIDE; unknown flag bits
+ * (EXA_DISTANCE_LABELS_DEVICE applies to the mask call only, EXA_DISTANCE_BELOW to the field calls only); label < -1; a failed
+ * allocation.  The kd descent's loop guard returns 3.
+ * exa_hip_distance_stage_ms: device ms of the last call's stages — values (the resampled field or the labels, and the inside
+ * test), rows, columns (y and z), finish; with EXA_DISTANCE_SIGNED the sums over both target sets.
+ *
+ * Memory.  While the call runs: 21 bytes per lattice point (a, b, c, gy and d2 of 4 bytes each and the inside byte; the
+ * values share d2's room and labels from the host share c's), and with host pointers 4 more for dist and 4 for nearest.
+ * Nothing is kept afterwards. */
+#define EXA_DISTANCE_BELOW          32   /* inside(v) = finite and v <  iso (default: finite and v >= iso; the regions' rule) */
+#define EXA_DISTANCE_TO_OUTSIDE     64   /* targets = the points that are NOT inside (default: the inside points) */
+#define EXA_DISTANCE_SIGNED        128   /* both: + distance to the inside set at non-inside points, - distance to the
+                                            non-inside set at inside points; excludes EXA_DISTANCE_TO_OUTSIDE */
+#define EXA_DISTANCE_LABELS_DEVICE 256   /* exa_hip_distance_mask: labels is memory of the handle's first device */
+typedef struct ExaHipDistanceStats { uint64_t points, inside, reached; float maxDistance; int32_t pad; } ExaHipDistanceStats;
+
+int exa_hip_distance(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel,
+                     float iso, float maxDistance, int32_t flags, float *dist /* n */, int32_t *nearest /* n, or NULL */,
+                     ExaHipDistanceStats *stats /* or NULL */, int32_t pointersAreDevice, void *hipStream);
+int exa_hip_distance_derived(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                             const int32_t channels[3], int32_t quantity, float iso, float maxDistance, int32_t flags,
+                             float *dist /* n */, int32_t *nearest /* n, or NULL */, ExaHipDistanceStats *stats /* or NULL */,
+                             int32_t pointersAreDevice, void *hipStream);
+int exa_hip_distance_mask(ExaHipRenderer *, const float lo[3], const float hi[3], const int32_t dims[3],
+                          const int32_t *labels /* n */, int32_t label, float maxDistance, int32_t flags,
+                          float *dist /* n */, int32_t *nearest /* n, or NULL */, ExaHipDistanceStats *stats /* or NULL */,
+                          int32_t pointersAreDevice, void *hipStream);
+int exa_hip_distance_stage_ms(ExaHipRenderer *, float ms[4]);   /* values, rows, columns (y and z), finish */
+
 /* ---- streamlines: field lines of the vector field formed by three channels, integrated from seed points with classical
  * RK4 at a fixed step and handed out as packed polylines.  An extraction, not the viewer's animation: the reference's tracer
  * (exa_hip_reset_tracer / exa_hip_advance_tracer) takes one step per rendered frame, forward only, at a trace count and

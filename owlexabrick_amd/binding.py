@@ -325,6 +325,10 @@ _ABI = {
     "exa_hip_profile": (None, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                _P(ExaHipProfileStats), _vp]),
     "exa_hip_profile_stage_ms": (None, [_vp, _vp]),
+    "exa_hip_distance": (None, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_distance_derived": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_distance_mask": (None, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "exa_hip_distance_stage_ms": (None, [_vp, _vp]),
     "exa_hip_histogram_ms": (None, [_vp, _P(_f32)]),
     "exa_hip_histogram": (None, [_vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _P(ExaHipFieldStats), _vp]),
     "exa_hip_streamlines": (None, [_vp, _vp, _u64, _vp, _f32, _i32, _i32, _P(_u64), _vp]),

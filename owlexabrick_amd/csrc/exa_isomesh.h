@@ -365,4 +365,56 @@ hipError_t launchIsoProfileClassify(const IsoProfileArgs &a, hipStream_t s);
 hipError_t launchIsoProfileAccumulate(const IsoProfileArgs &a, hipStream_t s);     // LDS or HBM by isoProfileLdsTable
 hipError_t launchIsoProfileFinish(const IsoProfileArgs &a, hipStream_t s);
 
+// ---- exact Euclidean distance transform on the lattice (exa_hip_distance): per lattice point the distance to the nearest
+// point of a target set and that point's index, by one pass per axis (include/exa_hip.h states the passes; they are the
+// contract).  A run of the passes serves one target set: the inside points, or (toOutside) the others.
+//   inside   the regions' inside test on the values, or the label rule on the labels: a byte per point, and the count
+//   row      a wave per row (j, k), 64 points per step: a ballot of the target bytes, per lane the nearest set bit at or below
+//            and at or above it by clz / ctz on the masked ballot; the last target of the chunks behind and the next one of
+//            the chunks ahead are carried along the row (the look-ahead reads every chunk once).  Writes a; gx is never
+//            stored, it is term_x(i - a)
+//   column   one lane per point, lanes along x, so a neighbouring row is read in whole lines.  A lane scans d = 0, 1, 2, ...
+//            on both sides and stops once term(d) > min(best, limit): the terms are monotone in d and a sum is no smaller
+//            than its term, so nothing further out can win or tie, and what lies beyond the limit is dropped by the finish
+//            pass anyway.  The minus side accepts <=, the plus side <: of equal candidates the smallest index stays.  Two
+//            steps a round, their four loads issued ahead of the stop tests (a side beyond the axis reads its own point).  Runs
+//            along y (reads a; writes b, gy), then along z (reads gy; writes c, d2).  EXA_DISTANCE_LDS: a block stages a slab
+//            of 64 columns by the whole scan axis in LDS first, where the axis fits (kIsoDistanceLdsAxis); plain loads beyond
+//   finish   the reach test, the square root, the sign, the two dependent gathers of `nearest`; reached points and the
+//            largest |dist| (an integer max on the float's bits).  With onlyOthers only the points that are not targets are
+//            written: EXA_DISTANCE_SIGNED runs the passes once per target set and each finish writes its own half
+#ifndef EXA_DISTANCE_LDS
+#define EXA_DISTANCE_LDS 0
+#endif
+static const uint32_t kIsoDistanceTiles = 16;             // blocks of the lattice per block of the inside and the finish pass
+static const uint32_t kIsoDistanceLdsAxis = 256;          // 64 columns x 256 floats = 64 KiB of LDS per workgroup
+static const int kIsoDistanceInside = 0, kIsoDistanceReached = 1, kIsoDistanceMaxBits = 2, kIsoDistanceCounters = 3;
+
+struct IsoDistanceArgs {
+  uint32_t numPoints;         // nx*ny*nz <= 2^31 - 1
+  uint32_t nx, ny, nz;
+  uint32_t numBlocks;         // of kIsoBlock points
+  float h[3];                 // the spacing; term_a(d) = o*o, o = h[a] * float(d)
+  float limit;                // maxDistance * maxDistance
+  const float *values;        // the inside pass of a field: numPoints
+  const int32_t *labels;      // the inside pass of a mask: numPoints
+  int32_t label;              // -1: any label >= 0
+  float iso;
+  uint32_t byLabel : 1, below : 1;
+  uint32_t toOutside : 1;     // the run: the targets are the points that are not inside
+  uint32_t negative : 1;      // finish: -dist
+  uint32_t onlyOthers : 1;    // finish: leave the targets' outputs alone
+  uint8_t *inside;            // numPoints
+  int32_t *a, *b, *c;         // numPoints each: the nearest target of the row, the argmin along y, along z (-1: none)
+  float *gy, *d2;             // numPoints each
+  float *dist;                // numPoints
+  int32_t *nearest;           // numPoints, or nullptr
+  unsigned long long *counters;   // [kIsoDistanceCounters], zeroed by the host
+};
+
+hipError_t launchIsoDistanceInside(const IsoDistanceArgs &a, hipStream_t s);
+hipError_t launchIsoDistanceRows(const IsoDistanceArgs &a, hipStream_t s);
+hipError_t launchIsoDistanceColumns(const IsoDistanceArgs &a, int axis, hipStream_t s);       // axis 1, then axis 2
+hipError_t launchIsoDistanceFinish(const IsoDistanceArgs &a, hipStream_t s);
+
 } // namespace exa

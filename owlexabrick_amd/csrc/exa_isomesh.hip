@@ -1685,6 +1685,204 @@ __global__ __launch_bounds__(kIsoBlock) void isoProfileFinishKernel(const IsoPro
   a.keyMax[at] = any ? __float_as_uint(regionValueOfKey(a.keyMax[at])) : 0xff800000u;
 }
 
+// ---- exact Euclidean distance transform (exa_hip_distance): the passes of exa_isomesh.h ----
+// term_a(d) of the contract: two roundings, nothing contracted
+__device__ __forceinline__ float distanceTerm(float h, uint32_t d)
+{
+  const float o = h * float(d);
+  return o * o;
+}
+
+// A count and the bits of a non-negative float of every lane, over the block, to counters[countSlot] and to the low word of
+// counters[bitsSlot]: one atomic each per block.  Every lane of the block comes here.
+__device__ __forceinline__ void distanceTotals(const IsoDistanceArgs &a, uint32_t *lds, uint32_t count, uint32_t bits, int countSlot, int bitsSlot)
+{
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t m = uint32_t(__shfl_xor(int(bits), o));
+    bits = m > bits ? m : bits;
+    count += uint32_t(__shfl_xor(int(count), o));
+  }
+  if ((threadIdx.x & 63u) == 0u) { lds[threadIdx.x >> 6] = count; lds[kIsoBlock / 64 + (threadIdx.x >> 6)] = bits; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t sum = 0, top = 0;
+    for (uint32_t w = 0; w < kIsoBlock / 64; w++) {
+      sum += lds[w];
+      top = lds[kIsoBlock / 64 + w] > top ? lds[kIsoBlock / 64 + w] : top;
+    }
+    if (sum) atomicAdd(a.counters + countSlot, (unsigned long long)sum);
+    if (top) atomicMax(reinterpret_cast<uint32_t *>(a.counters + bitsSlot), top);
+  }
+}
+
+__global__ __launch_bounds__(kIsoBlock) void isoDistanceInsideKernel(const IsoDistanceArgs a)
+{
+  __shared__ uint32_t lds[2 * (kIsoBlock / 64)];
+  uint32_t count = 0;
+  for (uint32_t t = 0; t < kIsoDistanceTiles; t++) {
+    const uint64_t at = (uint64_t(blockIdx.x) * kIsoDistanceTiles + t) * kIsoBlock + threadIdx.x;
+    if (at >= a.numPoints) break;
+    bool in;
+    if (a.byLabel) {
+      const int32_t l = a.labels[at];
+      in = a.label < 0 ? l >= 0 : l == a.label;
+    } else {
+      in = regionInside(a, a.values[at]);
+    }
+    a.inside[at] = in ? 1 : 0;
+    count += in ? 1u : 0u;
+  }
+  distanceTotals(a, lds, count, 0u, kIsoDistanceInside, kIsoDistanceMaxBits);
+}
+
+__device__ __forceinline__ bool distanceTarget(const IsoDistanceArgs &a, const uint8_t *row, uint32_t x)
+{
+  return x < a.nx && (row[x] != 0) != (a.toOutside != 0);
+}
+
+// A wave per row.  `last`: the largest target of the chunks behind this one; `next`: the smallest target of the chunks in
+// (c, looked), which the look-ahead has read, -1 if they hold none.  Every chunk is looked at once ahead and once in turn.
+__global__ __launch_bounds__(kIsoBlock) void isoDistanceRowKernel(const IsoDistanceArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t row = uint64_t(blockIdx.x) * (kIsoBlock / 64) + (threadIdx.x >> 6);
+  if (row >= uint64_t(a.ny) * a.nz) return;
+  const uint8_t *bits = a.inside + row * a.nx;
+  int32_t *out = a.a + row * a.nx;
+  const uint32_t chunks = (a.nx + 63u) / 64u;
+  const uint64_t atOrBelow = (2ull << lane) - 1ull, atOrAbove = ~((1ull << lane) - 1ull);
+  int32_t last = -1, next = -1;
+  uint32_t looked = 0;
+  for (uint32_t c = 0; c < chunks; c++) {
+    const uint32_t x = c * 64u + lane;
+    const uint64_t m = __ballot(distanceTarget(a, bits, x));
+    if (next >= 0 && uint32_t(next) < (c + 1u) * 64u) next = -1;        // it lies in this chunk now
+    if (looked < c + 1u) looked = c + 1u;
+    while (next < 0 && looked < chunks) {
+      const uint64_t f = __ballot(distanceTarget(a, bits, looked * 64u + lane));
+      if (f) next = int32_t(looked * 64u + uint32_t(__builtin_ctzll(f)));
+      looked++;
+    }
+    const uint64_t lowm = m & atOrBelow, highm = m & atOrAbove;
+    const int32_t lo = lowm ? int32_t(c * 64u + 63u - uint32_t(__builtin_clzll(lowm))) : last;
+    const int32_t hi = highm ? int32_t(c * 64u + uint32_t(__builtin_ctzll(highm))) : next;
+    if (x < a.nx) out[x] = (lo < 0 || (hi >= 0 && uint32_t(hi) - x < x - uint32_t(lo))) ? hi : lo;     // of two, the smaller
+    if (m) last = int32_t(c * 64u + 63u - uint32_t(__builtin_clzll(m)));
+  }
+}
+
+// The scan of one point at position p of an axis of n points: value(q) is gx or gy at position q of the point's column.
+// best / arg: the minimum of value(q) + term(|p - q|) and the smallest q that holds it, -1 where the minimum is +INF.
+template <typename F>
+__device__ __forceinline__ void distanceScan(uint32_t p, uint32_t n, float h, float limit, F value, float &best, int32_t &arg)
+{
+  best = value(p);                                      // + term(0), which is +0
+  arg = best < INFINITY ? int32_t(p) : -1;
+  const uint32_t reach = p > n - 1u - p ? p : n - 1u - p, above = n - p;
+  // one step: the candidates at distance d on both sides; a side that has left the axis reads position p and counts as +INF
+  auto step = [&](uint32_t d, float t, float below, float over) {
+    const float vm = d <= p ? below + t : INFINITY, vp = d < above ? over + t : INFINITY;
+    if (vm < INFINITY && vm <= best) { best = vm; arg = int32_t(p - d); }
+    if (vp < best) { best = vp; arg = int32_t(p + d); }
+  };
+  // two steps per round, their four loads issued together ahead of the first stop test: the loads of the second step are
+  // wasted where the first one ends the scan, and hide each other's latency on a long one
+  for (uint32_t d = 1; d <= reach; d += 2) {
+    const float t0 = distanceTerm(h, d), t1 = distanceTerm(h, d + 1u);
+    const float m0 = value(d <= p ? p - d : p), p0 = value(d < above ? p + d : p);
+    const float m1 = value(d + 1u <= p ? p - d - 1u : p), p1 = value(d + 1u < above ? p + d + 1u : p);
+    if (t0 > fminf(best, limit)) break;
+    step(d, t0, m0, p0);
+    if (d + 1u > reach || t1 > fminf(best, limit)) break;
+    step(d + 1u, t1, m1, p1);
+  }
+}
+
+template <int AXIS>
+__device__ __forceinline__ float distanceColumnValue(const IsoDistanceArgs &a, uint64_t at, uint32_t i)
+{
+  if (AXIS == 2) return a.gy[at];
+  const int32_t t = a.a[at];
+  return t < 0 ? INFINITY : distanceTerm(a.h[0], uint32_t(t) > i ? uint32_t(t) - i : i - uint32_t(t));
+}
+
+template <int AXIS>
+__device__ __forceinline__ void distanceColumnStore(const IsoDistanceArgs &a, uint64_t at, float best, int32_t arg)
+{
+  (AXIS == 1 ? a.b : a.c)[at] = arg;
+  (AXIS == 1 ? a.gy : a.d2)[at] = best;
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(kIsoBlock) void isoDistanceColumnKernel(const IsoDistanceArgs a)
+{
+  const uint64_t at = uint64_t(blockIdx.x) * kIsoBlock + threadIdx.x;
+  if (at >= a.numPoints) return;
+  const uint32_t L = uint32_t(at), i = L % a.nx, row = L / a.nx;
+  const uint32_t n = AXIS == 1 ? a.ny : a.nz, p = AXIS == 1 ? row % a.ny : row / a.ny;
+  const uint64_t stride = AXIS == 1 ? uint64_t(a.nx) : uint64_t(a.nx) * a.ny, base = at - p * stride;
+  float best;
+  int32_t arg;
+  distanceScan(p, n, a.h[AXIS], a.limit, [&](uint32_t q) { return distanceColumnValue<AXIS>(a, base + q * stride, i); }, best, arg);
+  distanceColumnStore<AXIS>(a, at, best, arg);
+}
+
+#if EXA_DISTANCE_LDS
+// The column pass out of a slab in LDS: a block takes 64 columns (consecutive x) of one plane of the scan (AXIS 1: the plane
+// k = blockIdx.y, AXIS 2: the plane j = blockIdx.y), stages value(q) of all n <= kIsoDistanceLdsAxis positions, 64 floats a
+// row (a wave's access is one bank row, no conflicts), and its four waves take the positions in turn.
+template <int AXIS>
+__global__ __launch_bounds__(kIsoBlock) void isoDistanceColumnLdsKernel(const IsoDistanceArgs a)
+{
+  extern __shared__ float slab[];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, i = blockIdx.x * 64u + lane;
+  const uint32_t n = AXIS == 1 ? a.ny : a.nz;
+  const uint64_t stride = AXIS == 1 ? uint64_t(a.nx) : uint64_t(a.nx) * a.ny;
+  const uint64_t base = (AXIS == 1 ? uint64_t(blockIdx.y) * a.ny * a.nx : uint64_t(blockIdx.y) * a.nx) + i;
+  for (uint32_t q = wave; q < n; q += kIsoBlock / 64)
+    slab[q * 64u + lane] = i < a.nx ? distanceColumnValue<AXIS>(a, base + q * stride, i) : INFINITY;
+  __syncthreads();
+  if (i >= a.nx) return;
+  for (uint32_t p = wave; p < n; p += kIsoBlock / 64) {
+    float best;
+    int32_t arg;
+    distanceScan(p, n, a.h[AXIS], a.limit, [&](uint32_t q) { return slab[q * 64u + lane]; }, best, arg);
+    distanceColumnStore<AXIS>(a, base + p * stride, best, arg);
+  }
+}
+#endif
+
+__global__ __launch_bounds__(kIsoBlock) void isoDistanceFinishKernel(const IsoDistanceArgs a)
+{
+  __shared__ uint32_t lds[2 * (kIsoBlock / 64)];
+  uint32_t count = 0, top = 0;
+  for (uint32_t t = 0; t < kIsoDistanceTiles; t++) {
+    const uint64_t at = (uint64_t(blockIdx.x) * kIsoDistanceTiles + t) * kIsoBlock + threadIdx.x;
+    if (at >= a.numPoints) break;
+    if (a.onlyOthers && (a.inside[at] != 0) != (a.toOutside != 0)) continue;
+    const float d2 = a.d2[at];
+    const bool reached = d2 <= a.limit && d2 < INFINITY;
+    const float d = reached ? sqrtf(d2) : INFINITY;
+    a.dist[at] = a.negative ? -d : d;
+    if (reached) {
+      const uint32_t bits = __float_as_uint(d);
+      top = bits > top ? bits : top;
+      count++;
+    }
+    if (a.nearest) {
+      int32_t to = -1;
+      if (reached) {
+        const uint32_t L = uint32_t(at), i = L % a.nx, j = (L / a.nx) % a.ny;
+        const uint64_t plane = uint64_t(uint32_t(a.c[at])) * a.ny;
+        const uint32_t b = uint32_t(a.b[(plane + j) * a.nx + i]);
+        to = int32_t((plane + b) * a.nx + uint32_t(a.a[(plane + b) * a.nx + i]));
+      }
+      a.nearest[at] = to;
+    }
+  }
+  distanceTotals(a, lds, count, top, kIsoDistanceReached, kIsoDistanceMaxBits);
+}
+
 // ---- the launchers: every kernel runs in blocks of kIsoBlock lanes and takes its argument struct by value ----
 template <typename A>
 hipError_t launch(void (*kernel)(A), dim3 grid, hipStream_t s, const A &a)
@@ -1801,5 +1999,24 @@ hipError_t launchIsoProfileAccumulate(const IsoProfileArgs &a, hipStream_t s)
   return hipGetLastError();
 }
 hipError_t launchIsoProfileFinish(const IsoProfileArgs &a, hipStream_t s) { return launch(isoProfileFinishKernel, blocksOf(uint64_t(a.numValues) * a.numBins), s, a); }
+
+hipError_t launchIsoDistanceInside(const IsoDistanceArgs &a, hipStream_t s) { return launch(isoDistanceInsideKernel, blocksOf(a.numBlocks, kIsoDistanceTiles), s, a); }
+hipError_t launchIsoDistanceRows(const IsoDistanceArgs &a, hipStream_t s) { return launch(isoDistanceRowKernel, blocksOf(uint64_t(a.ny) * a.nz, kIsoBlock / 64), s, a); }
+hipError_t launchIsoDistanceFinish(const IsoDistanceArgs &a, hipStream_t s) { return launch(isoDistanceFinishKernel, blocksOf(a.numBlocks, kIsoDistanceTiles), s, a); }
+
+hipError_t launchIsoDistanceColumns(const IsoDistanceArgs &a, int axis, hipStream_t s)
+{
+#if EXA_DISTANCE_LDS
+  // the slab where the axis fits it and the planes fit the grid's second dimension
+  const uint32_t n = axis == 1 ? a.ny : a.nz, planes = axis == 1 ? a.nz : a.ny;
+  if (n <= kIsoDistanceLdsAxis && planes <= 65535u) {
+    const dim3 grid(blocksOf(a.nx, 64), planes);
+    if (axis == 1) hipLaunchKernelGGL(isoDistanceColumnLdsKernel<1>, grid, dim3(kIsoBlock), n * 64u * sizeof(float), s, a);
+    else hipLaunchKernelGGL(isoDistanceColumnLdsKernel<2>, grid, dim3(kIsoBlock), n * 64u * sizeof(float), s, a);
+    return hipGetLastError();
+  }
+#endif
+  return axis == 1 ? launch(isoDistanceColumnKernel<1>, a.numBlocks, s, a) : launch(isoDistanceColumnKernel<2>, a.numBlocks, s, a);
+}
 
 } // namespace exa

@@ -6,7 +6,8 @@
 // contour lines on a plane lattice beside it (exa_hip_isolines, exa_hip_isolines_derived; the same unit) and the connected
 // regions of field >= iso on the lattice (exa_hip_regions, exa_hip_regions_derived; the same unit), its basins, one per peak
 // (exa_hip_basins, exa_hip_basins_derived; the same unit), the critical points of a flow on it (exa_hip_critical_points;
-// the same unit), and the profiles and phase plots of fields on it (exa_hip_profile; the same unit).
+// the same unit), the profiles and phase plots of fields on it (exa_hip_profile; the same unit), and the distance transform
+// of a set of its points (exa_hip_distance, exa_hip_distance_derived, exa_hip_distance_mask; the same unit).
 #include "exa_renderer.h"
 #include "exa_isomesh.h"
 
@@ -1790,6 +1791,172 @@ int exa_hip_profile_stage_ms(ExaHipRenderer *h, float ms[4])
 {
   if (!h || !ms) return 1;
   for (int k = 0; k < 4; k++) ms[k] = firstChild(h)->profile.stageMs[k];
+  return 0;
+}
+
+} // extern "C"
+
+// ---- exact Euclidean distance transform on a lattice (exa_isomesh.hip) ----
+// exa_hip_distance (quantity < 0: the lattice holds the one channel channels[0]), exa_hip_distance_derived (it holds the
+// quantity of channels[0..2]) and exa_hip_distance_mask (channels == nullptr: inside by `labels` and `label`).  The flags,
+// the channels and the quantity are checked by the caller.  One run of the passes per target set, two with
+// EXA_DISTANCE_SIGNED, each with a finish pass that writes its share of the outputs; one read-back, the three counters.
+static int distanceTransform(ExaHipRenderer *h, const char *fn, const float lo[3], const float hi[3], const int32_t dims[3],
+                             const int32_t *channels, int32_t quantity, float iso, const int32_t *labels, int32_t label,
+                             float maxDistance, int32_t flags, float *dist, int32_t *nearest, ExaHipDistanceStats *stats,
+                             int32_t pointersAreDevice, void *hipStream)
+{
+  ExaHipRenderer *r = firstChild(h);
+  for (float &ms : r->distance.stageMs) ms = 0.f;
+  const bool mask = channels == nullptr;
+  if (!lo || !hi || !dims || !dist) { h->fail(std::string(fn) + ": null argument (lo, hi, dims or dist)"); return 1; }
+  if (mask && !labels) { h->fail(std::string(fn) + ": null labels"); return 1; }
+  if (mask && label < -1) { h->fail(std::string(fn) + ": label must be >= -1 (-1: every label >= 0)"); return 1; }
+  if (!mask && !std::isfinite(iso)) { h->fail(std::string(fn) + ": the iso value must be finite"); return 1; }
+  if (!(maxDistance > 0.f)) { h->fail(std::string(fn) + ": maxDistance must be > 0 (+INF for no limit)"); return 1; }
+  if ((flags & EXA_DISTANCE_SIGNED) && (flags & EXA_DISTANCE_TO_OUTSIDE)) {
+    h->fail(std::string(fn) + ": EXA_DISTANCE_SIGNED excludes EXA_DISTANCE_TO_OUTSIDE");
+    return 1;
+  }
+  const uint64_t n = latticePoints(h, fn, lo, hi, dims, 1, "dims must be >= 1 on every axis", "the box must be finite", false);
+  if (!n) return 1;
+
+  IsoDistanceArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.numPoints = uint32_t(n);
+  a.nx = uint32_t(dims[0]); a.ny = uint32_t(dims[1]); a.nz = uint32_t(dims[2]);
+  a.numBlocks = uint32_t((n + kIsoBlock - 1) / kIsoBlock);
+  for (int k = 0; k < 3; k++) {
+    a.h[k] = (hi[k] - lo[k]) / float(dims[k]);
+    if (!std::isfinite(a.h[k])) { h->fail(std::string(fn) + ": the spacing (hi - lo) / dims must be finite in float32"); return 1; }
+  }
+  a.limit = maxDistance * maxDistance;
+  a.iso = iso;
+  a.label = label;
+  a.byLabel = mask ? 1 : 0;
+  a.below = (flags & EXA_DISTANCE_BELOW) ? 1 : 0;
+
+  EXA_ON_DEVICE_OF(h, r);
+  hipStream_t s = (hipStream_t)hipStream;
+  if (!mask && r->applyBrickOrder(s)) { h->fail(r->err); return 1; }
+
+  // the work space: a | b | c | gy | d2 | dist and nearest for host pointers | the inside bytes | and the counters
+  const bool staged = !pointersAreDevice, hostLabels = mask && !(flags & EXA_DISTANCE_LABELS_DEVICE);
+  const size_t N = size_t(n), words = 5 + (staged ? 1 + (nearest ? 1 : 0) : 0);
+  DevBuf<char> work;
+  DevBuf<unsigned long long> counters;
+  hipError_t e = work.alloc(words * 4 * N + N);
+  if (e == hipSuccess) e = counters.alloc(kIsoDistanceCounters);
+  if (e != hipSuccess)
+    return failNoMemory(h, fn, "no device memory for the passes (21 bytes per point, and 4 each for dist and nearest with host pointers)", e);
+  int32_t *ints = reinterpret_cast<int32_t *>(work.p);
+  a.a = ints; a.b = ints + N; a.c = ints + 2 * N;
+  a.gy = reinterpret_cast<float *>(ints + 3 * N); a.d2 = reinterpret_cast<float *>(ints + 4 * N);
+  a.dist = staged ? reinterpret_cast<float *>(ints + 5 * N) : dist;
+  a.nearest = !nearest ? nullptr : staged ? ints + 6 * N : nearest;
+  a.inside = reinterpret_cast<uint8_t *>(ints + words * N);
+  a.counters = counters.p;
+  a.values = a.d2;                                      // read by the inside pass only, d2 is written behind it
+  a.labels = hostLabels ? a.c : labels;                 // likewise
+
+  TimingEvents<8> t;
+  HIP_TRY(h, t.create());
+  HIP_TRY(h, hipEventRecord(t.ev[0], s));
+  if (!mask) {
+    if (int rc = fillLattice(h, fn, lo, hi, dims, channels, quantity, flags & EXA_SAMPLE_WORLD_SPACE, a.d2, hipStream)) return rc;
+  } else if (hostLabels) {
+    HIP_TRY(h, hipMemcpyAsync(a.c, labels, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(h, hipMemsetAsync(counters.p, 0, kIsoDistanceCounters * sizeof(unsigned long long), s));
+  HIP_TRY(h, launchIsoDistanceInside(a, s));
+  HIP_TRY(h, hipEventRecord(t.ev[1], s));
+  const bool isSigned = (flags & EXA_DISTANCE_SIGNED) != 0;
+  const int runs = isSigned ? 2 : 1;
+  for (int run = 0; run < runs; run++) {
+    a.toOutside = isSigned ? run : (flags & EXA_DISTANCE_TO_OUTSIDE) ? 1 : 0;
+    a.negative = isSigned && run == 1 ? 1 : 0;
+    a.onlyOthers = isSigned ? 1 : 0;
+    HIP_TRY(h, launchIsoDistanceRows(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[2 + 3 * run], s));
+    HIP_TRY(h, launchIsoDistanceColumns(a, 1, s));
+    HIP_TRY(h, launchIsoDistanceColumns(a, 2, s));
+    HIP_TRY(h, hipEventRecord(t.ev[3 + 3 * run], s));
+    HIP_TRY(h, launchIsoDistanceFinish(a, s));
+    HIP_TRY(h, hipEventRecord(t.ev[4 + 3 * run], s));
+  }
+  if (staged) {
+    HIP_TRY(h, hipMemcpyAsync(dist, a.dist, N * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (nearest) HIP_TRY(h, hipMemcpyAsync(nearest, a.nearest, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  }
+  unsigned long long got[kIsoDistanceCounters] = {};
+  if (readBack(h, got, counters.p, sizeof(got), s)) return 1;         // the work space is freed behind it
+  float *ms = r->distance.stageMs;
+  HIP_TRY(h, t.elapsed(0, 1, &ms[0]));
+  for (int run = 0; run < runs; run++)
+    for (int k = 0; k < 3; k++) {
+      float part = 0.f;
+      HIP_TRY(h, t.elapsed(1 + 3 * run + k, 2 + 3 * run + k, &part));
+      ms[1 + k] += part;
+    }
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->points = n;
+    stats->inside = got[kIsoDistanceInside];
+    stats->reached = got[kIsoDistanceReached];
+    const uint32_t bits = uint32_t(got[kIsoDistanceMaxBits]);
+    std::memcpy(&stats->maxDistance, &bits, sizeof(bits));
+  }
+  return 0;
+}
+
+static const int32_t kDistanceFieldFlags = EXA_SAMPLE_WORLD_SPACE | EXA_DISTANCE_BELOW | EXA_DISTANCE_TO_OUTSIDE | EXA_DISTANCE_SIGNED;
+static const char *const kDistanceFieldHint = " (EXA_SAMPLE_WORLD_SPACE, EXA_DISTANCE_BELOW, EXA_DISTANCE_TO_OUTSIDE and EXA_DISTANCE_SIGNED apply)";
+
+extern "C" {
+
+int exa_hip_distance(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], int32_t channel, float iso,
+                     float maxDistance, int32_t flags, float *dist, int32_t *nearest, ExaHipDistanceStats *stats,
+                     int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_distance";
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!checkFlags(h, fn, flags, kDistanceFieldFlags, kDistanceFieldHint) || !checkChannel(h, fn, channel)) return 1;
+  return distanceTransform(h, fn, lo, hi, dims, &channel, -1, iso, nullptr, 0, maxDistance, flags, dist, nearest, stats,
+                           pointersAreDevice, hipStream);
+}
+
+int exa_hip_distance_derived(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t channels[3],
+                             int32_t quantity, float iso, float maxDistance, int32_t flags, float *dist, int32_t *nearest,
+                             ExaHipDistanceStats *stats, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_distance_derived";
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!checkFlags(h, fn, flags, kDistanceFieldFlags, kDistanceFieldHint)) return 1;
+  if (!channels) { h->fail(std::string(fn) + ": null argument (channels)"); return 1; }
+  if (!oneComponent(h, fn, channels, quantity, "the distance needs")) return 1;
+  return distanceTransform(h, fn, lo, hi, dims, channels, quantity, iso, nullptr, 0, maxDistance, flags, dist, nearest, stats,
+                           pointersAreDevice, hipStream);
+}
+
+int exa_hip_distance_mask(ExaHipRenderer *h, const float lo[3], const float hi[3], const int32_t dims[3], const int32_t *labels,
+                          int32_t label, float maxDistance, int32_t flags, float *dist, int32_t *nearest,
+                          ExaHipDistanceStats *stats, int32_t pointersAreDevice, void *hipStream)
+{
+  if (!h) return 1;
+  const char *fn = "exa_hip_distance_mask";
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!checkFlags(h, fn, flags, EXA_SAMPLE_WORLD_SPACE | EXA_DISTANCE_TO_OUTSIDE | EXA_DISTANCE_SIGNED | EXA_DISTANCE_LABELS_DEVICE,
+                  " (EXA_DISTANCE_TO_OUTSIDE, EXA_DISTANCE_SIGNED and EXA_DISTANCE_LABELS_DEVICE apply)")) return 1;
+  return distanceTransform(h, fn, lo, hi, dims, nullptr, -1, 0.f, labels, label, maxDistance, flags, dist, nearest, stats,
+                           pointersAreDevice, hipStream);
+}
+
+int exa_hip_distance_stage_ms(ExaHipRenderer *h, float ms[4])
+{
+  if (!h || !ms) return 1;
+  for (int k = 0; k < 4; k++) ms[k] = firstChild(h)->distance.stageMs[k];
   return 0;
 }
 

@@ -414,6 +414,11 @@ struct ExaHipRenderer {
   struct Profile {
     float stageMs[4] = { 0.f, 0.f, 0.f, 0.f };
   } profile;
+  // the device time of the stages of the last exa_hip_distance[_derived|_mask] (in the renderer of devices[0]): values,
+  // rows, columns, finish; the call keeps nothing else
+  struct Distance {
+    float stageMs[4] = { 0.f, 0.f, 0.f, 0.f };
+  } distance;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   ExaHipStats last{};
 

@@ -101,6 +101,18 @@
 //             [--profile-weight SOURCE]      sums of weight * value, and the weight's own sums
 //             [--profile-box lx ly lz ux uy uz] [--profile-world] (box default as for --resample)
 //             [--profile-log]                the uniform axes' bins spaced logarithmically: edges float(LO * (HI / LO)^(b / BINS))
+//             [--distance CHANNEL ISO MAXDIST NX NY NZ out.dist] per point of that lattice the exact Euclidean distance, in the
+//                                            space of the box, to the nearest point where the field of CHANNEL is >= ISO, and
+//                                            that point (exa_hip_distance; MAXDIST may be `inf`).  With
+//                                            --derived the set of that quantity (exa_hip_distance_derived; CHANNEL is read and
+//                                            ignored, vorticity refused).  One text line `distance NX NY NZ points P inside I
+//                                            reached R maxDistance D`, then raw little-endian arrays over the lattice, x fastest:
+//                                            dist (float32; +-inf beyond MAXDIST or with no target) and nearest (int32: the
+//                                            linear index of the nearest target, -1 for none); --frames 0 renders nothing; with
+//             [--distance-box lx ly lz ux uy uz] (box default as for --resample)
+//             [--distance-signed]            + the distance to the set outside it, - the distance to the others inside it
+//             [--distance-outside]           the distance to the nearest point that is not in the set (with ISO -3.4028235e38,
+//                                            -FLT_MAX: the wall distance, to the nearest point without data)
 //             [--histogram BINS file.txt]   the exact histogram of a channel's cell values (exa_hip_histogram), one line
 //                                            `cells volume` per bin (cell slots; the same weighted with 8^level finest voxels), with
 //             [--histogram-channel c] [--histogram-range lo hi] [--histogram-box lx ly lz ux uy uz]
@@ -185,6 +197,7 @@ struct LicOpts { std::string name; vec3i channels{ 0, 1, 2 }; PlaneOpts plane; f
 struct FtleOpts { std::string name; vec3i channels{ 0, 1, 2 }, dims{ 1, 1, 1 }; box3f box; float step = 0.5f; int numSteps = 20; bool backward = false; };
 struct CriticalOpts { std::string name; vec3i channels{ 0, 1, 2 }, dims{ 2, 2, 2 }; box3f box; int iterations = 8; float tolerance = 0.0009765625f; };
 struct RegionsOpts { std::string name; int channel = 0; float iso = 0.f; vec3i dims; };
+struct DistanceOpts { std::string name; int channel = 0; float iso = 0.f, maxDistance = INFINITY; vec3i dims; box3f box; bool haveBox = false, isSigned = false, outside = false; };
 struct BasinsOpts { std::string name; int channel = 0; float iso = 0.f, minDepth = 0.f; vec3i dims; };
 struct ProfileOpts {
   std::string name, axes, values, weight; vec3i dims; box3f box; bool haveBox = false, world = false, log = false;
@@ -214,7 +227,7 @@ struct FrameOpts {                                           // what the referen
 };
 struct Options {
   FrameOpts frame; DerivedOpts derived; LatticeFlags lattice; ResampleOpts resample; IsoMeshOpts isomesh; IsolinesOpts isolines; LicOpts lic;
-  FtleOpts ftle; CriticalOpts critical; RegionsOpts regions; BasinsOpts basins; ProfileOpts profile; SurfaceOpts surface; HistogramOpts histogram;
+  FtleOpts ftle; CriticalOpts critical; RegionsOpts regions; BasinsOpts basins; DistanceOpts distance; ProfileOpts profile; SurfaceOpts surface; HistogramOpts histogram;
   StreamlinesOpts streamlines; ProjectOpts project; RaycastOpts raycast;
 };
 
@@ -364,6 +377,14 @@ bool parseLatticeOutputFlag(Args &a, Options &o)
   else if (f == "--profile-box") { o.profile.box = a.box(); o.profile.haveBox = true; }
   else if (f == "--profile-world") o.profile.world = true;
   else if (f == "--profile-log") o.profile.log = true;
+  else if (f == "--distance") {
+    DistanceOpts &d = o.distance;
+    d.channel = a.count(); d.iso = a.number(); d.maxDistance = a.number(); d.dims = a.int3();
+    d.name = a.word("missing file after --distance CHANNEL ISO MAXDIST NX NY NZ");
+  }
+  else if (f == "--distance-box") { o.distance.box = a.box(); o.distance.haveBox = true; }
+  else if (f == "--distance-signed") o.distance.isSigned = true;
+  else if (f == "--distance-outside") o.distance.outside = true;
   else if (f == "--regions-box") { o.lattice.box = a.box(); o.lattice.haveBox = true; }
   else if (f == "--regions-world") o.lattice.world = true;
   else if (f == "--regions-below") o.lattice.below = true;
@@ -678,6 +699,20 @@ void writeBasins(const BasinsOpts &o, const LatticeFlags &lf, const DerivedOpts 
   keepLabels(keep, B, B.basins.size(), o.dims, box, lf.world);
 }
 
+void writeDistance(const DistanceOpts &o, const DerivedOpts &dv, Renderer &r)
+{
+  const box3f box = boxOr(o.haveBox, o.box, false, r);
+  const int flags = (o.isSigned ? EXA_DISTANCE_SIGNED : 0) | (o.outside ? EXA_DISTANCE_TO_OUTSIDE : 0);
+  const Renderer::Distance D = dv.on() ? r.distanceDerived(box, o.dims, dv.channels, dv.quantity, o.iso, o.maxDistance, flags, true)
+                                       : r.distance(box, o.dims, o.channel, o.iso, o.maxDistance, flags, true);
+  const std::string counts = format("points %llu inside %llu reached %llu maxDistance %.9g\n", ull(D.stats.points), ull(D.stats.inside),
+                                    ull(D.stats.reached), D.stats.maxDistance);
+  writeRaw(o.name, format("distance %d %d %d ", o.dims.x, o.dims.y, o.dims.z) + counts,
+           { { D.dist.data(), 4, D.dist.size() }, { D.nearest.data(), 4, D.nearest.size() } });
+  std::printf("distance %d %d %d %siso %.9g maxDistance %.9g signed %d outside %d %s", o.dims.x, o.dims.y, o.dims.z,
+              fieldWords(dv, o.channel).c_str(), o.iso, o.maxDistance, o.isSigned ? 1 : 0, o.outside ? 1 : 0, counts.c_str());
+}
+
 void writeProfile(const ProfileOpts &o, const KeptLabels &regions, const KeptLabels &basins, Renderer &r)
 {
   const box3f box = boxOr(o.haveBox, o.box, o.world, r);
@@ -829,6 +864,7 @@ bool writeOutputs(const Options &o, Renderer &r)
   if (wanted(o.regions.name)) writeRegions(o.regions, o.lattice, o.derived, profile ? &regionLabels : nullptr, r);
   if (wanted(o.basins.name)) writeBasins(o.basins, o.lattice, o.derived, profile ? &basinLabels : nullptr, r);
   if (wanted(o.profile.name)) writeProfile(o.profile, regionLabels, basinLabels, r);
+  if (wanted(o.distance.name)) writeDistance(o.distance, o.derived, r);
   if (wanted(o.surface.name)) writeSurface(o.surface, isoMesh, r);
   if (wanted(o.histogram.name)) writeHistogram(o.histogram, r);
   if (wanted(o.streamlines.name)) writeStreamlines(o.streamlines, r);

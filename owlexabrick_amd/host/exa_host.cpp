@@ -805,6 +805,44 @@ Renderer::Profile Renderer::profile(const box3f &box, vec3i dims, const std::vec
   return P;
 }
 
+static Renderer::Distance distanceOf(ExaHipRenderer *handle, const box3f &box, vec3i dims, const Field *f, float iso,
+                                     const int32_t *labels, int32_t label, float maxDistance, int flags, bool nearest)
+{
+  const Lattice L(box, dims);
+  Renderer::Distance D;
+  D.dims = dims;
+  D.dist.resize(latticePoints(dims));
+  if (nearest) D.nearest.resize(latticePoints(dims));
+  int32_t *near = nearest ? D.nearest.data() : nullptr;
+  check(!f ? exa_hip_distance_mask(handle, L.lo, L.hi, L.d, labels, label, maxDistance, flags, D.dist.data(), near, &D.stats, 0, nullptr)
+        : f->derived ? exa_hip_distance_derived(handle, L.lo, L.hi, L.d, f->ch.data(), f->quantity, iso, maxDistance, flags, D.dist.data(), near, &D.stats, 0, nullptr)
+                     : exa_hip_distance(handle, L.lo, L.hi, L.d, f->channel, iso, maxDistance, flags, D.dist.data(), near, &D.stats, 0, nullptr),
+        handle);
+  return D;
+}
+
+Renderer::Distance Renderer::distance(const box3f &box, vec3i dims, int channel, float iso, float maxDistance, int flags,
+                                      bool nearest, bool worldSpace)
+{
+  if (worldSpace) pushState();
+  const Field f(channel);
+  return distanceOf(handle, box, dims, &f, iso, nullptr, 0, maxDistance, flags | spaceFlag(worldSpace), nearest);
+}
+
+Renderer::Distance Renderer::distanceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, float maxDistance,
+                                             int flags, bool nearest, bool worldSpace)
+{
+  if (worldSpace) pushState();
+  const Field f(channels, quantity);
+  return distanceOf(handle, box, dims, &f, iso, nullptr, 0, maxDistance, flags | spaceFlag(worldSpace), nearest);
+}
+
+Renderer::Distance Renderer::distanceMask(const box3f &box, vec3i dims, const int32_t *labels, int label, float maxDistance, int flags,
+                                          bool nearest)
+{
+  return distanceOf(handle, box, dims, nullptr, 0.f, labels, label, maxDistance, flags, nearest);
+}
+
 void Renderer::computeHistogram(int channel, const interval<float> &range, int numBins, std::vector<uint64_t> &cells,
                                 std::vector<uint64_t> *volume, ExaHipFieldStats *stats, const box3i *box)
 {

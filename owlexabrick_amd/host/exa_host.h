@@ -305,6 +305,24 @@ struct Renderer {
   Profile profile(const box3f &box, vec3i dims, const std::vector<ExaHipProfileAxis> &axes, const std::vector<ExaHipSource> &values,
                   const ExaHipSource *weight = nullptr, bool worldSpace = false, bool minMax = true, bool labelsOnDevice = false);
 
+  // per point of the lattice of resample(box, dims) the exact Euclidean distance, in the space of the box, to the nearest
+  // point where the field is >= iso and (nearest) that point's linear index (exa_hip_distance; include/exa_hip.h states the
+  // contract).  flags: EXA_DISTANCE_BELOW, EXA_DISTANCE_TO_OUTSIDE, EXA_DISTANCE_SIGNED.  distanceMask: the set is
+  // labels == label (-1: labels >= 0), host memory, or device memory with EXA_DISTANCE_LABELS_DEVICE; the box and dims give
+  // only the spacing.  Beyond maxDistance, or with no target: +INF (-INF on the inside branch of SIGNED) and -1.
+  struct Distance {
+    vec3i dims;
+    std::vector<float> dist;             // numPoints
+    std::vector<int32_t> nearest;        // numPoints, empty without `nearest`
+    ExaHipDistanceStats stats;
+  };
+  Distance distance(const box3f &box, vec3i dims, int channel, float iso, float maxDistance = INFINITY, int flags = 0,
+                    bool nearest = false, bool worldSpace = false);
+  Distance distanceDerived(const box3f &box, vec3i dims, vec3i channels, int quantity, float iso, float maxDistance = INFINITY,
+                           int flags = 0, bool nearest = false, bool worldSpace = false);
+  Distance distanceMask(const box3f &box, vec3i dims, const int32_t *labels, int label = -1, float maxDistance = INFINITY,
+                        int flags = 0, bool nearest = false);
+
   // the histogram the reference's viewer meant to hand its transfer-function editor (exa/viewer.cpp:1274-1276,
   // setHistogram(computeHistogram(scalarField)), commented out there), computed on the device from the cells of `channel`
   // (exa_hip_histogram; include/exa_hip.h states the contract): cells[b] = cell slots whose value falls into bin b of
